@@ -13,6 +13,12 @@ timed region (weak scaling: the per-GPU work is fixed).
 Started without a launcher (`WORLD_SIZE` unset) and with --gpus N > 1 the script starts the N ranks itself
 (`python -m torch.distributed.run`), from a parent that never touches the GPU, and relays rank 0's line.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  `--full` adds what takes runs of its own
+after the timed region: the short legs of the other configs (`other_configs`, `hbm_honest`), the host-fed and call-size
+legs (`host_fed`, `host_fed_small`, `device_fed_calls`) and the CPU baseline (`cpu_baseline`).
+`--dump-outputs DIR` writes what the timed path's read-out returned after the last step (psd.npy, frequencies.npy,
+breaks.npy; see dump_outputs) for output-for-output comparison of two builds; the inputs are seeded, identical run to run.
 """
 import argparse
 import json
@@ -364,6 +370,41 @@ def measured_traffic(kernel, n, channels, samples, window="hann"):
     return best
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # all arrays of --dump-outputs together (64 MB cap)
+BREAK_FIELDS = ("start", "include", "count", "avg", "bins_start", "bins_stop", "fft_size", "decimation", "pending", "processed")
+
+
+def dump_outputs(pkg, merged, out_dir):
+    """What a caller of the timed path receives from its read-out (PsdCascade::psd per channel: the merged spectrum and its
+    breaks), as .npy files in `out_dir`:
+      psd.npy          float32 [channels, bins]   merged PSD (NaN-padded if channels differ in length)
+      frequencies.npy  float32 [channels, bins]   Break::frequencies of the same breaks
+      breaks.npy       float64 [channels, stages, len(BREAK_FIELDS)], fields in BREAK_FIELDS order (-1-padded)
+    If psd + frequencies would exceed the budget, the same fixed, seeded sample of bin columns is kept in both and its
+    indices are written as bin_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ch = len(merged)
+    freqs = [pkg.Break.frequencies(br) for _, br in merged]
+    nb = max(p.size for p, _ in merged)
+    ns = max(len(br) for _, br in merged)
+    psd = np.full((ch, nb), np.nan, dtype=np.float32)
+    fr = np.full((ch, nb), np.nan, dtype=np.float32)
+    brk = np.full((ch, max(1, ns), len(BREAK_FIELDS)), -1.0, dtype=np.float64)
+    for c, ((p, br), f) in enumerate(zip(merged, freqs)):
+        psd[c, :p.size] = p
+        fr[c, :f.size] = f
+        for k, b in enumerate(br):
+            brk[c, k] = (b.start, b.include, b.count, b.avg, b.bins.start, b.bins.stop, b.fft_size, b.decimation, b.pending, b.processed)
+    keep = (DUMP_BUDGET_BYTES - brk.nbytes) // (2 * 4 * ch)
+    files = {"psd": psd, "frequencies": fr, "breaks": brk}
+    if nb > keep:
+        idx = np.sort(np.random.default_rng(0x7654321).choice(nb, size=int(keep), replace=False))
+        files.update(psd=psd[:, idx], frequencies=fr[:, idx], bin_index=idx.astype(np.float64))
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(files)
+
+
 def launch_ranks(args, argv):
     """--gpus N > 1 without a launcher: start N ranks (one per GPU) under torch.distributed.run from this
     process, which has not initialised the GPU (no torch.cuda / HIP call so far), relay their output and
@@ -413,9 +454,14 @@ def main():
     ap.add_argument("--eager", action="store_true", help="PSDC_OPT_EAGER: held spans go out when the device is seen idle (timing-dependent rounds; A/B aid)")
     ap.add_argument("--min-pairs", type=int, default=None, help="PSDC_OPT_MIN_PAIRS (library default 32 x teams per workgroup)")
     ap.add_argument("--avg", default=None, help="finite averaging 'limit,count' (AvgOpts, src/psd.rs:360-376); default: plain sum")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the side legs (other configs, 2^28-sample footprint, host-fed and call-size legs) "
+                         "and the CPU baseline; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's read-out after the last step (psd, frequencies, breaks) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-fed legs and the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short side legs after the headline (configs[2] frames, configs[4] N=16384, 2^28-sample footprint)")
+                    help="with --full: skip the short side legs after the headline (configs[2] frames, configs[4] N=16384, 2^28-sample footprint)")
     ap.add_argument("--side-seconds", type=float, default=1.5, help="wall time of each side leg")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsal)")
     ap.add_argument("--single-device", action="store_true",
@@ -680,9 +726,11 @@ def main():
                                                        "and the sub-nominal clock both sit between this fraction and the VALU's busy fraction",
                                  "algorithmic_flop_per_sample": flop},
         }
+        if args.dump_outputs:
+            dump_outputs(pkg, merged, args.dump_outputs)
         bank.close()
         bank = None
-        if world == 1 and not args.no_other_configs and n == 1024 and C == 1 and not frames:
+        if args.full and world == 1 and not args.no_other_configs and n == 1024 and C == 1 and not frames:
             # short legs of the other single-GPU configs, after (and outside) the headline's timed region
             del bufs
             torch.cuda.empty_cache()
@@ -695,7 +743,7 @@ def main():
             out["other_configs"] = oc
             # the headline shape beyond the 256 MiB Infinity Cache (FETCH_SIZE counts fabric requests, MALL hits included)
             out["hbm_honest"] = side_leg_raw(pkg, torch, 1024, 28, local_rank, args.side_seconds)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if world == 1 and not frames:
                 out["host_fed"] = host_fed_rate(pkg, n, local_rank)
                 out["host_fed_small"] = host_fed_small(n, local_rank)

@@ -16,8 +16,9 @@
 
 using namespace stabilizer_stream;
 
-int main()
+int main(int argc, char **argv)
 {
+    const std::string dir = argc > 1 ? argv[1] : "/tmp"; // (the test passes a private directory)
     constexpr size_t N = 1 << 9;
     std::vector<PsdCascade<N>> dec;
     for (int i = 0; i < 4; ++i)
@@ -152,8 +153,12 @@ int main()
         std::vector<float> xs(total);
         for (auto &v : xs)
             v = (u(rng) - 0.5f) * std::sqrt(12.0f);
-        const std::string path = "/tmp/psd_cpp_mirror_raw.f32";
+        const std::string path = dir + "/psd_cpp_mirror_raw.f32";
         std::FILE *fp = std::fopen(path.c_str(), "wb");
+        if (!fp) {
+            std::printf("cannot write %s\n", path.c_str());
+            return 1;
+        }
         std::fwrite(xs.data(), 4, xs.size(), fp);
         std::fclose(fp);
         SourceOpts so;

@@ -354,13 +354,13 @@ def test_packed_record_rejects_hostile_headers(pkg):
 
 
 @pytest.mark.timeout(900)
-def test_kernels_pass_the_machine_verifier():
+def test_kernels_pass_the_machine_verifier(tmp_path):
     """`make verify` (csrc/Makefile): every kernel TU through the gfx950 backend with LLVM's machine verifier on after
     each pass.  It is the check that names the miscompile round 3 met in one kernel variant (si-form-memory-clauses left
     a truncated live subrange; the allocator then reused the VGPR of a live sample -- DESIGN.md section 4): a restructured
     kernel that trips it again fails HERE, on the CPU, instead of as wrong spectra in one template variant on the GPU."""
     csrc = os.path.join(ROOT, "stabilizer-stream_amd", "csrc")
-    r = subprocess.run(["make", "-j8", "-C", csrc, "verify"], capture_output=True, text=True, timeout=880)
+    r = subprocess.run(["make", "-j8", "-C", csrc, "verify", f"VERIFY_DIR={tmp_path}"], capture_output=True, text=True, timeout=880)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "every kernel TU clean" in r.stdout
 

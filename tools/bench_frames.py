@@ -1,7 +1,7 @@
 """BASELINE config 3: 4-channel dual-iir (AdcDac) frame stream, N=4096, 50 % overlap, one GPU.
 Frames live in host memory (as read from a frame file / UDP); rate = samples of all 4 traces per second."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import __graft_entry__ as entry
 pkg = entry.load_package()

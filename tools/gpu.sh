@@ -6,7 +6,7 @@
 #   tests [pytest args]     pytest -m gpu
 #   allvariants [args]      pytest -m gpu under PSDC_DBG_VARIANT = 0, 1, 2, 3 (every fused launch on the EWMA / FRAMES kernel variants)
 #   smoke                   __graft_entry__.smoke()
-#   bench [bench args]      one bench.py line, condensed
+#   bench [bench args]      one bench.py --full line, condensed
 #   lines "<args>" ...      one condensed bench line per quoted argument string
 #   shapes                  the standard table: every N, detrends, EWMA, multi-channel
 #   stats TAG [bench args]  rocprofv3 --kernel-trace --stats of bench.py  -> gpurun_out/stats/TAG_*
@@ -55,7 +55,7 @@ allvariants)
 smoke)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ;;
 bench)
-  timeout -k 10 900 python bench.py "$@" > "$out/bench.log" 2>&1; rc=$?
+  timeout -k 10 900 python bench.py --full "$@" > "$out/bench.log" 2>&1; rc=$?
   grep '^{' "$out/bench.log" | python -c "$condense" "$*" || tail -20 "$out/bench.log"
   grep '^{' "$out/bench.log" | cut -c1-1500; exit $rc ;;
 lines)
