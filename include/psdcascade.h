@@ -465,6 +465,74 @@ int psdc_fill_noise_device(int device, float *d_x, size_t len, uint64_t seed,
 
 int psdc_profile_read(psdc_handle *h, psdc_profile *out, int reset);
 
+/* ---- cross-spectral density cascade ---------------------------------------------------------------------
+ * The design PsdCascade's doc comment names as its model (src/psd.rs:393, `csdl`): `n_pairs` independent pairs of
+ * real f32 streams (x, y), always fed together with equal lengths.  Per stage a pair is two Psd<N> stages
+ * (src/psd.rs:195-269) in lockstep: the same segmentation, Window<N>, Detrend (applied to each channel's segment
+ * separately), /8 half-band decimation of each channel with the drain of 35 outputs, and lazy stages
+ * (src/psd.rs:445-468) -- a pair has exactly the stages and counts of a PsdCascade fed x alone.  Per bin k <= N/2 a
+ * stage keeps, with the EWMA factor g of src/psd.rs:218-233:
+ *     Sxx[k] = g Sxx[k] + |X[k]|^2,   Syy[k] = g Syy[k] + |Y[k]|^2,   Sxy[k] = g Sxy[k] + conj(X[k]) Y[k]
+ * Sign convention: conj(X) Y, that of scipy.signal.csd(x, y): the transfer function is H1 = Sxy / Sxx, the coherence
+ * |Sxy|^2 / (Sxx Syy).  The read-out is PsdCascade::psd (src/psd.rs:479-543) applied to each of the four real rows
+ * (Sxx, Syy, Re Sxy, Im Sxy) with the same bins, Breaks and 1 / (gain() decimation): Sxx IS the psd() of a
+ * PsdCascade fed x, and y = x gives Sxy == Sxx up to rounding.  The accumulators are f64 on the device.
+ * Sizes: n a power of two 64 ... 4096; Window::hann(), Window::rectangular(), or a caller's table with
+ * (n - overlap) % 8 == 0.  Anything else is PSDC_ERR_ARG (psdc_cross_last_error(NULL) says why).
+ * Stream ordering: an object works on a non-blocking stream of its own.  psdc_cross_process_device copies the samples
+ * on that stream; with `producer_event` (a hipEvent_t recorded behind the producer) the copy waits for it on the
+ * device, without it the producer must have completed.  The caller keeps d_x / d_y unchanged until psdc_cross_sync or a
+ * read-out returns.  Every call restores the caller's current device.  Counts are 64-bit as in psdc_stitch_window.
+ * A process call runs one round of the pipeline: three kernel launches (the segments of every (pair, stage), the
+ * decimators, the fold + stream tails) whatever the depth, as long as a round's job tables fit one launch each: 128
+ * (pair, stage) segment jobs, 320 decimator jobs (two a (pair, stage)), 128 folds and 256 tail carries.  A round with
+ * more -- from about 12 pairs with 10 stages each -- takes one more launch of a kind per table it overflows.  Read-outs
+ * run rounds until no stage has work.
+ * Memory: per (pair, stage) two ping-pong buffers per channel, each sized to the largest call the stage has seen
+ * (x 1.25, never shrunk: a 2^26-sample call leaves about 1.3 GB at stage 0 of its pair), plus 64 MB of pinned host
+ * staging per object. */
+typedef struct psdc_cross psdc_cross;
+/* PsdCascade::<N>::default() (src/psd.rs:408-423) for n_pairs pairs; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_cross *psdc_cross_create(uint32_t n, int window_kind, uint32_t n_pairs, int device);
+/* the same with a caller-built Window<N> (src/psd.rs:12-20), as psdc_create_window */
+psdc_cross *psdc_cross_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap,
+                                     uint32_t n_pairs, int device);
+void psdc_cross_destroy(psdc_cross *h);
+/* back to the state of a fresh object (stages, buffers, settings and statistics) */
+int psdc_cross_reset(psdc_cross *h);
+/* PsdCascade::set_detrend (src/psd.rs:438-443); samples fed before the call are analysed with the old setting */
+int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind);
+/* PsdCascade::set_avg (src/psd.rs:431-436) */
+int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count);
+/* PsdCascade::process (src/psd.rs:456-468) of x and y: host memory (copied through pinned staging) */
+int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float *y, size_t len);
+/* the same from device memory; producer_event: hipEvent_t or NULL (see Stream ordering above) */
+int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
+                              void *producer_event);
+/* run every pending round and wait for the device */
+int psdc_cross_sync(psdc_cross *h);
+/* PsdCascade stages of a pair (src/psd.rs:400) */
+int psdc_cross_num_stages(psdc_cross *h, uint32_t pair);
+/* raw accumulators of one stage (PsdStage::spectrum / count, src/psd.rs:271-287): sxx, syy n/2+1 floats, sxy
+ * 2(n/2+1) floats (re, im); any may be NULL */
+int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat,
+                             float *sxx, float *syy, float *sxy);
+/* PsdCascade::psd (src/psd.rs:479-543) of the four rows: sxx, syy `cap` floats, sxy 2 cap floats (re, im) */
+int psdc_cross_csd(psdc_cross *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                   float *sxx, float *syy, float *sxy, size_t cap, size_t *len,
+                   psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* the stitch of psdc_cross_csd on caller-provided rows (n_stages x 4 x (n/2+1): xx, yy, re, im; stage 0 first):
+ * psdc_stitch_window (src/psd.rs:479-543) on each row.  Pure host code. */
+int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages,
+                      const uint64_t *counts64, const uint32_t *avgs, const uint64_t *pendings,
+                      const float *rows, int keep_overlap,
+                      uint32_t min_count, int keep_transition_band, float *sxx, float *syy, float *sxy,
+                      size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and sample pairs accepted since creation or the last reset of the statistics */
+int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in, int reset);
+/* last error text of an object; with h == NULL, of the calling thread's last failed cross call */
+const char *psdc_cross_last_error(const psdc_cross *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

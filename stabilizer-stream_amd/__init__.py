@@ -307,6 +307,22 @@ def lib():
     f("psdc_stage_get_gain", i32, [H, fp])
     f("psdc_stage_get_buf", i32, [H, fp, sz, C.POINTER(sz)])
     f("psdc_stage_last_error", C.c_char_p, [H])
+    f("psdc_cross_create", H, [u32, i32, u32, i32])
+    f("psdc_cross_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_cross_destroy", None, [H])
+    f("psdc_cross_reset", i32, [H])
+    f("psdc_cross_set_detrend", i32, [H, i32])
+    f("psdc_cross_set_avg", i32, [H, u32, u32])
+    f("psdc_cross_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_cross_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_cross_sync", i32, [H])
+    f("psdc_cross_num_stages", i32, [H, u32])
+    f("psdc_cross_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp, fp])
+    f("psdc_cross_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_cross_stitch", i32, [u32, C.c_float, C.c_float, sz, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp,
+                                 i32, u32, i32, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_cross_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_cross_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -325,6 +341,9 @@ EXPORTS = [
     "psdc_create_window", "psdc_window_get", "psdc_window_table", "psdc_stage_create_window", "psdc_stitch_window",
     "psdc_readout_bytes", "psdc_pack_readout", "psdc_unpack_info", "psdc_unpack_stitch",
     "psdc_pack_init", "psdc_pack_channel", "psdc_pack_pad",
+    "psdc_cross_create", "psdc_cross_create_window", "psdc_cross_destroy", "psdc_cross_reset", "psdc_cross_set_detrend",
+    "psdc_cross_set_avg", "psdc_cross_process", "psdc_cross_process_device", "psdc_cross_sync", "psdc_cross_num_stages",
+    "psdc_cross_stage_spectra", "psdc_cross_csd", "psdc_cross_stitch", "psdc_cross_stats_read", "psdc_cross_last_error",
 ]
 
 
@@ -593,6 +612,161 @@ class PsdCascade:
 
     def close(self):
         self._b.close()
+
+
+def _raise_cross(code, h=None):
+    msg = lib().psdc_cross_last_error(h)
+    raise PsdError(code, msg.decode() if msg else "")
+
+
+class CsdCascadeBank:
+    """`n_pairs` independent cross-spectral cascades (psdc_cross_*): pairs of streams x, y fed together.  Per stage the
+    accumulators Sxx, Syy and Sxy = sum conj(X) Y (scipy.signal.csd's convention: H1 = Sxy / Sxx); the read-out is
+    PsdCascade::psd (src/psd.rs:479-543) applied to each row, so Sxx is the psd() of a PsdCascade fed x."""
+
+    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
+        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_cross_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs,
+                                                       device)
+        else:
+            self._h = self._L.psdc_cross_create(n, int(window), n_pairs, device)
+        if not self._h:
+            msg = self._L.psdc_cross_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_cross_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_cross(rc, self._h)
+        return rc
+
+    def reset(self):
+        self._ck(self._L.psdc_cross_reset(self._h))
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_cross_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_cross_set_avg(self._h, avg.limit, avg.count))
+
+    def process(self, pair, x, y):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        if x.size != y.size:
+            raise PsdError(ERR_ARG, "x and y must have equal lengths")
+        self._ck(self._L.psdc_cross_process(self._h, pair, _fptr(x), _fptr(y), x.size))
+
+    def process_device(self, pair, px, py, length, after=None):
+        """px, py: device addresses of `length` f32 samples each; after: a hipEvent_t handle recorded behind their
+        producer (torch.cuda.Event.cuda_event), or None when the producer has completed.  The samples must stay
+        unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_cross_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
+                                                   C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._L.psdc_cross_sync(self._h))
+
+    def num_stages(self, pair=0):
+        return self._ck(self._L.psdc_cross_num_stages(self._h, pair))
+
+    def stage_spectra(self, pair, stage):
+        """(info, sxx, syy, sxy) of one stage's raw accumulators; sxy complex64."""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        xx, yy, xy = np.empty(b, np.float32), np.empty(b, np.float32), np.empty(2 * b, np.float32)
+        self._ck(self._L.psdc_cross_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(xx), _fptr(yy), _fptr(xy)))
+        info = {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
+        return info, xx, yy, xy.view(np.complex64)
+
+    def csd(self, pair=0, opts=MergeOpts()):
+        """(sxx, syy, sxy complex64, breaks): PsdCascade::psd of each row."""
+        ns = self.num_stages(pair)
+        cap = max(1, ns * (self.n // 2 + 1))
+        xx, yy, xy = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(2 * cap, np.float32)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_cross_csd(self._h, pair, int(opts.keep_overlap), opts.min_count,
+                                        int(opts.keep_transition_band), _fptr(xx), _fptr(yy), _fptr(xy), cap,
+                                        C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        return (xx[:m].copy(), yy[:m].copy(), xy[:2 * m].view(np.complex64).copy(),
+                [Break._from_c(br[i]) for i in range(nb.value)])
+
+    def stats_read(self, reset=False):
+        la, pi = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_cross_stats_read(self._h, C.byref(la), C.byref(pi), int(reset)))
+        return {"launches": la.value, "pairs_in": pi.value}
+
+
+class CsdCascade:
+    """One pair of streams: the cross-spectral form of PsdCascade (src/psd.rs:393 names `csdl` as its model)."""
+
+    def __init__(self, n, window=Window.HANN, device=0):
+        self.n = n
+        self._b = CsdCascadeBank(n, 1, window, device)
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x, y):
+        self._b.process(0, x, y)
+
+    def process_device(self, px, py, length, after=None):
+        self._b.process_device(0, px, py, length, after)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        self._b.reset()
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+def coherence(sxx, syy, sxy):
+    """|Sxy|^2 / (Sxx Syy), NaN where the denominator is zero."""
+    sxx, syy = np.asarray(sxx, np.float64), np.asarray(syy, np.float64)
+    num = np.abs(np.asarray(sxy, np.complex128)) ** 2
+    den = sxx * syy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0, num / np.where(den != 0, den, 1.0), np.nan)
+
+
+def transfer(sxx, sxy):
+    """H1 = Sxy / Sxx (complex), NaN where Sxx is zero."""
+    sxx = np.asarray(sxx, np.float64)
+    sxy = np.asarray(sxy, np.complex128)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(sxx != 0, sxy / np.where(sxx != 0, sxx, 1.0), np.nan + 0j)
 
 
 class Psd:

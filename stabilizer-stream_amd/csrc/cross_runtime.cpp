@@ -1,0 +1,847 @@
+// cross_runtime.cpp -- the cross-spectral density cascade behind psdc_cross_* (include/psdcascade.h).
+//
+// `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
+// (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
+// three accumulators (xx, yy, and the complex xy = sum conj(X) Y as re / im rows) in f64 on the device.
+//
+// A round plans every (pair, stage) at once from the host-side stream positions (plan.h):
+//   1. cross_kernel   the new complete segments of every (pair, stage): partial rows per workgroup
+//   2. hbf_dec8       the /8 decimator of each channel into the next stage's stream (kernels.hip, unchanged)
+//   3. cross_post     fold the partials into the accumulators, carry the stream tails into the other buffer
+// Stage k + 1 consumes what stage k produced in earlier rounds, so a round is three launches whatever the depth and the pair
+// count (more only when a round's job tables overflow a launch).  Read-outs drain: rounds until no stage has work.
+// There is no CPU compute path.
+#include "cross.h"
+#include "host_runtime.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+using namespace psdk;
+
+namespace {
+
+constexpr uint32_t X_MAX_STAGES = 16;
+constexpr uint32_t X_MAX_PAIRS = 65536;
+constexpr size_t STAGING = (size_t)1 << 22; // host-fed samples a channel per pinned staging slot
+
+thread_local std::string x_last_error;
+
+struct XBuf {
+    float *p[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; // [channel][ping-pong]
+    int cur = 0;
+    size_t cap = 0;    // floats per buffer
+    uint64_t base = 0; // absolute stream index of p[c][cur][0] (both channels)
+};
+
+struct XStage {
+    uint64_t total = 0; // samples received (each channel)
+    uint64_t segs = 0;  // segments issued
+    uint64_t dec = 0;   // samples handed to the decimator
+    uint64_t count64 = 0;
+    XBuf buf;
+    double *acc = nullptr; // device [4][n/2 + 1]: xx, yy, re xy, im xy
+};
+
+} // namespace
+
+struct psdc_cross {
+    uint32_t n = 0, n_pairs = 0;
+    int device = 0;
+    Geometry geo;
+    float power = 0.25f, nenbw = 1.5f;
+    int detrend = PSDC_DETREND_NONE;
+    uint32_t avg_limit = 0xFFFFFFFFu, avg_count = 0xFFFFFFFFu;
+    hipStream_t stream = nullptr;
+    // Device-fed samples are copied into stage 0 on a stream of their own, beside the kernels of the round before: the copy of
+    // the samples of round R writes stage-0 buffer regions that only rounds <= R - 2 read (the round before has carried its
+    // tail to the front of the buffer the copy appends to, or left the region behind its stream end alone), so it waits for
+    // round R - 2 (ev_round[R & 1]) and the round waits for it (ev_copy).  A buffer that grows is copied on the compute stream
+    // first (ev_grow).
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_round[2] = {nullptr, nullptr}, ev_copy = nullptr, ev_grow = nullptr;
+    bool round_recorded[2] = {false, false};
+    uint64_t rounds = 0; // rounds enqueued
+    bool grew = false;   // ensure_room replaced a buffer since the flag was cleared
+    float *d_win = nullptr;
+    cf *d_tw = nullptr;
+    std::vector<std::vector<XStage>> pairs;
+    float *d_partial = nullptr;
+    size_t partial_cap = 0;
+    float *h_stage[2] = {nullptr, nullptr}; // pinned staging: [2 channels][STAGING] each
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    bool ev_pending[2] = {false, false};
+    int stage_cur = 0;
+    std::vector<void *> retired; // replaced device buffers, freed at the next sync point
+    bool idle = true;            // every stage drained
+    uint64_t launches = 0, pairs_in = 0;
+    int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
+    std::string err;
+};
+
+namespace {
+
+int xfail(psdc_cross *h, int code, const std::string &msg)
+{
+    if (h)
+        h->err = msg;
+    x_last_error = msg;
+    return code;
+}
+
+#define XCHK(h, expr)                                                                                                  \
+    do {                                                                                                               \
+        hipError_t e_ = (expr);                                                                                        \
+        if (e_ != hipSuccess)                                                                                          \
+            return xfail(h, PSDC_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                       \
+    } while (0)
+
+#define X_ON_DEVICE(h)                                                                                                 \
+    psdrt::DevScope dev_scope_((h)->device);                                                                           \
+    if (dev_scope_.err != hipSuccess)                                                                                  \
+    return xfail(h, PSDC_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(dev_scope_.err))
+
+size_t bins(const psdc_cross *h) { return h->n / 2 + 1; }
+uint32_t cur_avg(const psdc_cross *h, size_t k) { return stage_avg(h->avg_limit, h->avg_count, (unsigned)k); }
+
+// lowest absolute index a stage keeps: the decimator's history, which also covers the next segment
+uint64_t keep_from(const Geometry &g, const XStage &s)
+{
+    if (s.segs == 0)
+        return 0;
+    const uint64_t back = std::max<uint64_t>(g.overlap, HBF_HALO);
+    return s.dec > back ? s.dec - back : 0;
+}
+
+int free_retired(psdc_cross *h)
+{
+    for (void *p : h->retired)
+        XCHK(h, hipFree(p));
+    h->retired.clear();
+    return PSDC_OK;
+}
+
+// room for the stream up to absolute index new_end in the current buffers; growing allocates a new pair of buffers and
+// copies what the stage holds on the stream (no host wait); the old ones are retired
+int ensure_room(psdc_cross *h, XStage &s, uint64_t new_end)
+{
+    const size_t need = (size_t)(new_end - s.buf.base);
+    if (need <= s.buf.cap)
+        return PSDC_OK;
+    const size_t cap = std::max<size_t>(need + need / 4, 4 * (size_t)h->n + 2 * HBF_HALO);
+    XBuf nb;
+    nb.cap = cap;
+    nb.base = s.buf.base;
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 2; ++i)
+            XCHK(h, hipMalloc(&nb.p[c][i], sizeof(float) * cap));
+    const size_t held = (size_t)(s.total - s.buf.base);
+    h->grew = true;
+    for (int c = 0; c < 2; ++c) {
+        if (held)
+            XCHK(h, hipMemcpyAsync(nb.p[c][0], s.buf.p[c][s.buf.cur], sizeof(float) * held, hipMemcpyDeviceToDevice, h->stream));
+        for (int i = 0; i < 2; ++i)
+            if (s.buf.p[c][i])
+                h->retired.push_back(s.buf.p[c][i]);
+    }
+    s.buf = nb;
+    return PSDC_OK;
+}
+
+int add_stage(psdc_cross *h, std::vector<XStage> &st)
+{
+    if (st.size() >= X_MAX_STAGES)
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross: more than 16 stages");
+    XStage s;
+    XCHK(h, hipMalloc(&s.acc, sizeof(double) * 4 * bins(h)));
+    XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * 4 * bins(h), h->stream));
+    st.push_back(s);
+    return PSDC_OK;
+}
+
+int ensure_partial(psdc_cross *h, size_t floats)
+{
+    if (floats <= h->partial_cap)
+        return PSDC_OK;
+    if (h->d_partial)
+        h->retired.push_back(h->d_partial);
+    h->d_partial = nullptr;
+    const size_t cap = floats + floats / 4;
+    XCHK(h, hipMalloc(&h->d_partial, sizeof(float) * cap));
+    h->partial_cap = cap;
+    return PSDC_OK;
+}
+
+struct PlannedCross {
+    CrossJob job;
+    CrossFoldJob fold;
+};
+
+// one pipeline round over every (pair, stage); *did: some stage had work
+int run_round(psdc_cross *h, bool *did)
+{
+    const Geometry &g = h->geo;
+    const int spt = cross_segments_per_tile((int)h->n);
+    std::vector<PlannedCross> cross;
+    std::vector<DecJob> decs;
+    std::vector<CrossTailJob> tails;
+    for (auto &st : h->pairs) {
+        std::vector<uint64_t> tot0(st.size());
+        for (size_t k = 0; k < st.size(); ++k)
+            tot0[k] = st[k].total;
+        for (size_t k = 0; k < st.size(); ++k) {
+            const uint64_t j_new = segments_for(g, tot0[k]);
+            if (j_new <= st[k].segs)
+                continue;
+            XStage &s = st[k];
+            const uint64_t nb = j_new - s.segs;
+            if (nb > (uint64_t)std::numeric_limits<int>::max() / 2)
+                return xfail(h, PSDC_ERR_ARG, "psdc_cross: too many segments in one round");
+            const uint32_t avg = cur_avg(h, k);
+            const EwmaPlan ew = plan_ewma(count_report(s.count64), avg, nb);
+            PlannedCross pc{};
+            CrossJob &cj = pc.job;
+            cj.src[0] = s.buf.p[0][s.buf.cur];
+            cj.src[1] = s.buf.p[1][s.buf.cur];
+            cj.src_base = (long long)s.buf.base;
+            cj.seg0 = (long long)s.segs;
+            cj.log2_gamma = ew.gamma > 0.0f ? std::log2((double)ew.gamma) : -std::numeric_limits<double>::infinity();
+            cj.nseg = (int)nb;
+            cj.ntiles = (int)((nb + spt - 1) / spt);
+            cj.step0 = 1;
+            cj.nb = (int)ew.nb;
+            cj.is_m1 = (int)std::min<int64_t>(ew.i_s - 1, std::numeric_limits<int>::max());
+            cj.ewma = ew.ewma ? 1 : 0;
+            pc.fold.acc = s.acc;
+            pc.fold.g_total = ew.g_total;
+            cross.push_back(pc);
+            // decimator: samples [dec, p_new) of each channel, outputs m >= drain land in stage k + 1
+            const uint64_t p_new = decimated_prefix(g, j_new);
+            const uint64_t e_old = emitted_for(g, s.dec), e_new = emitted_for(g, p_new);
+            if (e_new > e_old) {
+                if (k + 1 == st.size()) {
+                    int rc = add_stage(h, st);
+                    if (rc)
+                        return rc;
+                    tot0.push_back(0); // (a stage made in this round has no work in it)
+                }
+                XStage &s0 = st[k], &s1 = st[k + 1];
+                int rc = ensure_room(h, s1, s1.total + (e_new - e_old));
+                if (rc)
+                    return rc;
+                const uint64_t m0 = std::max<uint64_t>(s0.dec >> 3, g.drain), m1 = p_new >> 3;
+                for (int c = 0; c < 2; ++c) {
+                    DecJob dj{};
+                    dj.src = s0.buf.p[c][s0.buf.cur];
+                    dj.src_base = (long long)s0.buf.base;
+                    dj.m0 = (long long)m0;
+                    dj.nout = (int)(m1 - m0);
+                    dj.dst = s1.buf.p[c][s1.buf.cur];
+                    dj.dst_base = (long long)s1.buf.base;
+                    decs.push_back(dj);
+                }
+                s1.total += e_new - e_old;
+            }
+            XStage &sk = st[k];
+            sk.segs = j_new;
+            sk.dec = p_new;
+            sk.count64 = count_after64(sk.count64, avg, nb);
+        }
+        // stream tails: what each stage still needs moves to the front of its other buffers
+        for (auto &s : st) {
+            const uint64_t keep = keep_from(g, s);
+            if (keep <= s.buf.base)
+                continue;
+            const uint64_t count = s.total - keep;
+            if (count) {
+                for (int c = 0; c < 2; ++c) {
+                    CrossTailJob tj{};
+                    tj.src = s.buf.p[c][s.buf.cur] + (keep - s.buf.base);
+                    tj.dst = s.buf.p[c][s.buf.cur ^ 1];
+                    tj.count = (long long)count;
+                    tj.nblocks = (int)((count + CROSS_TAIL_CHUNK - 1) / CROSS_TAIL_CHUNK);
+                    tails.push_back(tj);
+                }
+                s.buf.cur ^= 1;
+            }
+            s.buf.base = keep;
+        }
+    }
+    *did = !cross.empty();
+    if (cross.empty() && decs.empty() && tails.empty())
+        return PSDC_OK;
+
+    // partial slab and workgroups: every workgroup of a launch walks the same number of tiles, and the launch's workgroups are
+    // about what the device holds at once (a job of few tiles next to one of many would otherwise make some workgroups walk
+    // one tile more than the rest: a round with the decimated stages read 240 us where stage 0 alone read 160)
+    const size_t rows = 4 * bins(h);
+    std::vector<int> nblk(cross.size());
+    size_t slab = 0;
+    for (size_t b0 = 0; b0 < cross.size(); b0 += CROSS_MAX_JOBS) {
+        const size_t b1 = std::min(cross.size(), b0 + CROSS_MAX_JOBS);
+        int64_t tiles = 0;
+        for (size_t i = b0; i < b1; ++i)
+            tiles += cross[i].job.ntiles;
+        const int64_t per = (tiles + h->resident - 1) / h->resident; // tiles a workgroup
+        for (size_t i = b0; i < b1; ++i) {
+            const int64_t t = cross[i].job.ntiles;
+            nblk[i] = (int)((t + per - 1) / per);
+            slab += (size_t)nblk[i] * rows;
+        }
+    }
+    int rc = ensure_partial(h, slab);
+    if (rc)
+        return rc;
+    size_t off = 0;
+    for (size_t b0 = 0; b0 < cross.size(); b0 += CROSS_MAX_JOBS) {
+        CrossBatch *cb = new CrossBatch();
+        cb->hop = (int)g.hop;
+        cb->detrend = h->detrend;
+        for (size_t i = b0; i < std::min(cross.size(), b0 + CROSS_MAX_JOBS); ++i) {
+            CrossJob &cj = cross[i].job;
+            cj.partial = h->d_partial + off;
+            cj.nblocks = nblk[i];
+            cj.block_begin = cb->nblocks;
+            cross[i].fold.partial = cj.partial;
+            cross[i].fold.nparts = nblk[i];
+            off += (size_t)nblk[i] * rows;
+            cb->jobs[cb->njobs++] = cj;
+            cb->nblocks += nblk[i];
+        }
+        hipError_t e = launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
+        delete cb;
+        XCHK(h, e);
+        ++h->launches;
+    }
+    for (size_t b0 = 0; b0 < decs.size(); b0 += MAX_JOBS) {
+        DecBatch *db = new DecBatch();
+        db->drain = (int)g.drain;
+        for (size_t i = b0; i < std::min(decs.size(), b0 + MAX_JOBS); ++i) {
+            DecJob dj = decs[i];
+            dj.tile_begin = db->ntiles;
+            db->jobs[db->njobs++] = dj;
+            db->ntiles += (dj.nout + DEC_TILE - 1) / DEC_TILE;
+        }
+        hipError_t e = launch_dec(*db, h->stream);
+        const bool any = db->ntiles > 0;
+        delete db;
+        XCHK(h, e);
+        if (any)
+            ++h->launches;
+    }
+    size_t fi = 0, ti = 0;
+    while (fi < cross.size() || ti < tails.size()) {
+        CrossPostBatch *pb = new CrossPostBatch();
+        pb->nbins = (int)bins(h);
+        pb->fold_xb = cross_fold_blocks((int)bins(h));
+        for (; fi < cross.size() && pb->nfold < CROSS_MAX_FOLD; ++fi)
+            pb->fold[pb->nfold++] = cross[fi].fold;
+        for (; ti < tails.size() && pb->ntail < CROSS_MAX_TAIL; ++ti) {
+            CrossTailJob tj = tails[ti];
+            tj.block_begin = pb->tail_blocks;
+            pb->tail_blocks += tj.nblocks;
+            pb->tail[pb->ntail++] = tj;
+        }
+        hipError_t e = launch_cross_post(*pb, h->stream);
+        delete pb;
+        XCHK(h, e);
+        ++h->launches;
+    }
+    const int slot = (int)(h->rounds & 1);
+    XCHK(h, hipEventRecord(h->ev_round[slot], h->stream));
+    h->round_recorded[slot] = true;
+    ++h->rounds;
+    return PSDC_OK;
+}
+
+int drain(psdc_cross *h)
+{
+    if (h->idle)
+        return PSDC_OK;
+    for (;;) {
+        bool did = false;
+        int rc = run_round(h, &did);
+        if (rc)
+            return rc;
+        if (!did)
+            break;
+    }
+    h->idle = true;
+    return PSDC_OK;
+}
+
+int sync_all(psdc_cross *h)
+{
+    XCHK(h, hipStreamSynchronize(h->copy_stream));
+    XCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 2; ++i)
+        h->ev_pending[i] = false;
+    return free_retired(h);
+}
+
+int check_pair(psdc_cross *h, uint32_t pair)
+{
+    if (pair >= h->n_pairs)
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross: pair " + std::to_string(pair) + " out of range (n_pairs " +
+                                          std::to_string(h->n_pairs) + ")");
+    return PSDC_OK;
+}
+
+// stage 0 of a pair takes len more samples of each channel: room for them, and where they go
+int stage0_room(psdc_cross *h, uint32_t pair, size_t len, XStage **out)
+{
+    auto &st = h->pairs[pair];
+    if (st.empty()) {
+        int rc = add_stage(h, st);
+        if (rc)
+            return rc;
+    }
+    int rc = ensure_room(h, st[0], st[0].total + len);
+    if (rc)
+        return rc;
+    *out = &st[0];
+    return PSDC_OK;
+}
+
+void free_all(psdc_cross *h)
+{
+    (void)hipStreamSynchronize(h->copy_stream);
+    (void)hipStreamSynchronize(h->stream);
+    for (auto &st : h->pairs)
+        for (auto &s : st) {
+            for (int c = 0; c < 2; ++c)
+                for (int i = 0; i < 2; ++i)
+                    if (s.buf.p[c][i])
+                        (void)hipFree(s.buf.p[c][i]);
+            if (s.acc)
+                (void)hipFree(s.acc);
+        }
+    h->pairs.assign(h->n_pairs, {});
+    for (void *p : h->retired)
+        (void)hipFree(p);
+    h->retired.clear();
+    if (h->d_partial)
+        (void)hipFree(h->d_partial);
+    h->d_partial = nullptr;
+    h->partial_cap = 0;
+    h->idle = true;
+}
+
+const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs)
+{
+    if (n < 64 || n > 4096 || (n & (n - 1)) != 0)
+        return "n must be a power of two in [64, 4096]";
+    if (!win)
+        return "null window table";
+    if (overlap >= n || (n - overlap) % 8 != 0)
+        return "the window's overlap must be < n with (n - overlap) % 8 == 0";
+    if (!(power > 0.0f) || !(nenbw > 0.0f))
+        return "window power and nenbw must be > 0";
+    if (n_pairs < 1 || n_pairs > X_MAX_PAIRS)
+        return "n_pairs must be in [1, 65536]";
+    return nullptr;
+}
+
+psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, int device,
+                        const char *who)
+{
+    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs)) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
+        return nullptr;
+    }
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": no HIP device (there is no CPU fallback): " +
+                                            (e != hipSuccess ? hipGetErrorString(e) : "device count 0"));
+        return nullptr;
+    }
+    if (device < 0 || device >= ndev) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": device " + std::to_string(device) + " out of range");
+        return nullptr;
+    }
+    psdrt::DevScope scope(device);
+    if (scope.err != hipSuccess) {
+        xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": hipSetDevice: " + hipGetErrorString(scope.err));
+        return nullptr;
+    }
+    psdc_cross *h = new psdc_cross();
+    h->n = n;
+    h->n_pairs = n_pairs;
+    h->device = device;
+    h->geo.n = n;
+    h->geo.overlap = (uint32_t)overlap;
+    h->geo.hop = n - (uint32_t)overlap;
+    h->geo.drain = 35;
+    h->power = power;
+    h->nenbw = nenbw;
+    h->pairs.assign(n_pairs, {});
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
+        // twice what is resident at one wavefront a SIMD (the kernel's registers allow no more); once and twice read the same
+        // end to end within the noise of tools/cross_probe.py (N = 1024, one pair: 43.9 against 45.4 G pairs/s)
+        h->resident = std::max<int64_t>(1, 2 * (int64_t)cus * 4 * 64 / cross_block_threads((int)n));
+    std::vector<cf> tw(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        const double a = -2.0 * M_PI * (double)j / (double)n;
+        tw[j] = {(float)cos(a), (float)sin(a)};
+    }
+    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&h->ev_round[0], hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&h->ev_round[1], hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&h->ev_grow, hipEventDisableTiming) == hipSuccess &&
+              hipMalloc(&h->d_win, sizeof(float) * n) == hipSuccess && hipMalloc(&h->d_tw, sizeof(cf) * n) == hipSuccess &&
+              hipMemcpy(h->d_win, win, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(h->d_tw, tw.data(), sizeof(cf) * n, hipMemcpyHostToDevice) == hipSuccess;
+    for (int i = 0; ok && i < 2; ++i)
+        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * 2 * STAGING) == hipSuccess &&
+             hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": device allocation failed");
+        psdc_cross_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+} // namespace
+
+extern "C" {
+
+psdc_cross *psdc_cross_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                     int device)
+{
+    return create_impl(n, win, power, nenbw, overlap, n_pairs, device, "psdc_cross_create_window");
+}
+
+psdc_cross *psdc_cross_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    psdrt::WindowConsts wc{};
+    if (window_kind == PSDC_WINDOW_CUSTOM || !psdrt::window_consts(n, window_kind, &wc)) {
+        xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_create: window_kind must be PSDC_WINDOW_HANN or PSDC_WINDOW_RECTANGULAR");
+        return nullptr;
+    }
+    if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
+        xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_create: n must be a power of two in [64, 4096]");
+        return nullptr;
+    }
+    std::vector<float> win(n);
+    psdrt::window_weights(n, window_kind, win.data());
+    return create_impl(n, win.data(), wc.power, wc.nenbw, wc.overlap, n_pairs, device, "psdc_cross_create");
+}
+
+void psdc_cross_destroy(psdc_cross *h)
+{
+    if (!h)
+        return;
+    psdrt::DevScope scope(h->device);
+    if (h->stream && h->copy_stream)
+        free_all(h);
+    for (int i = 0; i < 2; ++i) {
+        if (h->h_stage[i])
+            (void)hipHostFree(h->h_stage[i]);
+        if (h->stage_ev[i])
+            (void)hipEventDestroy(h->stage_ev[i]);
+    }
+    if (h->d_win)
+        (void)hipFree(h->d_win);
+    if (h->d_tw)
+        (void)hipFree(h->d_tw);
+    for (hipEvent_t e : {h->ev_round[0], h->ev_round[1], h->ev_copy, h->ev_grow})
+        if (e)
+            (void)hipEventDestroy(e);
+    if (h->copy_stream)
+        (void)hipStreamDestroy(h->copy_stream);
+    if (h->stream)
+        (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+#define X_HANDLE(h, who)                                                                                               \
+    if (!(h))                                                                                                          \
+    return xfail(nullptr, PSDC_ERR_ARG, who ": null handle")
+
+int psdc_cross_reset(psdc_cross *h)
+{
+    X_HANDLE(h, "psdc_cross_reset");
+    X_ON_DEVICE(h);
+    // everything the object made since it was created goes: stages, buffers, partial slab, counters
+    free_all(h);
+    h->detrend = PSDC_DETREND_NONE;
+    h->avg_limit = h->avg_count = 0xFFFFFFFFu;
+    h->stage_cur = 0;
+    h->ev_pending[0] = h->ev_pending[1] = false;
+    h->launches = h->pairs_in = 0;
+    h->rounds = 0;
+    h->round_recorded[0] = h->round_recorded[1] = false;
+    return PSDC_OK;
+}
+
+int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind)
+{
+    X_HANDLE(h, "psdc_cross_set_detrend");
+    if (detrend_kind == PSDC_DETREND_LINEAR)
+        return xfail(h, PSDC_ERR_UNIMPLEMENTED, "psdc_cross_set_detrend: Detrend::Linear is unimplemented (src/psd.rs:110)");
+    if (detrend_kind < PSDC_DETREND_NONE || detrend_kind > PSDC_DETREND_MEAN)
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross_set_detrend: unknown detrend kind");
+    X_ON_DEVICE(h);
+    int rc = drain(h); // segments already fed are analysed with the setting they were fed under
+    if (rc)
+        return rc;
+    h->detrend = detrend_kind;
+    return PSDC_OK;
+}
+
+int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count)
+{
+    X_HANDLE(h, "psdc_cross_set_avg");
+    X_ON_DEVICE(h);
+    int rc = drain(h);
+    if (rc)
+        return rc;
+    h->avg_limit = limit;
+    h->avg_count = count;
+    return PSDC_OK;
+}
+
+int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float *y, size_t len)
+{
+    X_HANDLE(h, "psdc_cross_process");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    if (!x || !y)
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross_process: null sample pointer");
+    X_ON_DEVICE(h);
+    XStage *s = nullptr;
+    if ((rc = stage0_room(h, pair, len, &s)))
+        return rc;
+    for (size_t done = 0; done < len;) {
+        const size_t m = std::min(STAGING, len - done);
+        const int slot = h->stage_cur;
+        if (h->ev_pending[slot])
+            XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+        float *stg = h->h_stage[slot];
+        memcpy(stg, x + done, sizeof(float) * m);
+        memcpy(stg + STAGING, y + done, sizeof(float) * m);
+        const size_t at = (size_t)(s->total + done - s->buf.base);
+        for (int c = 0; c < 2; ++c)
+            XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, stg + c * STAGING, sizeof(float) * m, hipMemcpyHostToDevice,
+                                   h->stream));
+        XCHK(h, hipEventRecord(h->stage_ev[slot], h->stream));
+        h->ev_pending[slot] = true;
+        h->stage_cur ^= 1;
+        done += m;
+    }
+    s->total += len;
+    h->pairs_in += len;
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
+int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
+                              void *producer_event)
+{
+    X_HANDLE(h, "psdc_cross_process_device");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    if (!d_x || !d_y)
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross_process_device: null sample pointer");
+    X_ON_DEVICE(h);
+    if (producer_event)
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    XStage *s = nullptr;
+    h->grew = false;
+    if ((rc = stage0_room(h, pair, len, &s)))
+        return rc;
+    if (h->grew) { // the held samples move to the new buffers on the compute stream: the copy goes behind them
+        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+    }
+    const int slot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
+    if (h->round_recorded[slot])
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
+    const size_t at = (size_t)(s->total - s->buf.base);
+    XCHK(h, hipMemcpyAsync(s->buf.p[0][s->buf.cur] + at, d_x, sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    XCHK(h, hipMemcpyAsync(s->buf.p[1][s->buf.cur] + at, d_y, sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+    s->total += len;
+    h->pairs_in += len;
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
+int psdc_cross_sync(psdc_cross *h)
+{
+    X_HANDLE(h, "psdc_cross_sync");
+    X_ON_DEVICE(h);
+    int rc = drain(h);
+    if (rc)
+        return rc;
+    return sync_all(h);
+}
+
+int psdc_cross_num_stages(psdc_cross *h, uint32_t pair)
+{
+    X_HANDLE(h, "psdc_cross_num_stages");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    if ((rc = drain(h)))
+        return rc;
+    return (int)h->pairs[pair].size();
+}
+
+int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *sxx, float *syy,
+                             float *sxy)
+{
+    X_HANDLE(h, "psdc_cross_stage_spectra");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    if ((rc = drain(h)))
+        return rc;
+    auto &st = h->pairs[pair];
+    if (stage >= st.size())
+        return xfail(h, PSDC_ERR_ARG, "psdc_cross_stage_spectra: stage " + std::to_string(stage) + " out of range (" +
+                                          std::to_string(st.size()) + " stages)");
+    const XStage &s = st[stage];
+    if (stat) {
+        const uint32_t c = count_report(s.count64);
+        stat->count = c;
+        stat->avg = cur_avg(h, stage);
+        stat->pending = pending_for(h->geo, s.total);
+        stat->processed = (uint64_t)h->n * c - (uint64_t)h->geo.overlap * (c ? c - 1 : 0);
+    }
+    if (sxx || syy || sxy) {
+        if ((rc = sync_all(h)))
+            return rc;
+        const size_t b = bins(h);
+        std::vector<double> acc(4 * b);
+        XCHK(h, hipMemcpy(acc.data(), s.acc, sizeof(double) * 4 * b, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < b; ++k) {
+            if (sxx)
+                sxx[k] = (float)acc[k];
+            if (syy)
+                syy[k] = (float)acc[b + k];
+            if (sxy) {
+                sxy[2 * k] = (float)acc[2 * b + k];
+                sxy[2 * k + 1] = (float)acc[3 * b + k];
+            }
+        }
+    }
+    return PSDC_OK;
+}
+
+int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
+                      const uint32_t *avgs, const uint64_t *pendings, const float *rows, int keep_overlap, uint32_t min_count,
+                      int keep_transition_band, float *sxx, float *syy, float *sxy, size_t cap, size_t *len,
+                      psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    if (n < 2 || overlap >= n || n_stages > 20)
+        return xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_stitch: bad arguments");
+    if (n_stages && (!counts64 || !avgs || !pendings || !rows))
+        return xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_stitch: null input");
+    const size_t b = n / 2 + 1;
+    // the four rows of every stage as four spectra slabs, each stitched exactly as PsdCascade::psd
+    std::vector<float> sp[4];
+    for (int r = 0; r < 4; ++r) {
+        sp[r].resize(std::max<size_t>(1, (size_t)n_stages * b));
+        for (uint32_t i = 0; i < n_stages; ++i)
+            memcpy(&sp[r][(size_t)i * b], rows + ((size_t)i * 4 + r) * b, sizeof(float) * b);
+    }
+    std::vector<float> re(cap ? cap : 1), im(cap ? cap : 1);
+    float *outs[4] = {sxx, syy, sxy ? re.data() : nullptr, sxy ? im.data() : nullptr};
+    size_t plen = 0;
+    for (int r = 0; r < 4; ++r) {
+        size_t l = 0, nb = 0;
+        int rc = psdc_stitch_window(n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, sp[r].data(), keep_overlap,
+                                    min_count, keep_transition_band, outs[r], outs[r] ? cap : 0, &l, r == 0 ? breaks : nullptr,
+                                    r == 0 ? breaks_cap : 0, &nb);
+        if (rc == PSDC_ERR_CAPACITY)
+            return xfail(nullptr, rc, "psdc_cross_stitch: output too small");
+        if (rc)
+            return xfail(nullptr, rc, std::string("psdc_cross_stitch: ") + psdc_last_error(nullptr));
+        if (r == 0) {
+            plen = l;
+            if (n_breaks)
+                *n_breaks = nb;
+            if (breaks && nb > breaks_cap)
+                return xfail(nullptr, PSDC_ERR_CAPACITY, "psdc_cross_stitch: breaks output too small");
+        }
+    }
+    if ((sxx || syy || sxy) && plen > cap)
+        return xfail(nullptr, PSDC_ERR_CAPACITY, "psdc_cross_stitch: output too small");
+    if (sxy)
+        for (size_t k = 0; k < plen; ++k) {
+            sxy[2 * k] = re[k];
+            sxy[2 * k + 1] = im[k];
+        }
+    if (len)
+        *len = plen;
+    return PSDC_OK;
+}
+
+int psdc_cross_csd(psdc_cross *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *sxx,
+                   float *syy, float *sxy, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    X_HANDLE(h, "psdc_cross_csd");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    if ((rc = drain(h)) || (rc = sync_all(h)))
+        return rc;
+    const auto &st = h->pairs[pair];
+    const uint32_t ns = (uint32_t)st.size();
+    const size_t b = bins(h);
+    std::vector<uint64_t> c64(std::max<uint32_t>(ns, 1)), pend(std::max<uint32_t>(ns, 1));
+    std::vector<uint32_t> avgs(std::max<uint32_t>(ns, 1));
+    std::vector<double> acc(4 * b);
+    std::vector<float> rows(std::max<size_t>(1, (size_t)ns * 4 * b));
+    for (uint32_t i = 0; i < ns; ++i) {
+        c64[i] = st[i].count64;
+        pend[i] = pending_for(h->geo, st[i].total);
+        avgs[i] = cur_avg(h, i);
+        XCHK(h, hipMemcpy(acc.data(), st[i].acc, sizeof(double) * 4 * b, hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < 4 * b; ++e)
+            rows[(size_t)i * 4 * b + e] = (float)acc[e];
+    }
+    rc = psdc_cross_stitch(h->n, h->power, h->nenbw, h->geo.overlap, ns, c64.data(), avgs.data(), pend.data(), rows.data(),
+                           keep_overlap, min_count, keep_transition_band, sxx, syy, sxy, cap, len, breaks, breaks_cap, n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    return PSDC_OK;
+}
+
+int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    X_HANDLE(h, "psdc_cross_stats_read");
+    if (launches)
+        *launches = h->launches;
+    if (pairs_in)
+        *pairs_in = h->pairs_in;
+    if (reset)
+        h->launches = h->pairs_in = 0;
+    return PSDC_OK;
+}
+
+const char *psdc_cross_last_error(const psdc_cross *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+} // extern "C"

@@ -1,0 +1,227 @@
+"""Cross-spectral density cascade (psdc_cross_*): the parts that run without a GPU.
+
+The restatement below is the yardstick of tests/test_gpu_cross.py: a cross cascade written out from the oracle's own
+pieces (detrend_apply, fft_forward, hbf_dec8) and the closed-form stage lengths.  Its Sxx is held to the oracle's f64
+PsdCascade here, which is what makes its Sxy trustworthy there.
+"""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+U32_MAX = 0xFFFFFFFF
+DRAIN = 35
+
+
+def _window(ora, n, window):
+    """(win f64, power, nenbw, overlap, oracle kind or None) of "hann" / "rect" / (win, power, nenbw, overlap)"""
+    if isinstance(window, str):
+        w, p, e, ov = ora.window(n, window, "f32")
+        return np.asarray(w, np.float64), p, e, ov, window
+    w, p, e, ov = window
+    return np.asarray(w, np.float32).astype(np.float64), p, e, ov, None
+
+
+def restate(ora, x, y, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64"):
+    """Cross cascade of the streams x, y: per stage dict(count, avg, pending, sxx, syy, sxy complex), stage 0 first.
+    prec "f64": truth; "f32": the reference's arithmetic (f32 detrend / FFT / decimator, f32 accumulation)."""
+    win, _, _, overlap, kind = _window(ora, n, window)
+    hop = n - overlap
+    h = n // 2 + 1
+    ft = np.float64 if prec == "f64" else np.float32
+    ct = np.complex128 if prec == "f64" else np.complex64
+    xs, ys = np.asarray(x, np.float32), np.asarray(y, np.float32)
+    stages = []
+    k = 0
+    while xs.size:
+        nseg = 0 if xs.size < n else 1 + (xs.size - n) // hop
+        sh = 3 * k
+        a = min((avg[1] >> sh) if sh < 32 else 0, avg[0])
+        sxx, syy, sxy = np.zeros(h, ft), np.zeros(h, ft), np.zeros(h, ct)
+        count = 0
+
+        def spec(seg):
+            if kind is not None:
+                c = ora.detrend_apply(seg, detrend, kind, prec)
+            else:
+                c = ora.detrend_apply(seg, detrend, "rect", prec) * win.astype(ft)
+            return ora.fft_forward(c.astype(ct), prec)[:h].astype(ct)
+
+        for j in range(nseg):
+            X, Y = spec(xs[j * hop:j * hop + n]), spec(ys[j * hop:j * hop + n])
+            g = 1.0
+            if count > a:
+                g = float(np.float32(a) / np.float32(count))  # src/psd.rs:220: defined in f32
+                count = a
+            count += 1
+            sxx = ft(g) * sxx + (X.real * X.real + X.imag * X.imag).astype(ft)
+            syy = ft(g) * syy + (Y.real * Y.real + Y.imag * Y.imag).astype(ft)
+            sxy = ft(g) * sxy + (np.conj(X) * Y).astype(ct)
+        pending = xs.size if nseg == 0 else xs.size - nseg * hop
+        stages.append(dict(count=count, avg=a, pending=pending, sxx=sxx, syy=syy, sxy=sxy))
+        p = nseg * hop + overlap if nseg else 0
+        xs = ora.hbf_dec8(xs[:p], prec)[DRAIN:].astype(ft)  # (the f64 oracle carries its stages in f64)
+        ys = ora.hbf_dec8(ys[:p], prec)[DRAIN:].astype(ft)
+        k += 1
+    return stages
+
+
+def stitch_rows(pkg, n, window, stages, opts):
+    """The four rows of a restatement through psdc_cross_stitch: (sxx, syy, sxy, breaks)."""
+    wt = window if isinstance(window, pkg.WindowTable) else pkg.WindowTable._kind(n, window)
+    return cross_stitch(pkg, n, wt, [s["count"] for s in stages], [s["avg"] for s in stages],
+                        [s["pending"] for s in stages],
+                        np.stack([np.stack([s["sxx"], s["syy"], s["sxy"].real, s["sxy"].imag]) for s in stages])
+                        if stages else np.zeros((0, 4, n // 2 + 1)), opts)
+
+
+def cross_stitch(pkg, n, wt, counts, avgs, pendings, rows, opts):
+    import ctypes as C
+    L = pkg.lib()
+    ns = len(counts)
+    h = n // 2 + 1
+    c64 = (C.c_uint64 * max(1, ns))(*[int(c) for c in counts])
+    aa = (C.c_uint32 * max(1, ns))(*[int(a) for a in avgs])
+    pp = (C.c_uint64 * max(1, ns))(*[int(p) for p in pendings])
+    r = np.ascontiguousarray(rows, dtype=np.float32).reshape(max(1, ns) if ns else 1, -1) if ns else np.zeros(4 * h, np.float32)
+    cap = max(1, ns * h)
+    xx, yy, xy = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(2 * cap, np.float32)
+    br = (pkg._CBreak * max(1, ns))()
+    ln, nb = C.c_size_t(), C.c_size_t()
+    fp = pkg._fptr
+    rc = L.psdc_cross_stitch(n, wt.power, wt.nenbw, wt.overlap, ns, c64, aa, pp, fp(r), int(opts.keep_overlap),
+                             opts.min_count, int(opts.keep_transition_band), fp(xx), fp(yy), fp(xy), cap, C.byref(ln), br, ns,
+                             C.byref(nb))
+    assert rc == 0, L.psdc_cross_last_error(None)
+    m = ln.value
+    return xx[:m].copy(), yy[:m].copy(), xy[:2 * m].view(np.complex64).copy(), [pkg.Break._from_c(br[i]) for i in range(nb.value)]
+
+
+CROSS_SYMBOLS = ["psdc_cross_create", "psdc_cross_create_window", "psdc_cross_destroy", "psdc_cross_reset",
+                 "psdc_cross_set_detrend", "psdc_cross_set_avg", "psdc_cross_process", "psdc_cross_process_device",
+                 "psdc_cross_sync", "psdc_cross_num_stages", "psdc_cross_stage_spectra", "psdc_cross_csd",
+                 "psdc_cross_stitch", "psdc_cross_stats_read", "psdc_cross_last_error"]
+
+
+def test_cross_exports(pkg):
+    hdr = open(os.path.join(ROOT, "include", "psdcascade.h")).read()
+    declared = set(re.findall(r"\b(psdc_cross_[a-z0-9_]+)\s*\(", hdr))
+    assert declared == set(CROSS_SYMBOLS)
+    out = subprocess.run(["nm", "-D", "--defined-only", pkg.LIB_PATH], capture_output=True, text=True).stdout
+    exported = set(re.findall(r" T (psdc_cross_[a-z0-9_]+)", out))
+    assert exported == declared
+    assert declared <= set(pkg.EXPORTS)
+    assert "conj(X) Y" in hdr and "scipy.signal.csd" in hdr  # the sign convention is written down
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_cross_stitch_exact(pkg, seed):
+    """psdc_cross_stitch == psdc_stitch_window on each row, bit for bit, Breaks field by field."""
+    rng = np.random.default_rng(seed)
+    n = int(rng.choice([64, 256, 1024, 4096]))
+    h = n // 2 + 1
+    wt = pkg.WindowTable.hann(n) if seed % 2 == 0 else pkg.WindowTable.rectangular(n)
+    ns = int(rng.integers(1, 9))
+    counts = [int(c) for c in rng.integers(0, 5000, ns)]
+    if seed == 5:
+        counts[0] = (1 << 33) + 7  # 64-bit counts
+    avgs = [int(a) for a in rng.integers(1, 1 << 20, ns)]
+    pend = [int(p) for p in rng.integers(0, n, ns)]
+    rows = rng.standard_normal((ns, 4, h)).astype(np.float32)
+    rows[:, :2] = np.abs(rows[:, :2])
+    opts = pkg.MergeOpts(keep_overlap=bool(rng.integers(2)), min_count=int(rng.integers(0, 3000)),
+                         keep_transition_band=bool(rng.integers(2)))
+    xx, yy, xy, br = cross_stitch(pkg, n, wt, counts, avgs, pend, rows, opts)
+    for r, got in ((0, xx), (1, yy), (2, xy.real.copy()), (3, xy.imag.copy())):
+        want, wbr = pkg.stitch(n, counts, avgs, pend, rows[:, r], opts, window=wt)
+        assert got.tobytes() == want.tobytes(), r
+        assert br == wbr
+
+
+def test_cross_argument_errors(pkg):
+    import ctypes as C
+    L = pkg.lib()
+    for n in (1000, 32, 8192, 0):
+        with pytest.raises(pkg.PsdError) as e:
+            pkg.CsdCascadeBank(n, 1)
+        assert e.value.code == pkg.ERR_ARG and "power of two in [64, 4096]" in str(e.value)
+    w = np.ones(256, np.float32)
+    for ov, msg in ((4, "overlap"), (256, "overlap")):
+        h = L.psdc_cross_create_window(256, pkg._fptr(w), 1.0, 1.0, ov, 1, 0)
+        assert not h and msg in L.psdc_cross_last_error(None).decode()
+    assert not L.psdc_cross_create_window(256, None, 1.0, 1.0, 0, 1, 0)
+    assert "null window" in L.psdc_cross_last_error(None).decode()
+    assert not L.psdc_cross_create(256, 1, 0, 0)
+    assert "n_pairs" in L.psdc_cross_last_error(None).decode()
+    # null handles and pointers
+    assert L.psdc_cross_process(None, 0, None, None, 4) == pkg.ERR_ARG
+    assert "null handle" in L.psdc_cross_last_error(None).decode()
+    assert L.psdc_cross_sync(None) == pkg.ERR_ARG
+    assert L.psdc_cross_stitch(64, 1.0, 1.0, 0, 2, None, None, None, None, 0, 1, 0, None, None, None, 0, None, None, 0,
+                               None) == pkg.ERR_ARG
+    assert "null input" in L.psdc_cross_last_error(None).decode()
+    assert L.psdc_cross_stitch(64, 1.0, 1.0, 64, 0, None, None, None, None, 0, 1, 0, None, None, None, 0, None, None, 0,
+                               None) == pkg.ERR_ARG
+    L.psdc_cross_destroy(None)
+    st = C.c_uint64()
+    assert L.psdc_cross_stats_read(None, C.byref(st), None, 0) == pkg.ERR_ARG
+
+
+def test_cross_no_gpu_fails_loudly(pkg):
+    from conftest import has_gpu
+    if has_gpu():
+        pytest.skip("a HIP device is visible")
+    with pytest.raises(pkg.PsdError) as e:
+        pkg.CsdCascade(1024)
+    assert e.value.code == pkg.ERR_DEVICE and "no CPU fallback" in str(e.value)
+
+
+def _noise(n, seed):
+    return np.random.default_rng(seed).standard_normal(n).astype(np.float32)
+
+
+@pytest.mark.parametrize("n,window,detrend,avg,length", [
+    (64, "hann", "none", None, 40_000),
+    (128, "rect", "mean", None, 30_000),
+    (256, "hann", "span", (U32_MAX, 500), 60_000),
+    (64, "custom", "midpoint", (40, U32_MAX), 30_000),
+])
+def test_restatement_sxx_is_the_oracle(pkg, ora, n, window, detrend, avg, length):
+    """The restatement's Sxx (and, fed y, Syy) is the oracle's f64 PsdCascade to 1e-12; counts and pendings equal.
+    (A check of the yardstick, not of the library: it uses the oracle alone and so passes without the feature.)"""
+    x = _noise(length, n)
+    y = (0.3 * x + _noise(length, n + 1)).astype(np.float32)
+    if window == "custom":
+        wt = pkg.WindowTable.hann(n)
+        win = (np.sqrt(wt.win).astype(np.float32), 0.5, 1.2, n // 4)
+    else:
+        win = window
+    avg = avg or (U32_MAX, U32_MAX)
+    st = restate(ora, x, y, n, win, detrend, avg, "f64")
+    for chan, key in ((x, "sxx"), (y, "syy")):
+        ref = ora.PsdCascade(n, "f64", window=win)
+        ref.set_detrend(detrend)
+        ref.set_avg(*avg)
+        ref.process(chan)
+        assert ref.num_stages == len(st)
+        for k, s in enumerate(st):
+            info = ref.stage_info(k)
+            assert (info["count"], info["pending"]) == (s["count"], s["pending"]), k
+            r = ref.stage_spectrum(k)
+            assert np.max(np.abs(s[key] - r) / np.maximum(r, 1e-300)) <= 1e-12, (key, k)
+    # y = x: Sxy is Sxx
+    st2 = restate(ora, x, x, n, win, detrend, avg, "f64")
+    for s in st2:
+        assert np.allclose(s["sxy"].real, s["sxx"], rtol=1e-12, atol=0) and np.all(np.abs(s["sxy"].imag) <= 1e-12 * s["sxx"] + 1e-300)
+
+
+def test_lane_emulation(tmp_path):
+    """The kernel's per-lane transform, natural-order store and separation (csrc/cross_fft.h) against an f64 DFT."""
+    exe = str(tmp_path / "cross_emul")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "stabilizer-stream_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "cross_emul.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:]
