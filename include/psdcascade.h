@@ -32,7 +32,8 @@
  *     sequence alone (PSDC_OPT_COALESCE), never by how busy the device happens to be.  Only a handle switched to
  *     PSDC_OPT_EAGER gives that up: its held spans go out as soon as the device is seen idle, so its round composition
  *     follows host timing and repeated runs agree to the same <= 2e-6, not to the bit (host-fed samples and one-span feeds
- *     stay bit-reproducible there too).
+ *     stay bit-reproducible there too).  This is stated for an environment with none of the library's A/B and debugging
+ *     switches set (PSDC_NO_*, PSDC_DBG_*, PSDC_FFT3: tools/README.md); they are read when a handle is made.
  *     Either grouping is closer to the exact sum than the reference's sequential f32 accumulation.
  */
 #ifndef PSDCASCADE_H

@@ -524,7 +524,7 @@ template <int N>
 hipError_t launch_bigfused3_n(const FusedBatch &b, const float *win, const cf *tw0g, hipStream_t s, hipEvent_t ea, hipEvent_t eb)
 {
     const dim3 grid(b.nblocks), block(Big3Geo<N>::THREADS);
-    const bool ew_ = b.any_ewma || (dbg_variant() & 1), frm_ = b.any_frames || (dbg_variant() & 2);
+    const bool ew_ = b.any_ewma, frm_ = b.any_frames;
 #define PSDK_BIG3_CASE(D)                                                                         \
     case D:                                                                                       \
         if (frm_ && ew_)                                                                          \

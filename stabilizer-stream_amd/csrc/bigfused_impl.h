@@ -816,7 +816,7 @@ hipError_t launch_bigfused_n(const FusedBatch &b, const float *win, const cf *tw
                              hipEvent_t ea, hipEvent_t eb)
 {
     const dim3 grid(b.nblocks), block(BigGeo<N>::THREADS);
-    const bool ew_ = b.any_ewma || (dbg_variant() & 1), frm_ = b.any_frames || (dbg_variant() & 2);
+    const bool ew_ = b.any_ewma, frm_ = b.any_frames;
 #define PSDK_BIG_CASE(D)                                                                          \
     case D:                                                                                       \
         if (frm_ && ew_)                                                                          \

@@ -951,7 +951,7 @@ static hipError_t launch_fused_n(const FusedBatch &b, const float *win, hipStrea
 #else
     const dim3 grid(b.nblocks), block(FUSED_WAVES * 64);
 #endif
-    const bool ew_ = b.any_ewma || (dbg_variant() & 1), frm_ = b.any_frames || (dbg_variant() & 2);
+    const bool ew_ = b.any_ewma, frm_ = b.any_frames;
 #define PSDK_FUSED_CASE(D)                                                                \
     case D:                                                                               \
         if (frm_ && ew_)                                                                  \
@@ -1012,9 +1012,9 @@ hipError_t launch_fused(int n, const FusedBatch &b, const float *win, const cf *
 {
     if (b.nblocks <= 0)
         return hipSuccess;
-    // N = 2048 / 4096: the three-pass kernels (bigfused3_impl.h).  PSDC_FFT3=0 selects the four-pass kernels (A/B aid).
-    static const bool fft3 = !(getenv("PSDC_FFT3") && getenv("PSDC_FFT3")[0] == '0');
-    if (fft3 && tw3g) {
+    // N = 2048 / 4096: the three-pass kernels (bigfused3_impl.h), unless the caller passes no seeds (PSDC_FFT3=0, A/B aid: the
+    // four-pass kernels)
+    if (tw3g) {
         if (n == 2048)
             return launch_bigfused3_2048(b, win, tw3g, s, ea, eb);
         if (n == 4096)

@@ -38,12 +38,6 @@ constexpr int MAX_COALESCE_OPT = 16; // ... as an explicit PSDC_OPT_COALESCE, an
 // gaps and run starts a sample).  A span merged from contiguous calls stops growing at HOLD_MAX_SAMPLES either way: 2^31 bytes, so
 // every byte offset into a span fits 32 bits.
 constexpr size_t HOLD_MAX_SAMPLES = (size_t)1 << 29;
-inline size_t hold_cap_from_env()
-{
-    const char *e = getenv("PSDC_DBG_HOLD_LOG2"); // (testing aid: tests/host/round_plan_check.cpp reaches the caps with streams of a few million samples)
-    const long v = e ? strtol(e, nullptr, 10) : 0;
-    return v >= 12 && v <= 29 ? (size_t)1 << v : HOLD_MAX_SAMPLES;
-}
 static_assert(MAX_COALESCE_OPT <= MAX_FSPANS, "a launch's frame-span table holds every FRAMED span of a round (frame calls hold at most PSDC_OPT_COALESCE <= 16)");
 
 extern thread_local std::string g_last_error;
@@ -106,6 +100,25 @@ struct WindowConsts {
     uint32_t overlap;
 };
 
+// The library's A/B and debugging switches (tools/README.md), read from the environment by read_knobs (runtime.cpp) when a handle
+// is made and nowhere else.  The defaults are the shipped behaviour.
+struct Knobs {
+    bool no_fold = false;      // PSDC_NO_FOLD: every round through post_kernel (bit-identical results)
+    size_t hold_cap = HOLD_MAX_SAMPLES; // PSDC_DBG_HOLD_LOG2: cap on a merged span and on what a channel holds (hold_max)
+    int bigfft_chunk = 0;      // PSDC_DBG_BIGFFT_CHUNK: pairs per chunk of the four-step FFT (0: what the scratch allows)
+    bool no_single = false;    // PSDC_NO_SINGLE: overlap 0 on the generic kernels
+    bool no_double = false;    // PSDC_NO_DOUBLE: one segment per transform
+    bool no_oversub = false;   // PSDC_NO_OVERSUB: small jobs count against a launch's workgroup capacity
+    bool no_fastpath = false;  // PSDC_NO_FASTPATH: every psdc_process call through the general path
+    bool fft3 = true;          // PSDC_FFT3=0 clears it: N = 2048 / 4096 on the four-pass kernels
+    int variant = 0;           // PSDC_DBG_VARIANT: bit 0 EWMA, bit 1 FRAMES kernel variants for every fused launch (Round::launch)
+    uint64_t fixed_run = 0;    // PSDC_DBG_FIXED_RUN: one run length for every fused launch (0: sized to the launch)
+    bool no_groups = false;    // PSDC_DBG_NOGROUPS: no XCD grouping of the four traces of a frame span
+    bool plan = false;         // PSDC_DBG_PLAN: every fused launch's jobs on stderr
+    bool host_timing = false;  // PSDC_DBG_HOST_TIMING: host time of the rounds, printed at exit (process-wide totals)
+    bool skip_post = false;    // PSDC_DBG_SKIP_POST, read in a -DPSDC_DEBUG_KNOBS build only (WRONG results: a timing bound)
+};
+
 } // namespace psdrt
 
 struct psdc_handle {
@@ -138,7 +151,6 @@ struct psdc_handle {
     psdk::cf *d_chirp = nullptr, *d_bhat = nullptr; // chirp-z tables of a size that is not a power of two (launch_welch)
     psdk::cf *d_bigfft = nullptr;                   // n > 16384: the ping-pong frames of the global-memory FFT (launch_welch_big)
     size_t bigfft_elems = 0;
-    int bigfft_chunk_limit = 0;               // PSDC_DBG_BIGFFT_CHUNK at create: pairs per chunk (tests: a job split over chunks)
     int detrend = PSDC_DETREND_NONE;
     uint32_t avg_limit = 0xFFFFFFFFu, avg_count = 0xFFFFFFFFu;
     std::vector<psdrt::Channel> ch;
@@ -178,11 +190,10 @@ struct psdc_handle {
     bool coalesce_auto = true; // PSDC_OPT_COALESCE not set: `coalesce`, or 16 ... MAX_COALESCE for one channel fed in short spans (coalesce_limit)
     uint32_t stage_limit = psdrt::MAX_STAGES; // stages that analyse their stream; 1 for a single Psd<N> (psdc_stage_*)
     uint32_t min_pairs = 0; // PSDC_OPT_MIN_PAIRS: segment pairs a decimated stage collects before it issues on the ingest path
-    size_t span_cap = psdrt::hold_cap_from_env(); // HOLD_MAX_SAMPLES ($PSDC_DBG_HOLD_LOG2, read when the handle is made: the CPU model's streams are short)
     bool merge = true;  // PSDC_OPT_MERGE: a device span that continues the last held one in memory extends it
-    bool fold = getenv("PSDC_NO_FOLD") == nullptr; // (A/B aid, read when the handle is made: unset = one launch per round where the kernel allows)
     bool eager = false; // PSDC_OPT_EAGER: a held span goes out as soon as the device is seen idle (round composition then follows host timing)
     bool profile = false;
+    psdrt::Knobs knobs; // the environment's switches as they were when the handle was made (psdc_clone copies them)
     std::vector<psdrt::ProfEvents> prof_pending;
     psdc_profile prof{};
     psdc_loss loss{};
@@ -253,7 +264,7 @@ int collect_profile(psdc_handle *h);
 uint32_t coalesce_limit(const psdc_handle *h, const Channel &c, size_t len = 0);
 bool device_idle(psdc_handle *h);
 size_t held_samples(const Channel &c);
-inline size_t hold_max(const psdc_handle *h) { return h->n_channels == 1 ? 2 * h->span_cap : h->span_cap; }
+inline size_t hold_max(const psdc_handle *h) { return h->n_channels == 1 ? 2 * h->knobs.hold_cap : h->knobs.hold_cap; }
 int settle_short_span(psdc_handle *h, Channel &c);
 bool holds_short_span(const psdc_handle *h, const Channel &c);
 int submit_host(psdc_handle *h, Channel &c);

@@ -150,8 +150,8 @@ struct FusedBatch {
     int njobs;
     int nblocks;
     int detrend;  // Detrend kind 0..3 for every job of the launch
-    int any_ewma; // some job has finite averaging weights
-    int any_frames; // some job reads AdcDac frames (the kernels built with the frame loads run this launch)
+    int any_ewma; // some job has finite averaging weights (or $PSDC_DBG_VARIANT bit 0: planner.cpp Round::launch)
+    int any_frames; // some job reads AdcDac frames (the kernels built with the frame loads run this launch; or $PSDC_DBG_VARIANT bit 1)
     // overlap 0 (Window::rectangular(), src/psd.rs:24-32, or a caller's table with overlap 0): a "pair" is ONE segment -- pair i =
     // segment seg_a + i = samples src[N i + N/2 .. N i + 3N/2), transformed with a zero imaginary part: exactly the N samples the
     // pair decimates, as ever; src points HALF A SEGMENT IN FRONT of segment seg_a (that half chunk is read for the decimator's
@@ -249,6 +249,7 @@ int fused_block_threads(int n);              // threads of one such workgroup
 void fused_big_tables(int n, std::vector<cf> &tw0, std::vector<cf> &twa);
 // twiddle seeds of the three-pass kernels (N = 2048, 4096: fft_block3.h) [2][N/16]: W_N^tl, W_N^(4 tl); empty otherwise
 void fused_big3_table(int n, std::vector<cf> &tw3);
+// tw3g == nullptr: N = 2048 / 4096 on the four-pass kernels (PSDC_FFT3=0)
 // ev_a / ev_b (both or neither): events that receive the kernel's own start and stop times
 // (hipExtLaunchKernelGGL), for PSDC_OPT_PROFILE
 hipError_t launch_fused(int n, const FusedBatch &b, const float *win, const cf *tw0g, const cf *twag, const cf *tw3g,
@@ -277,18 +278,6 @@ hipError_t launch_header_gather(const uint8_t *frames, size_t frame_size, size_t
 // max ~(index << 2 | code) over the bad frames (0: none), [1] batches received, [2] sequence gaps, [3] first seq | next seq
 // << 32.  acc: 5 device words, zero before the first call (the kernel leaves them zero).
 constexpr int FRAME_RESERVE_BLOCKS = 8; // workgroup slots a frame round leaves free for it (it runs beside the fused launch)
-// $PSDC_DBG_VARIANT (test aid, read once): bit 0 runs every fused launch on the EWMA kernel variants (weights of 1 for plain
-// sums), bit 1 on the FRAMES variants (no framed job: the f32 path of those kernels) -- the whole suite then exercises the
-// variants that only finite averaging / AdcDac frames reach otherwise.
-inline int dbg_variant()
-{
-    static const int v = [] {
-        const char *e = getenv("PSDC_DBG_VARIANT");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
 hipError_t launch_adcdac_verdict(const uint8_t *frames, size_t frame_size, size_t n_frames, int batches, int payload_ok, int check,
                                  size_t n_loss, unsigned long long *acc, unsigned long long *host_out, hipStream_t s);
 

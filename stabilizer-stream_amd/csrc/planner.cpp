@@ -43,9 +43,10 @@ struct Work {
 } // namespace
 
 namespace {
-// $PSDC_DBG_HOST_TIMING (debugging aid): where the HOST time of a round goes -- totals printed at exit
+// $PSDC_DBG_HOST_TIMING (debugging aid): where the HOST time of a round goes -- totals of the whole process printed at exit, switched
+// on by the first round of a handle made with Knobs::host_timing
 struct HostTiming {
-    bool on = getenv("PSDC_DBG_HOST_TIMING") != nullptr;
+    bool on = false;
     double round = 0, post = 0, fused = 0, other_launch = 0;
     unsigned long rounds = 0, spans = 0, span_hist[66] = {};
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -88,8 +89,7 @@ int fused_window(const psdc_handle *h)
 {
     if (h->window_kind == PSDC_WINDOW_HANN || (h->window_kind == PSDC_WINDOW_CUSTOM && 2 * (uint64_t)h->geo.overlap == h->n))
         return 1;
-    static const bool no_single = getenv("PSDC_NO_SINGLE") != nullptr; // (A/B aid: rectangular windows on the generic kernels)
-    if (h->geo.overlap == 0 && !no_single)
+    if (h->geo.overlap == 0 && !h->knobs.no_single) // (PSDC_NO_SINGLE, A/B aid: rectangular windows on the generic kernels)
         return 2;
     return 0;
 }
@@ -160,8 +160,7 @@ struct Round {
           seam(std::max<uint64_t>((uint64_t)h_->n + HBF_HALO, fmode != 0 ? need_pre + 3 * half : 0)),
           teams((uint64_t)std::max(1, fused_pairs_per_block((int)h_->n, 1))), regions(h_->n_channels), seam_ref(h_->n_channels)
     {
-        static const bool no_double = getenv("PSDC_NO_DOUBLE") != nullptr;
-        dbl = single && !no_double && fused_double_supported((int)h->n);
+        dbl = single && !h->knobs.no_double && fused_double_supported((int)h->n);
     }
     // a fused run starting at segment j decimates from sample j hop + N/2 on (half-overlapped pairs: the pair's new samples) -- or,
     // overlap 0, from j N on: a single-segment step transforms exactly the samples it decimates, and its source pointer sits half
@@ -545,8 +544,8 @@ void Round::share_workgroups()
         // jobs, so the launch asks for cap + (small jobs) workgroups and ends about one small job later than a launch of
         // the large jobs alone -- where counting them against the capacity left their slots empty for nearly the whole launch
         // (8 channels x 8 deep stages: 64 of 512 slots).
-        static const bool no_oversub = getenv("PSDC_NO_OVERSUB") != nullptr; // (A/B aid)
-        auto small_at = [&](uint64_t np, uint64_t r) { return !no_oversub && 4 * np <= r * teams; };
+        // (PSDC_NO_OVERSUB, A/B aid: every job counts)
+        auto small_at = [&](uint64_t np, uint64_t r) { return !h->knobs.no_oversub && 4 * np <= r * teams; };
         auto plan_r = [&](uint64_t r_small) { // the smallest R whose LARGE jobs fit the capacity, given which jobs count as small
             uint64_t pairs = 0, nlarge = 0;
             for (size_t i = b0; i < b1; ++i)
@@ -579,9 +578,8 @@ void Round::share_workgroups()
         // $PSDC_DBG_FIXED_RUN=<pairs> (measurement aid): ONE run length whatever the launch holds -- what run boundaries that are a
         // function of the absolute pair index (chunk-invariant grouping of the partial sums, include/psdcascade.h Conventions)
         // would cost: launches then ask for more or fewer workgroups than are resident at once.  Results stay correct.
-        static const uint64_t fixed_run = getenv("PSDC_DBG_FIXED_RUN") ? strtoull(getenv("PSDC_DBG_FIXED_RUN"), nullptr, 10) : 0;
-        if (fixed_run)
-            R = fixed_run;
+        if (h->knobs.fixed_run)
+            R = h->knobs.fixed_run;
         for (size_t i = b0; i < b1; ++i) {
             FusedJob &j = fjobs[i].j;
             const uint64_t np = (uint64_t)j.npairs;
@@ -691,8 +689,14 @@ int Round::launch(const FusedAux *aux)
                 j.pre_first = j.pre_count = 0;
             fb.jobs[fb.njobs++] = j;
         }
-        static const bool no_groups = getenv("PSDC_DBG_NOGROUPS") != nullptr; // (debugging aid)
-        for (int a = 0; !no_groups && a + 3 < fb.njobs && fb.n_fgroups < MAX_FSPANS; ) { // the four traces of one span, side by side
+        // $PSDC_DBG_VARIANT (test aid): bit 0 runs the launch on the EWMA kernel variants (weights of 1 for plain sums), bit 1 on the
+        // FRAMES variants (no framed job: the f32 path of those kernels) -- the whole suite then exercises the variants that only
+        // finite averaging / AdcDac frames reach otherwise.  The two flags only choose the kernel on the host; the single-segment
+        // kernels have no FRAMES variant (their launchers refuse any_frames), so bit 1 leaves them alone.
+        fb.any_ewma |= h->knobs.variant & 1;
+        if ((h->knobs.variant & 2) && !fb.single)
+            fb.any_frames = 1;
+        for (int a = 0; !h->knobs.no_groups && a + 3 < fb.njobs && fb.n_fgroups < MAX_FSPANS; ) { // the four traces of one span, side by side
             const FusedJob *q = fb.jobs + a;
             const bool group = q[0].fspan >= 0 && q[0].fch == 0 && q[1].fch == 1 && q[2].fch == 2 && q[3].fch == 3 &&
                                q[1].fspan == q[0].fspan && q[2].fspan == q[0].fspan && q[3].fspan == q[0].fspan &&
@@ -707,8 +711,7 @@ int Round::launch(const FusedAux *aux)
             ++fb.n_fgroups;
             a += 4;
         }
-        static const bool dbg_plan = getenv("PSDC_DBG_PLAN") != nullptr; // (debugging aid: what each fused launch holds)
-        if (dbg_plan) {
+        if (h->knobs.plan) { // (PSDC_DBG_PLAN, debugging aid: what each fused launch holds)
             long long np = 0;
             for (int q = 0; q < fb.njobs; ++q)
                 np += fb.jobs[q].npairs;
@@ -723,7 +726,8 @@ int Round::launch(const FusedAux *aux)
             return rc;
         {
             HtScope ht_f(g_ht.fused);
-            HIPCHK(h, launch_fused((int)h->n, fb, h->d_win, h->d_tw0g, h->d_twag, h->d_tw3g, h->stream, pe.a, pe.b, aux));
+            HIPCHK(h, launch_fused((int)h->n, fb, h->d_win, h->d_tw0g, h->d_twag, h->knobs.fft3 ? h->d_tw3g : nullptr, h->stream, pe.a,
+                                   pe.b, aux));
         }
         if ((rc = prof_end(pe, first, false)))
             return rc;
@@ -746,7 +750,7 @@ int Round::launch(const FusedAux *aux)
         if (!prof_fused && (rc = prof_begin(pe, true)))
             return rc;
         if (bigfft_size((int)h->n))
-            HIPCHK(h, launch_welch_big((int)h->n, wb, h->d_win, h->d_tw, h->d_bigfft, h->bigfft_elems, h->bigfft_chunk_limit, h->stream));
+            HIPCHK(h, launch_welch_big((int)h->n, wb, h->d_win, h->d_tw, h->d_bigfft, h->bigfft_elems, h->knobs.bigfft_chunk, h->stream));
         else
             HIPCHK(h, launch_welch((int)h->n, wb, h->d_win, h->d_tw, h->d_chirp, h->d_bhat, h->stream));
         if (!prof_fused && (rc = prof_end(pe, first, true)))
@@ -842,7 +846,7 @@ int Round::book()
 // fold_tails: this round's launch can carry aux workgroups at all; fold_seams: and the post launch in front of it can go.
 bool Round::fold_tails() const
 {
-    if (!h->fold || !fused_fold_supported((int)h->n) || fjobs.empty() || !sjobs.empty() || !djobs.empty() || fjobs.size() > fused_jpl)
+    if (h->knobs.no_fold || !fused_fold_supported((int)h->n) || fjobs.empty() || !sjobs.empty() || !djobs.empty() || fjobs.size() > fused_jpl)
         return false; // (a round of several fused launches: measured for eight channels x eight spans with the aux workgroups in the first of them -- -0.6 %)
     size_t pieces = 0;
     for (const TailJob &t : tjobs) {
@@ -963,6 +967,8 @@ static void compact_fs_pool(psdc_handle *h)
 int advance_round(psdc_handle *h, bool *did_work, bool all)
 {
     *did_work = false;
+    if (h->knobs.host_timing)
+        g_ht.on = true;
     HtScope ht_round(g_ht.round);
     if (g_ht.on) {
         ++g_ht.rounds;

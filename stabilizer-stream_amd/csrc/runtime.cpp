@@ -196,6 +196,36 @@ int classify_window(uint32_t n, const float *win, float power, float nenbw, size
     return PSDC_WINDOW_CUSTOM;
 }
 
+// The switches of Knobs (host_runtime.h), read when a handle is made: the library's only reads of PSDC_NO_*, PSDC_DBG_* and PSDC_FFT3.
+Knobs read_knobs()
+{
+    auto set = [](const char *name) { return getenv(name) != nullptr; };
+    Knobs k;
+    k.no_fold = set("PSDC_NO_FOLD");
+    // (testing aid: tests/host/round_plan_check.cpp reaches the caps with streams of a few million samples)
+    const char *e = getenv("PSDC_DBG_HOLD_LOG2");
+    const long v = e ? strtol(e, nullptr, 10) : 0;
+    k.hold_cap = v >= 12 && v <= 29 ? (size_t)1 << v : HOLD_MAX_SAMPLES;
+    if ((e = getenv("PSDC_DBG_BIGFFT_CHUNK")))
+        k.bigfft_chunk = atoi(e);
+    k.no_single = set("PSDC_NO_SINGLE");
+    k.no_double = set("PSDC_NO_DOUBLE");
+    k.no_oversub = set("PSDC_NO_OVERSUB");
+    k.no_fastpath = set("PSDC_NO_FASTPATH");
+    k.fft3 = !((e = getenv("PSDC_FFT3")) && e[0] == '0');
+    if ((e = getenv("PSDC_DBG_VARIANT")))
+        k.variant = atoi(e);
+    if ((e = getenv("PSDC_DBG_FIXED_RUN")))
+        k.fixed_run = strtoull(e, nullptr, 10);
+    k.no_groups = set("PSDC_DBG_NOGROUPS");
+    k.plan = set("PSDC_DBG_PLAN");
+    k.host_timing = set("PSDC_DBG_HOST_TIMING");
+#ifdef PSDC_DEBUG_KNOBS
+    k.skip_post = set("PSDC_DBG_SKIP_POST");
+#endif
+    return k;
+}
+
 // PSDC_DEVICE_DEFAULT -> the index in $PSDC_DEVICE (0 when unset or unparsable)
 int resolve_device(int device)
 {
@@ -331,14 +361,15 @@ int launch_deferred(psdc_handle *h, const std::vector<TailJob> &extra)
     tails.reserve(h->pend_tail.size() + extra.size());
     split_copy_jobs(h->pend_tail, tails);
     split_copy_jobs(extra, tails);
+#ifdef PSDC_DEBUG_KNOBS
     // $PSDC_DBG_SKIP_POST (timing only, WRONG results): the epilogue and the seam copies are dropped, not launched -- the upper bound of
     // what folding post_kernel's work into the fused launch can buy (one launch per round)
-    static const bool skip_post = getenv("PSDC_DBG_SKIP_POST") != nullptr;
-    if (skip_post) {
+    if (h->knobs.skip_post) {
         h->pend_red.clear();
         h->pend_tail.clear();
         return PSDC_OK;
     }
+#endif
     const size_t nr = h->pend_red.size(), nt = tails.size();
     for (size_t ri = 0, ti = 0; ri < nr || ti < nt;) {
         RedBatch rb{};
@@ -731,6 +762,7 @@ psdc_handle *create_impl(uint32_t n, int window_kind, const float *win_in, Windo
         fail(nullptr, PSDC_ERR_NOMEM, "psdc_create: out of memory");
         return nullptr;
     }
+    h->knobs = read_knobs();
     h->n = n;
     h->window_kind = window_kind;
     h->geo.n = n;
@@ -837,8 +869,6 @@ psdc_handle *create_impl(uint32_t n, int window_kind, const float *win_in, Windo
                                          : (size_t)(fused_max_blocks((int)n) + WELCH_MAX_BLOCKS + 4 * MAX_JOBS) * n;
     if (bigfft_size((int)n)) {
         h->bigfft_elems = BIGFFT_SCRATCH_ELEMS;
-        if (const char *e = getenv("PSDC_DBG_BIGFFT_CHUNK"))
-            h->bigfft_chunk_limit = atoi(e);
         if ((e = hipMalloc(&h->d_bigfft, sizeof(cf) * h->bigfft_elems)) != hipSuccess)
             return dev_fail(e, "hipMalloc(big FFT frames)");
     }
@@ -1142,8 +1172,7 @@ int psdc_process(psdc_handle *h, uint32_t channel, const float *x, size_t len)
     // (src/bin/psd.rs:172-181): a call that only adds to a staging buffer which stays below its quantum is a bounds check and a
     // memcpy -- no HIP call at all, not even the device query of ON_DEVICE (tests/host/smallcall_probe.cpp measures the boundary
     // at these sizes).  Everything else takes the general path below.
-    static const bool no_fast = getenv("PSDC_NO_FASTPATH") != nullptr; // (A/B aid: every call through the general path)
-    if (h && channel < h->n_channels && x && len && !no_fast) {
+    if (h && channel < h->n_channels && x && len && !h->knobs.no_fastpath) {
         Channel &cf_ = h->ch[channel];
         if (cf_.stage_host[0] && !cf_.st.empty() && cf_.spans.empty() && len < h->quantum - cf_.fill && len < ((size_t)1 << 19)) { // (>= 2 MiB: the copy threads)
             memcpy(cf_.stage_host[cf_.cur_stage] + cf_.fill, x, sizeof(float) * len);
@@ -1226,7 +1255,7 @@ int psdc_process_device_after(psdc_handle *h, uint32_t channel, const float *d_x
     // grouping stays deterministic.  PSDC_OPT_MERGE = 0 turns it off (tests of the multi-span planner).
     if (h->merge && c.has_span() && c.fill == 0 && !c.submitted) {
         DeviceSpan &last = c.spans.back();
-        if (!last.framed() && last.d_x + last.len == d_x && last.len + len <= h->span_cap && held_samples(c) + len <= hold_max(h)) {
+        if (!last.framed() && last.d_x + last.len == d_x && last.len + len <= h->knobs.hold_cap && held_samples(c) + len <= hold_max(h)) {
             last.len += len;
             c.st[0].total += len;
             c.span_max = std::max(c.span_max, last.len);

@@ -40,6 +40,20 @@ def test_library_does_not_link_the_oracle(pkg):
     assert "oracle" not in init.lower()
 
 
+def test_library_reads_its_switches_in_one_place(pkg):
+    """The environment is read by three functions of runtime.cpp alone: read_knobs (the A/B and debugging switches, when a handle
+    is made), resolve_device (PSDC_DEVICE) and CopyPool (PSDC_COPY_THREADS); no kernel TU or header reads it.  The switch that
+    drops work (PSDC_DBG_SKIP_POST) exists only in a -DPSDC_DEBUG_KNOBS build."""
+    csrc = os.path.join(ROOT, "stabilizer-stream_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f), errors="ignore").read() for f in os.listdir(csrc) if f.endswith((".h", ".hip", ".cpp"))}
+    assert [f for f, s in src.items() if "getenv(" in s] == ["runtime.cpp"]
+    rt = src["runtime.cpp"]
+    a = rt.index("\nKnobs read_knobs()\n")
+    b = rt.index("\n}\n", a)
+    assert re.findall(r"getenv\((.*?)\)", rt[:a] + rt[b:]) == ['"PSDC_COPY_THREADS"', '"PSDC_DEVICE"']
+    assert b"PSDC_DBG_SKIP_POST" not in open(pkg.LIB_PATH, "rb").read()
+
+
 @pytest.mark.skipif(has_gpu(), reason="checks the no-GPU failure mode")
 def test_no_gpu_fails_loudly(pkg):
     with pytest.raises(pkg.PsdError) as e:
