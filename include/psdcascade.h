@@ -534,6 +534,40 @@ int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in,
 /* last error text of an object; with h == NULL, of the calling thread's last failed cross call */
 const char *psdc_cross_last_error(const psdc_cross *h);
 
+/* ---- stream frames into a cross object ------------------------------------------------------------------
+ * Frames in, cross spectra out: the frames of psdc_process_frames (any of the four formats, in runs) feed pairs of their
+ * traces.  Pair p takes x = trace pair_traces[2p] and y = trace pair_traces[2p + 1] of every frame, in Payload::traces order:
+ * AdcDac ADC0 ADC1 DAC0 DAC1, Fls AR AP BI BQ, ThermostatEem T00 T20 I0 I1, Mpll phase frequency amplitude.  The map has
+ * 2 n_pairs entries; a pair whose two entries are PSDC_TRACE_NONE is not fed by the call.  A trace may feed several pairs and
+ * x == y is allowed.  The map belongs to the call and is not stored.  Example: the map {2, 0} (pair 0 = (DAC0, ADC0)) of AdcDac
+ * frames makes transfer() = H1 from DAC0 to ADC0 and coherence() that of the two.
+ * Frames: headers, runs of one format, de::Error codes and *n_ok work exactly as in psdc_process_frames: on a bad frame the
+ * frames before it are ingested, *n_ok says how many, and the frame's PSDC_ERR_FRAME_HEADER / _FORMAT / _SIZE is returned.
+ * Header-only frames (0 batches) count in Loss only.  The decoded traces are bit-identical to Payload::traces.
+ * Map errors: PSDC_ERR_ARG without ingesting anything for a NULL map, an entry with exactly one PSDC_TRACE_NONE, or a trace
+ * index >= 4.  A run whose format carries fewer traces than the map names (Mpll has 3) is PSDC_ERR_ARG at the run's first
+ * frame: the frames before it are ingested and *n_ok counts them.
+ * Loss: one psdc_loss per object over every frame either call ingested (src/loss.rs:11-26); a reset zeroes it.
+ * Rounds: a call is cut into pieces of whole frames of at most 2^22 samples a trace, in runs of one format; each piece is decoded
+ * on the device (one launch per 16 fed pairs) into the stage-0 streams of its pairs and followed by one round, as a sample
+ * call is.  The cut depends on the frames alone and is the same for both calls: the same calls give the same bits, and frames
+ * in host memory the same bits as the same frames in device memory.
+ * Memory: the first host-memory call allocates a 32 MB device buffer the frames go up through (in the object's pinned
+ * staging); the device call keeps 8 bytes of pinned memory a frame of its largest call (at least 64 KB) and a third stream. */
+#define PSDC_TRACE_NONE 0xFFFFFFFFu
+/* frames in host memory */
+int psdc_csd_process_frames(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size,
+                            size_t n_frames, size_t *n_ok);
+/* frames in device memory.  The headers are gathered by one small launch on a side stream of the object and validated on the
+ * host; the call waits for that launch alone, so *n_ok and the de::Error are final when it returns.  producer_event: a
+ * hipEvent_t recorded behind the producer of d_frames, or NULL when the producer has completed; the gather and the decode wait
+ * for it on the device.  Header bytes may be rewritten once the call has returned; payload bytes must stay unchanged until
+ * the object's sync or a read-out returns.  Any base address is accepted. */
+int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *d_frames,
+                                   size_t frame_size, size_t n_frames, size_t *n_ok, void *producer_event);
+/* the Loss counters of the frames the object ingested (psdc_loss_read); reset != 0 zeroes them after reading */
+int psdc_csd_loss_read(psdc_cross *h, psdc_loss *out, int reset);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -323,6 +323,9 @@ def lib():
                                  i32, u32, i32, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_cross_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_cross_last_error", C.c_char_p, [H])
+    f("psdc_csd_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_csd_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_csd_loss_read", i32, [H, C.POINTER(_CLoss), i32])
     _lib = L
     return L
 
@@ -344,6 +347,7 @@ EXPORTS = [
     "psdc_cross_create", "psdc_cross_create_window", "psdc_cross_destroy", "psdc_cross_reset", "psdc_cross_set_detrend",
     "psdc_cross_set_avg", "psdc_cross_process", "psdc_cross_process_device", "psdc_cross_sync", "psdc_cross_num_stages",
     "psdc_cross_stage_spectra", "psdc_cross_csd", "psdc_cross_stitch", "psdc_cross_stats_read", "psdc_cross_last_error",
+    "psdc_csd_process_frames", "psdc_csd_process_frames_device", "psdc_csd_loss_read",
 ]
 
 
@@ -616,7 +620,33 @@ class PsdCascade:
 
 def _raise_cross(code, h=None):
     msg = lib().psdc_cross_last_error(h)
-    raise PsdError(code, msg.decode() if msg else "")
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
+
+
+TRACE_NONE = 0xFFFFFFFF
+
+
+def trace_index(t):
+    """A trace of Payload::traces as its index: an int, or a TRACE_NAMES label (the labels of the four formats are distinct)."""
+    if isinstance(t, str):
+        for names in TRACE_NAMES.values():
+            if t in names:
+                return names.index(t)
+        raise PsdError(ERR_ARG, f"unknown trace label {t!r}")
+    return int(t)
+
+
+def pair_map(pairs, n_pairs):
+    """The psdc_csd_* map of `pairs`: entry p is (x, y) -- trace indices or TRACE_NAMES labels -- or None (pair p not fed);
+    pairs past the end of the list are not fed."""
+    if len(pairs) > n_pairs:
+        raise PsdError(ERR_ARG, f"{len(pairs)} pairs for a bank of {n_pairs}")
+    m = np.full(2 * n_pairs, TRACE_NONE, np.uint32)
+    for p, xy in enumerate(pairs):
+        if xy is not None:
+            m[2 * p], m[2 * p + 1] = trace_index(xy[0]), trace_index(xy[1])
+    return m
 
 
 class CsdCascadeBank:
@@ -676,6 +706,34 @@ class CsdCascadeBank:
         self._ck(self._L.psdc_cross_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
                                                    C.c_void_p(after) if after else None))
 
+    def process_frames(self, data, frame_size, pairs):
+        """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] = (x, y)
+        feeds pair p with traces x and y of every frame (indices or TRACE_NAMES labels), None leaves it unfed.  Returns the
+        number of frames ingested; a bad frame raises FrameError after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_csd_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
+                                             frame_size, buf.size // frame_size, C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
+        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
+        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
+        m = pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_csd_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
+                                                    frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(self._L.psdc_csd_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
     def sync(self):
         self._ck(self._L.psdc_cross_sync(self._h))
 
@@ -729,6 +787,16 @@ class CsdCascade:
 
     def process_device(self, px, py, length, after=None):
         self._b.process_device(0, px, py, length, after)
+
+    def process_frames(self, data, frame_size, pair):
+        """pair: (x, y) traces of the frames (CsdCascadeBank.process_frames)"""
+        return self._b.process_frames(data, frame_size, [pair])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
 
     def csd(self, opts=MergeOpts()):
         return self._b.csd(0, opts)

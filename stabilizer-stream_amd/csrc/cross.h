@@ -69,11 +69,27 @@ struct CrossPostBatch {
     CrossTailJob tail[CROSS_MAX_TAIL];
 };
 
+// Frames decoded straight into the stage-0 streams (cross_frames.hip): one launch reads n_frames frames of format `fmt` and writes
+// trace trace[k] of them to dst[k], k < ndst (the x / y buffers of up to 16 pairs; a trace may go to several).  dst[k] receives
+// n_frames * batches * (8 for AdcDac, else 1) samples.
+constexpr int CROSS_FRAMES_MAX_DST = 32;
+struct CrossFramesBatch {
+    const uint8_t *frames;
+    unsigned long long frame_size;
+    unsigned n_frames;
+    int batches;
+    int fmt;  // 1 AdcDac, 2 Fls, 3 ThermostatEem, 4 Mpll
+    int ndst;
+    int trace[CROSS_FRAMES_MAX_DST];
+    float *dst[CROSS_FRAMES_MAX_DST];
+};
+
 bool cross_supported(int n);             // 64 ... 4096, powers of two
 int cross_segments_per_tile(int n);
 int cross_block_threads(int n); // threads of a cross_kernel workgroup (one wavefront a SIMD: its registers allow no more)
 int cross_fold_blocks(int nbins); // workgroups of one fold job
 hipError_t launch_cross(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s);
 hipError_t launch_cross_post(const CrossPostBatch &b, hipStream_t s);
+hipError_t launch_cross_frames(const CrossFramesBatch &b, hipStream_t s);
 
 } // namespace psdk

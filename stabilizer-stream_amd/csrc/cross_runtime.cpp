@@ -28,6 +28,8 @@ namespace {
 constexpr uint32_t X_MAX_STAGES = 16;
 constexpr uint32_t X_MAX_PAIRS = 65536;
 constexpr size_t STAGING = (size_t)1 << 22; // host-fed samples a channel per pinned staging slot
+constexpr size_t FRAMES_CHUNK = 2 * STAGING * sizeof(float); // host-memory frame bytes a pinned staging slot takes at once
+constexpr size_t PIECE_SAMPLES = (size_t)1 << 22;            // a frames call is cut into pieces of <= this many samples a trace
 
 thread_local std::string x_last_error;
 
@@ -79,6 +81,14 @@ struct psdc_cross {
     std::vector<void *> retired; // replaced device buffers, freed at the next sync point
     bool idle = true;            // every stage drained
     uint64_t launches = 0, pairs_in = 0;
+    // frames (psdc_csd_process_frames[_device]): Loss over every frame either call ingested; host-memory frames go up through
+    // h_stage into d_frames (FRAMES_CHUNK bytes, made by the first host-frames call); device frames' headers come to h_hdr
+    // (8 bytes a frame, grown to the largest call) through a gather launch on hdr_stream
+    psdc_loss loss{};
+    uint8_t *d_frames = nullptr;
+    uint8_t *h_hdr = nullptr;
+    size_t h_hdr_cap = 0;
+    hipStream_t hdr_stream = nullptr;
     int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
     std::string err;
 };
@@ -510,6 +520,238 @@ psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, 
     return h;
 }
 
+
+// ---- frames (psdc_csd_process_frames[_device]) ----
+
+// Payload layouts by Format id (src/de/mod.rs:12-17; src/de/data.rs:13, 86, 144, 168): bytes per batch, samples per batch and
+// trace, traces (Payload::traces)
+struct XWireFmt {
+    int id;
+    size_t batch_bytes;
+    int spb, ntr;
+    const char *what;
+};
+const XWireFmt *x_wire_fmt(int id)
+{
+    static const XWireFmt t[4] = {{1, 64, 8, 4, "AdcDac"}, {2, 56, 1, 4, "Fls"}, {3, 80, 1, 4, "ThermostatEem"}, {4, 24, 1, 3, "Mpll"}};
+    return id >= 1 && id <= 4 ? &t[id - 1] : nullptr;
+}
+
+struct FedPair {
+    uint32_t pair, tx, ty;
+};
+
+// the pairs a call feeds, from its map; PSDC_ERR_ARG for a NULL map, an entry with exactly one PSDC_TRACE_NONE or a trace no
+// format carries
+int read_map(psdc_cross *h, const uint32_t *map, const char *who, std::vector<FedPair> *fed)
+{
+    if (!map)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null pair map");
+    fed->clear();
+    for (uint32_t p = 0; p < h->n_pairs; ++p) {
+        const uint32_t tx = map[2 * p], ty = map[2 * p + 1];
+        if ((tx == PSDC_TRACE_NONE) != (ty == PSDC_TRACE_NONE))
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(p) + " names one trace and PSDC_TRACE_NONE");
+        if (tx == PSDC_TRACE_NONE)
+            continue;
+        if (tx >= 4 || ty >= 4)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(p) + " names trace " +
+                                              std::to_string(std::max(tx, ty)) + " (frames carry at most 4)");
+        fed->push_back({p, tx, ty});
+    }
+    return PSDC_OK;
+}
+
+// Where a call's frames are: the payloads in host memory (host) or on the device (dev), the 8 header bytes of frame f at
+// hdr + f * hdr_stride (host memory either way)
+struct FrameSrc {
+    const uint8_t *host = nullptr;
+    const uint8_t *dev = nullptr;
+    const uint8_t *hdr = nullptr;
+    size_t hdr_stride = 0;
+};
+
+// decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[2 i + c] (pair fed[i], channel
+// c), one launch per 16 pairs, on the copy stream
+int decode_frames(psdc_cross *h, const FrameSrc &src, size_t frame_size, const XWireFmt *wf, int batches, size_t f, size_t cnt,
+                  const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
+{
+    const uint8_t *frames = src.dev ? src.dev + f * frame_size : nullptr;
+    if (!src.dev) { // host memory: up through a pinned staging slot into d_frames (the decode of the chunk before has read it:
+                    // both are on the copy stream)
+        if (!h->d_frames)
+            XCHK(h, hipMalloc(&h->d_frames, FRAMES_CHUNK));
+        const int slot = h->stage_cur;
+        if (h->ev_pending[slot])
+            XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+        uint8_t *stg = reinterpret_cast<uint8_t *>(h->h_stage[slot]);
+        psdrt::pinned_copy(stg, src.host + f * frame_size, cnt * frame_size);
+        XCHK(h, hipMemcpyAsync(h->d_frames, stg, cnt * frame_size, hipMemcpyHostToDevice, h->copy_stream));
+        XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
+        h->ev_pending[slot] = true;
+        h->stage_cur ^= 1;
+        frames = h->d_frames;
+    }
+    for (size_t i0 = 0; i0 < fed.size(); i0 += CROSS_FRAMES_MAX_DST / 2) {
+        CrossFramesBatch b{};
+        b.frames = frames;
+        b.frame_size = frame_size;
+        b.n_frames = (unsigned)cnt;
+        b.batches = batches;
+        b.fmt = wf->id;
+        for (size_t i = i0; i < std::min(fed.size(), i0 + CROSS_FRAMES_MAX_DST / 2); ++i)
+            for (int c = 0; c < 2; ++c) {
+                b.trace[b.ndst] = (int)(c ? fed[i].ty : fed[i].tx);
+                b.dst[b.ndst] = dst[2 * i + c] + dst_off;
+                ++b.ndst;
+            }
+        XCHK(h, launch_cross_frames(b, h->copy_stream));
+        ++h->launches;
+    }
+    return PSDC_OK;
+}
+
+// One call's frames, as psdc_process_frames takes them (src/de/frame.rs:49-60, src/loss.rs:11-26): runs of one format, every
+// header validated on the host, Loss committed piece by piece once the piece's samples are in the streams.  A run is cut into
+// pieces of whole frames of <= PIECE_SAMPLES samples a trace; each piece is decoded and followed by one round.  The cut depends on
+// the headers alone, so host and device frames give the same rounds.
+int ingest_frames(psdc_cross *h, const std::vector<FedPair> &fed, const FrameSrc &src, size_t frame_size, size_t n_frames,
+                  size_t *good_out, const char *who)
+{
+    size_t &good = *good_out;
+    const size_t payload = frame_size - 8;
+    int bad = PSDC_OK;
+    size_t f0 = 0;
+    auto hdr = [&](size_t f) { return src.hdr + f * src.hdr_stride; };
+    while (f0 < n_frames && bad == PSDC_OK) {
+        const uint8_t *first = hdr(f0);
+        if (first[0] != 0x7b || first[1] != 0x05) { // Header::parse (src/de/frame.rs:25-37)
+            bad = PSDC_ERR_FRAME_HEADER;
+            break;
+        }
+        const XWireFmt *wf = x_wire_fmt(first[2]);
+        if (!wf) {
+            bad = PSDC_ERR_FRAME_FORMAT;
+            break;
+        }
+        for (const FedPair &fp : fed)
+            if ((int)std::max(fp.tx, fp.ty) >= wf->ntr)
+                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(fp.pair) + " names trace " +
+                                                  std::to_string(std::max(fp.tx, fp.ty)) + " but " + wf->what + " frames carry " +
+                                                  std::to_string(wf->ntr) + " (frame " + std::to_string(f0) + ")");
+        const int batches = (int)(payload / wf->batch_bytes);
+        const size_t per_frame = (size_t)batches * (size_t)wf->spb; // samples a trace and frame
+        const size_t piece_frames = per_frame ? std::max<size_t>(1, PIECE_SAMPLES / per_frame) : n_frames;
+        bool run_end = false;
+        while (f0 < n_frames && bad == PSDC_OK && !run_end) {
+            // the piece: headers + the payload's size checks + Loss::update, as ingest_frames_host's scan (frames_ingest.cpp)
+            psdc_loss trial = h->loss;
+            const size_t lim = std::min(piece_frames, n_frames - f0);
+            size_t cnt = 0;
+            for (; cnt < lim; ++cnt) {
+                const uint8_t *p = hdr(f0 + cnt);
+                if (p[0] != 0x7b || p[1] != 0x05) {
+                    bad = PSDC_ERR_FRAME_HEADER;
+                    break;
+                }
+                if (p[2] != wf->id) {
+                    if (x_wire_fmt(p[2]))
+                        run_end = true;
+                    else
+                        bad = PSDC_ERR_FRAME_FORMAT;
+                    break;
+                }
+                if (payload % wf->batch_bytes != 0 || (int)p[3] != batches) {
+                    bad = PSDC_ERR_FRAME_SIZE;
+                    break;
+                }
+                const uint32_t seq = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+                trial.received += p[3];
+                if (trial.have_seq)
+                    trial.dropped += (uint32_t)(seq - trial.next_seq); // wrapping_sub
+                trial.next_seq = seq + p[3];                            // wrapping_add
+                trial.have_seq = 1;
+            }
+            if (cnt == 0)
+                break;
+            if (batches > 0 && !fed.empty()) {
+                const size_t per_ch = cnt * per_frame;
+                // stage 0 of every fed pair takes per_ch more samples of each channel
+                std::vector<float *> dst(2 * fed.size());
+                h->grew = false;
+                for (size_t i = 0; i < fed.size(); ++i) {
+                    XStage *s = nullptr;
+                    int rc = stage0_room(h, fed[i].pair, per_ch, &s);
+                    if (rc)
+                        return rc;
+                    for (int c = 0; c < 2; ++c)
+                        dst[2 * i + c] = s->buf.p[c][s->buf.cur] + (s->total - s->buf.base);
+                }
+                // the same order as psdc_cross_process_device's copies: behind a buffer's growth and round R - 2, before round R
+                if (h->grew) {
+                    XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+                    XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+                }
+                const int slot = (int)(h->rounds & 1);
+                if (h->round_recorded[slot])
+                    XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
+                const size_t chunk = src.dev ? cnt : std::max<size_t>(1, FRAMES_CHUNK / frame_size);
+                for (size_t c0 = 0; c0 < cnt; c0 += chunk) {
+                    int rc = decode_frames(h, src, frame_size, wf, batches, f0 + c0, std::min(chunk, cnt - c0), fed, dst,
+                                           c0 * per_frame);
+                    if (rc)
+                        return rc;
+                }
+                XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+                XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+                for (const FedPair &fp : fed) {
+                    h->pairs[fp.pair][0].total += per_ch;
+                    h->pairs_in += per_ch;
+                }
+                h->idle = false;
+                h->loss = trial; // the piece is in the streams: its frames count from here on
+                good += cnt;
+                bool did = false;
+                int rc = run_round(h, &did);
+                if (rc)
+                    return rc;
+            } else { // header-only frames, or no pair fed: Loss only
+                h->loss = trial;
+                good += cnt;
+            }
+            f0 += cnt;
+        }
+    }
+    if (bad != PSDC_OK)
+        return xfail(h, bad,
+                     std::string(who) + ": " +
+                         (bad == PSDC_ERR_FRAME_HEADER   ? "Invalid frame header"
+                          : bad == PSDC_ERR_FRAME_FORMAT ? "Unknown format ID"
+                                                         : "Payload size") +
+                         " (frame " + std::to_string(good) + ")");
+    return PSDC_OK;
+}
+
+// the checks both frames calls begin with; *go: there are frames to take
+int frames_args(psdc_cross *h, const uint32_t *map, const void *frames, size_t frame_size, size_t n_frames, const char *who,
+                std::vector<FedPair> *fed, bool *go)
+{
+    *go = false;
+    int rc = read_map(h, map, who, fed);
+    if (rc)
+        return rc;
+    if (n_frames == 0)
+        return PSDC_OK;
+    if (!frames)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null frames");
+    if (frame_size < 8) // &input[..HEADER_SIZE] panics (src/de/frame.rs:50)
+        return xfail(h, PSDC_ERR_FRAME_SIZE, std::string(who) + ": frame shorter than its header");
+    if (n_frames > (size_t)std::numeric_limits<uint32_t>::max())
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": more than 2^32 - 1 frames in one call");
+    *go = true;
+    return PSDC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -549,6 +791,12 @@ void psdc_cross_destroy(psdc_cross *h)
         if (h->stage_ev[i])
             (void)hipEventDestroy(h->stage_ev[i]);
     }
+    if (h->d_frames)
+        (void)hipFree(h->d_frames);
+    if (h->h_hdr)
+        (void)hipHostFree(h->h_hdr);
+    if (h->hdr_stream)
+        (void)hipStreamDestroy(h->hdr_stream);
     if (h->d_win)
         (void)hipFree(h->d_win);
     if (h->d_tw)
@@ -578,6 +826,7 @@ int psdc_cross_reset(psdc_cross *h)
     h->stage_cur = 0;
     h->ev_pending[0] = h->ev_pending[1] = false;
     h->launches = h->pairs_in = 0;
+    h->loss = psdc_loss{};
     h->rounds = 0;
     h->round_recorded[0] = h->round_recorded[1] = false;
     return PSDC_OK;
@@ -839,6 +1088,85 @@ int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in,
         *pairs_in = h->pairs_in;
     if (reset)
         h->launches = h->pairs_in = 0;
+    return PSDC_OK;
+}
+
+int psdc_csd_process_frames(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                            size_t *n_ok)
+{
+    static const char *who = "psdc_csd_process_frames";
+    if (n_ok)
+        *n_ok = 0;
+    X_HANDLE(h, "psdc_csd_process_frames");
+    std::vector<FedPair> fed;
+    bool go = false;
+    int rc = frames_args(h, pair_traces, frames, frame_size, n_frames, who, &fed, &go);
+    if (rc || !go)
+        return rc;
+    X_ON_DEVICE(h);
+    FrameSrc src;
+    src.host = frames;
+    src.hdr = frames;
+    src.hdr_stride = frame_size;
+    size_t good = 0;
+    rc = ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
+    if (n_ok)
+        *n_ok = good;
+    return rc;
+}
+
+int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
+                                   size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    static const char *who = "psdc_csd_process_frames_device";
+    if (n_ok)
+        *n_ok = 0;
+    X_HANDLE(h, "psdc_csd_process_frames_device");
+    std::vector<FedPair> fed;
+    bool go = false;
+    int rc = frames_args(h, pair_traces, d_frames, frame_size, n_frames, who, &fed, &go);
+    if (rc || !go)
+        return rc;
+    X_ON_DEVICE(h);
+    // the headers come to the host through one gather launch on a stream of the object's own; the host waits for that launch
+    // alone while the compute stream goes on with the rounds of earlier calls
+    if (!h->hdr_stream)
+        XCHK(h, hipStreamCreateWithFlags(&h->hdr_stream, hipStreamNonBlocking));
+    if (h->h_hdr_cap < 8 * n_frames) {
+        const size_t cap = std::max<size_t>(8 * n_frames + (8 * n_frames) / 2, (size_t)1 << 16);
+        uint8_t *nb = nullptr;
+        XCHK(h, hipHostMalloc(reinterpret_cast<void **>(&nb), cap, hipHostMallocDefault));
+        if (h->h_hdr)
+            (void)hipHostFree(h->h_hdr);
+        h->h_hdr = nb;
+        h->h_hdr_cap = cap;
+    }
+    if (producer_event) {
+        XCHK(h, hipStreamWaitEvent(h->hdr_stream, (hipEvent_t)producer_event, 0));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    }
+    XCHK(h, launch_header_gather(d_frames, frame_size, n_frames, h->h_hdr, h->hdr_stream));
+    ++h->launches;
+    XCHK(h, hipStreamSynchronize(h->hdr_stream));
+    FrameSrc src;
+    src.dev = d_frames;
+    src.hdr = h->h_hdr;
+    src.hdr_stride = 8;
+    size_t good = 0;
+    rc = ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
+    if (n_ok)
+        *n_ok = good;
+    return rc;
+}
+
+int psdc_csd_loss_read(psdc_cross *h, psdc_loss *out, int reset)
+{
+    X_HANDLE(h, "psdc_csd_loss_read");
+    if (!out)
+        return xfail(h, PSDC_ERR_ARG, "psdc_csd_loss_read: null output");
+    *out = h->loss;
+    if (reset)
+        h->loss = psdc_loss{};
     return PSDC_OK;
 }
 

@@ -1,5 +1,5 @@
-// frames.h -- device side of the AdcDac frame source (kernels.h FrameSpan): where a sample of a trace sits in a run of
-// frames and how its wire word becomes f32 (src/de/frame.rs:5-9 header of 8 bytes, src/de/data.rs:11-82 payload).
+// frames.h -- device side of the frame sources: where a sample of an AdcDac trace sits in a run of frames (kernels.h FrameSpan)
+// and how the wire words of every payload format become f32 (src/de/frame.rs:5-9 header of 8 bytes, src/de/data.rs payloads).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +43,74 @@ __device__ __forceinline__ float4 frame_sample4(const FrameSpan &fs, int ch, uns
     const bool dac = ch >= 2;
     return make_float4(adcdac_volts(r.x & 0xffffu, dac), adcdac_volts(r.x >> 16, dac), adcdac_volts(r.y & 0xffffu, dac),
                        adcdac_volts(r.y >> 16, dac));
+}
+
+// The other payload formats (src/de/data.rs:84-212) -- Fls (format id 2), ThermostatEem (3), Mpll (4): ONE sample per batch and
+// trace.  The arithmetic is the reference's, operation by operation in f32 (`as f32` conversions, separate products and sum --
+// rustc never fuses them --, a correctly rounded square root, the scale constants evaluated in f32 in the reference's order): the
+// traces are bit-identical to Payload::traces.  (payload_kernel in kernels.hip, cross_frames_kernel in cross_frames.hip.)
+struct PayloadFmt {
+    int batch_bytes, ntraces;
+};
+__host__ __device__ constexpr PayloadFmt payload_fmt(int id)
+{
+    return id == 2 ? PayloadFmt{56, 4}   // [[[u8;4];7];2]  data.rs:86
+         : id == 3 ? PayloadFmt{80, 4}   // [[u8;4];16+4]   data.rs:144
+                   : PayloadFmt{24, 3};  // [[u8;4];6]      data.rs:168
+}
+
+// u32::from_le_bytes of word i of the batch at p: one load when the frames are 4-byte aligned (every valid frame_size is a multiple
+// of 8; the base is the caller's), bytes otherwise
+__device__ __forceinline__ uint32_t payload_word(const uint8_t *p, int i, bool aligned)
+{
+    const uint8_t *q = p + 4 * i;
+    if (aligned)
+        return *reinterpret_cast<const uint32_t *>(q);
+    return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+}
+
+// a.powi(2) + c.powi(2), .sqrt(): two products, one sum, a correctly rounded root.  (HIP's __fmul_rn / __fadd_rn are plain
+// operators the backend may fuse, and __fsqrt_rn is the approximate native root: the pragma and sqrtf -- IEEE under hipcc's
+// default -fhip-fp32-correctly-rounded-divide-sqrt -- are what pins the arithmetic.)
+__device__ __forceinline__ float payload_hyp(float a, float c)
+{
+#pragma clang fp contract(off)
+    const float aa = a * a, cc = c * c;
+    const float sum = aa + cc;
+    return sqrtf(sum);
+}
+
+// trace T of one batch of format FMT; word(i) = u32::from_le_bytes of the batch's word i
+template <int FMT, int T, class Word>
+__device__ __forceinline__ float payload_trace(const Word &word)
+{
+    auto i32f = [&](int i) { return (float)(int32_t)word(i); }; // i32::from_le_bytes(..) as f32
+    if constexpr (FMT == 2) { // Fls::traces, data.rs:97-139
+        constexpr float inv_max = 1.0f / 2147483648.0f;          // 1.0 / (i32::MAX as f32)
+        constexpr float ap = 6.28318530717958647692f / 65536.0f; // TAU / (1i64 << 16) as f32
+        if constexpr (T == 0)
+            return payload_hyp(i32f(0), i32f(1)) * inv_max; // "AR" :100-110
+        if constexpr (T == 1) {
+            const long long ph = (long long)((unsigned long long)word(2) | ((unsigned long long)word(3) << 32));
+            return (float)ph * ap; // "AP" :111-123
+        }
+        if constexpr (T == 2)
+            return i32f(7) / 2147483648.0f; // "BI" b[1][0] :124-130 (a power of two: exact)
+        return i32f(8) / 2147483648.0f;     // "BQ" b[1][1] :131-137
+    } else if constexpr (FMT == 3) { // ThermostatEem::traces, data.rs:154-163: words 0, 8, 13, 16 as f32
+        return __uint_as_float(word(T == 0 ? 0 : T == 1 ? 8 : T == 2 ? 13 : 16));
+    } else { // Mpll::traces, data.rs:178-211
+        static_assert(FMT == 4 && T < 3, "Mpll carries three traces");
+        constexpr float two32 = 4294967296.0f;
+        constexpr float c_phase = 6.28318530717958647692f / two32;    // TAU / (1u64 << 32) as f32
+        constexpr float c_freq = 1.0f / 1.28e-3f / two32;             // 1.0 / 1.28e-3 / (1u64 << 32) as f32
+        constexpr float c_amp = 10.24f / 10.0f * 2.0f * 2.0f / two32; // 10.24 / 10.0 * 2.0 * 2.0 / (1u64 << 32) as f32
+        if constexpr (T == 0)
+            return i32f(4) * c_phase; // "phase (rad)"
+        if constexpr (T == 1)
+            return i32f(5) * c_freq; // "frequency (kHz)"
+        return payload_hyp(i32f(0), i32f(1)) * c_amp; // "amplitude (V/G10)"
+    }
 }
 
 } // namespace psdk

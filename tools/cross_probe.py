@@ -1,10 +1,14 @@
 """Measure the cross-spectral cascade (psdc_cross_*): one JSON line.
 
     python tools/cross_probe.py [--seconds 0.5]
+    python tools/cross_probe.py --frames [--out profiles/cross_frames_probe.json]
 
 Legs: device-resident pairs at N = 512, 1024, 4096 with 1 and 4 pairs in 2^24-pair calls (warm-up, then a window of at
 least --seconds timed on the host clock ending in psdc_cross_sync); kernel launches of one steady-state call; one
 host-fed leg.  Roofline: 8 algorithmic bytes a pair (x and y read once) against 8 TB/s of HBM.
+--frames: device-resident AdcDac frames (128 batches a frame) into the pairs (ADC0, DAC0), (ADC1, DAC1) at N = 512, 1024, 4096
+in calls of 2^22 samples a trace (psdc_csd_process_frames_device), next to the same two pairs fed f32 (psdc_cross_process_device,
+2^22 samples a call and pair); both timed the same way, G pairs/s = pairs fed / second.
 """
 import argparse
 import json
@@ -79,13 +83,80 @@ def host_leg(pkg, n, call, seconds):
     return {"n": n, "call": call, "calls": calls, "seconds": round(dt, 4), "gpairs_s": round(calls * call / dt / 1e9, 3)}
 
 
+def timed(step, sync, seconds):
+    """pairs fed per second by back-to-back step() calls (each returns the pairs it fed): a window of >= seconds ending in sync()"""
+    for _ in range(3):
+        step()
+    sync()
+    calls = 4
+    while True:
+        t0 = time.perf_counter()
+        fed = sum(step() for _ in range(calls))
+        sync()
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return fed / dt, calls, dt
+        calls = int(calls * 1.2 * seconds / dt) + 1
+
+
+def frames_legs(pkg, torch, seconds):
+    call = 1 << 22
+    batches = 128
+    rng = np.random.default_rng(7)
+    w = rng.integers(-20000, 20000, size=(4, call), dtype=np.int64).astype(np.int16)
+    data, fs = pkg.make_adcdac_frames(w, batches)
+    nf = len(data) // fs
+    d = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
+    lsb = np.float32(4.096) * np.float32(2.5) / np.float32(32768.0)
+    tr = [torch.from_numpy(w[c].astype(np.float32) * lsb).cuda() for c in range(4)]
+    torch.cuda.synchronize()
+    pairs = [("ADC0", "DAC0"), ("ADC1", "DAC1")]
+    legs = []
+    for n in (512, 1024, 4096):
+        fb = pkg.CsdCascadeBank(n, 2)
+
+        def fstep():
+            fb.process_frames_device(d.data_ptr(), fs, nf, pairs)
+            return 2 * call
+
+        fr, fcalls, fdt = timed(fstep, fb.sync, seconds)
+        fb.stats_read(reset=True)
+        fstep()
+        flaunch = fb.stats_read()["launches"]
+        xb = pkg.CsdCascadeBank(n, 2)
+
+        def xstep():
+            xb.process_device(0, tr[0].data_ptr(), tr[2].data_ptr(), call)
+            xb.process_device(1, tr[1].data_ptr(), tr[3].data_ptr(), call)
+            return 2 * call
+
+        xr, xcalls, xdt = timed(xstep, xb.sync, seconds)
+        legs.append({"n": n, "pairs": 2, "call_samples_per_trace": call, "frame_size": fs,
+                     "frames_gpairs_s": round(fr / 1e9, 2), "frames_calls": fcalls, "frames_seconds": round(fdt, 4),
+                     "frames_launches_per_call": flaunch,
+                     "f32_gpairs_s": round(xr / 1e9, 2), "f32_calls": xcalls, "f32_seconds": round(xdt, 4),
+                     "ratio": round(fr / xr, 3)})
+        fb.close()
+        xb.close()
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--call-log2", type=int, default=24)
+    ap.add_argument("--frames", action="store_true", help="the frames leg only")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.frames:
+        line = json.dumps({"metric": "cross_frames_gpairs_s", "legs": frames_legs(pkg, torch, a.seconds)})
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     call = 1 << a.call_log2
     legs = [rate(pkg, torch, n, p, call, a.seconds) for n in (512, 1024, 4096) for p in (1, 4)]
     host = host_leg(pkg, 1024, 1 << 22, a.seconds)

@@ -4,10 +4,14 @@
 `psd(&merge_opts)`, `Break::frequencies`, `Trace::plot` (integrated RMS and plot points, `:125-157`).  Same option names and defaults
 as `SourceOpts` (file-backed subset, src/source.rs:16-48) and `AcqOpts` (src/bin/psd.rs:31-72).
 usage: tools/psd_cli.py (--file FRAMES [--frame-size N] | --raw RAW) [AcqOpts ...] [--max-bytes B] [--csv DIR]
-Prints one line per trace: name, stages, averages of the top stage, bins, integrated RMS; --csv writes DIR/<trace>.csv (the plot points)."""
+Prints one line per trace: name, stages, averages of the top stage, bins, integrated RMS; --csv writes DIR/<trace>.csv (the plot points).
+--pair X:Y (repeatable; trace labels or indices, frames only) also feeds the frames to a CsdCascadeBank(512, ...) and prints, per
+pair, its bins and median coherence; with --csv it writes DIR/<x>__<y>.csv (f, |H1|, arg H1, coherence; H1 = Sxy / Sxx)."""
 import argparse
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,7 +35,10 @@ def main(argv=None):
     ap.add_argument("--integral-end", type=float, default=0.5)
     ap.add_argument("--max-bytes", type=int, default=None, help="stop after this many input bytes (needed with --repeat)")
     ap.add_argument("--csv", default=None, help="directory for the plot points of every trace")
+    ap.add_argument("--pair", action="append", default=[], help="X:Y -- cross spectrum of traces X and Y (repeatable)")
     a = ap.parse_args(argv)
+    if a.pair and a.raw:
+        raise SystemExit("--pair needs --file")
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
@@ -71,12 +78,53 @@ def main(argv=None):
             safe = "".join(ch if ch.isalnum() else "_" for ch in name)
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(f"{x:.9g},{y:.9g}\n" for x, y in xy)
+    if a.pair:
+        cross_pairs(pkg, source, a, merge)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
         print(f"loss: {loss['dropped']} of {tot} batches ({(loss['dropped'] / tot if loss['received'] else 0.0):.3e})")  # Loss::analyze
     bank.close()
     return 0
+
+
+def cross_pairs(pkg, source, a, merge):
+    """--pair: the file's frames again, through the same Source reads, into one cross cascade per pair"""
+    pairs = [tuple(p.split(":", 1)) for p in a.pair]
+    if any(len(p) != 2 for p in pairs):
+        raise SystemExit("--pair takes X:Y")
+    pairs = [tuple(int(t) if t.isdigit() else t for t in p) for p in pairs]
+    cross = pkg.CsdCascadeBank(1 << 9, len(pairs))
+    cross.set_detrend(pkg.Detrend[a.detrend.upper()])
+    cross.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+
+    class Feed:  # what Source.feed calls on a bank
+        def process_frames(self, buf, fs):
+            cross.process_frames(buf, fs, pairs)
+
+    src = source.Source(source.SourceOpts(file=a.file, frame_size=a.frame_size, repeat=a.repeat), pkg)
+    total = 0
+    while a.max_bytes is None or total < a.max_bytes:
+        got = src.feed(Feed(), max_bytes=(64 << 20) if a.max_bytes is None else min(64 << 20, max(a.frame_size, a.max_bytes - total)))
+        if got == 0:
+            break
+        total += got
+    src.close()
+    for i, (x, y) in enumerate(pairs):
+        label = f"{x}:{y}"
+        if cross.num_stages(i) == 0:
+            print(f"{label}: no samples")
+            continue
+        sxx, syy, sxy, breaks = cross.csd(i, merge)
+        freqs = pkg.Break.frequencies(breaks) * a.fs
+        coh = pkg.coherence(sxx, syy, sxy)
+        h1 = pkg.transfer(sxx, sxy)
+        print(f"{label}: bins {sxx.size} median coherence {np.nanmedian(coh):.6g}")
+        if a.csv:
+            safe = "__".join("".join(ch if ch.isalnum() else "_" for ch in str(t)) for t in (x, y))
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(f"{fr:.9g},{abs(h):.9g},{np.angle(h):.9g},{c:.9g}\n" for fr, h, c in zip(freqs, h1, coh))
+    cross.close()
 
 
 if __name__ == "__main__":
