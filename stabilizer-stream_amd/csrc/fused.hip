@@ -81,6 +81,23 @@ __device__ __forceinline__ float team_bcast(float v, int team_lane0, int tl)
         return __shfl(v, team_lane0 + tl, 64);
 }
 
+// two floats to dwords dwa + lane and dwb + lane of the wavefront's LDS frame (m0: TeamFft::lds_base; dwa, dwb constants once the
+// loops are unrolled).  M0 is saved, set and restored in the block, as in TeamFft::store1_rows.  (One block per step of stage A and
+// not one for all four: the eight outputs would have to stay live to the end of the stage in a kernel that sits at 128 VGPRs.)
+__device__ __forceinline__ void addtid_st2(unsigned m0, int dwa, float xa, int dwb, float xb)
+{
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\t"
+                 "s_mov_b32 m0, %1\n\t"
+                 "s_nop 0\n\t"
+                 "ds_write_addtid_b32 %2 offset:%4\n\t"
+                 "ds_write_addtid_b32 %3 offset:%5\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(m0), "v"(xa), "v"(xb), "i"(4 * dwa), "i"(4 * dwb)
+                 : "memory");
+}
+
 // sum over the lanes of a team, the same value in every lane (row_sum16 / wave_sum64 of
 // fused_common.h; only the 32-lane team needs one shuffle to join its two rows)
 template <int TEAM>
@@ -337,6 +354,12 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
     cf *frame = s_frames + team * T::FRAME;
     float *sf = reinterpret_cast<float *>(frame);
     float *hs = s_hist + team * G::HIST; // [0,11) AE, [11,22) AO, [22,51) BE, [51,80) BO
+    const unsigned m0f = T::PLANES ? T::lds_base(frame) : 0u; // (TEAM == 64: the frame is the wavefront's)
+    if constexpr (T::PLANES) { // an add-tid store takes M0[15:0]: every frame of the workgroup must start below 64 KiB (s_frames is
+        // the kernel's first LDS array, so the last one starts at 60 928; a layout that ever moved it up would wrap silently)
+        if (T::lds_base(s_frames + (TEAMS - 1) * T::FRAME) >= T::M0_LIMIT)
+            __builtin_trap();
+    }
 
     const float ta[HBF_MA] = {PSDK_HBF_TAPS_A};
     const float tb[HBF_MB] = {PSDK_HBF_TAPS_B};
@@ -556,9 +579,13 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                 a1 += (s2w + cu.y) * ta[1];
                 a0 += (s2w + s1y) * ta[2];
                 a1 += (s1y + s1w) * ta[2];
-                const int u = tl + TEAM * r;
-                sf[G::AE + 11 + u] = s1x + a0;
-                sf[G::AO + 11 + u] = s1z + a1;
+                if constexpr (T::PLANES) { // "constant + lane": ds_write_addtid_b32, 2 store-path cycles where ds_write_b32 takes 4
+                    addtid_st2(m0f, G::AE + 11 + TEAM * r, s1x + a0, G::AO + 11 + TEAM * r, s1z + a1);
+                } else {
+                    const int u = tl + TEAM * r;
+                    sf[G::AE + 11 + u] = s1x + a0;
+                    sf[G::AO + 11 + u] = s1z + a1;
+                }
                 p1y = s1y;
                 p1w = s1w;
                 p2w = s2w;
@@ -764,10 +791,16 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
             Dft<T::R1>::run(v);
         else
             T::pass1(tl, v, s_tw1);
-        T::store1(tl, v, frame); // in place: each lane rewrites exactly what it read
+        if constexpr (T::PLANES)
+            T::store1_planes(tl, v, frame, m0f); // over the cf frame: every load1 of the wavefront is ahead of it in program order
+        else
+            T::store1(tl, v, frame); // in place: each lane rewrites exactly what it read
         wave_sync();
         PSDK_STAMP(7);
-        T::load2(tl, v, frame);
+        if constexpr (T::PLANES)
+            T::load2_planes(tl, v, frame);
+        else
+            T::load2(tl, v, frame);
         T::pass2(v);
         }
 #pragma unroll
