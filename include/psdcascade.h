@@ -568,6 +568,84 @@ int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, c
 /* the Loss counters of the frames the object ingested (psdc_loss_read); reset != 0 zeroes them after reading */
 int psdc_csd_loss_read(psdc_cross *h, psdc_loss *out, int reset);
 
+/* ---- cross-spectral matrix cascade -------------------------------------------------------------------------
+ * The full spectral matrix of a group of channels from ONE transform per channel: `n_groups` independent groups of `m`
+ * real f32 streams (2 <= m <= 4, fixed per object), the channels of a group always fed together with equal lengths.
+ * Per stage a group is m Psd<N> stages in lockstep exactly as a pair is two (see the cross-spectral density cascade
+ * above): the same segmentation, Window<N>, Detrend of each channel's segment separately, /8 half-band decimation of
+ * each channel with the drain of 35 outputs, lazy stages, EWMA factor g of src/psd.rs:218-233, 64-bit counts.  A group
+ * has exactly the stages, counts, pendings and Breaks of a PsdCascade fed channel 0 alone.  Per bin k <= N/2 a stage
+ * keeps the Hermitian matrix
+ *     S_ab[k] = g S_ab[k] + conj(X_a[k]) X_b[k],   0 <= a <= b < m
+ * with the pair object's sign convention (conj(X) Y, scipy.signal.csd).
+ * Row layout: m*m real rows of n/2 + 1 values, f64 on the device: row a*m + a is S_aa; for a < b, row a*m + b is
+ * Re S_ab and row b*m + a is Im S_ab.  For m = 2 these are the pair object's rows in the order xx, re, im, yy.
+ * The read-out is PsdCascade::psd (src/psd.rs:479-543) applied to each real row with the same bins, Breaks and
+ * 1 / (gain() decimation), as psdc_cross_csd does for its four rows.
+ * Each channel of a group is loaded, detrended, windowed, transformed and decimated once per segment and stage and has
+ * one stream buffer set per stage: six pairs of four traces cost four transforms and four decimations a segment, not
+ * twelve.
+ * Sizes: n a power of two 64 ... 2048 for every m, and 4096 for m = 2 and m = 3 (psdc_csm_supported).  n = 4096 with
+ * m = 4 is refused: its 144 accumulators a thread do not fit the registers beside the transform.  A refused size is
+ * PSDC_ERR_ARG with a text that names it (psdc_csm_last_error(NULL)).  Windows as for pairs.
+ * Stream ordering, the caller-keeps-memory rule, errors and the device rule are those of psdc_cross_*: status codes, a
+ * text per object, with a NULL object the calling thread's last failure; every call restores the caller's current
+ * device; there is no CPU fallback.
+ * Rounds: a process call is one round of three kernel launches (the segments of every (group, stage), the decimators, the
+ * fold + stream tails) whatever the depth and whatever m, as long as the round's job tables fit one launch each: 128
+ * (group, stage) segment jobs and 128 folds; 320 decimator jobs and 256 tail carries, m a (group, stage): 80 and 64
+ * (group, stage) at m = 4, 106 and 85 at m = 3, 160 and 128 at m = 2.  A round with more takes one more launch of a
+ * kind per table it overflows.  Read-outs run rounds until no stage has work.
+ * Determinism: workgroup partial rows are folded in f64 in a fixed order: the same calls give the same bits, and frames
+ * in host memory the same bits as the same frames in device memory.
+ * Memory: per (group, stage) two ping-pong buffers per channel as for pairs (m channels, not 2 per pair), plus 32 MB of
+ * pinned host staging per channel and object (2 x m x 16 MB). */
+typedef struct psdc_csm psdc_csm;
+/* 1 if an object of (n, m) can be created, else 0.  Pure host code. */
+int psdc_csm_supported(uint32_t n, uint32_t m);
+/* n_groups groups of m channels; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_csm *psdc_csm_create(uint32_t n, int window_kind, uint32_t m, uint32_t n_groups, int device);
+/* the same with a caller-built Window<N>, as psdc_cross_create_window */
+psdc_csm *psdc_csm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m,
+                                 uint32_t n_groups, int device);
+void psdc_csm_destroy(psdc_csm *h);
+int psdc_csm_reset(psdc_csm *h);
+/* Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere */
+int psdc_csm_set_detrend(psdc_csm *h, int detrend_kind);
+int psdc_csm_set_avg(psdc_csm *h, uint32_t limit, uint32_t count);
+/* x: m pointers to len samples each, host memory */
+int psdc_csm_process(psdc_csm *h, uint32_t group, const float *const *x, size_t len);
+/* d_x: m device pointers (the array itself is host memory); producer_event and the caller-keeps-memory rule as
+ * psdc_cross_process_device */
+int psdc_csm_process_device(psdc_csm *h, uint32_t group, const float *const *d_x, size_t len, void *producer_event);
+/* Stream frames into groups: the map has m * n_groups entries; channel c of group g takes trace group_traces[g*m + c]
+ * of every frame.  A group whose entries are all PSDC_TRACE_NONE is not fed; a group with some but not all
+ * PSDC_TRACE_NONE is PSDC_ERR_ARG before anything is ingested.  Headers, runs of one format, de::Error codes, *n_ok,
+ * header-only frames, the too-few-traces rule (PSDC_ERR_ARG at the run's first frame) and the cut into pieces of at
+ * most 2^22 samples a trace are those of psdc_csd_process_frames.  A cell is decoded once and stored once per group
+ * (one launch per 32 / m fed groups). */
+int psdc_csm_process_frames(psdc_csm *h, const uint32_t *group_traces, const uint8_t *frames, size_t frame_size,
+                            size_t n_frames, size_t *n_ok);
+int psdc_csm_process_frames_device(psdc_csm *h, const uint32_t *group_traces, const uint8_t *d_frames,
+                                   size_t frame_size, size_t n_frames, size_t *n_ok, void *producer_event);
+int psdc_csm_loss_read(psdc_csm *h, psdc_loss *out, int reset);
+int psdc_csm_sync(psdc_csm *h);
+int psdc_csm_num_stages(psdc_csm *h, uint32_t group);
+/* raw accumulators of one stage: rows m*m*(n/2+1) floats in the row layout above; stat and rows may be NULL */
+int psdc_csm_stage_spectra(psdc_csm *h, uint32_t group, uint32_t stage, psdc_stage_stat *stat, float *rows);
+/* PsdCascade::psd of every row: rows holds m*m rows of `cap` floats each, the first *len of each filled */
+int psdc_csm_csd(psdc_csm *h, uint32_t group, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                 float *rows, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* the stitch of psdc_csm_csd on caller-provided stages (rows_in: n_stages x m*m x (n/2+1), stage 0 first):
+ * psdc_stitch_window on each of the m*m rows, into rows (m*m rows of cap floats).  Pure host code. */
+int psdc_csm_stitch(uint32_t n, uint32_t m, float power, float nenbw, size_t overlap, uint32_t n_stages,
+                    const uint64_t *counts64, const uint32_t *avgs, const uint64_t *pendings, const float *rows_in,
+                    int keep_overlap, uint32_t min_count, int keep_transition_band, float *rows, size_t cap,
+                    size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and sample times accepted (one sample time = one sample of every channel of a group) */
+int psdc_csm_stats_read(psdc_csm *h, uint64_t *launches, uint64_t *sample_times_in, int reset);
+const char *psdc_csm_last_error(const psdc_csm *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -326,6 +326,27 @@ def lib():
     f("psdc_csd_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
     f("psdc_csd_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
     f("psdc_csd_loss_read", i32, [H, C.POINTER(_CLoss), i32])
+    pp = C.POINTER(C.c_void_p)
+    f("psdc_csm_supported", i32, [u32, u32])
+    f("psdc_csm_create", H, [u32, i32, u32, u32, i32])
+    f("psdc_csm_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, u32, i32])
+    f("psdc_csm_destroy", None, [H])
+    f("psdc_csm_reset", i32, [H])
+    f("psdc_csm_set_detrend", i32, [H, i32])
+    f("psdc_csm_set_avg", i32, [H, u32, u32])
+    f("psdc_csm_process", i32, [H, u32, pp, sz])
+    f("psdc_csm_process_device", i32, [H, u32, pp, sz, C.c_void_p])
+    f("psdc_csm_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_csm_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_csm_loss_read", i32, [H, C.POINTER(_CLoss), i32])
+    f("psdc_csm_sync", i32, [H])
+    f("psdc_csm_num_stages", i32, [H, u32])
+    f("psdc_csm_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
+    f("psdc_csm_csd", i32, [H, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_csm_stitch", i32, [u32, u32, C.c_float, C.c_float, sz, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp,
+                               i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_csm_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_csm_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -348,6 +369,10 @@ EXPORTS = [
     "psdc_cross_set_avg", "psdc_cross_process", "psdc_cross_process_device", "psdc_cross_sync", "psdc_cross_num_stages",
     "psdc_cross_stage_spectra", "psdc_cross_csd", "psdc_cross_stitch", "psdc_cross_stats_read", "psdc_cross_last_error",
     "psdc_csd_process_frames", "psdc_csd_process_frames_device", "psdc_csd_loss_read",
+    "psdc_csm_supported", "psdc_csm_create", "psdc_csm_create_window", "psdc_csm_destroy", "psdc_csm_reset",
+    "psdc_csm_set_detrend", "psdc_csm_set_avg", "psdc_csm_process", "psdc_csm_process_device", "psdc_csm_process_frames",
+    "psdc_csm_process_frames_device", "psdc_csm_loss_read", "psdc_csm_sync", "psdc_csm_num_stages", "psdc_csm_stage_spectra",
+    "psdc_csm_csd", "psdc_csm_stitch", "psdc_csm_stats_read", "psdc_csm_last_error",
 ]
 
 
@@ -820,6 +845,217 @@ class CsdCascade:
         self._b.close()
 
 
+def group_map(groups, m, n_groups):
+    """The psdc_csm_* map of `groups`: entry g is m traces -- indices or TRACE_NAMES labels -- or None (group g not fed);
+    groups past the end of the list are not fed."""
+    if len(groups) > n_groups:
+        raise PsdError(ERR_ARG, f"{len(groups)} groups for a bank of {n_groups}")
+    out = np.full(m * n_groups, TRACE_NONE, np.uint32)
+    for g, tr in enumerate(groups):
+        if tr is None:
+            continue
+        if len(tr) != m:
+            raise PsdError(ERR_ARG, f"group {g} names {len(tr)} traces for m = {m}")
+        out[m * g:m * g + m] = [trace_index(t) for t in tr]
+    return out
+
+
+def _raise_csm(code, h=None):
+    msg = lib().psdc_csm_last_error(h)
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
+
+
+def csm_supported(n, m):
+    """Whether CsmCascadeBank(n, m) can be created (psdc_csm_supported; pure host code)."""
+    return bool(0 <= n < 2 ** 32 and 0 <= m < 2 ** 32 and lib().psdc_csm_supported(n, m))
+
+
+def csm_matrix(rows, m):
+    """The Hermitian matrix (m, m, bins) complex64 of m*m real rows in the layout of include/psdcascade.h: row a*m + a is
+    S_aa, for a < b row a*m + b is Re S_ab and row b*m + a is Im S_ab.  Both sides filled, S[b, a] = conj(S[a, b])."""
+    rows = np.asarray(rows, np.float32).reshape(m * m, -1)
+    S = np.zeros((m, m, rows.shape[1]), np.complex64)
+    for a in range(m):
+        S[a, a] = rows[a * m + a]
+        for b in range(a + 1, m):
+            S[a, b].real, S[a, b].imag = rows[a * m + b], rows[b * m + a]
+            S[b, a] = np.conj(S[a, b])
+    return S
+
+
+class CsmCascadeBank:
+    """`n_groups` independent cross-spectral MATRIX cascades (psdc_csm_*): groups of m = 2 ... 4 streams fed together, each
+    transformed and decimated once a segment; per stage the Hermitian matrix S_ab = sum conj(X_a) X_b (the pair object's
+    convention).  The read-out is PsdCascade::psd applied to each real row: S[a, a] is the psd() of a PsdCascade fed channel a."""
+
+    def __init__(self, n, m, n_groups=1, window=Window.HANN, device=0):
+        self.n, self.m, self.n_groups, self.window, self.device = n, m, n_groups, window, device
+        self._L = lib()
+        if not (0 <= n < 2 ** 32 and 0 <= m < 2 ** 32):
+            raise PsdError(ERR_ARG, f"n = {n} with m = {m} is not supported")
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_csm_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, m, n_groups,
+                                                     device)
+        else:
+            self._h = self._L.psdc_csm_create(n, int(window), m, n_groups, device)
+        if not self._h:
+            msg = self._L.psdc_csm_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_csm_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_csm(rc, self._h)
+        return rc
+
+    def reset(self):
+        self._ck(self._L.psdc_csm_reset(self._h))
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_csm_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_csm_set_avg(self._h, avg.limit, avg.count))
+
+    def _ptrs(self, ptrs):
+        if len(ptrs) != self.m:
+            raise PsdError(ERR_ARG, f"{len(ptrs)} channels for m = {self.m}")
+        return (C.c_void_p * self.m)(*ptrs)
+
+    def process(self, group, xs):
+        """xs: m arrays of equal length, one per channel of the group"""
+        xs = [np.ascontiguousarray(x, dtype=np.float32) for x in xs]
+        if len({x.size for x in xs}) > 1:
+            raise PsdError(ERR_ARG, "the channels of a group must have equal lengths")
+        arr = self._ptrs([x.ctypes.data for x in xs])
+        self._ck(self._L.psdc_csm_process(self._h, group, arr, xs[0].size))
+
+    def process_device(self, group, ptrs, length, after=None):
+        """ptrs: m device addresses of `length` f32 samples each; after: a hipEvent_t handle recorded behind their producer
+        (torch.cuda.Event.cuda_event), or None when the producer has completed.  The samples must stay unchanged until
+        sync() or a read-out returns."""
+        self._ck(self._L.psdc_csm_process_device(self._h, group, self._ptrs([int(p) for p in ptrs]), length,
+                                                 C.c_void_p(after) if after else None))
+
+    def process_frames(self, data, frame_size, groups):
+        """Stream frames (bytes-like holding whole frames) into the groups: groups[g] = m traces (indices or TRACE_NAMES
+        labels) feeds group g, None leaves it unfed.  Returns the number of frames ingested; a bad frame raises FrameError
+        after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        gm = group_map(groups, self.m, self.n_groups)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_csm_process_frames(self._h, gm.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
+                                             frame_size, buf.size // frame_size, C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, groups, after=None):
+        """process_frames for frames resident in device memory at address `ptr` (CsdCascadeBank.process_frames_device)."""
+        gm = group_map(groups, self.m, self.n_groups)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_csm_process_frames_device(self._h, gm.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
+                                                    frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        l = _CLoss()
+        self._ck(self._L.psdc_csm_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
+    def sync(self):
+        self._ck(self._L.psdc_csm_sync(self._h))
+
+    def num_stages(self, group=0):
+        return self._ck(self._L.psdc_csm_num_stages(self._h, group))
+
+    def stage_spectra(self, group, stage):
+        """(info, S) of one stage's raw accumulators; S complex64 (m, m, n/2 + 1), Hermitian."""
+        st = _CStageStat()
+        rows = np.empty(self.m * self.m * (self.n // 2 + 1), np.float32)
+        self._ck(self._L.psdc_csm_stage_spectra(self._h, group, stage, C.byref(st), _fptr(rows)))
+        info = {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
+        return info, csm_matrix(rows, self.m)
+
+    def csd(self, group=0, opts=MergeOpts()):
+        """(S, breaks): S complex64 (m, m, bins), Hermitian and filled on both sides; PsdCascade::psd of each real row."""
+        ns = self.num_stages(group)
+        cap = max(1, ns * (self.n // 2 + 1))
+        rows = np.empty((self.m * self.m, cap), np.float32)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_csm_csd(self._h, group, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                      _fptr(rows), cap, C.byref(plen), br, ns, C.byref(nb)))
+        return csm_matrix(rows[:, :plen.value], self.m), [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_csm_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "sample_times_in": si.value}
+
+
+class CsmCascade:
+    """One group of m streams (CsmCascadeBank with n_groups = 1)."""
+
+    def __init__(self, n, m, window=Window.HANN, device=0):
+        self.n, self.m = n, m
+        self._b = CsmCascadeBank(n, m, 1, window, device)
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, xs):
+        self._b.process(0, xs)
+
+    def process_device(self, ptrs, length, after=None):
+        self._b.process_device(0, ptrs, length, after)
+
+    def process_frames(self, data, frame_size, group):
+        return self._b.process_frames(data, frame_size, [group])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, group, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [group], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        self._b.reset()
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
 def coherence(sxx, syy, sxy):
     """|Sxy|^2 / (Sxx Syy), NaN where the denominator is zero."""
     sxx, syy = np.asarray(sxx, np.float64), np.asarray(syy, np.float64)
@@ -835,6 +1071,42 @@ def transfer(sxx, sxy):
     sxy = np.asarray(sxy, np.complex128)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(sxx != 0, sxy / np.where(sxx != 0, sxx, 1.0), np.nan + 0j)
+
+
+def mimo_transfer(S, inputs, outputs):
+    """The multi-input H1 of a spectral matrix S (m, m, bins): H of shape (len(outputs), len(inputs), bins) solving
+    S[inputs, inputs] H^T = S[inputs, outputs] per bin, in complex128.  Unlike the single-input transfer() it is unbiased when
+    the inputs are correlated; with one input it equals transfer().  NaN where the input matrix is singular."""
+    S = np.asarray(S, np.complex128)
+    ii, oo = list(inputs), list(outputs)
+    sxx = np.moveaxis(S[np.ix_(ii, ii)], 2, 0)  # (bins, ni, ni)
+    sxy = np.moveaxis(S[np.ix_(ii, oo)], 2, 0)  # (bins, ni, no)
+    H = np.full((len(oo), len(ii), S.shape[2]), np.nan + 0j, np.complex128)
+    for k in range(S.shape[2]):
+        try:
+            H[:, :, k] = np.linalg.solve(sxx[k], sxy[k]).T
+        except np.linalg.LinAlgError:
+            pass
+    return H
+
+
+def multiple_coherence(S, inputs, output):
+    """S_xy^H S_xx^-1 S_xy / S_yy per bin (real, in [0, 1] up to rounding): the share of the output's power the inputs explain
+    together.  With one input it equals coherence().  NaN where S_yy is zero or the input matrix is singular."""
+    S = np.asarray(S, np.complex128)
+    ii = list(inputs)
+    sxx = np.moveaxis(S[np.ix_(ii, ii)], 2, 0)
+    sxy = np.moveaxis(S[np.ix_(ii, [output])], 2, 0)
+    syy = S[output, output].real
+    out = np.full(S.shape[2], np.nan)
+    for k in range(S.shape[2]):
+        if syy[k] == 0:
+            continue
+        try:
+            out[k] = (np.conj(sxy[k]).T @ np.linalg.solve(sxx[k], sxy[k]))[0, 0].real / syy[k]
+        except np.linalg.LinAlgError:
+            pass
+    return out
 
 
 class Psd:

@@ -38,10 +38,10 @@ struct CrossBatch {
     CrossJob jobs[CROSS_MAX_JOBS];
 };
 
-// acc[r][k] = g_total acc[r][k] + sum_b partial[b][r][k], in f64, b in order
+// acc[r][k] = g_total acc[r][k] + sum_b partial[b][r][k], in f64, b in order; r < CrossPostBatch::nrows
 struct CrossFoldJob {
     const float *partial;
-    double *acc; // [4][n/2 + 1]
+    double *acc; // [nrows][n/2 + 1]
     double g_total;
     int nparts;
     int pad;
@@ -62,6 +62,7 @@ struct CrossTailJob {
 struct CrossPostBatch {
     int nfold;
     int nbins;      // n/2 + 1
+    int nrows;      // real rows of every fold job: 4 for a pair, m * m for a group of m channels (csm.h)
     int fold_xb;    // workgroups per fold job (cross_fold_blocks)
     int ntail;
     int tail_blocks;
@@ -87,7 +88,7 @@ struct CrossFramesBatch {
 bool cross_supported(int n);             // 64 ... 4096, powers of two
 int cross_segments_per_tile(int n);
 int cross_block_threads(int n); // threads of a cross_kernel workgroup (one wavefront a SIMD: its registers allow no more)
-int cross_fold_blocks(int nbins); // workgroups of one fold job
+int cross_fold_blocks(int nrows, int nbins); // workgroups of one fold job
 hipError_t launch_cross(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s);
 hipError_t launch_cross_post(const CrossPostBatch &b, hipStream_t s);
 hipError_t launch_cross_frames(const CrossFramesBatch &b, hipStream_t s);

@@ -1,0 +1,160 @@
+// cross_channel.h -- one channel of the cross-spectral kernels, shared by cross.hip (pairs) and csm.hip (groups of m channels):
+// load, detrend and window two consecutive segments of a channel, transform them as one complex signal and leave the spectrum
+// in natural order in an LDS frame (cross_fft.h).  Device code only.
+#pragma once
+#include "cross_fft.h"
+
+namespace psdk {
+
+template <int N>
+struct CrossCfg {
+    using Plan = FftPlan<N>;
+    static constexpr int E = Plan::E;
+    static constexpr int TEAM = Plan::TEAM;
+    static constexpr int BLOCK = TEAM > 128 ? TEAM : 128;
+    static constexpr int TEAMS = BLOCK / TEAM;
+    static constexpr int SPT = 2 * TEAMS; // segments per tile: one pair a team (fine tiles keep the workgroups of a launch even)
+    static constexpr int WAVES = BLOCK / 64;
+    static constexpr int H = N / 2 + 1;
+    static constexpr int FRAME = LdsFrame<N>::SIZE;
+    static_assert(E == 16, "cross kernel: sixteen elements a thread");
+    static_assert(H <= FRAME, "partial rows reuse the frames' LDS");
+};
+
+template <class Job>
+__device__ __forceinline__ float cross_amp(const Job &job, int step)
+{
+    const int m = step > job.is_m1 ? step : job.is_m1;
+    const int na = job.nb - m;
+    if (na <= 0)
+        return 1.0f;
+    return (float)exp2(0.5 * (double)na * job.log2_gamma);
+}
+
+template <int TEAM>
+__device__ __forceinline__ void xteam_sync()
+{
+    if constexpr (TEAM <= 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+template <int N, int P>
+__device__ __forceinline__ void xfft_run(int t, cf *v, cf *frame, const cf *__restrict__ tw)
+{
+    using PI = PassInfo<N, P>;
+    if constexpr (P == 0)
+        xteam_sync<PI::TEAM>(); // the frame's previous readers (separation) are done
+    xfft_pass<N, P>(t, v, frame, tw);
+    xteam_sync<PI::TEAM>();
+    if constexpr (!PI::LAST)
+        xfft_run<N, P + 1>(t, v, frame, tw);
+}
+
+// Load, detrend, window one channel's segment pair (a = segment la, b = la + 1) into v, transform, and leave the spectrum of
+// z = a + i b in natural order in `frame`.
+template <int N>
+__device__ __forceinline__ void cross_channel(const float *__restrict__ src, long long ofs_la, long long ofs_lb, bool act_a,
+                                              bool act_b, int detrend, float ampa, float ampb, int t, int team, cf *frame,
+                                              float *red, const float *__restrict__ win, const cf *__restrict__ tw)
+{
+    using Cfg = CrossCfg<N>;
+    using P0 = PassInfo<N, 0>;
+    constexpr int E = Cfg::E, TEAM = Cfg::TEAM;
+    float ra[E], rb[E];
+#pragma unroll
+    for (int i = 0; i < P0::NB; ++i)
+#pragma unroll
+        for (int m = 0; m < P0::R; ++m) {
+            const int nidx = P0::elem(t, i, m);
+            const float va = src[ofs_la + nidx], vb = src[ofs_lb + nidx];
+            ra[i * P0::R + m] = act_a ? va : 0.0f;
+            rb[i * P0::R + m] = act_b ? vb : 0.0f;
+        }
+    // detrend as welch_kernel: (x - o) - (m + n s)
+    float oa = 0.0f, ob = 0.0f, ma = 0.0f, mb = 0.0f;
+    slope2 sa = {0.0f, 0.0f}, sb = {0.0f, 0.0f};
+    if (detrend == 1) { // Midpoint src/psd.rs:87-93
+        const float va = src[ofs_la + N / 2], vb = src[ofs_lb + N / 2];
+        oa = act_a ? va : 0.0f;
+        ob = act_b ? vb : 0.0f;
+    } else if (detrend == 2) { // Span :94-102
+        const float a0 = src[ofs_la], a1 = src[ofs_la + N - 1], b0 = src[ofs_lb], b1 = src[ofs_lb + N - 1];
+        if (act_a) {
+            oa = a0;
+            sa = span_slope(oa, a1, N);
+        }
+        if (act_b) {
+            ob = b0;
+            sb = span_slope(ob, b1, N);
+        }
+    } else if (detrend == 3) { // Mean :103-109: o = f32 mean, m = mean of x - o
+        auto team_sum2 = [&](float &pa, float &pb) __attribute__((always_inline)) {
+            constexpr int W = TEAM < 64 ? TEAM : 64;
+#pragma unroll
+            for (int o = W / 2; o > 0; o >>= 1) {
+                pa += __shfl_xor(pa, o);
+                pb += __shfl_xor(pb, o);
+            }
+            if constexpr (TEAM > 64) { // one team a workgroup: combine its wavefronts through LDS
+                constexpr int WPT = TEAM / 64;
+                const int w = threadIdx.x >> 6;
+                if ((threadIdx.x & 63) == 0) {
+                    red[2 * w] = pa;
+                    red[2 * w + 1] = pb;
+                }
+                __syncthreads();
+                pa = 0.0f;
+                pb = 0.0f;
+                for (int i = 0; i < WPT; ++i) {
+                    pa += red[2 * (team * WPT + i)];
+                    pb += red[2 * (team * WPT + i) + 1];
+                }
+                __syncthreads();
+            }
+        };
+        float pa = 0.0f, pb = 0.0f;
+#pragma unroll
+        for (int s = 0; s < E; ++s) {
+            pa += ra[s];
+            pb += rb[s];
+        }
+        team_sum2(pa, pb);
+        oa = pa / (float)N;
+        ob = pb / (float)N;
+        pa = 0.0f;
+        pb = 0.0f;
+#pragma unroll
+        for (int s = 0; s < E; ++s) {
+            pa += ra[s] - oa;
+            pb += rb[s] - ob;
+        }
+        team_sum2(pa, pb);
+        ma = pa / (float)N;
+        mb = pb / (float)N;
+    }
+    cf v[E];
+#pragma unroll
+    for (int i = 0; i < P0::NB; ++i)
+#pragma unroll
+        for (int m = 0; m < P0::R; ++m) {
+            const int s = i * P0::R + m;
+            const int nidx = P0::elem(t, i, m);
+            const float w = win[nidx];
+            float a = ra[s], b = rb[s];
+            if (detrend != 0) {
+                a = fmaf(-(float)nidx, sa.lo, fmaf(-(float)nidx, sa.hi, a - oa)) - ma;
+                b = fmaf(-(float)nidx, sb.lo, fmaf(-(float)nidx, sb.hi, b - ob)) - mb;
+            }
+            v[s].re = a * w * ampa;
+            v[s].im = b * w * ampb;
+        }
+    xfft_run<N, 0>(t, v, frame, tw);
+    store_natural<N>(t, v, frame);
+}
+
+} // namespace psdk

@@ -1,4 +1,7 @@
-// cross_runtime.cpp -- the cross-spectral density cascade behind psdc_cross_* (include/psdcascade.h).
+// cross_runtime.cpp -- the cross-spectral cascades behind psdc_cross_* / psdc_csd_* (pairs) and psdc_csm_* (groups of m = 2 ... 4
+// channels with their full spectral matrix) of include/psdcascade.h.  One runtime over the channel count: a pair object is
+// m = 2 on cross_kernel with the rows xx, yy, re, im; a matrix object runs csm_kernel<N, M> with m * m rows (csm_fft.h).  Below,
+// "pair" stands for either unit.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -11,7 +14,7 @@
 // Stage k + 1 consumes what stage k produced in earlier rounds, so a round is three launches whatever the depth and the pair
 // count (more only when a round's job tables overflow a launch).  Read-outs drain: rounds until no stage has work.
 // There is no CPU compute path.
-#include "cross.h"
+#include "csm.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -19,6 +22,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace psdk;
@@ -34,7 +38,7 @@ constexpr size_t PIECE_SAMPLES = (size_t)1 << 22;            // a frames call is
 thread_local std::string x_last_error;
 
 struct XBuf {
-    float *p[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; // [channel][ping-pong]
+    float *p[CSM_MAX_M][2] = {}; // [channel][ping-pong]
     int cur = 0;
     size_t cap = 0;    // floats per buffer
     uint64_t base = 0; // absolute stream index of p[c][cur][0] (both channels)
@@ -46,13 +50,15 @@ struct XStage {
     uint64_t dec = 0;   // samples handed to the decimator
     uint64_t count64 = 0;
     XBuf buf;
-    double *acc = nullptr; // device [4][n/2 + 1]: xx, yy, re xy, im xy
+    double *acc = nullptr; // device [rows][n/2 + 1]: xx, yy, re xy, im xy of a pair; the m * m rows of csm_fft.h of a group
 };
 
-} // namespace
-
-struct psdc_cross {
+struct XObj {
     uint32_t n = 0, n_pairs = 0;
+    uint32_t m = 2;      // channels of a pair / group
+    bool matrix = false; // psdc_csm: csm_kernel and its row layout
+    const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
+    uint32_t rows() const { return matrix ? m * m : 4; }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -74,7 +80,7 @@ struct psdc_cross {
     std::vector<std::vector<XStage>> pairs;
     float *d_partial = nullptr;
     size_t partial_cap = 0;
-    float *h_stage[2] = {nullptr, nullptr}; // pinned staging: [2 channels][STAGING] each
+    float *h_stage[2] = {nullptr, nullptr}; // pinned staging: [m channels][STAGING] each
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     bool ev_pending[2] = {false, false};
     int stage_cur = 0;
@@ -93,9 +99,16 @@ struct psdc_cross {
     std::string err;
 };
 
+} // namespace
+
+struct psdc_cross : XObj {};
+struct psdc_csm : XObj {};
+
 namespace {
 
-int xfail(psdc_cross *h, int code, const std::string &msg)
+static_assert(CSM_MAX_JOBS == CROSS_MAX_JOBS, "one job table length for both segment kernels");
+
+int xfail(XObj *h, int code, const std::string &msg)
 {
     if (h)
         h->err = msg;
@@ -115,8 +128,8 @@ int xfail(psdc_cross *h, int code, const std::string &msg)
     if (dev_scope_.err != hipSuccess)                                                                                  \
     return xfail(h, PSDC_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(dev_scope_.err))
 
-size_t bins(const psdc_cross *h) { return h->n / 2 + 1; }
-uint32_t cur_avg(const psdc_cross *h, size_t k) { return stage_avg(h->avg_limit, h->avg_count, (unsigned)k); }
+size_t bins(const XObj *h) { return h->n / 2 + 1; }
+uint32_t cur_avg(const XObj *h, size_t k) { return stage_avg(h->avg_limit, h->avg_count, (unsigned)k); }
 
 // lowest absolute index a stage keeps: the decimator's history, which also covers the next segment
 uint64_t keep_from(const Geometry &g, const XStage &s)
@@ -127,7 +140,7 @@ uint64_t keep_from(const Geometry &g, const XStage &s)
     return s.dec > back ? s.dec - back : 0;
 }
 
-int free_retired(psdc_cross *h)
+int free_retired(XObj *h)
 {
     for (void *p : h->retired)
         XCHK(h, hipFree(p));
@@ -137,7 +150,7 @@ int free_retired(psdc_cross *h)
 
 // room for the stream up to absolute index new_end in the current buffers; growing allocates a new pair of buffers and
 // copies what the stage holds on the stream (no host wait); the old ones are retired
-int ensure_room(psdc_cross *h, XStage &s, uint64_t new_end)
+int ensure_room(XObj *h, XStage &s, uint64_t new_end)
 {
     const size_t need = (size_t)(new_end - s.buf.base);
     if (need <= s.buf.cap)
@@ -146,12 +159,12 @@ int ensure_room(psdc_cross *h, XStage &s, uint64_t new_end)
     XBuf nb;
     nb.cap = cap;
     nb.base = s.buf.base;
-    for (int c = 0; c < 2; ++c)
+    for (uint32_t c = 0; c < h->m; ++c)
         for (int i = 0; i < 2; ++i)
             XCHK(h, hipMalloc(&nb.p[c][i], sizeof(float) * cap));
     const size_t held = (size_t)(s.total - s.buf.base);
     h->grew = true;
-    for (int c = 0; c < 2; ++c) {
+    for (uint32_t c = 0; c < h->m; ++c) {
         if (held)
             XCHK(h, hipMemcpyAsync(nb.p[c][0], s.buf.p[c][s.buf.cur], sizeof(float) * held, hipMemcpyDeviceToDevice, h->stream));
         for (int i = 0; i < 2; ++i)
@@ -162,18 +175,18 @@ int ensure_room(psdc_cross *h, XStage &s, uint64_t new_end)
     return PSDC_OK;
 }
 
-int add_stage(psdc_cross *h, std::vector<XStage> &st)
+int add_stage(XObj *h, std::vector<XStage> &st)
 {
     if (st.size() >= X_MAX_STAGES)
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross: more than 16 stages");
+        return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": more than 16 stages");
     XStage s;
-    XCHK(h, hipMalloc(&s.acc, sizeof(double) * 4 * bins(h)));
-    XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * 4 * bins(h), h->stream));
+    XCHK(h, hipMalloc(&s.acc, sizeof(double) * h->rows() * bins(h)));
+    XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * h->rows() * bins(h), h->stream));
     st.push_back(s);
     return PSDC_OK;
 }
 
-int ensure_partial(psdc_cross *h, size_t floats)
+int ensure_partial(XObj *h, size_t floats)
 {
     if (floats <= h->partial_cap)
         return PSDC_OK;
@@ -187,15 +200,36 @@ int ensure_partial(psdc_cross *h, size_t floats)
 }
 
 struct PlannedCross {
-    CrossJob job;
+    CsmJob job; // (CrossJob's fields with room for four channels)
     CrossFoldJob fold;
 };
 
+CrossJob pair_job(const CsmJob &j)
+{
+    CrossJob c{};
+    c.src[0] = j.src[0];
+    c.src[1] = j.src[1];
+    c.src_base = j.src_base;
+    c.seg0 = j.seg0;
+    c.partial = j.partial;
+    c.log2_gamma = j.log2_gamma;
+    c.nseg = j.nseg;
+    c.block_begin = j.block_begin;
+    c.nblocks = j.nblocks;
+    c.ntiles = j.ntiles;
+    c.step0 = j.step0;
+    c.nb = j.nb;
+    c.is_m1 = j.is_m1;
+    c.ewma = j.ewma;
+    return c;
+}
+
 // one pipeline round over every (pair, stage); *did: some stage had work
-int run_round(psdc_cross *h, bool *did)
+int run_round(XObj *h, bool *did)
 {
     const Geometry &g = h->geo;
-    const int spt = cross_segments_per_tile((int)h->n);
+    const int spt = h->matrix ? csm_segments_per_tile((int)h->n, (int)h->m) : cross_segments_per_tile((int)h->n);
+    const int nch = (int)h->m;
     std::vector<PlannedCross> cross;
     std::vector<DecJob> decs;
     std::vector<CrossTailJob> tails;
@@ -210,13 +244,13 @@ int run_round(psdc_cross *h, bool *did)
             XStage &s = st[k];
             const uint64_t nb = j_new - s.segs;
             if (nb > (uint64_t)std::numeric_limits<int>::max() / 2)
-                return xfail(h, PSDC_ERR_ARG, "psdc_cross: too many segments in one round");
+                return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": too many segments in one round");
             const uint32_t avg = cur_avg(h, k);
             const EwmaPlan ew = plan_ewma(count_report(s.count64), avg, nb);
             PlannedCross pc{};
-            CrossJob &cj = pc.job;
-            cj.src[0] = s.buf.p[0][s.buf.cur];
-            cj.src[1] = s.buf.p[1][s.buf.cur];
+            CsmJob &cj = pc.job;
+            for (int c = 0; c < nch; ++c)
+                cj.src[c] = s.buf.p[c][s.buf.cur];
             cj.src_base = (long long)s.buf.base;
             cj.seg0 = (long long)s.segs;
             cj.log2_gamma = ew.gamma > 0.0f ? std::log2((double)ew.gamma) : -std::numeric_limits<double>::infinity();
@@ -244,7 +278,7 @@ int run_round(psdc_cross *h, bool *did)
                 if (rc)
                     return rc;
                 const uint64_t m0 = std::max<uint64_t>(s0.dec >> 3, g.drain), m1 = p_new >> 3;
-                for (int c = 0; c < 2; ++c) {
+                for (int c = 0; c < nch; ++c) {
                     DecJob dj{};
                     dj.src = s0.buf.p[c][s0.buf.cur];
                     dj.src_base = (long long)s0.buf.base;
@@ -268,7 +302,7 @@ int run_round(psdc_cross *h, bool *did)
                 continue;
             const uint64_t count = s.total - keep;
             if (count) {
-                for (int c = 0; c < 2; ++c) {
+                for (int c = 0; c < nch; ++c) {
                     CrossTailJob tj{};
                     tj.src = s.buf.p[c][s.buf.cur] + (keep - s.buf.base);
                     tj.dst = s.buf.p[c][s.buf.cur ^ 1];
@@ -288,7 +322,7 @@ int run_round(psdc_cross *h, bool *did)
     // partial slab and workgroups: every workgroup of a launch walks the same number of tiles, and the launch's workgroups are
     // about what the device holds at once (a job of few tiles next to one of many would otherwise make some workgroups walk
     // one tile more than the rest: a round with the decimated stages read 240 us where stage 0 alone read 160)
-    const size_t rows = 4 * bins(h);
+    const size_t rows = h->rows() * bins(h);
     std::vector<int> nblk(cross.size());
     size_t slab = 0;
     for (size_t b0 = 0; b0 < cross.size(); b0 += CROSS_MAX_JOBS) {
@@ -308,22 +342,36 @@ int run_round(psdc_cross *h, bool *did)
         return rc;
     size_t off = 0;
     for (size_t b0 = 0; b0 < cross.size(); b0 += CROSS_MAX_JOBS) {
-        CrossBatch *cb = new CrossBatch();
-        cb->hop = (int)g.hop;
-        cb->detrend = h->detrend;
+        int nblocks = 0;
         for (size_t i = b0; i < std::min(cross.size(), b0 + CROSS_MAX_JOBS); ++i) {
-            CrossJob &cj = cross[i].job;
+            CsmJob &cj = cross[i].job;
             cj.partial = h->d_partial + off;
             cj.nblocks = nblk[i];
-            cj.block_begin = cb->nblocks;
+            cj.block_begin = nblocks;
             cross[i].fold.partial = cj.partial;
             cross[i].fold.nparts = nblk[i];
             off += (size_t)nblk[i] * rows;
-            cb->jobs[cb->njobs++] = cj;
-            cb->nblocks += nblk[i];
+            nblocks += nblk[i];
         }
-        hipError_t e = launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
-        delete cb;
+        auto fill = [&](auto *cb, auto conv) {
+            cb->hop = (int)g.hop;
+            cb->detrend = h->detrend;
+            cb->nblocks = nblocks;
+            for (size_t i = b0; i < std::min(cross.size(), b0 + CROSS_MAX_JOBS); ++i)
+                cb->jobs[cb->njobs++] = conv(cross[i].job);
+        };
+        hipError_t e;
+        if (h->matrix) {
+            CsmBatch *cb = new CsmBatch();
+            fill(cb, [](const CsmJob &j) { return j; });
+            e = launch_csm((int)h->n, (int)h->m, *cb, h->d_win, h->d_tw, h->stream);
+            delete cb;
+        } else {
+            CrossBatch *cb = new CrossBatch();
+            fill(cb, pair_job);
+            e = launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
+            delete cb;
+        }
         XCHK(h, e);
         ++h->launches;
     }
@@ -347,7 +395,8 @@ int run_round(psdc_cross *h, bool *did)
     while (fi < cross.size() || ti < tails.size()) {
         CrossPostBatch *pb = new CrossPostBatch();
         pb->nbins = (int)bins(h);
-        pb->fold_xb = cross_fold_blocks((int)bins(h));
+        pb->nrows = (int)h->rows();
+        pb->fold_xb = cross_fold_blocks((int)h->rows(), (int)bins(h));
         for (; fi < cross.size() && pb->nfold < CROSS_MAX_FOLD; ++fi)
             pb->fold[pb->nfold++] = cross[fi].fold;
         for (; ti < tails.size() && pb->ntail < CROSS_MAX_TAIL; ++ti) {
@@ -368,7 +417,7 @@ int run_round(psdc_cross *h, bool *did)
     return PSDC_OK;
 }
 
-int drain(psdc_cross *h)
+int drain(XObj *h)
 {
     if (h->idle)
         return PSDC_OK;
@@ -384,7 +433,7 @@ int drain(psdc_cross *h)
     return PSDC_OK;
 }
 
-int sync_all(psdc_cross *h)
+int sync_all(XObj *h)
 {
     XCHK(h, hipStreamSynchronize(h->copy_stream));
     XCHK(h, hipStreamSynchronize(h->stream));
@@ -393,16 +442,16 @@ int sync_all(psdc_cross *h)
     return free_retired(h);
 }
 
-int check_pair(psdc_cross *h, uint32_t pair)
+int check_pair(XObj *h, uint32_t pair)
 {
     if (pair >= h->n_pairs)
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross: pair " + std::to_string(pair) + " out of range (n_pairs " +
-                                          std::to_string(h->n_pairs) + ")");
+        return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": " + h->unit + " " + std::to_string(pair) + " out of range (" +
+                                          h->units + " " + std::to_string(h->n_pairs) + ")");
     return PSDC_OK;
 }
 
 // stage 0 of a pair takes len more samples of each channel: room for them, and where they go
-int stage0_room(psdc_cross *h, uint32_t pair, size_t len, XStage **out)
+int stage0_room(XObj *h, uint32_t pair, size_t len, XStage **out)
 {
     auto &st = h->pairs[pair];
     if (st.empty()) {
@@ -417,13 +466,13 @@ int stage0_room(psdc_cross *h, uint32_t pair, size_t len, XStage **out)
     return PSDC_OK;
 }
 
-void free_all(psdc_cross *h)
+void free_all(XObj *h)
 {
     (void)hipStreamSynchronize(h->copy_stream);
     (void)hipStreamSynchronize(h->stream);
     for (auto &st : h->pairs)
         for (auto &s : st) {
-            for (int c = 0; c < 2; ++c)
+            for (int c = 0; c < CSM_MAX_M; ++c)
                 for (int i = 0; i < 2; ++i)
                     if (s.buf.p[c][i])
                         (void)hipFree(s.buf.p[c][i]);
@@ -441,9 +490,18 @@ void free_all(psdc_cross *h)
     h->idle = true;
 }
 
-const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs)
+// the sizes of a matrix object, as text for a refusal
+std::string csm_size_text(uint32_t n, uint32_t m)
 {
-    if (n < 64 || n > 4096 || (n & (n - 1)) != 0)
+    if (m < 2 || m > CSM_MAX_M)
+        return "m = " + std::to_string(m) + " is not supported: a group has 2 to 4 channels";
+    return "n = " + std::to_string(n) + " with m = " + std::to_string(m) +
+           " is not supported: n must be a power of two in [64, 2048], or 4096 with m = 2 or 3";
+}
+
+const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, bool matrix)
+{
+    if (!matrix && (n < 64 || n > 4096 || (n & (n - 1)) != 0))
         return "n must be a power of two in [64, 4096]";
     if (!win)
         return "null window table";
@@ -452,14 +510,23 @@ const char *check_args(uint32_t n, const float *win, float power, float nenbw, s
     if (!(power > 0.0f) || !(nenbw > 0.0f))
         return "window power and nenbw must be > 0";
     if (n_pairs < 1 || n_pairs > X_MAX_PAIRS)
-        return "n_pairs must be in [1, 65536]";
+        return matrix ? "n_groups must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
     return nullptr;
 }
 
-psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, int device,
-                        const char *who)
+void destroy_impl(XObj *h);
+
+// T = psdc_cross (m = 2, cross_kernel) or psdc_csm (2 <= m <= 4, csm_kernel)
+template <class T>
+T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
+               const char *who)
 {
-    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs)) {
+    constexpr bool matrix = std::is_same<T, psdc_csm>::value;
+    if (matrix && !csm_supported((int)n, (int)m)) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
+        return nullptr;
+    }
+    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
         return nullptr;
     }
@@ -479,8 +546,15 @@ psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, 
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": hipSetDevice: " + hipGetErrorString(scope.err));
         return nullptr;
     }
-    psdc_cross *h = new psdc_cross();
+    T *h = new T();
     h->n = n;
+    h->m = m;
+    h->matrix = matrix;
+    if (matrix) {
+        h->tag = "psdc_csm";
+        h->unit = "group";
+        h->units = "n_groups";
+    }
     h->n_pairs = n_pairs;
     h->device = device;
     h->geo.n = n;
@@ -494,7 +568,8 @@ psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, 
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
         // twice what is resident at one wavefront a SIMD (the kernel's registers allow no more); once and twice read the same
         // end to end within the noise of tools/cross_probe.py (N = 1024, one pair: 43.9 against 45.4 G pairs/s)
-        h->resident = std::max<int64_t>(1, 2 * (int64_t)cus * 4 * 64 / cross_block_threads((int)n));
+        h->resident = std::max<int64_t>(1, 2 * (int64_t)cus * 4 * 64 /
+                                               (matrix ? csm_block_threads((int)n, (int)m) : cross_block_threads((int)n)));
     std::vector<cf> tw(n);
     for (uint32_t j = 0; j < n; ++j) {
         const double a = -2.0 * M_PI * (double)j / (double)n;
@@ -510,11 +585,12 @@ psdc_cross *create_impl(uint32_t n, const float *win, float power, float nenbw, 
               hipMemcpy(h->d_win, win, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_tw, tw.data(), sizeof(cf) * n, hipMemcpyHostToDevice) == hipSuccess;
     for (int i = 0; ok && i < 2; ++i)
-        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * 2 * STAGING) == hipSuccess &&
+        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * m * STAGING) == hipSuccess &&
              hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": device allocation failed");
-        psdc_cross_destroy(h);
+        destroy_impl(h);
+        delete h;
         return nullptr;
     }
     return h;
@@ -538,26 +614,38 @@ const XWireFmt *x_wire_fmt(int id)
 }
 
 struct FedPair {
-    uint32_t pair, tx, ty;
+    uint32_t pair;
+    uint32_t tr[CSM_MAX_M]; // the trace of each channel
 };
 
 // the pairs a call feeds, from its map; PSDC_ERR_ARG for a NULL map, an entry with exactly one PSDC_TRACE_NONE or a trace no
 // format carries
-int read_map(psdc_cross *h, const uint32_t *map, const char *who, std::vector<FedPair> *fed)
+int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair> *fed)
 {
     if (!map)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null pair map");
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null " + h->unit + " map");
     fed->clear();
     for (uint32_t p = 0; p < h->n_pairs; ++p) {
-        const uint32_t tx = map[2 * p], ty = map[2 * p + 1];
-        if ((tx == PSDC_TRACE_NONE) != (ty == PSDC_TRACE_NONE))
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(p) + " names one trace and PSDC_TRACE_NONE");
-        if (tx == PSDC_TRACE_NONE)
+        FedPair fp{};
+        fp.pair = p;
+        uint32_t none = 0, top = 0;
+        for (uint32_t c = 0; c < h->m; ++c) {
+            fp.tr[c] = map[h->m * p + c];
+            if (fp.tr[c] == PSDC_TRACE_NONE)
+                ++none;
+            else
+                top = std::max(top, fp.tr[c]);
+        }
+        if (none == h->m)
             continue;
-        if (tx >= 4 || ty >= 4)
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(p) + " names trace " +
-                                              std::to_string(std::max(tx, ty)) + " (frames carry at most 4)");
-        fed->push_back({p, tx, ty});
+        if (none)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) +
+                                              (h->m == 2 ? " names one trace and PSDC_TRACE_NONE"
+                                                         : " names PSDC_TRACE_NONE for some of its traces only"));
+        if (top >= 4)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) + " names trace " +
+                                              std::to_string(top) + " (frames carry at most 4)");
+        fed->push_back(fp);
     }
     return PSDC_OK;
 }
@@ -571,9 +659,9 @@ struct FrameSrc {
     size_t hdr_stride = 0;
 };
 
-// decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[2 i + c] (pair fed[i], channel
-// c), one launch per 16 pairs, on the copy stream
-int decode_frames(psdc_cross *h, const FrameSrc &src, size_t frame_size, const XWireFmt *wf, int batches, size_t f, size_t cnt,
+// decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[m i + c] (pair fed[i], channel
+// c), one launch per 32 / m pairs, on the copy stream
+int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const XWireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
     const uint8_t *frames = src.dev ? src.dev + f * frame_size : nullptr;
@@ -592,17 +680,18 @@ int decode_frames(psdc_cross *h, const FrameSrc &src, size_t frame_size, const X
         h->stage_cur ^= 1;
         frames = h->d_frames;
     }
-    for (size_t i0 = 0; i0 < fed.size(); i0 += CROSS_FRAMES_MAX_DST / 2) {
+    const size_t per_launch = CROSS_FRAMES_MAX_DST / h->m;
+    for (size_t i0 = 0; i0 < fed.size(); i0 += per_launch) {
         CrossFramesBatch b{};
         b.frames = frames;
         b.frame_size = frame_size;
         b.n_frames = (unsigned)cnt;
         b.batches = batches;
         b.fmt = wf->id;
-        for (size_t i = i0; i < std::min(fed.size(), i0 + CROSS_FRAMES_MAX_DST / 2); ++i)
-            for (int c = 0; c < 2; ++c) {
-                b.trace[b.ndst] = (int)(c ? fed[i].ty : fed[i].tx);
-                b.dst[b.ndst] = dst[2 * i + c] + dst_off;
+        for (size_t i = i0; i < std::min(fed.size(), i0 + per_launch); ++i)
+            for (uint32_t c = 0; c < h->m; ++c) {
+                b.trace[b.ndst] = (int)fed[i].tr[c];
+                b.dst[b.ndst] = dst[h->m * i + c] + dst_off;
                 ++b.ndst;
             }
         XCHK(h, launch_cross_frames(b, h->copy_stream));
@@ -615,7 +704,7 @@ int decode_frames(psdc_cross *h, const FrameSrc &src, size_t frame_size, const X
 // header validated on the host, Loss committed piece by piece once the piece's samples are in the streams.  A run is cut into
 // pieces of whole frames of <= PIECE_SAMPLES samples a trace; each piece is decoded and followed by one round.  The cut depends on
 // the headers alone, so host and device frames give the same rounds.
-int ingest_frames(psdc_cross *h, const std::vector<FedPair> &fed, const FrameSrc &src, size_t frame_size, size_t n_frames,
+int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src, size_t frame_size, size_t n_frames,
                   size_t *good_out, const char *who)
 {
     size_t &good = *good_out;
@@ -634,11 +723,13 @@ int ingest_frames(psdc_cross *h, const std::vector<FedPair> &fed, const FrameSrc
             bad = PSDC_ERR_FRAME_FORMAT;
             break;
         }
-        for (const FedPair &fp : fed)
-            if ((int)std::max(fp.tx, fp.ty) >= wf->ntr)
-                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(fp.pair) + " names trace " +
-                                                  std::to_string(std::max(fp.tx, fp.ty)) + " but " + wf->what + " frames carry " +
+        for (const FedPair &fp : fed) {
+            const uint32_t top = *std::max_element(fp.tr, fp.tr + h->m);
+            if ((int)top >= wf->ntr)
+                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(fp.pair) + " names trace " +
+                                                  std::to_string(top) + " but " + wf->what + " frames carry " +
                                                   std::to_string(wf->ntr) + " (frame " + std::to_string(f0) + ")");
+        }
         const int batches = (int)(payload / wf->batch_bytes);
         const size_t per_frame = (size_t)batches * (size_t)wf->spb; // samples a trace and frame
         const size_t piece_frames = per_frame ? std::max<size_t>(1, PIECE_SAMPLES / per_frame) : n_frames;
@@ -677,15 +768,15 @@ int ingest_frames(psdc_cross *h, const std::vector<FedPair> &fed, const FrameSrc
             if (batches > 0 && !fed.empty()) {
                 const size_t per_ch = cnt * per_frame;
                 // stage 0 of every fed pair takes per_ch more samples of each channel
-                std::vector<float *> dst(2 * fed.size());
+                std::vector<float *> dst(h->m * fed.size());
                 h->grew = false;
                 for (size_t i = 0; i < fed.size(); ++i) {
                     XStage *s = nullptr;
                     int rc = stage0_room(h, fed[i].pair, per_ch, &s);
                     if (rc)
                         return rc;
-                    for (int c = 0; c < 2; ++c)
-                        dst[2 * i + c] = s->buf.p[c][s->buf.cur] + (s->total - s->buf.base);
+                    for (uint32_t c = 0; c < h->m; ++c)
+                        dst[h->m * i + c] = s->buf.p[c][s->buf.cur] + (s->total - s->buf.base);
                 }
                 // the same order as psdc_cross_process_device's copies: behind a buffer's growth and round R - 2, before round R
                 if (h->grew) {
@@ -733,7 +824,7 @@ int ingest_frames(psdc_cross *h, const std::vector<FedPair> &fed, const FrameSrc
 }
 
 // the checks both frames calls begin with; *go: there are frames to take
-int frames_args(psdc_cross *h, const uint32_t *map, const void *frames, size_t frame_size, size_t n_frames, const char *who,
+int frames_args(XObj *h, const uint32_t *map, const void *frames, size_t frame_size, size_t n_frames, const char *who,
                 std::vector<FedPair> *fed, bool *go)
 {
     *go = false;
@@ -752,36 +843,13 @@ int frames_args(psdc_cross *h, const uint32_t *map, const void *frames, size_t f
     return PSDC_OK;
 }
 
-} // namespace
 
-extern "C" {
+#define X_HANDLE(h, who)                                                                                               \
+    if (!(h))                                                                                                          \
+    return xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": null handle")
 
-psdc_cross *psdc_cross_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
-                                     int device)
+void destroy_impl(XObj *h)
 {
-    return create_impl(n, win, power, nenbw, overlap, n_pairs, device, "psdc_cross_create_window");
-}
-
-psdc_cross *psdc_cross_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
-{
-    psdrt::WindowConsts wc{};
-    if (window_kind == PSDC_WINDOW_CUSTOM || !psdrt::window_consts(n, window_kind, &wc)) {
-        xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_create: window_kind must be PSDC_WINDOW_HANN or PSDC_WINDOW_RECTANGULAR");
-        return nullptr;
-    }
-    if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
-        xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_create: n must be a power of two in [64, 4096]");
-        return nullptr;
-    }
-    std::vector<float> win(n);
-    psdrt::window_weights(n, window_kind, win.data());
-    return create_impl(n, win.data(), wc.power, wc.nenbw, wc.overlap, n_pairs, device, "psdc_cross_create");
-}
-
-void psdc_cross_destroy(psdc_cross *h)
-{
-    if (!h)
-        return;
     psdrt::DevScope scope(h->device);
     if (h->stream && h->copy_stream)
         free_all(h);
@@ -808,16 +876,33 @@ void psdc_cross_destroy(psdc_cross *h)
         (void)hipStreamDestroy(h->copy_stream);
     if (h->stream)
         (void)hipStreamDestroy(h->stream);
-    delete h;
 }
 
-#define X_HANDLE(h, who)                                                                                               \
-    if (!(h))                                                                                                          \
-    return xfail(nullptr, PSDC_ERR_ARG, who ": null handle")
-
-int psdc_cross_reset(psdc_cross *h)
+template <class T>
+T *create_kind(uint32_t n, int window_kind, uint32_t m, uint32_t n_pairs, int device, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_reset");
+    constexpr bool matrix = std::is_same<T, psdc_csm>::value;
+    psdrt::WindowConsts wc{};
+    if (window_kind == PSDC_WINDOW_CUSTOM || !psdrt::window_consts(n, window_kind, &wc)) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": window_kind must be PSDC_WINDOW_HANN or PSDC_WINDOW_RECTANGULAR");
+        return nullptr;
+    }
+    if (matrix && !csm_supported((int)n, (int)m)) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
+        return nullptr;
+    }
+    if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": n must be a power of two in [64, 4096]");
+        return nullptr;
+    }
+    std::vector<float> win(n);
+    psdrt::window_weights(n, window_kind, win.data());
+    return create_impl<T>(n, win.data(), wc.power, wc.nenbw, wc.overlap, m, n_pairs, device, who);
+}
+
+int reset_impl(XObj *h, const char *who)
+{
+    X_HANDLE(h, who);
     X_ON_DEVICE(h);
     // everything the object made since it was created goes: stages, buffers, partial slab, counters
     free_all(h);
@@ -832,13 +917,13 @@ int psdc_cross_reset(psdc_cross *h)
     return PSDC_OK;
 }
 
-int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind)
+int set_detrend_impl(XObj *h, int detrend_kind, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_set_detrend");
+    X_HANDLE(h, who);
     if (detrend_kind == PSDC_DETREND_LINEAR)
-        return xfail(h, PSDC_ERR_UNIMPLEMENTED, "psdc_cross_set_detrend: Detrend::Linear is unimplemented (src/psd.rs:110)");
+        return xfail(h, PSDC_ERR_UNIMPLEMENTED, std::string(who) + ": Detrend::Linear is unimplemented (src/psd.rs:110)");
     if (detrend_kind < PSDC_DETREND_NONE || detrend_kind > PSDC_DETREND_MEAN)
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross_set_detrend: unknown detrend kind");
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": unknown detrend kind");
     X_ON_DEVICE(h);
     int rc = drain(h); // segments already fed are analysed with the setting they were fed under
     if (rc)
@@ -847,9 +932,9 @@ int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind)
     return PSDC_OK;
 }
 
-int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count)
+int set_avg_impl(XObj *h, uint32_t limit, uint32_t count, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_set_avg");
+    X_HANDLE(h, who);
     X_ON_DEVICE(h);
     int rc = drain(h);
     if (rc)
@@ -859,16 +944,18 @@ int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count)
     return PSDC_OK;
 }
 
-int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float *y, size_t len)
+// x: h->m pointers (host memory)
+int process_impl(XObj *h, uint32_t pair, const float *const *x, size_t len, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_process");
+    X_HANDLE(h, who);
     int rc = check_pair(h, pair);
     if (rc)
         return rc;
     if (len == 0)
         return PSDC_OK;
-    if (!x || !y)
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross_process: null sample pointer");
+    for (uint32_t c = 0; c < h->m; ++c)
+        if (!x || !x[c])
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
     X_ON_DEVICE(h);
     XStage *s = nullptr;
     if ((rc = stage0_room(h, pair, len, &s)))
@@ -879,10 +966,10 @@ int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float
         if (h->ev_pending[slot])
             XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
         float *stg = h->h_stage[slot];
-        memcpy(stg, x + done, sizeof(float) * m);
-        memcpy(stg + STAGING, y + done, sizeof(float) * m);
+        for (uint32_t c = 0; c < h->m; ++c)
+            memcpy(stg + c * STAGING, x[c] + done, sizeof(float) * m);
         const size_t at = (size_t)(s->total + done - s->buf.base);
-        for (int c = 0; c < 2; ++c)
+        for (uint32_t c = 0; c < h->m; ++c)
             XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, stg + c * STAGING, sizeof(float) * m, hipMemcpyHostToDevice,
                                    h->stream));
         XCHK(h, hipEventRecord(h->stage_ev[slot], h->stream));
@@ -897,17 +984,18 @@ int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float
     return run_round(h, &did);
 }
 
-int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
-                              void *producer_event)
+// d_x: h->m device pointers (the array itself is host memory)
+int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t len, void *producer_event, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_process_device");
+    X_HANDLE(h, who);
     int rc = check_pair(h, pair);
     if (rc)
         return rc;
     if (len == 0)
         return PSDC_OK;
-    if (!d_x || !d_y)
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross_process_device: null sample pointer");
+    for (uint32_t c = 0; c < h->m; ++c)
+        if (!d_x || !d_x[c])
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
     X_ON_DEVICE(h);
     if (producer_event)
         XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
@@ -923,8 +1011,8 @@ int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, co
     if (h->round_recorded[slot])
         XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
     const size_t at = (size_t)(s->total - s->buf.base);
-    XCHK(h, hipMemcpyAsync(s->buf.p[0][s->buf.cur] + at, d_x, sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
-    XCHK(h, hipMemcpyAsync(s->buf.p[1][s->buf.cur] + at, d_y, sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    for (uint32_t c = 0; c < h->m; ++c)
+        XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, d_x[c], sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
     XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
     XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
     s->total += len;
@@ -934,9 +1022,9 @@ int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, co
     return run_round(h, &did);
 }
 
-int psdc_cross_sync(psdc_cross *h)
+int sync_impl(XObj *h, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_sync");
+    X_HANDLE(h, who);
     X_ON_DEVICE(h);
     int rc = drain(h);
     if (rc)
@@ -944,9 +1032,9 @@ int psdc_cross_sync(psdc_cross *h)
     return sync_all(h);
 }
 
-int psdc_cross_num_stages(psdc_cross *h, uint32_t pair)
+int num_stages_impl(XObj *h, uint32_t pair, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_num_stages");
+    X_HANDLE(h, who);
     int rc = check_pair(h, pair);
     if (rc)
         return rc;
@@ -956,10 +1044,10 @@ int psdc_cross_num_stages(psdc_cross *h, uint32_t pair)
     return (int)h->pairs[pair].size();
 }
 
-int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *sxx, float *syy,
-                             float *sxy)
+// one stage's statistics and, with acc != NULL, its rows() x bins accumulators as they lie on the device
+int stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, std::vector<double> *acc, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_stage_spectra");
+    X_HANDLE(h, who);
     int rc = check_pair(h, pair);
     if (rc)
         return rc;
@@ -968,7 +1056,7 @@ int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_
         return rc;
     auto &st = h->pairs[pair];
     if (stage >= st.size())
-        return xfail(h, PSDC_ERR_ARG, "psdc_cross_stage_spectra: stage " + std::to_string(stage) + " out of range (" +
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": stage " + std::to_string(stage) + " out of range (" +
                                           std::to_string(st.size()) + " stages)");
     const XStage &s = st[stage];
     if (stat) {
@@ -978,129 +1066,111 @@ int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_
         stat->pending = pending_for(h->geo, s.total);
         stat->processed = (uint64_t)h->n * c - (uint64_t)h->geo.overlap * (c ? c - 1 : 0);
     }
-    if (sxx || syy || sxy) {
+    if (acc) {
         if ((rc = sync_all(h)))
             return rc;
-        const size_t b = bins(h);
-        std::vector<double> acc(4 * b);
-        XCHK(h, hipMemcpy(acc.data(), s.acc, sizeof(double) * 4 * b, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < b; ++k) {
-            if (sxx)
-                sxx[k] = (float)acc[k];
-            if (syy)
-                syy[k] = (float)acc[b + k];
-            if (sxy) {
-                sxy[2 * k] = (float)acc[2 * b + k];
-                sxy[2 * k + 1] = (float)acc[3 * b + k];
-            }
-        }
+        acc->resize(h->rows() * bins(h));
+        XCHK(h, hipMemcpy(acc->data(), s.acc, sizeof(double) * acc->size(), hipMemcpyDeviceToHost));
     }
     return PSDC_OK;
 }
 
-int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
-                      const uint32_t *avgs, const uint64_t *pendings, const float *rows, int keep_overlap, uint32_t min_count,
-                      int keep_transition_band, float *sxx, float *syy, float *sxy, size_t cap, size_t *len,
-                      psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+// what a stitch of one pair / group needs: counts, averages, pendings and the f32 rows of every stage (n_stages x rows() x bins)
+struct StitchIn {
+    std::vector<uint64_t> c64, pend;
+    std::vector<uint32_t> avgs;
+    std::vector<float> rows;
+    uint32_t ns = 0;
+};
+
+int stitch_in(XObj *h, uint32_t pair, StitchIn *in)
+{
+    int rc;
+    if ((rc = drain(h)) || (rc = sync_all(h)))
+        return rc;
+    const auto &st = h->pairs[pair];
+    const uint32_t ns = (uint32_t)st.size();
+    const size_t e = h->rows() * bins(h);
+    in->ns = ns;
+    in->c64.resize(std::max<uint32_t>(ns, 1));
+    in->pend.resize(std::max<uint32_t>(ns, 1));
+    in->avgs.resize(std::max<uint32_t>(ns, 1));
+    in->rows.resize(std::max<size_t>(1, (size_t)ns * e));
+    std::vector<double> acc(e);
+    for (uint32_t i = 0; i < ns; ++i) {
+        in->c64[i] = st[i].count64;
+        in->pend[i] = pending_for(h->geo, st[i].total);
+        in->avgs[i] = cur_avg(h, i);
+        XCHK(h, hipMemcpy(acc.data(), st[i].acc, sizeof(double) * e, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < e; ++k)
+            in->rows[(size_t)i * e + k] = (float)acc[k];
+    }
+    return PSDC_OK;
+}
+
+// psdc_stitch_window on each of `nrows` rows of caller stages (n_stages x nrows x (n/2+1)); outs[r] NULL: that row is not
+// wanted (its length is still computed); Breaks from row 0
+int stitch_rows_impl(const char *who, uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
+                     const uint32_t *avgs, const uint64_t *pendings, const float *rows, uint32_t nrows, int keep_overlap,
+                     uint32_t min_count, int keep_transition_band, float *const *outs, size_t cap, size_t *len, psdc_break *breaks,
+                     size_t breaks_cap, size_t *n_breaks)
 {
     if (n < 2 || overlap >= n || n_stages > 20)
-        return xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_stitch: bad arguments");
+        return xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": bad arguments");
     if (n_stages && (!counts64 || !avgs || !pendings || !rows))
-        return xfail(nullptr, PSDC_ERR_ARG, "psdc_cross_stitch: null input");
+        return xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": null input");
     const size_t b = n / 2 + 1;
-    // the four rows of every stage as four spectra slabs, each stitched exactly as PsdCascade::psd
-    std::vector<float> sp[4];
-    for (int r = 0; r < 4; ++r) {
-        sp[r].resize(std::max<size_t>(1, (size_t)n_stages * b));
-        for (uint32_t i = 0; i < n_stages; ++i)
-            memcpy(&sp[r][(size_t)i * b], rows + ((size_t)i * 4 + r) * b, sizeof(float) * b);
-    }
-    std::vector<float> re(cap ? cap : 1), im(cap ? cap : 1);
-    float *outs[4] = {sxx, syy, sxy ? re.data() : nullptr, sxy ? im.data() : nullptr};
+    std::vector<float> sp(std::max<size_t>(1, (size_t)n_stages * b));
     size_t plen = 0;
-    for (int r = 0; r < 4; ++r) {
+    bool any = false;
+    for (uint32_t r = 0; r < nrows; ++r) {
+        for (uint32_t i = 0; i < n_stages; ++i)
+            memcpy(&sp[(size_t)i * b], rows + ((size_t)i * nrows + r) * b, sizeof(float) * b);
+        any = any || outs[r];
         size_t l = 0, nb = 0;
-        int rc = psdc_stitch_window(n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, sp[r].data(), keep_overlap,
+        int rc = psdc_stitch_window(n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, sp.data(), keep_overlap,
                                     min_count, keep_transition_band, outs[r], outs[r] ? cap : 0, &l, r == 0 ? breaks : nullptr,
                                     r == 0 ? breaks_cap : 0, &nb);
         if (rc == PSDC_ERR_CAPACITY)
-            return xfail(nullptr, rc, "psdc_cross_stitch: output too small");
+            return xfail(nullptr, rc, std::string(who) + ": output too small");
         if (rc)
-            return xfail(nullptr, rc, std::string("psdc_cross_stitch: ") + psdc_last_error(nullptr));
+            return xfail(nullptr, rc, std::string(who) + ": " + psdc_last_error(nullptr));
         if (r == 0) {
             plen = l;
             if (n_breaks)
                 *n_breaks = nb;
             if (breaks && nb > breaks_cap)
-                return xfail(nullptr, PSDC_ERR_CAPACITY, "psdc_cross_stitch: breaks output too small");
+                return xfail(nullptr, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
         }
     }
-    if ((sxx || syy || sxy) && plen > cap)
-        return xfail(nullptr, PSDC_ERR_CAPACITY, "psdc_cross_stitch: output too small");
-    if (sxy)
-        for (size_t k = 0; k < plen; ++k) {
-            sxy[2 * k] = re[k];
-            sxy[2 * k + 1] = im[k];
-        }
+    if (any && plen > cap)
+        return xfail(nullptr, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
     if (len)
         *len = plen;
     return PSDC_OK;
 }
 
-int psdc_cross_csd(psdc_cross *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *sxx,
-                   float *syy, float *sxy, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+int stats_impl(XObj *h, uint64_t *launches, uint64_t *in, int reset, const char *who)
 {
-    X_HANDLE(h, "psdc_cross_csd");
-    int rc = check_pair(h, pair);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    if ((rc = drain(h)) || (rc = sync_all(h)))
-        return rc;
-    const auto &st = h->pairs[pair];
-    const uint32_t ns = (uint32_t)st.size();
-    const size_t b = bins(h);
-    std::vector<uint64_t> c64(std::max<uint32_t>(ns, 1)), pend(std::max<uint32_t>(ns, 1));
-    std::vector<uint32_t> avgs(std::max<uint32_t>(ns, 1));
-    std::vector<double> acc(4 * b);
-    std::vector<float> rows(std::max<size_t>(1, (size_t)ns * 4 * b));
-    for (uint32_t i = 0; i < ns; ++i) {
-        c64[i] = st[i].count64;
-        pend[i] = pending_for(h->geo, st[i].total);
-        avgs[i] = cur_avg(h, i);
-        XCHK(h, hipMemcpy(acc.data(), st[i].acc, sizeof(double) * 4 * b, hipMemcpyDeviceToHost));
-        for (size_t e = 0; e < 4 * b; ++e)
-            rows[(size_t)i * 4 * b + e] = (float)acc[e];
-    }
-    rc = psdc_cross_stitch(h->n, h->power, h->nenbw, h->geo.overlap, ns, c64.data(), avgs.data(), pend.data(), rows.data(),
-                           keep_overlap, min_count, keep_transition_band, sxx, syy, sxy, cap, len, breaks, breaks_cap, n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    return PSDC_OK;
-}
-
-int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in, int reset)
-{
-    X_HANDLE(h, "psdc_cross_stats_read");
+    X_HANDLE(h, who);
     if (launches)
         *launches = h->launches;
-    if (pairs_in)
-        *pairs_in = h->pairs_in;
+    if (in)
+        *in = h->pairs_in;
     if (reset)
         h->launches = h->pairs_in = 0;
     return PSDC_OK;
 }
 
-int psdc_csd_process_frames(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
-                            size_t *n_ok)
+int frames_host_impl(XObj *h, const uint32_t *map, const uint8_t *frames, size_t frame_size, size_t n_frames, size_t *n_ok,
+                     const char *who)
 {
-    static const char *who = "psdc_csd_process_frames";
     if (n_ok)
         *n_ok = 0;
-    X_HANDLE(h, "psdc_csd_process_frames");
+    X_HANDLE(h, who);
     std::vector<FedPair> fed;
     bool go = false;
-    int rc = frames_args(h, pair_traces, frames, frame_size, n_frames, who, &fed, &go);
+    int rc = frames_args(h, map, frames, frame_size, n_frames, who, &fed, &go);
     if (rc || !go)
         return rc;
     X_ON_DEVICE(h);
@@ -1115,16 +1185,15 @@ int psdc_csd_process_frames(psdc_cross *h, const uint32_t *pair_traces, const ui
     return rc;
 }
 
-int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
-                                   size_t n_frames, size_t *n_ok, void *producer_event)
+int frames_device_impl(XObj *h, const uint32_t *map, const uint8_t *d_frames, size_t frame_size, size_t n_frames, size_t *n_ok,
+                       void *producer_event, const char *who)
 {
-    static const char *who = "psdc_csd_process_frames_device";
     if (n_ok)
         *n_ok = 0;
-    X_HANDLE(h, "psdc_csd_process_frames_device");
+    X_HANDLE(h, who);
     std::vector<FedPair> fed;
     bool go = false;
-    int rc = frames_args(h, pair_traces, d_frames, frame_size, n_frames, who, &fed, &go);
+    int rc = frames_args(h, map, d_frames, frame_size, n_frames, who, &fed, &go);
     if (rc || !go)
         return rc;
     X_ON_DEVICE(h);
@@ -1159,17 +1228,252 @@ int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, c
     return rc;
 }
 
-int psdc_csd_loss_read(psdc_cross *h, psdc_loss *out, int reset)
+int loss_impl(XObj *h, psdc_loss *out, int reset, const char *who)
 {
-    X_HANDLE(h, "psdc_csd_loss_read");
+    X_HANDLE(h, who);
     if (!out)
-        return xfail(h, PSDC_ERR_ARG, "psdc_csd_loss_read: null output");
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output");
     *out = h->loss;
     if (reset)
         h->loss = psdc_loss{};
     return PSDC_OK;
 }
 
+} // namespace
+
+extern "C" {
+
+// ---- pairs: m = 2 on cross_kernel, rows xx, yy, re, im ----
+
+psdc_cross *psdc_cross_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                     int device)
+{
+    return create_impl<psdc_cross>(n, win, power, nenbw, overlap, 2, n_pairs, device, "psdc_cross_create_window");
+}
+
+psdc_cross *psdc_cross_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    return create_kind<psdc_cross>(n, window_kind, 2, n_pairs, device, "psdc_cross_create");
+}
+
+void psdc_cross_destroy(psdc_cross *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_cross_reset(psdc_cross *h) { return reset_impl(h, "psdc_cross_reset"); }
+int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_cross_set_detrend"); }
+int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_cross_set_avg"); }
+
+int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float *y, size_t len)
+{
+    const float *xs[2] = {x, y};
+    return process_impl(h, pair, xs, len, "psdc_cross_process");
+}
+
+int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
+                              void *producer_event)
+{
+    const float *xs[2] = {d_x, d_y};
+    return process_device_impl(h, pair, xs, len, producer_event, "psdc_cross_process_device");
+}
+
+int psdc_cross_sync(psdc_cross *h) { return sync_impl(h, "psdc_cross_sync"); }
+int psdc_cross_num_stages(psdc_cross *h, uint32_t pair) { return num_stages_impl(h, pair, "psdc_cross_num_stages"); }
+
+int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *sxx, float *syy,
+                             float *sxy)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, pair, stage, stat, sxx || syy || sxy ? &acc : nullptr, "psdc_cross_stage_spectra");
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    for (size_t k = 0; k < b; ++k) {
+        if (sxx)
+            sxx[k] = (float)acc[k];
+        if (syy)
+            syy[k] = (float)acc[b + k];
+        if (sxy) {
+            sxy[2 * k] = (float)acc[2 * b + k];
+            sxy[2 * k + 1] = (float)acc[3 * b + k];
+        }
+    }
+    return PSDC_OK;
+}
+
+int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
+                      const uint32_t *avgs, const uint64_t *pendings, const float *rows, int keep_overlap, uint32_t min_count,
+                      int keep_transition_band, float *sxx, float *syy, float *sxy, size_t cap, size_t *len,
+                      psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    // the four rows of every stage as four spectra slabs, each stitched exactly as PsdCascade::psd
+    std::vector<float> re(cap ? cap : 1), im(cap ? cap : 1);
+    float *outs[4] = {sxx, syy, sxy ? re.data() : nullptr, sxy ? im.data() : nullptr};
+    size_t plen = 0;
+    int rc = stitch_rows_impl("psdc_cross_stitch", n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, rows, 4, keep_overlap,
+                              min_count, keep_transition_band, outs, cap, &plen, breaks, breaks_cap, n_breaks);
+    if (rc)
+        return rc;
+    if (sxy)
+        for (size_t k = 0; k < plen; ++k) {
+            sxy[2 * k] = re[k];
+            sxy[2 * k + 1] = im[k];
+        }
+    if (len)
+        *len = plen;
+    return PSDC_OK;
+}
+
+int psdc_cross_csd(psdc_cross *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *sxx,
+                   float *syy, float *sxy, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    X_HANDLE(h, "psdc_cross_csd");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, pair, &in)))
+        return rc;
+    rc = psdc_cross_stitch(h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                           in.rows.data(), keep_overlap, min_count, keep_transition_band, sxx, syy, sxy, cap, len, breaks,
+                           breaks_cap, n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    return PSDC_OK;
+}
+
+int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    return stats_impl(h, launches, pairs_in, reset, "psdc_cross_stats_read");
+}
+
+int psdc_csd_process_frames(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                            size_t *n_ok)
+{
+    return frames_host_impl(h, pair_traces, frames, frame_size, n_frames, n_ok, "psdc_csd_process_frames");
+}
+
+int psdc_csd_process_frames_device(psdc_cross *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
+                                   size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, pair_traces, d_frames, frame_size, n_frames, n_ok, producer_event, "psdc_csd_process_frames_device");
+}
+
+int psdc_csd_loss_read(psdc_cross *h, psdc_loss *out, int reset) { return loss_impl(h, out, reset, "psdc_csd_loss_read"); }
+
 const char *psdc_cross_last_error(const psdc_cross *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- groups of m channels: csm_kernel, the m * m rows of csm_fft.h ----
+
+int psdc_csm_supported(uint32_t n, uint32_t m) { return n <= 4096 && m <= CSM_MAX_M && csm_supported((int)n, (int)m) ? 1 : 0; }
+
+psdc_csm *psdc_csm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m,
+                                 uint32_t n_groups, int device)
+{
+    return create_impl<psdc_csm>(n, win, power, nenbw, overlap, m, n_groups, device, "psdc_csm_create_window");
+}
+
+psdc_csm *psdc_csm_create(uint32_t n, int window_kind, uint32_t m, uint32_t n_groups, int device)
+{
+    if (!csm_supported(n <= 4096 ? (int)n : 0, m <= CSM_MAX_M ? (int)m : 0)) { // (before the window: a refused size names itself)
+        xfail(nullptr, PSDC_ERR_ARG, "psdc_csm_create: " + csm_size_text(n, m));
+        return nullptr;
+    }
+    return create_kind<psdc_csm>(n, window_kind, m, n_groups, device, "psdc_csm_create");
+}
+
+void psdc_csm_destroy(psdc_csm *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_csm_reset(psdc_csm *h) { return reset_impl(h, "psdc_csm_reset"); }
+int psdc_csm_set_detrend(psdc_csm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_csm_set_detrend"); }
+int psdc_csm_set_avg(psdc_csm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_csm_set_avg"); }
+
+int psdc_csm_process(psdc_csm *h, uint32_t group, const float *const *x, size_t len)
+{
+    return process_impl(h, group, x, len, "psdc_csm_process");
+}
+
+int psdc_csm_process_device(psdc_csm *h, uint32_t group, const float *const *d_x, size_t len, void *producer_event)
+{
+    return process_device_impl(h, group, d_x, len, producer_event, "psdc_csm_process_device");
+}
+
+int psdc_csm_process_frames(psdc_csm *h, const uint32_t *group_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                            size_t *n_ok)
+{
+    return frames_host_impl(h, group_traces, frames, frame_size, n_frames, n_ok, "psdc_csm_process_frames");
+}
+
+int psdc_csm_process_frames_device(psdc_csm *h, const uint32_t *group_traces, const uint8_t *d_frames, size_t frame_size,
+                                   size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, group_traces, d_frames, frame_size, n_frames, n_ok, producer_event, "psdc_csm_process_frames_device");
+}
+
+int psdc_csm_loss_read(psdc_csm *h, psdc_loss *out, int reset) { return loss_impl(h, out, reset, "psdc_csm_loss_read"); }
+int psdc_csm_sync(psdc_csm *h) { return sync_impl(h, "psdc_csm_sync"); }
+int psdc_csm_num_stages(psdc_csm *h, uint32_t group) { return num_stages_impl(h, group, "psdc_csm_num_stages"); }
+
+int psdc_csm_stage_spectra(psdc_csm *h, uint32_t group, uint32_t stage, psdc_stage_stat *stat, float *rows)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, group, stage, stat, rows ? &acc : nullptr, "psdc_csm_stage_spectra");
+    if (rc)
+        return rc;
+    for (size_t e = 0; e < acc.size(); ++e)
+        rows[e] = (float)acc[e];
+    return PSDC_OK;
+}
+
+int psdc_csm_stitch(uint32_t n, uint32_t m, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
+                    const uint32_t *avgs, const uint64_t *pendings, const float *rows_in, int keep_overlap, uint32_t min_count,
+                    int keep_transition_band, float *rows, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
+                    size_t *n_breaks)
+{
+    if (m < 2 || m > CSM_MAX_M)
+        return xfail(nullptr, PSDC_ERR_ARG, "psdc_csm_stitch: m must be 2, 3 or 4");
+    float *outs[CSM_MAX_M * CSM_MAX_M];
+    for (uint32_t r = 0; r < m * m; ++r)
+        outs[r] = rows ? rows + (size_t)r * cap : nullptr;
+    return stitch_rows_impl("psdc_csm_stitch", n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, rows_in, m * m,
+                            keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks);
+}
+
+int psdc_csm_csd(psdc_csm *h, uint32_t group, int keep_overlap, uint32_t min_count, int keep_transition_band, float *rows,
+                 size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    X_HANDLE(h, "psdc_csm_csd");
+    int rc = check_pair(h, group);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, group, &in)))
+        return rc;
+    rc = psdc_csm_stitch(h->n, h->m, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                         in.rows.data(), keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap,
+                         n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    return PSDC_OK;
+}
+
+int psdc_csm_stats_read(psdc_csm *h, uint64_t *launches, uint64_t *sample_times_in, int reset)
+{
+    return stats_impl(h, launches, sample_times_in, reset, "psdc_csm_stats_read");
+}
+
+const char *psdc_csm_last_error(const psdc_csm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

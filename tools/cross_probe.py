@@ -9,6 +9,12 @@ host-fed leg.  Roofline: 8 algorithmic bytes a pair (x and y read once) against 
 --frames: device-resident AdcDac frames (128 batches a frame) into the pairs (ADC0, DAC0), (ADC1, DAC1) at N = 512, 1024, 4096
 in calls of 2^22 samples a trace (psdc_csd_process_frames_device), next to the same two pairs fed f32 (psdc_cross_process_device,
 2^22 samples a call and pair); both timed the same way, G pairs/s = pairs fed / second.
+--matrix: one m = 4 group (psdc_csm_*) against the six pairs it replaces.  Four device-resident f32 streams of 2^22 samples a call
+at N = 512, 1024, 2048; leg A is CsdCascadeBank(n, 6) fed the six pairs of the four streams (six calls a step), leg B is
+CsmCascadeBank(n, 4) (one call a step); unit: sample times a second (one sample of each of the four streams).  A, B and A again
+are timed in turn --reps times in one session: the ratio B / A per turn, and |A' - A| / A as the session's spread.  Also one
+m = 2 group against one pair.  --matrix --only-a times leg A alone (for a run on another build of the library through PSDC_LIB).
+--matrix --frames: the four traces of device-resident AdcDac frames as one m = 4 group against the two-pair frames leg above.
 """
 import argparse
 import json
@@ -141,15 +147,124 @@ def frames_legs(pkg, torch, seconds):
     return legs
 
 
+def matrix_legs(pkg, torch, seconds, reps, only_a):
+    call = 1 << 22
+    xs = [torch.randn(call, device="cuda")]
+    xs += [(0.5 * xs[0] + torch.randn(call, device="cuda")) for _ in range(3)]
+    torch.cuda.synchronize()
+    ptr = [x.data_ptr() for x in xs]
+    six = [(a, b) for a in range(4) for b in range(a + 1, 4)]
+    legs = []
+    for n in (512, 1024, 2048):
+        pa = pkg.CsdCascadeBank(n, 6)
+
+        def a_step():
+            for p, (a, b) in enumerate(six):
+                pa.process_device(p, ptr[a], ptr[b], call)
+            return call
+
+        if only_a:
+            series = [round(timed(a_step, pa.sync, seconds)[0] / 1e9, 3) for _ in range(reps)]
+            legs.append({"n": n, "a_gst_s": series})
+            pa.close()
+            continue
+        gb = pkg.CsmCascadeBank(n, 4)
+        p1 = pkg.CsdCascadeBank(n, 1)
+        g2 = pkg.CsmCascadeBank(n, 2)
+
+        def b_step():
+            gb.process_device(0, ptr, call)
+            return call
+
+        def p1_step():
+            p1.process_device(0, ptr[0], ptr[1], call)
+            return call
+
+        def g2_step():
+            g2.process_device(0, ptr[:2], call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, gb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+        gb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = gb.stats_read()["launches"] / 8
+        gb.sync()
+        pair = timed(p1_step, p1.sync, seconds)[0] / 1e9
+        grp2 = timed(g2_step, g2.sync, seconds)[0] / 1e9
+        ratios = [y / x for x, y in zip(a1, b)]
+        spread = max(abs(y - x) / x for x, y in zip(a1, a2))
+        legs.append({"n": n, "call": call, "a_six_pairs_gst_s": [round(v, 3) for v in a1], "b_group4_gst_s": [round(v, 3) for v in b],
+                     "a_again_gst_s": [round(v, 3) for v in a2], "ratio_b_over_a": [round(r, 3) for r in ratios],
+                     "ratio_min": round(min(ratios), 3), "aa_spread_max": round(spread, 4),
+                     "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": gb.num_stages(0),
+                     "one_pair_gst_s": round(pair, 3), "group2_gst_s": round(grp2, 3), "group2_over_pair": round(grp2 / pair, 3)})
+        for o in (pa, gb, p1, g2):
+            o.close()
+    return legs
+
+
+def matrix_frames_legs(pkg, torch, seconds, reps):
+    call = 1 << 22
+    batches = 128
+    rng = np.random.default_rng(7)
+    w = rng.integers(-20000, 20000, size=(4, call), dtype=np.int64).astype(np.int16)
+    data, fs = pkg.make_adcdac_frames(w, batches)
+    nf = len(data) // fs
+    d = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
+    torch.cuda.synchronize()
+    legs = []
+    for n in (512, 1024, 2048):
+        fb = pkg.CsdCascadeBank(n, 2)
+        gb = pkg.CsmCascadeBank(n, 4)
+
+        def pstep():
+            fb.process_frames_device(d.data_ptr(), fs, nf, [("ADC0", "DAC0"), ("ADC1", "DAC1")])
+            return call
+
+        def gstep():
+            gb.process_frames_device(d.data_ptr(), fs, nf, [("ADC0", "ADC1", "DAC0", "DAC1")])
+            return call
+
+        pr, gr = [], []
+        for _ in range(reps):
+            pr.append(timed(pstep, fb.sync, seconds)[0] / 1e9)
+            gr.append(timed(gstep, gb.sync, seconds)[0] / 1e9)
+        legs.append({"n": n, "call_samples_per_trace": call, "frame_size": fs, "two_pairs_gst_s": [round(v, 3) for v in pr],
+                     "group4_gst_s": [round(v, 3) for v in gr], "ratio_group_over_two_pairs": round(min(gr) / max(pr), 3)})
+        fb.close()
+        gb.close()
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--call-log2", type=int, default=24)
     ap.add_argument("--frames", action="store_true", help="the frames leg only")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--matrix", action="store_true", help="one m = 4 group against the six pairs it replaces")
+    ap.add_argument("--only-a", action="store_true", help="with --matrix: leg A (six pairs) alone")
+    ap.add_argument("--reps", type=int, default=5, help="with --matrix: turns of A, B, A")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.matrix:
+        if a.frames:
+            out = {"metric": "csm_frames_gsampletimes_s", "legs": matrix_frames_legs(pkg, torch, a.seconds, a.reps)}
+        else:
+            out = {"metric": "csm_gsampletimes_s", "unit": "1e9 sample times a second (one sample of each of four streams)",
+                   "only_a": a.only_a, "legs": matrix_legs(pkg, torch, a.seconds, a.reps, a.only_a)}
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.frames:
         line = json.dumps({"metric": "cross_frames_gpairs_s", "legs": frames_legs(pkg, torch, a.seconds)})
         print(line)
