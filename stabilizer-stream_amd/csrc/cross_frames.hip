@@ -25,7 +25,7 @@ __device__ __forceinline__ bool aligned16(const float *p) { return (reinterpret_
 template <int FMT, int T, class Word>
 __device__ __forceinline__ void decode_trace(const Word &word, unsigned used, float &out)
 {
-    if constexpr (T < payload_fmt(FMT).ntraces)
+    if constexpr (T < wire_fmt_v(FMT).ntraces)
         if ((used >> T) & 1u)
             out = payload_trace<FMT, T>(word);
 }
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(CF_THREADS) void cross_frames_kernel(const CrossFra
             }
         }
     } else {
-        constexpr int BB = payload_fmt(FMT).batch_bytes;
-        constexpr int NT = payload_fmt(FMT).ntraces;
+        constexpr int BB = wire_fmt_v(FMT).batch_bytes;
+        constexpr int NT = wire_fmt_v(FMT).ntraces;
         const bool al4 = ((reinterpret_cast<uintptr_t>(b.frames) | b.frame_size) & 3u) == 0;
         const unsigned runs = (total + CF_RUN - 1) / CF_RUN;
         for (unsigned r = blockIdx.x * CF_THREADS + threadIdx.x; r < runs; r += gridDim.x * CF_THREADS) {
@@ -138,7 +138,7 @@ hipError_t launch_cross_frames(const CrossFramesBatch &b, hipStream_t s)
     if (total >= (1ull << 31))
         return hipErrorInvalidValue;
     for (int k = 0; k < b.ndst; ++k)
-        if (!b.dst[k] || b.trace[k] < 0 || b.trace[k] >= (b.fmt == 1 ? 4 : payload_fmt(b.fmt).ntraces))
+        if (!b.dst[k] || b.trace[k] < 0 || b.trace[k] >= wire_fmt_v(b.fmt).ntraces)
             return hipErrorInvalidValue;
     const unsigned long long items = b.fmt == 1 ? total : (total + CF_RUN - 1) / CF_RUN;
     const unsigned blocks = (unsigned)std::min<unsigned long long>(CF_MAX_BLOCKS, (items + CF_THREADS - 1) / CF_THREADS);

@@ -88,13 +88,11 @@ struct XObj {
     bool idle = true;            // every stage drained
     uint64_t launches = 0, pairs_in = 0;
     // frames (psdc_csd_process_frames[_device]): Loss over every frame either call ingested; host-memory frames go up through
-    // h_stage into d_frames (FRAMES_CHUNK bytes, made by the first host-frames call); device frames' headers come to h_hdr
-    // (8 bytes a frame, grown to the largest call) through a gather launch on hdr_stream
+    // h_stage into d_frames (FRAMES_CHUNK bytes, made by the first host-frames call); device frames' headers come to the host
+    // through `hdr`
     psdc_loss loss{};
     uint8_t *d_frames = nullptr;
-    uint8_t *h_hdr = nullptr;
-    size_t h_hdr_cap = 0;
-    hipStream_t hdr_stream = nullptr;
+    psdrt::HeaderGather hdr;
     int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
     std::string err;
 };
@@ -599,20 +597,6 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
 
 // ---- frames (psdc_csd_process_frames[_device]) ----
 
-// Payload layouts by Format id (src/de/mod.rs:12-17; src/de/data.rs:13, 86, 144, 168): bytes per batch, samples per batch and
-// trace, traces (Payload::traces)
-struct XWireFmt {
-    int id;
-    size_t batch_bytes;
-    int spb, ntr;
-    const char *what;
-};
-const XWireFmt *x_wire_fmt(int id)
-{
-    static const XWireFmt t[4] = {{1, 64, 8, 4, "AdcDac"}, {2, 56, 1, 4, "Fls"}, {3, 80, 1, 4, "ThermostatEem"}, {4, 24, 1, 3, "Mpll"}};
-    return id >= 1 && id <= 4 ? &t[id - 1] : nullptr;
-}
-
 struct FedPair {
     uint32_t pair;
     uint32_t tr[CSM_MAX_M]; // the trace of each channel
@@ -650,18 +634,16 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
     return PSDC_OK;
 }
 
-// Where a call's frames are: the payloads in host memory (host) or on the device (dev), the 8 header bytes of frame f at
-// hdr + f * hdr_stride (host memory either way)
+// Where a call's frames are: the payloads in host memory (host) or on the device (dev), the headers in host memory either way
 struct FrameSrc {
     const uint8_t *host = nullptr;
     const uint8_t *dev = nullptr;
-    const uint8_t *hdr = nullptr;
-    size_t hdr_stride = 0;
+    psdrt::HdrView hdr{nullptr, 0};
 };
 
 // decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[m i + c] (pair fed[i], channel
 // c), one launch per 32 / m pairs, on the copy stream
-int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const XWireFmt *wf, int batches, size_t f, size_t cnt,
+int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
     const uint8_t *frames = src.dev ? src.dev + f * frame_size : nullptr;
@@ -700,8 +682,8 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const XWireFm
     return PSDC_OK;
 }
 
-// One call's frames, as psdc_process_frames takes them (src/de/frame.rs:49-60, src/loss.rs:11-26): runs of one format, every
-// header validated on the host, Loss committed piece by piece once the piece's samples are in the streams.  A run is cut into
+// One call's frames, taken by the rule of psdc_process_frames -- run_start and scan_piece of frame_scan.h: runs of one format, every
+// header validated on the host -- with Loss committed piece by piece once the piece's samples are in the streams.  A run is cut into
 // pieces of whole frames of <= PIECE_SAMPLES samples a trace; each piece is decoded and followed by one round.  The cut depends on
 // the headers alone, so host and device frames give the same rounds.
 int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src, size_t frame_size, size_t n_frames,
@@ -711,58 +693,25 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
     const size_t payload = frame_size - 8;
     int bad = PSDC_OK;
     size_t f0 = 0;
-    auto hdr = [&](size_t f) { return src.hdr + f * src.hdr_stride; };
     while (f0 < n_frames && bad == PSDC_OK) {
-        const uint8_t *first = hdr(f0);
-        if (first[0] != 0x7b || first[1] != 0x05) { // Header::parse (src/de/frame.rs:25-37)
-            bad = PSDC_ERR_FRAME_HEADER;
+        const WireFmt *wf = nullptr;
+        bad = psdrt::run_start(src.hdr, f0, false, &wf);
+        if (bad != PSDC_OK)
             break;
-        }
-        const XWireFmt *wf = x_wire_fmt(first[2]);
-        if (!wf) {
-            bad = PSDC_ERR_FRAME_FORMAT;
-            break;
-        }
         for (const FedPair &fp : fed) {
             const uint32_t top = *std::max_element(fp.tr, fp.tr + h->m);
-            if ((int)top >= wf->ntr)
+            if ((int)top >= wf->ntraces)
                 return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(fp.pair) + " names trace " +
-                                                  std::to_string(top) + " but " + wf->what + " frames carry " +
-                                                  std::to_string(wf->ntr) + " (frame " + std::to_string(f0) + ")");
+                                                  std::to_string(top) + " but " + wf->name + " frames carry " +
+                                                  std::to_string(wf->ntraces) + " (frame " + std::to_string(f0) + ")");
         }
-        const int batches = (int)(payload / wf->batch_bytes);
+        const int batches = (int)(payload / (size_t)wf->batch_bytes);
         const size_t per_frame = (size_t)batches * (size_t)wf->spb; // samples a trace and frame
         const size_t piece_frames = per_frame ? std::max<size_t>(1, PIECE_SAMPLES / per_frame) : n_frames;
-        bool run_end = false;
-        while (f0 < n_frames && bad == PSDC_OK && !run_end) {
-            // the piece: headers + the payload's size checks + Loss::update, as ingest_frames_host's scan (frames_ingest.cpp)
-            psdc_loss trial = h->loss;
-            const size_t lim = std::min(piece_frames, n_frames - f0);
-            size_t cnt = 0;
-            for (; cnt < lim; ++cnt) {
-                const uint8_t *p = hdr(f0 + cnt);
-                if (p[0] != 0x7b || p[1] != 0x05) {
-                    bad = PSDC_ERR_FRAME_HEADER;
-                    break;
-                }
-                if (p[2] != wf->id) {
-                    if (x_wire_fmt(p[2]))
-                        run_end = true;
-                    else
-                        bad = PSDC_ERR_FRAME_FORMAT;
-                    break;
-                }
-                if (payload % wf->batch_bytes != 0 || (int)p[3] != batches) {
-                    bad = PSDC_ERR_FRAME_SIZE;
-                    break;
-                }
-                const uint32_t seq = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
-                trial.received += p[3];
-                if (trial.have_seq)
-                    trial.dropped += (uint32_t)(seq - trial.next_seq); // wrapping_sub
-                trial.next_seq = seq + p[3];                            // wrapping_add
-                trial.have_seq = 1;
-            }
+        int stop = psdrt::SCAN_LIMIT;
+        while (f0 < n_frames && stop == psdrt::SCAN_LIMIT) {
+            psdc_loss trial = h->loss; // the piece's headers and Loss::update
+            const size_t cnt = psdrt::scan_piece(src.hdr, *wf, payload, f0, std::min(piece_frames, n_frames - f0), false, &trial, &stop);
             if (cnt == 0)
                 break;
             if (batches > 0 && !fed.empty()) {
@@ -812,14 +761,11 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
             }
             f0 += cnt;
         }
+        if (stop < 0)
+            bad = stop;
     }
     if (bad != PSDC_OK)
-        return xfail(h, bad,
-                     std::string(who) + ": " +
-                         (bad == PSDC_ERR_FRAME_HEADER   ? "Invalid frame header"
-                          : bad == PSDC_ERR_FRAME_FORMAT ? "Unknown format ID"
-                                                         : "Payload size") +
-                         " (frame " + std::to_string(good) + ")");
+        return xfail(h, bad, std::string(who) + ": " + psdrt::frame_error_text(bad) + " (frame " + std::to_string(good) + ")");
     return PSDC_OK;
 }
 
@@ -831,15 +777,11 @@ int frames_args(XObj *h, const uint32_t *map, const void *frames, size_t frame_s
     int rc = read_map(h, map, who, fed);
     if (rc)
         return rc;
-    if (n_frames == 0)
-        return PSDC_OK;
-    if (!frames)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null frames");
-    if (frame_size < 8) // &input[..HEADER_SIZE] panics (src/de/frame.rs:50)
-        return xfail(h, PSDC_ERR_FRAME_SIZE, std::string(who) + ": frame shorter than its header");
+    rc = psdrt::check_frames_call(frames, frame_size, n_frames, go);
+    if (rc)
+        return xfail(h, rc, std::string(who) + ": " + (rc == PSDC_ERR_ARG ? "null frames" : psdrt::FRAME_SHORT_TEXT));
     if (n_frames > (size_t)std::numeric_limits<uint32_t>::max())
         return xfail(h, PSDC_ERR_ARG, std::string(who) + ": more than 2^32 - 1 frames in one call");
-    *go = true;
     return PSDC_OK;
 }
 
@@ -861,10 +803,7 @@ void destroy_impl(XObj *h)
     }
     if (h->d_frames)
         (void)hipFree(h->d_frames);
-    if (h->h_hdr)
-        (void)hipHostFree(h->h_hdr);
-    if (h->hdr_stream)
-        (void)hipStreamDestroy(h->hdr_stream);
+    h->hdr.release();
     if (h->d_win)
         (void)hipFree(h->d_win);
     if (h->d_tw)
@@ -1165,8 +1104,8 @@ int stats_impl(XObj *h, uint64_t *launches, uint64_t *in, int reset, const char 
 int frames_host_impl(XObj *h, const uint32_t *map, const uint8_t *frames, size_t frame_size, size_t n_frames, size_t *n_ok,
                      const char *who)
 {
-    if (n_ok)
-        *n_ok = 0;
+    size_t good = 0;
+    psdrt::StoreOk store_ok{n_ok, good};
     X_HANDLE(h, who);
     std::vector<FedPair> fed;
     bool go = false;
@@ -1176,20 +1115,15 @@ int frames_host_impl(XObj *h, const uint32_t *map, const uint8_t *frames, size_t
     X_ON_DEVICE(h);
     FrameSrc src;
     src.host = frames;
-    src.hdr = frames;
-    src.hdr_stride = frame_size;
-    size_t good = 0;
-    rc = ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
-    if (n_ok)
-        *n_ok = good;
-    return rc;
+    src.hdr = {frames, frame_size};
+    return ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
 }
 
 int frames_device_impl(XObj *h, const uint32_t *map, const uint8_t *d_frames, size_t frame_size, size_t n_frames, size_t *n_ok,
                        void *producer_event, const char *who)
 {
-    if (n_ok)
-        *n_ok = 0;
+    size_t good = 0;
+    psdrt::StoreOk store_ok{n_ok, good};
     X_HANDLE(h, who);
     std::vector<FedPair> fed;
     bool go = false;
@@ -1197,35 +1131,21 @@ int frames_device_impl(XObj *h, const uint32_t *map, const uint8_t *d_frames, si
     if (rc || !go)
         return rc;
     X_ON_DEVICE(h);
-    // the headers come to the host through one gather launch on a stream of the object's own; the host waits for that launch
-    // alone while the compute stream goes on with the rounds of earlier calls
-    if (!h->hdr_stream)
-        XCHK(h, hipStreamCreateWithFlags(&h->hdr_stream, hipStreamNonBlocking));
-    if (h->h_hdr_cap < 8 * n_frames) {
-        const size_t cap = std::max<size_t>(8 * n_frames + (8 * n_frames) / 2, (size_t)1 << 16);
-        uint8_t *nb = nullptr;
-        XCHK(h, hipHostMalloc(reinterpret_cast<void **>(&nb), cap, hipHostMallocDefault));
-        if (h->h_hdr)
-            (void)hipHostFree(h->h_hdr);
-        h->h_hdr = nb;
-        h->h_hdr_cap = cap;
-    }
+    // the headers come to the host through one gather launch on a stream of the object's own (behind the producer's event, as the
+    // copy stream's decodes are); the host waits for that launch alone while the compute stream goes on with the rounds of
+    // earlier calls
     if (producer_event) {
-        XCHK(h, hipStreamWaitEvent(h->hdr_stream, (hipEvent_t)producer_event, 0));
+        XCHK(h, h->hdr.open());
+        XCHK(h, hipStreamWaitEvent(h->hdr.stream, (hipEvent_t)producer_event, 0));
         XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
     }
-    XCHK(h, launch_header_gather(d_frames, frame_size, n_frames, h->h_hdr, h->hdr_stream));
+    XCHK(h, h->hdr.launch(d_frames, frame_size, n_frames));
     ++h->launches;
-    XCHK(h, hipStreamSynchronize(h->hdr_stream));
+    XCHK(h, hipStreamSynchronize(h->hdr.stream));
     FrameSrc src;
     src.dev = d_frames;
-    src.hdr = h->h_hdr;
-    src.hdr_stride = 8;
-    size_t good = 0;
-    rc = ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
-    if (n_ok)
-        *n_ok = good;
-    return rc;
+    src.hdr = {h->hdr.h_hdr, 8};
+    return ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
 }
 
 int loss_impl(XObj *h, psdc_loss *out, int reset, const char *who)

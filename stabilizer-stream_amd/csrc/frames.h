@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "wire_format.h"
 
 namespace psdk {
 
@@ -48,16 +49,7 @@ __device__ __forceinline__ float4 frame_sample4(const FrameSpan &fs, int ch, uns
 // The other payload formats (src/de/data.rs:84-212) -- Fls (format id 2), ThermostatEem (3), Mpll (4): ONE sample per batch and
 // trace.  The arithmetic is the reference's, operation by operation in f32 (`as f32` conversions, separate products and sum --
 // rustc never fuses them --, a correctly rounded square root, the scale constants evaluated in f32 in the reference's order): the
-// traces are bit-identical to Payload::traces.  (payload_kernel in kernels.hip, cross_frames_kernel in cross_frames.hip.)
-struct PayloadFmt {
-    int batch_bytes, ntraces;
-};
-__host__ __device__ constexpr PayloadFmt payload_fmt(int id)
-{
-    return id == 2 ? PayloadFmt{56, 4}   // [[[u8;4];7];2]  data.rs:86
-         : id == 3 ? PayloadFmt{80, 4}   // [[u8;4];16+4]   data.rs:144
-                   : PayloadFmt{24, 3};  // [[u8;4];6]      data.rs:168
-}
+// traces are bit-identical to Payload::traces.  (payload_kernel in kernels.hip, cross_frames_kernel in cross_frames.hip; bytes per batch and traces: wire_format.h.)
 
 // u32::from_le_bytes of word i of the batch at p: one load when the frames are 4-byte aligned (every valid frame_size is a multiple
 // of 8; the base is the caller's), bytes otherwise

@@ -17,18 +17,14 @@
 using namespace psdrt;
 
 namespace {
-// Payload layouts by Format id (src/de/mod.rs:12-17; src/de/data.rs:13, 86, 144, 168): bytes per batch, samples per batch and
-// trace, traces (Payload::traces).
-struct WireFmt {
-    int id;
-    size_t batch_bytes;
-    int spb, ntr;
-    const char *what;
-};
-const WireFmt *wire_fmt(int id)
+// what every frames call checks before it looks at a frame (check_frames_call, frame_scan.h); *go: there are frames to take
+int frames_begin(psdc_handle *h, bool four_traces, const void *frames, size_t frame_size, size_t n_frames, bool *go)
 {
-    static const WireFmt t[4] = {{1, 64, 8, 4, "AdcDac"}, {2, 56, 1, 4, "Fls"}, {3, 80, 1, 4, "ThermostatEem"}, {4, 24, 1, 3, "Mpll"}};
-    return id >= 1 && id <= 4 ? &t[id - 1] : nullptr;
+    *go = false;
+    if (four_traces && h->n_channels < 4)
+        return fail(h, PSDC_ERR_ARG, "AdcDac frames carry four traces: need n_channels >= 4");
+    const int rc = check_frames_call(frames, frame_size, n_frames, go);
+    return rc == PSDC_OK ? PSDC_OK : fail(h, rc, rc == PSDC_ERR_ARG ? "null input" : FRAME_SHORT_TEXT);
 }
 
 // Frames in host memory, frame by frame as Source::get does for Data::File / Data::Udp (src/source.rs:135-142, 158-165):
@@ -38,89 +34,41 @@ const WireFmt *wire_fmt(int id)
 // adcdac_only: any other valid format id is de::Error::UnknownFormat's code, as psdc_process_adcdac_frames documents.
 int ingest_frames_host(psdc_handle *h, bool adcdac_only, const uint8_t *frames, size_t frame_size, size_t n_frames, size_t *n_ok)
 {
-    if (n_ok)
-        *n_ok = 0;
+    size_t good = 0;
+    // *n_ok is the number of frames ingested at EVERY exit, device errors in mid-call included; a piece's frames enter `good` and
+    // Loss only once the piece is enqueued (its samples are in the streams), never before
+    StoreOk store_ok{n_ok, good};
     int rc = check_channel(h, 0);
     if (rc)
         return rc;
     ON_DEVICE(h, h->device);
-    if (adcdac_only && h->n_channels < 4)
-        return fail(h, PSDC_ERR_ARG, "AdcDac frames carry four traces: need n_channels >= 4");
-    if (n_frames == 0)
-        return PSDC_OK;
-    if (!frames)
-        return fail(h, PSDC_ERR_ARG, "null input");
-    if (frame_size < 8) // &input[..HEADER_SIZE] panics (src/de/frame.rs:50)
-        return fail(h, PSDC_ERR_FRAME_SIZE, "frame shorter than its header");
-    size_t good = 0;
-    // *n_ok is the number of frames ingested at EVERY exit, device errors in mid-call included; a piece's frames enter `good` and
-    // Loss only once the piece is enqueued (its samples are in the streams), never before
-    struct StoreOk {
-        size_t *p;
-        const size_t &v;
-        ~StoreOk()
-        {
-            if (p)
-                *p = v;
-        }
-    } store_ok{n_ok, good};
+    bool go = false;
+    rc = frames_begin(h, adcdac_only, frames, frame_size, n_frames, &go);
+    if (rc || !go)
+        return rc;
     int bad = PSDC_OK;
+    const HdrView hdr{frames, frame_size};
     const size_t payload = frame_size - 8;
     size_t f0 = 0;
     while (f0 < n_frames && bad == PSDC_OK) {
-        // the run's format: its first frame's (Header::parse, src/de/frame.rs:25-37)
-        const uint8_t *first = frames + f0 * frame_size;
-        if (first[0] != 0x7b || first[1] != 0x05) {
-            bad = PSDC_ERR_FRAME_HEADER;
+        const WireFmt *wf = nullptr;
+        bad = run_start(hdr, f0, adcdac_only, &wf);
+        if (bad != PSDC_OK)
             break;
-        }
-        const WireFmt *wf = wire_fmt(first[2]);
-        if (!wf || (adcdac_only && wf->id != 1)) { // unknown id -- or Fls / ThermostatEem / Mpll where only AdcDac is asked for
-            bad = PSDC_ERR_FRAME_FORMAT;
-            break;
-        }
-        if ((int)h->n_channels < wf->ntr)
+        if ((int)h->n_channels < wf->ntraces)
             return fail(h, PSDC_ERR_ARG, "the frames carry more traces than the handle has channels");
-        const int ntr = wf->ntr;
-        const int batches = (int)(payload / wf->batch_bytes);
-        bool run_end = false; // a frame of another (valid) format: the next run starts there
-        psdc_loss trial = h->loss; // Loss::update over the piece being scanned: committed to the handle with the piece
-        // host: validate headers (src/de/frame.rs:25-37, src/de/data.rs:22-25, 91-93, 149-150, 173-174) and keep the loss
-        // counters (Loss::update, src/loss.rs:11-26), piece by piece inside the upload loop below so
-        // that the scan of one piece runs while the piece before it is on the link
-        auto scan = [&](size_t fa, size_t cnt) -> size_t { // frames accepted from fa on; sets `bad` at the first bad one
-            for (size_t i = 0; i < cnt; ++i) {
-                const uint8_t *f = frames + (fa + i) * frame_size;
-                if (f[0] != 0x7b || f[1] != 0x05) {
-                    bad = PSDC_ERR_FRAME_HEADER;
-                    return i;
-                }
-                if (f[2] != wf->id) {
-                    if (!adcdac_only && wire_fmt(f[2])) {
-                        run_end = true;
-                        return i;
-                    }
-                    bad = PSDC_ERR_FRAME_FORMAT; // unknown id (or, for psdc_process_adcdac_frames, not AdcDac)
-                    return i;
-                }
-                if (payload % wf->batch_bytes != 0 || (int)f[3] != batches) {
-                    bad = PSDC_ERR_FRAME_SIZE;
-                    return i;
-                }
-                const uint32_t seq = (uint32_t)f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) | ((uint32_t)f[7] << 24);
-                trial.received += f[3];
-                if (trial.have_seq)
-                    trial.dropped += (uint32_t)(seq - trial.next_seq); // wrapping_sub
-                trial.next_seq = seq + f[3];                            // wrapping_add
-                trial.have_seq = 1;
-            }
-            return cnt;
-        };
-        if (batches == 0) {
-            const size_t cnt = scan(f0, n_frames - f0); // header-only frames carry no samples
-            h->loss = trial;
+        const int ntr = wf->ntraces;
+        const int batches = (int)(payload / (size_t)wf->batch_bytes);
+        // The headers are validated and the loss counters kept on the host (scan_piece), piece by piece inside the upload loop
+        // below so that the scan of one piece runs while the piece before it is on the link.  `trial` is Loss::update over the
+        // piece being scanned: committed to the handle with the piece.
+        int stop = SCAN_LIMIT;
+        if (batches == 0) { // header-only frames carry no samples: nothing to enqueue, Loss at once
+            const size_t cnt = scan_piece(hdr, *wf, payload, f0, n_frames - f0, adcdac_only, &h->loss, &stop);
             good += cnt;
             f0 += cnt;
+            if (stop < 0)
+                bad = stop;
             continue;
         }
         // order behind anything pending on these channels
@@ -158,9 +106,9 @@ int ingest_frames_host(psdc_handle *h, bool adcdac_only, const uint8_t *frames, 
             h->frames_cap = piece_bytes;
         }
         h->idle = false;
-        while (f0 < n_frames && bad == PSDC_OK && !run_end) {
-            trial = h->loss;
-            const size_t cnt = scan(f0, std::min(piece_frames, n_frames - f0));
+        while (f0 < n_frames && stop == SCAN_LIMIT) {
+            psdc_loss trial = h->loss;
+            const size_t cnt = scan_piece(hdr, *wf, payload, f0, std::min(piece_frames, n_frames - f0), adcdac_only, &trial, &stop);
             if (cnt == 0)
                 break;
             const size_t bytes = cnt * frame_size;
@@ -220,13 +168,10 @@ int ingest_frames_host(psdc_handle *h, bool adcdac_only, const uint8_t *frames, 
                 return rc;
             f0 += cnt;
         }
+        if (stop < 0)
+            bad = stop;
     }
-    if (bad != PSDC_OK)
-        return fail(h, bad,
-                    bad == PSDC_ERR_FRAME_HEADER   ? "Invalid frame header"
-                    : bad == PSDC_ERR_FRAME_FORMAT ? (adcdac_only ? "Unknown or non-AdcDac format ID" : "Unknown format ID")
-                                                   : "Payload size");
-    return PSDC_OK;
+    return bad == PSDC_OK ? PSDC_OK : fail(h, bad, frame_error_text(bad, adcdac_only));
 }
 } // namespace
 
@@ -245,20 +190,16 @@ int psdc_process_frames(psdc_handle *h, const uint8_t *frames, size_t frame_size
 int psdc_process_adcdac_frames_device(psdc_handle *h, const uint8_t *d_frames, size_t frame_size, size_t n_frames,
                                       size_t *n_ok)
 {
-    if (n_ok)
-        *n_ok = 0;
+    size_t enq = 0; // frames whose samples are in the streams
+    StoreOk store_ok{n_ok, enq};
     int rc = check_channel(h, 0);
     if (rc)
         return rc;
     ON_DEVICE(h, h->device);
-    if (h->n_channels < 4)
-        return fail(h, PSDC_ERR_ARG, "AdcDac frames carry four traces: need n_channels >= 4");
-    if (n_frames == 0)
-        return PSDC_OK;
-    if (!d_frames)
-        return fail(h, PSDC_ERR_ARG, "null input");
-    if (frame_size < 8) // &input[..HEADER_SIZE] panics (src/de/frame.rs:50)
-        return fail(h, PSDC_ERR_FRAME_SIZE, "frame shorter than its header");
+    bool go = false;
+    rc = frames_begin(h, true, d_frames, frame_size, n_frames, &go);
+    if (rc || !go)
+        return rc;
     const size_t payload = frame_size - 8;
     const int batches = (int)(payload / 64);
     // host-fed samples staged on these channels come first in their streams
@@ -339,16 +280,6 @@ int psdc_process_adcdac_frames_device(psdc_handle *h, const uint8_t *d_frames, s
         trial.next_seq = next;
         trial.have_seq = 1;
     }
-    size_t enq = 0; // frames whose samples are in the streams
-    struct StoreOk {
-        size_t *p;
-        const size_t &v;
-        ~StoreOk()
-        {
-            if (p)
-                *p = v;
-        }
-    } store_ok{n_ok, enq};
     if (good && batches > 0) {
         h->idle = false;
         const size_t per_frame = (size_t)batches * 8; // samples per trace and frame
@@ -482,88 +413,40 @@ int psdc_process_adcdac_frames_device(psdc_handle *h, const uint8_t *d_frames, s
     }
     enq = good; // (batches == 0: header-only frames carry no samples and count all the same)
     h->loss = trial;
-    if (bad != PSDC_OK)
-        return fail(h, bad,
-                    bad == PSDC_ERR_FRAME_HEADER   ? "Invalid frame header"
-                    : bad == PSDC_ERR_FRAME_FORMAT ? "Unknown or non-AdcDac format ID"
-                                                   : "Payload size");
-    return PSDC_OK;
+    return bad == PSDC_OK ? PSDC_OK : fail(h, bad, frame_error_text(bad, true));
 }
 
 // psdc_process_frames for frames that already sit in device memory.  The headers (8 of every frame_size bytes) come to the host through
-// one small gather kernel and are validated there exactly as ingest_frames_host does; the payloads never leave the device: runs of Fls /
-// ThermostatEem / Mpll frames are decoded by payload_kernel straight from the caller's buffer into the stage-0 streams, runs of AdcDac
-// frames go through psdc_process_adcdac_frames_device (read in place where a fused kernel exists).
+// one small gather kernel (HeaderGather, host_runtime.h) and are validated there by the scanner that ingest_frames_host uses; the
+// payloads never leave the device: runs of Fls / ThermostatEem / Mpll frames are decoded by payload_kernel straight from the caller's
+// buffer into the stage-0 streams, runs of AdcDac frames go through psdc_process_adcdac_frames_device (read in place where a fused
+// kernel exists).
 int psdc_process_frames_device(psdc_handle *h, const uint8_t *d_frames, size_t frame_size, size_t n_frames, size_t *n_ok)
 {
-    if (n_ok)
-        *n_ok = 0;
+    size_t good = 0, f0 = 0;
+    StoreOk store_ok{n_ok, good};
     int rc = check_channel(h, 0);
     if (rc)
         return rc;
     ON_DEVICE(h, h->device);
-    if (n_frames == 0)
-        return PSDC_OK;
-    if (!d_frames)
-        return fail(h, PSDC_ERR_ARG, "null input");
-    if (frame_size < 8) // &input[..HEADER_SIZE] panics (src/de/frame.rs:50)
-        return fail(h, PSDC_ERR_FRAME_SIZE, "frame shorter than its header");
-    // The headers come to the host through ONE small kernel that writes them into pinned memory, on a stream of its own: the host
-    // waits for that launch alone while the compute stream keeps working on earlier calls (a strided hipMemcpy2D of 70 000 headers
-    // took ~0.25 ms of a 0.39 ms call: Mpll frames 32 -> 84 GS/s, tools/bench_frames.py).
-    if (!h->hdr_stream) {
-        hipStream_t st = nullptr;
-        HIPCHK(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        h->hdr_stream = st;
-    }
-    if (h->h_hdr_cap < 8 * n_frames) {
-        const size_t cap = std::max<size_t>(8 * n_frames + (8 * n_frames) / 2, (size_t)1 << 16);
-        uint8_t *nb = nullptr;
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&nb), cap, hipHostMallocDefault));
-        if (h->h_hdr)
-            (void)hipHostFree(h->h_hdr);
-        h->h_hdr = nb;
-        h->h_hdr_cap = cap;
-    }
-    HIPCHK(h, launch_header_gather(d_frames, frame_size, n_frames, h->h_hdr, h->hdr_stream));
-    HIPCHK(h, hipStreamSynchronize(h->hdr_stream));
-    struct HdrView { // (hdr.data() / hdr[i] as the vector this replaced)
-        const uint8_t *p;
-        const uint8_t *data() const { return p; }
-        uint8_t operator[](size_t i) const { return p[i]; }
-    } hdr{h->h_hdr};
+    bool go = false;
+    rc = frames_begin(h, false, d_frames, frame_size, n_frames, &go);
+    if (rc || !go)
+        return rc;
+    HIPCHK(h, h->hdr.launch(d_frames, frame_size, n_frames));
+    HIPCHK(h, hipStreamSynchronize(h->hdr.stream));
+    const HdrView hdr{h->hdr.h_hdr, 8};
     const size_t payload = frame_size - 8;
-    size_t good = 0, f0 = 0;
     int bad = PSDC_OK;
-    struct StoreOk { // *n_ok = the frames ingested, at every exit (device errors in mid-call included)
-        size_t *p;
-        const size_t &v;
-        ~StoreOk()
-        {
-            if (p)
-                *p = v;
-        }
-    } store_ok{n_ok, good};
-    auto done = [&](int code) {
-        return code == PSDC_OK ? PSDC_OK
-                               : fail(h, code,
-                                      code == PSDC_ERR_FRAME_HEADER   ? "Invalid frame header"
-                                      : code == PSDC_ERR_FRAME_FORMAT ? "Unknown format ID"
-                                                                      : "Payload size");
-    };
-    while (f0 < n_frames) {
-        const uint8_t *first = hdr.data() + 8 * f0;
-        if (first[0] != 0x7b || first[1] != 0x05)
-            return done(PSDC_ERR_FRAME_HEADER);
-        const WireFmt *wf = wire_fmt(first[2]);
-        if (!wf)
-            return done(PSDC_ERR_FRAME_FORMAT);
-        if ((int)h->n_channels < wf->ntr)
+    while (f0 < n_frames && bad == PSDC_OK) {
+        const WireFmt *wf = nullptr;
+        bad = run_start(hdr, f0, false, &wf);
+        if (bad != PSDC_OK)
+            break;
+        if ((int)h->n_channels < wf->ntraces)
             return fail(h, PSDC_ERR_ARG, "the frames carry more traces than the handle has channels");
         if (wf->id == 1) { // a run of AdcDac frames: its own entry point checks them (and counts their Loss) on the device
-            size_t run = 1;
-            while (f0 + run < n_frames && hdr[8 * (f0 + run)] == 0x7b && hdr[8 * (f0 + run) + 1] == 0x05 && hdr[8 * (f0 + run) + 2] == 1)
-                ++run;
+            const size_t run = adcdac_run_length(hdr, f0, n_frames);
             size_t ok = 0;
             rc = psdc_process_adcdac_frames_device(h, d_frames + f0 * frame_size, frame_size, run, &ok);
             good += ok;
@@ -572,8 +455,8 @@ int psdc_process_frames_device(psdc_handle *h, const uint8_t *d_frames, size_t f
             f0 += run;
             continue;
         }
-        const int ntr = wf->ntr;
-        const int batches = (int)(payload / wf->batch_bytes);
+        const int ntr = wf->ntraces;
+        const int batches = (int)(payload / (size_t)wf->batch_bytes);
         // order behind anything pending on these channels (held spans, host-fed samples)
         bool pend = false;
         for (int ci = 0; ci < ntr; ++ci)
@@ -585,35 +468,10 @@ int psdc_process_frames_device(psdc_handle *h, const uint8_t *d_frames, size_t f
         }
         // pieces of ~2^22 samples per trace: a stage-0 stream buffer never grows by more than that at once
         const size_t piece_frames = std::max<size_t>(1, ((size_t)1 << 22) / (size_t)std::max(1, batches));
-        bool run_end = false;
-        while (f0 < n_frames && bad == PSDC_OK && !run_end) {
-            size_t cnt = 0;
-            const size_t lim = std::min(piece_frames, n_frames - f0);
+        int stop = SCAN_LIMIT;
+        while (f0 < n_frames && stop == SCAN_LIMIT) {
             psdc_loss trial = h->loss; // committed with the piece, once it is enqueued
-            for (; cnt < lim; ++cnt) { // Header::parse + the payload's size checks + Loss::update, as ingest_frames_host's scan
-                const uint8_t *f = hdr.data() + 8 * (f0 + cnt);
-                if (f[0] != 0x7b || f[1] != 0x05) {
-                    bad = PSDC_ERR_FRAME_HEADER;
-                    break;
-                }
-                if (f[2] != wf->id) {
-                    if (wire_fmt(f[2]))
-                        run_end = true;
-                    else
-                        bad = PSDC_ERR_FRAME_FORMAT;
-                    break;
-                }
-                if (payload % wf->batch_bytes != 0 || (int)f[3] != batches) {
-                    bad = PSDC_ERR_FRAME_SIZE;
-                    break;
-                }
-                const uint32_t seq = (uint32_t)f[4] | ((uint32_t)f[5] << 8) | ((uint32_t)f[6] << 16) | ((uint32_t)f[7] << 24);
-                trial.received += f[3];
-                if (trial.have_seq)
-                    trial.dropped += (uint32_t)(seq - trial.next_seq); // wrapping_sub
-                trial.next_seq = seq + f[3];                            // wrapping_add
-                trial.have_seq = 1;
-            }
+            const size_t cnt = scan_piece(hdr, *wf, payload, f0, std::min(piece_frames, n_frames - f0), false, &trial, &stop);
             if (cnt == 0)
                 break;
             if (batches == 0) { // header-only frames carry no samples
@@ -650,10 +508,10 @@ int psdc_process_frames_device(psdc_handle *h, const uint8_t *d_frames, size_t f
             }
             f0 += cnt;
         }
-        if (bad != PSDC_OK)
-            return done(bad);
+        if (stop < 0)
+            bad = stop;
     }
-    return done(PSDC_OK);
+    return bad == PSDC_OK ? PSDC_OK : fail(h, bad, frame_error_text(bad));
 }
 
 } // extern "C"

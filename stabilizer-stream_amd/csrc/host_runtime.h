@@ -4,6 +4,8 @@
 //   runtime.cpp        handle lifecycle, stream buffers, staging / uploads, psdc_process / psdc_process_device, flush / sync
 //   planner.cpp        advance_round: one round of the cascade pipeline turned into kernel jobs (plan.h gives the closed forms)
 //   frames_ingest.cpp  frames in host or device memory (Frame::from_bytes, Loss::update, Payload::traces)
+//   frame_scan.h       which frames of a call are taken and what Loss becomes: run_start / scan_piece, the one header scanner of
+//                      every frames call (here and in cross_runtime.cpp); wire_format.h is the one table of the payload layouts
 //   readout.cpp        PsdStage accessors, PsdCascade::psd stitch, Break, packed read-out, Var / Trace::plot, the single-stage Psd<N>
 //
 // Mirrors PsdCascade<N> (src/psd.rs:399-544) for `n_channels` independent traces on one MI355X: per (channel, stage) the
@@ -15,10 +17,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "frame_scan.h"
 #include "hbf_taps.h"
 #include "kernels.h"
 #include "plan.h"
@@ -119,6 +123,44 @@ struct Knobs {
     bool skip_post = false;    // PSDC_DBG_SKIP_POST, read in a -DPSDC_DEBUG_KNOBS build only (WRONG results: a timing bound)
 };
 
+// The 8 header bytes of every frame of a call whose frames sit in device memory, brought to pinned host memory by ONE small
+// kernel (launch_header_gather) on a stream of its own: the host waits for that launch alone while the compute stream keeps
+// working on earlier calls (a strided hipMemcpy2D of 70 000 headers took ~0.25 ms of a 0.39 ms call: Mpll frames 32 -> 84 GS/s,
+// tools/bench_frames.py).  The caller waits for `stream` before it reads `h_hdr`.
+struct HeaderGather {
+    uint8_t *h_hdr = nullptr; // pinned, 8 bytes a frame
+    size_t cap = 0;           // bytes: grown to 1.5 x the largest call
+    hipStream_t stream = nullptr;
+    // the stream, made on first use (launch does it too: for a caller that orders the stream behind an event before the gather)
+    hipError_t open() { return stream ? hipSuccess : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    hipError_t launch(const uint8_t *d_frames, size_t frame_size, size_t n_frames)
+    {
+        hipError_t e = open();
+        if (e == hipSuccess && cap < 8 * n_frames) {
+            const size_t grown = std::max<size_t>(8 * n_frames + (8 * n_frames) / 2, (size_t)1 << 16);
+            uint8_t *nb = nullptr;
+            e = hipHostMalloc(reinterpret_cast<void **>(&nb), grown, hipHostMallocDefault);
+            if (e == hipSuccess) {
+                if (h_hdr)
+                    (void)hipHostFree(h_hdr);
+                h_hdr = nb;
+                cap = grown;
+            }
+        }
+        return e == hipSuccess ? launch_header_gather(d_frames, frame_size, n_frames, h_hdr, stream) : e;
+    }
+    void release()
+    {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+        if (h_hdr)
+            (void)hipHostFree(h_hdr);
+        *this = HeaderGather{};
+    }
+};
+
 } // namespace psdrt
 
 struct psdc_handle {
@@ -157,9 +199,7 @@ struct psdc_handle {
     float *d_spectra = nullptr; // [n_channels][MAX_STAGES][n] accumulators, one slab
     float *h_read = nullptr;    // pinned bounce buffer for read-outs (MAX_STAGES * n floats)
     unsigned long long *d_scan = nullptr; // 5 words: accumulators of the device-side frame header scan + Loss sums (kept zero)
-    uint8_t *h_hdr = nullptr;             // pinned: the frame headers of one psdc_process_frames_device call (launch_header_gather)
-    size_t h_hdr_cap = 0;                 // bytes
-    hipStream_t hdr_stream = nullptr;     // the gather runs beside the compute stream's work (the host waits for it alone)
+    psdrt::HeaderGather hdr;              // the frame headers of one psdc_process_frames_device call
     unsigned long long *h_scan = nullptr; // pinned: its four result words
     hipStream_t scan_stream = nullptr;    // the scan runs beside the compute stream's work (the host waits for it alone)
     std::vector<psdk::FrameSpan> fs_pool;       // frame spans named by this round's jobs (FusedJob::fspan ... index this until a launch maps them)

@@ -822,7 +822,7 @@ template <int FMT>
 __global__ __launch_bounds__(256) void payload_kernel(const uint8_t *__restrict__ frames, size_t frame_size, size_t n_frames, int batches,
                                                       float *d0, float *d1, float *d2, float *d3)
 {
-    constexpr int BB = payload_fmt(FMT).batch_bytes;
+    constexpr int BB = wire_fmt_v(FMT).batch_bytes;
     const bool aligned = ((reinterpret_cast<uintptr_t>(frames) | frame_size) & 3u) == 0;
     const size_t total = n_frames * (size_t)batches;
     for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {

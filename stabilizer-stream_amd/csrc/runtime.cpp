@@ -1005,12 +1005,7 @@ void psdc_destroy(psdc_handle *h)
         (void)hipFree(h->d_scan);
     if (h->h_scan)
         (void)hipHostFree(h->h_scan);
-    if (h->hdr_stream) {
-        (void)hipStreamSynchronize(h->hdr_stream);
-        (void)hipStreamDestroy(h->hdr_stream);
-    }
-    if (h->h_hdr)
-        (void)hipHostFree(h->h_hdr);
+    h->hdr.release();
     for (int i = 0; i < 2; ++i) {
         if (h->d_frames[i])
             (void)hipFree(h->d_frames[i]);

@@ -522,6 +522,42 @@ void scenario_alloc_failure()
         fail("model: %s", e.c_str());
 }
 
+// ---- the general frames calls (psdc_process_frames[_device]) on a run of Mpll frames with one bad frame in the middle: what is
+// accepted, the code and Loss.  (The model's payload decode writes no identities, so the calls stay below one segment a trace.)
+void scenario_general_frames()
+{
+    new_scenario("general frames", 0);
+    const int batches = 3;
+    const size_t fs = 8 + 24 * (size_t)batches;
+    for (int dev = 0; dev < 2; ++dev) {
+        psdc_handle *h = psdc_create(1024, PSDC_WINDOW_HANN, 3, 0);
+        if (!h) {
+            fail("psdc_create: %s", psdc_last_error(nullptr));
+            return;
+        }
+        std::vector<uint8_t> fr = make_frames(8, batches, 100);
+        for (size_t f = 0; f < 8; ++f)
+            fr[f * (8 + 64 * (size_t)batches) + 2] = 4; // Mpll: 24 bytes a batch (the frames are cut to that size below)
+        std::vector<uint8_t> mp(8 * fs);
+        for (size_t f = 0; f < 8; ++f)
+            memcpy(&mp[f * fs], &fr[f * (8 + 64 * (size_t)batches)], fs);
+        mp[5 * fs + 3] = (uint8_t)(batches + 1); // frame 5 names a batch more than it carries
+        size_t ok = 99;
+        const int rc = dev ? psdc_process_frames_device(h, mp.data(), fs, 8, &ok) : psdc_process_frames(h, mp.data(), fs, 8, &ok);
+        if (rc != PSDC_ERR_FRAME_SIZE || ok != 5 || std::string(psdc_last_error(h)) != "Payload size")
+            fail("%s frames, bad frame 5 of 8: rc %d, %zu frames accepted (%s)", dev ? "device" : "host", rc, ok, psdc_last_error(h));
+        psdc_loss loss{};
+        CK(psdc_loss_read(h, &loss, 0));
+        if (loss.received != 15 || loss.dropped != 0 || loss.next_seq != 115 || loss.have_seq != 1)
+            fail("%s frames: Loss received %llu dropped %llu next_seq %u", dev ? "device" : "host", (unsigned long long)loss.received,
+                 (unsigned long long)loss.dropped, loss.next_seq);
+        CK(psdc_sync(h));
+        psdc_destroy(h);
+    }
+    for (const std::string &e : world().errors)
+        fail("model: %s", e.c_str());
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -549,6 +585,7 @@ int main(int argc, char **argv)
     }
     scenario_hold_rules();
     scenario_alloc_failure();
+    scenario_general_frames();
     new_scenario("end", 0);
     if (sim::rt().live_blocks != 0) {
         fprintf(stderr, "FAIL %zu device / pinned allocations were never freed\n", sim::rt().live_blocks);
