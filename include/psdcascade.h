@@ -646,6 +646,73 @@ int psdc_csm_stitch(uint32_t n, uint32_t m, float power, float nenbw, size_t ove
 int psdc_csm_stats_read(psdc_csm *h, uint64_t *launches, uint64_t *sample_times_in, int reset);
 const char *psdc_csm_last_error(const psdc_csm *h);
 
+/* ---- zoom cascade: log-resolution spectrum around a carrier --------------------------------------------------
+ * The cascade resolves 1 / (N 8^k) at stage k, but only towards frequency 0.  A zoom object puts an NCO mixer in front of
+ * the same cascade, as a phase-noise analyser does: `n_channels` independent real f32 streams, each with its own carrier,
+ * each mixed to a complex baseband pair (I, Q) whose two-sided spectrum is kept.
+ * Carrier: a 64-bit frequency tuning word `ftw` and a start phase `phase0`, both uint64_t in units of 2^-64 turn.  Sample
+ * j of the channel's stream, counted from create or reset in 64 bits, has the phase phi_j = phase0 + ftw j mod 2^64, exact
+ * in integer arithmetic however the stream is cut into calls; f0 = ftw / 2^64 cycles per sample.  The default is ftw = 0,
+ * phase0 = 0.  A carrier may be set only while the channel has taken no sample since create or reset (a reset also puts
+ * every carrier back to the default); otherwise PSDC_ERR_ARG with a text.
+ * Mixing: z_j = x_j exp(-2 pi i phi_j / 2^64), so I_j = x_j c and Q_j = -x_j s in f32 with (c, s) the f32 cosine and sine of
+ * the top 32 bits of phi_j: an exact integer octant reduction, then polynomials of explicit fused multiply-adds (csrc/zoom_lo.h,
+ * absolute error <= 2^-23, the same bits on host and device).  Quarter turns give exactly (+-1, 0) and (0, +-1).
+ * Stages: per stage (I, Q) are two Psd<N> stages (src/psd.rs:195-269) in lockstep exactly as a pair's two channels are (see
+ * the cross-spectral density cascade above): the same segmentation, Window<N>, Detrend applied to I and Q separately, /8
+ * half-band decimation of each with the drain of 35 outputs, lazy stages, the EWMA factor g of src/psd.rs:218-233 and
+ * 64-bit counts.  Mixing happens once, in front of stage 0.  A channel has exactly the stages, counts, pendings and Breaks of
+ * a PsdCascade fed x.
+ * Rows: each segment is ONE N-point complex transform Z of I + i Q.  A stage keeps two f64 rows of n/2 + 1 bins,
+ *     upper[k] = g upper[k] + |Z[k]|^2,   lower[k] = g lower[k] + |Z[(N - k) mod N]|^2,   k = 0 ... N/2
+ * (bins 0 and N/2 appear in both).  Nothing is subtracted anywhere: a single sideband does not leak into its image beyond
+ * the transform's own rounding, which the sums Sii + Sqq -+ 2 Im Siq of a pair object fed (I, Q) cannot offer.
+ * Read-out: PsdCascade::psd (src/psd.rs:479-543) applied to each row with the same bins, Breaks and 1 / (gain() decimation).
+ * With that unchanged gain `upper` at offset f is the reference's one-sided PSD of x at f0 + f and `lower` that at f0 - f (a
+ * real x has a two-sided density of half its one-sided one, and the factor N/2 of the cascade's gain restores it): white noise
+ * of variance 1 reads 2 in every bin of both rows.
+ * Sizes and windows are those of pairs: n a power of two 64 ... 4096; Window::hann(), Window::rectangular(), or a caller's
+ * table with (n - overlap) % 8 == 0.  Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere.  There is no CPU fallback.
+ * Stream ordering, the caller-keeps-memory rule, errors and the device rule are those of the pair object.  The mixer takes
+ * the place of the pair object's input copy, on the same side stream under the same events, so it overlaps the round before;
+ * host samples go up through the pinned staging into a 16 MB device landing buffer first (made by the first host call).  A
+ * steady-state call is 1 + 3 kernel launches (mixer; segments, decimators, fold + tails) whatever the depth, with the pair
+ * object's table limits.  Host and device calls of the same samples, and the same calls twice, give the same bits.
+ * A bank's channel equals a single object fed the same calls bit for bit only when its rounds are that object's: each
+ * channel fed and read out in turn.  A round plans every channel with work, so interleaved calls put a channel's decimated
+ * stages into other channels' rounds, cut a round's segments elsewhere and reorder f32 partial sums: the same spectra
+ * within 2e-6, as for the pairs of a pair object.
+ * Memory: per (channel, stage) two ping-pong buffers for each of I and Q as for a pair, plus 32 MB of pinned staging. */
+typedef struct psdc_zoom psdc_zoom;
+/* n_channels channels; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_zoom *psdc_zoom_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+/* the same with a caller-built Window<N> (src/psd.rs:12-20), as psdc_create_window */
+psdc_zoom *psdc_zoom_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap,
+                                   uint32_t n_channels, int device);
+void psdc_zoom_destroy(psdc_zoom *h);
+/* back to the state of a fresh object: stages, buffers, settings, carriers and statistics */
+int psdc_zoom_reset(psdc_zoom *h);
+int psdc_zoom_set_detrend(psdc_zoom *h, int detrend_kind);
+int psdc_zoom_set_avg(psdc_zoom *h, uint32_t limit, uint32_t count);
+/* the channel's carrier (see Carrier above); PSDC_ERR_ARG once the channel has taken a sample */
+int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* len real samples of a channel from host memory */
+int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len);
+/* the same from device memory (any 4-byte aligned address and any length); producer_event: hipEvent_t or NULL */
+int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_zoom_sync(psdc_zoom *h);
+int psdc_zoom_num_stages(psdc_zoom *h, uint32_t channel);
+/* raw accumulators of one stage: upper, lower n/2 + 1 floats each; any may be NULL */
+int psdc_zoom_stage_spectra(psdc_zoom *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper,
+                            float *lower);
+/* PsdCascade::psd (src/psd.rs:479-543) of both rows: upper, lower `cap` floats each (either may be NULL) */
+int psdc_zoom_psd(psdc_zoom *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                  float *upper, float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
+                  size_t *n_breaks);
+/* kernel launches issued and samples accepted since creation or the last reset of the statistics */
+int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_zoom_last_error(const psdc_zoom *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

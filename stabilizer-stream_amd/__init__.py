@@ -347,6 +347,21 @@ def lib():
                                i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_csm_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_csm_last_error", C.c_char_p, [H])
+    f("psdc_zoom_create", H, [u32, i32, u32, i32])
+    f("psdc_zoom_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_zoom_destroy", None, [H])
+    f("psdc_zoom_reset", i32, [H])
+    f("psdc_zoom_set_detrend", i32, [H, i32])
+    f("psdc_zoom_set_avg", i32, [H, u32, u32])
+    f("psdc_zoom_set_carrier", i32, [H, u32, u64, u64])
+    f("psdc_zoom_process", i32, [H, u32, fp, sz])
+    f("psdc_zoom_process_device", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
+    f("psdc_zoom_sync", i32, [H])
+    f("psdc_zoom_num_stages", i32, [H, u32])
+    f("psdc_zoom_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp])
+    f("psdc_zoom_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_zoom_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_zoom_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -373,6 +388,9 @@ EXPORTS = [
     "psdc_csm_set_detrend", "psdc_csm_set_avg", "psdc_csm_process", "psdc_csm_process_device", "psdc_csm_process_frames",
     "psdc_csm_process_frames_device", "psdc_csm_loss_read", "psdc_csm_sync", "psdc_csm_num_stages", "psdc_csm_stage_spectra",
     "psdc_csm_csd", "psdc_csm_stitch", "psdc_csm_stats_read", "psdc_csm_last_error",
+    "psdc_zoom_create", "psdc_zoom_create_window", "psdc_zoom_destroy", "psdc_zoom_reset", "psdc_zoom_set_detrend",
+    "psdc_zoom_set_avg", "psdc_zoom_set_carrier", "psdc_zoom_process", "psdc_zoom_process_device", "psdc_zoom_sync",
+    "psdc_zoom_num_stages", "psdc_zoom_stage_spectra", "psdc_zoom_psd", "psdc_zoom_stats_read", "psdc_zoom_last_error",
 ]
 
 
@@ -1045,6 +1063,184 @@ class CsmCascade:
 
     def reset(self):
         self._b.reset()
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+def zoom_ftw(f0):
+    """(ftw, f0 used): the 64-bit frequency tuning word of a carrier at f0 cycles per sample, round(f0 2^64) mod 2^64, and the
+    frequency ftw / 2^64 it stands for.  f0 may be a float, a Fraction or anything Fraction() takes: the product is exact."""
+    from fractions import Fraction
+    ftw = round(Fraction(f0) * (1 << 64)) % (1 << 64)
+    return ftw, ftw / float(1 << 64)
+
+
+def two_sided(upper, lower, breaks):
+    """(offsets, density) of a zoom read-out as one two-sided spectrum: the offsets from the carrier in cycles per sample,
+    ascending from -0.5 to 0.5, with the density at each: `lower` mirrored, then `upper`.  Offset 0 (in both rows) appears once,
+    from `upper`; so does Nyquist, at +0.5."""
+    f = np.asarray(Break.frequencies(breaks), np.float64)
+    up, lo = np.asarray(upper), np.asarray(lower)
+    order = np.argsort(f, kind="stable")
+    f, up, lo = f[order], up[order], lo[order]
+    neg = (f > 0) & (f < 0.5)
+    return np.concatenate([-f[neg][::-1], f]), np.concatenate([lo[neg][::-1], up])
+
+
+def _raise_zoom(code, h=None):
+    msg = lib().psdc_zoom_last_error(h)
+    raise PsdError(code, msg.decode() if msg else "")
+
+
+class ZoomCascadeBank:
+    """`n_channels` independent zoom cascades (psdc_zoom_*): each real stream is mixed down from its own carrier (a 64-bit
+    tuning word and start phase, exact in integers) to I + i Q in front of the cascade, and every stage keeps the two-sided
+    |Z|^2 of it as two rows: `upper` at offset f is the PSD of x at f0 + f, `lower` that at f0 - f, both scaled as
+    PsdCascade::psd scales its one-sided spectrum (white noise of variance 1 reads 2)."""
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_zoom_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels,
+                                                      device)
+        else:
+            self._h = self._L.psdc_zoom_create(n, int(window), n_channels, device)
+        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
+        if not self._h:
+            msg = self._L.psdc_zoom_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_zoom_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_zoom(rc, self._h)
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        self._ck(self._L.psdc_zoom_reset(self._h))
+        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_zoom_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_zoom_set_avg(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
+        """The channel's carrier, as f0 (cycles per sample, through zoom_ftw) or as the tuning word itself; phase0 in 2^-64
+        turn.  Only before the channel's first sample.  Returns the f0 actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        self._ck(self._L.psdc_zoom_set_carrier(self._h, channel, ftw, phase0))
+        self.carriers[channel] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._L.psdc_zoom_process(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zoom_process_device(self._h, channel, C.c_void_p(ptr), length,
+                                                  C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._L.psdc_zoom_sync(self._h))
+
+    def num_stages(self, channel=0):
+        return self._ck(self._L.psdc_zoom_num_stages(self._h, channel))
+
+    def stage_spectra(self, channel, stage):
+        """(info, upper, lower) of one stage's raw accumulators."""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        up, lo = np.empty(b, np.float32), np.empty(b, np.float32)
+        self._ck(self._L.psdc_zoom_stage_spectra(self._h, channel, stage, C.byref(st), _fptr(up), _fptr(lo)))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, up, lo
+
+    def psd(self, channel=0, opts=MergeOpts()):
+        """(upper, lower, breaks): PsdCascade::psd of each row; Break.frequencies(breaks) are the offsets of both."""
+        ns = self.num_stages(channel)
+        cap = max(1, ns * (self.n // 2 + 1))
+        up, lo = np.empty(cap, np.float32), np.empty(cap, np.float32)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_zoom_psd(self._h, channel, int(opts.keep_overlap), opts.min_count,
+                                       int(opts.keep_transition_band), _fptr(up), _fptr(lo), cap, C.byref(plen), br, ns,
+                                       C.byref(nb)))
+        m = plen.value
+        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_zoom_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+
+class ZoomCascade:
+    """One stream around one carrier: ZoomCascade(n, f0=0.2) or ZoomCascade(n, ftw=...).  `f0` is the frequency in use
+    (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = ZoomCascadeBank(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0):
+        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
+        self.ftw, self.phase0 = self._b.carriers[0]
+        return self.f0
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x):
+        self._b.process(0, x)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def psd(self, opts=MergeOpts()):
+        return self._b.psd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        self._b.reset()
+        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
 
     def sync(self):
         self._b.sync()

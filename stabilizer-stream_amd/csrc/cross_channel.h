@@ -1,6 +1,8 @@
-// cross_channel.h -- one channel of the cross-spectral kernels, shared by cross.hip (pairs) and csm.hip (groups of m channels):
+// cross_channel.h -- one channel of the cross-spectral kernels, shared by cross.hip (pairs), csm.hip (groups of m channels) and
+// zoom.hip (the I / Q pair of a mixed-down channel):
 // load, detrend and window two consecutive segments of a channel, transform them as one complex signal and leave the spectrum
-// in natural order in an LDS frame (cross_fft.h).  Device code only.
+// in natural order in an LDS frame (cross_fft.h) -- or, for the zoom kernel, leave nothing in the frame and add |Z|^2 of the
+// thread's bins to its registers.  Device code only.
 #pragma once
 #include "cross_fft.h"
 
@@ -57,11 +59,15 @@ __device__ __forceinline__ void xfft_run(int t, cf *v, cf *frame, const cf *__re
 
 // Load, detrend, window one channel's segment pair (a = segment la, b = la + 1) into v, transform, and leave the spectrum of
 // z = a + i b in natural order in `frame`.
-template <int N>
+// ZOOM = true (zoom.hip): segment b is read from the stream srcq in place of src -- a and b are the I and Q of ONE segment --
+// and the spectrum is not stored: |Z|^2 of the thread's bins is added to pw, pw[s] being bin freq_of_slot<N>(t, s).
+template <int N, bool ZOOM = false>
 __device__ __forceinline__ void cross_channel(const float *__restrict__ src, long long ofs_la, long long ofs_lb, bool act_a,
                                               bool act_b, int detrend, float ampa, float ampb, int t, int team, cf *frame,
-                                              float *red, const float *__restrict__ win, const cf *__restrict__ tw)
+                                              float *red, const float *__restrict__ win, const cf *__restrict__ tw,
+                                              const float *srcq = nullptr, float *pw = nullptr)
 {
+    const float *srcb = ZOOM ? srcq : src;
     using Cfg = CrossCfg<N>;
     using P0 = PassInfo<N, 0>;
     constexpr int E = Cfg::E, TEAM = Cfg::TEAM;
@@ -71,7 +77,7 @@ __device__ __forceinline__ void cross_channel(const float *__restrict__ src, lon
 #pragma unroll
         for (int m = 0; m < P0::R; ++m) {
             const int nidx = P0::elem(t, i, m);
-            const float va = src[ofs_la + nidx], vb = src[ofs_lb + nidx];
+            const float va = src[ofs_la + nidx], vb = srcb[ofs_lb + nidx];
             ra[i * P0::R + m] = act_a ? va : 0.0f;
             rb[i * P0::R + m] = act_b ? vb : 0.0f;
         }
@@ -79,11 +85,11 @@ __device__ __forceinline__ void cross_channel(const float *__restrict__ src, lon
     float oa = 0.0f, ob = 0.0f, ma = 0.0f, mb = 0.0f;
     slope2 sa = {0.0f, 0.0f}, sb = {0.0f, 0.0f};
     if (detrend == 1) { // Midpoint src/psd.rs:87-93
-        const float va = src[ofs_la + N / 2], vb = src[ofs_lb + N / 2];
+        const float va = src[ofs_la + N / 2], vb = srcb[ofs_lb + N / 2];
         oa = act_a ? va : 0.0f;
         ob = act_b ? vb : 0.0f;
     } else if (detrend == 2) { // Span :94-102
-        const float a0 = src[ofs_la], a1 = src[ofs_la + N - 1], b0 = src[ofs_lb], b1 = src[ofs_lb + N - 1];
+        const float a0 = src[ofs_la], a1 = src[ofs_la + N - 1], b0 = srcb[ofs_lb], b1 = srcb[ofs_lb + N - 1];
         if (act_a) {
             oa = a0;
             sa = span_slope(oa, a1, N);
@@ -154,7 +160,13 @@ __device__ __forceinline__ void cross_channel(const float *__restrict__ src, lon
             v[s].im = b * w * ampb;
         }
     xfft_run<N, 0>(t, v, frame, tw);
-    store_natural<N>(t, v, frame);
+    if constexpr (ZOOM) {
+#pragma unroll
+        for (int s = 0; s < E; ++s)
+            pw[s] += v[s].re * v[s].re + v[s].im * v[s].im;
+    } else {
+        store_natural<N>(t, v, frame);
+    }
 }
 
 } // namespace psdk

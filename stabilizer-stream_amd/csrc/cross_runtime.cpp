@@ -1,7 +1,9 @@
-// cross_runtime.cpp -- the cross-spectral cascades behind psdc_cross_* / psdc_csd_* (pairs) and psdc_csm_* (groups of m = 2 ... 4
-// channels with their full spectral matrix) of include/psdcascade.h.  One runtime over the channel count: a pair object is
-// m = 2 on cross_kernel with the rows xx, yy, re, im; a matrix object runs csm_kernel<N, M> with m * m rows (csm_fft.h).  Below,
-// "pair" stands for either unit.
+// cross_runtime.cpp -- the cross-spectral cascades behind psdc_cross_* / psdc_csd_* (pairs), psdc_csm_* (groups of m = 2 ... 4
+// channels with their full spectral matrix) and psdc_zoom_* (channels mixed down from a carrier) of include/psdcascade.h.  One
+// runtime over the channel count: a pair object is m = 2 on cross_kernel with the rows xx, yy, re, im; a matrix object runs
+// csm_kernel<N, M> with m * m rows (csm_fft.h); a zoom object's unit is one real channel whose m = 2 streams are the I and Q the
+// mixer (zoom_mix_kernel, in place of the input copy) makes of it, on zoom_kernel with the rows upper, lower.  Below, "pair"
+// stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -15,6 +17,7 @@
 // count (more only when a round's job tables overflow a launch).  Read-outs drain: rounds until no stage has work.
 // There is no CPU compute path.
 #include "csm.h"
+#include "zoom.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -57,8 +60,9 @@ struct XObj {
     uint32_t n = 0, n_pairs = 0;
     uint32_t m = 2;      // channels of a pair / group
     bool matrix = false; // psdc_csm: csm_kernel and its row layout
+    bool zoom = false;   // psdc_zoom: the streams are I and Q of one mixed channel, zoom_kernel and its two rows
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return matrix ? m * m : 4; }
+    uint32_t rows() const { return zoom ? 2 : matrix ? m * m : 4; }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -93,6 +97,9 @@ struct XObj {
     psdc_loss loss{};
     uint8_t *d_frames = nullptr;
     psdrt::HeaderGather hdr;
+    // zoom: a channel's carrier (2^-64 turn a sample, start phase) and the device buffer host samples land in before the mixer
+    std::vector<uint64_t> ftw, phase0;
+    float *d_land = nullptr;
     int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
     std::string err;
 };
@@ -101,6 +108,7 @@ struct XObj {
 
 struct psdc_cross : XObj {};
 struct psdc_csm : XObj {};
+struct psdc_zoom : XObj {};
 
 namespace {
 
@@ -226,7 +234,9 @@ CrossJob pair_job(const CsmJob &j)
 int run_round(XObj *h, bool *did)
 {
     const Geometry &g = h->geo;
-    const int spt = h->matrix ? csm_segments_per_tile((int)h->n, (int)h->m) : cross_segments_per_tile((int)h->n);
+    const int spt = h->matrix ? csm_segments_per_tile((int)h->n, (int)h->m)
+                    : h->zoom ? zoom_segments_per_tile((int)h->n)
+                              : cross_segments_per_tile((int)h->n);
     const int nch = (int)h->m;
     std::vector<PlannedCross> cross;
     std::vector<DecJob> decs;
@@ -367,7 +377,8 @@ int run_round(XObj *h, bool *did)
         } else {
             CrossBatch *cb = new CrossBatch();
             fill(cb, pair_job);
-            e = launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
+            e = h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                        : launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
             delete cb;
         }
         XCHK(h, e);
@@ -497,7 +508,8 @@ std::string csm_size_text(uint32_t n, uint32_t m)
            " is not supported: n must be a power of two in [64, 2048], or 4096 with m = 2 or 3";
 }
 
-const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, bool matrix)
+const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, bool matrix,
+                       bool zoom)
 {
     if (!matrix && (n < 64 || n > 4096 || (n & (n - 1)) != 0))
         return "n must be a power of two in [64, 4096]";
@@ -508,23 +520,24 @@ const char *check_args(uint32_t n, const float *win, float power, float nenbw, s
     if (!(power > 0.0f) || !(nenbw > 0.0f))
         return "window power and nenbw must be > 0";
     if (n_pairs < 1 || n_pairs > X_MAX_PAIRS)
-        return matrix ? "n_groups must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
+        return matrix ? "n_groups must be in [1, 65536]" : zoom ? "n_channels must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
     return nullptr;
 }
 
 void destroy_impl(XObj *h);
 
-// T = psdc_cross (m = 2, cross_kernel) or psdc_csm (2 <= m <= 4, csm_kernel)
+// T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel) or psdc_zoom (m = 2: I and Q, zoom_kernel)
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
 {
     constexpr bool matrix = std::is_same<T, psdc_csm>::value;
+    constexpr bool zoom = std::is_same<T, psdc_zoom>::value;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
         return nullptr;
     }
-    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix)) {
+    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
         return nullptr;
     }
@@ -552,6 +565,14 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         h->tag = "psdc_csm";
         h->unit = "group";
         h->units = "n_groups";
+    }
+    if (zoom) {
+        h->zoom = true;
+        h->tag = "psdc_zoom";
+        h->unit = "channel";
+        h->units = "n_channels";
+        h->ftw.assign(n_pairs, 0);
+        h->phase0.assign(n_pairs, 0);
     }
     h->n_pairs = n_pairs;
     h->device = device;
@@ -583,7 +604,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
               hipMemcpy(h->d_win, win, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_tw, tw.data(), sizeof(cf) * n, hipMemcpyHostToDevice) == hipSuccess;
     for (int i = 0; ok && i < 2; ++i)
-        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * m * STAGING) == hipSuccess &&
+        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * (zoom ? 1 : m) * STAGING) == hipSuccess &&
              hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": device allocation failed");
@@ -803,6 +824,8 @@ void destroy_impl(XObj *h)
     }
     if (h->d_frames)
         (void)hipFree(h->d_frames);
+    if (h->d_land)
+        (void)hipFree(h->d_land);
     h->hdr.release();
     if (h->d_win)
         (void)hipFree(h->d_win);
@@ -851,6 +874,8 @@ int reset_impl(XObj *h, const char *who)
     h->ev_pending[0] = h->ev_pending[1] = false;
     h->launches = h->pairs_in = 0;
     h->loss = psdc_loss{};
+    std::fill(h->ftw.begin(), h->ftw.end(), 0);
+    std::fill(h->phase0.begin(), h->phase0.end(), 0);
     h->rounds = 0;
     h->round_recorded[0] = h->round_recorded[1] = false;
     return PSDC_OK;
@@ -952,6 +977,74 @@ int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t 
     const size_t at = (size_t)(s->total - s->buf.base);
     for (uint32_t c = 0; c < h->m; ++c)
         XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, d_x[c], sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+    s->total += len;
+    h->pairs_in += len;
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
+// A zoom channel takes len real samples, from host memory (dev == false: up through the pinned staging into the landing buffer,
+// as host frames go) or from device memory.  The mixer stands where psdc_cross_process_device has its copies and under the same
+// event rules: on the copy stream, behind a buffer's growth and round R - 2, and round R waits for it.  Both sources make the
+// same launches on the same data, so the same calls give the same bits from either.
+int zoom_feed(XObj *h, uint32_t ch, const float *x, size_t len, bool dev, void *producer_event, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, ch);
+    if (rc)
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    if (!x)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if ((uintptr_t)x % sizeof(float))
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to 4 bytes");
+    X_ON_DEVICE(h);
+    if (producer_event)
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    if (!dev && !h->d_land)
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * STAGING));
+    XStage *s = nullptr;
+    h->grew = false;
+    if ((rc = stage0_room(h, ch, len, &s)))
+        return rc;
+    if (h->grew) {
+        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+    }
+    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
+    if (h->round_recorded[rslot])
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
+    const size_t piece = dev ? len : STAGING;
+    for (size_t done = 0; done < len;) {
+        const size_t cnt = std::min(piece, len - done);
+        ZoomMixJob mj{};
+        mj.x = x + done;
+        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
+            const int slot = h->stage_cur;
+            if (h->ev_pending[slot])
+                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+            memcpy(h->h_stage[slot], x + done, sizeof(float) * cnt);
+            XCHK(h, hipMemcpyAsync(h->d_land, h->h_stage[slot], sizeof(float) * cnt, hipMemcpyHostToDevice, h->copy_stream));
+            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
+            h->ev_pending[slot] = true;
+            h->stage_cur ^= 1;
+            mj.x = h->d_land;
+        }
+        const size_t at = (size_t)(s->total + done - s->buf.base);
+        mj.dst_i = s->buf.p[0][s->buf.cur] + at;
+        mj.dst_q = s->buf.p[1][s->buf.cur] + at;
+        mj.len = cnt;
+        mj.j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
+        mj.ftw = h->ftw[ch];
+        mj.phase0 = h->phase0[ch];
+        XCHK(h, launch_zoom_mix(mj, h->copy_stream));
+        ++h->launches;
+        done += cnt;
+    }
     XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
     XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
     s->total += len;
@@ -1395,5 +1488,101 @@ int psdc_csm_stats_read(psdc_csm *h, uint64_t *launches, uint64_t *sample_times_
 }
 
 const char *psdc_csm_last_error(const psdc_csm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- zoom: one real channel a unit, mixed to I and Q in front of stage 0; zoom_kernel, rows upper, lower ----
+
+psdc_zoom *psdc_zoom_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                   int device)
+{
+    return create_impl<psdc_zoom>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zoom_create_window");
+}
+
+psdc_zoom *psdc_zoom_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_zoom>(n, window_kind, 2, n_channels, device, "psdc_zoom_create");
+}
+
+void psdc_zoom_destroy(psdc_zoom *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_zoom_reset(psdc_zoom *h) { return reset_impl(h, "psdc_zoom_reset"); }
+int psdc_zoom_set_detrend(psdc_zoom *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zoom_set_detrend"); }
+int psdc_zoom_set_avg(psdc_zoom *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zoom_set_avg"); }
+
+int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    X_HANDLE(h, "psdc_zoom_set_carrier");
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    const auto &st = h->pairs[channel];
+    if (!st.empty() && st[0].total)
+        return xfail(h, PSDC_ERR_ARG, "psdc_zoom_set_carrier: channel " + std::to_string(channel) + " has taken " +
+                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
+    h->ftw[channel] = ftw;
+    h->phase0[channel] = phase0;
+    return PSDC_OK;
+}
+
+int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len)
+{
+    return zoom_feed(h, channel, x, len, false, nullptr, "psdc_zoom_process");
+}
+
+int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    return zoom_feed(h, channel, d_x, len, true, producer_event, "psdc_zoom_process_device");
+}
+
+int psdc_zoom_sync(psdc_zoom *h) { return sync_impl(h, "psdc_zoom_sync"); }
+int psdc_zoom_num_stages(psdc_zoom *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_zoom_num_stages"); }
+
+int psdc_zoom_stage_spectra(psdc_zoom *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, channel, stage, stat, upper || lower ? &acc : nullptr, "psdc_zoom_stage_spectra");
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    for (size_t k = 0; k < b; ++k) {
+        if (upper)
+            upper[k] = (float)acc[k];
+        if (lower)
+            lower[k] = (float)acc[b + k];
+    }
+    return PSDC_OK;
+}
+
+int psdc_zoom_psd(psdc_zoom *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                  float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    X_HANDLE(h, "psdc_zoom_psd");
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, channel, &in)))
+        return rc;
+    float *outs[2] = {upper, lower};
+    rc = stitch_rows_impl("psdc_zoom_psd", h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(),
+                          in.pend.data(), in.rows.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks,
+                          breaks_cap, n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    return PSDC_OK;
+}
+
+int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_zoom_stats_read");
+}
+
+const char *psdc_zoom_last_error(const psdc_zoom *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

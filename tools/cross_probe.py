@@ -208,6 +208,50 @@ def matrix_legs(pkg, torch, seconds, reps, only_a):
     return legs
 
 
+def zoom_legs(pkg, torch, seconds, reps, call):
+    """One device-resident f32 stream.  A: CsdCascadeBank(n, 1) fed the pre-mixed (I, Q) streams (the same transforms and
+    decimations, four rows and a separation).  B: ZoomCascadeBank(n, 1) fed x (two rows, plus the mixer).  A / B / A in turn."""
+    x = torch.randn(call, device="cuda")
+    ph = 2 * np.pi * 0.2 * torch.arange(call, device="cuda", dtype=torch.float64)
+    xi = (x * torch.cos(ph).float()).contiguous()
+    xq = (-x * torch.sin(ph).float()).contiguous()
+    del ph
+    torch.cuda.synchronize()
+    legs = []
+    for n in (512, 1024, 4096):
+        pa = pkg.CsdCascadeBank(n, 1)
+        zb = pkg.ZoomCascadeBank(n, 1)
+        zb.set_carrier(0, f0=0.2)
+
+        def a_step():
+            pa.process_device(0, xi.data_ptr(), xq.data_ptr(), call)
+            return call
+
+        def b_step():
+            zb.process_device(0, x.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+        zb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = zb.stats_read()["launches"] / 8
+        zb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        legs.append({"n": n, "call": call, "a_pair_fed_iq_gs_s": [round(v, 3) for v in a1], "b_zoom_gs_s": [round(v, 3) for v in b],
+                     "a_again_gs_s": [round(v, 3) for v in a2], "ratio_b_over_a": [round(r, 3) for r in ratios],
+                     "ratio_min": round(min(ratios), 3), "aa_spread_max": round(spread, 4),
+                     "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": zb.num_stages(0)})
+        pa.close()
+        zb.close()
+    return legs
+
+
 def matrix_frames_legs(pkg, torch, seconds, reps):
     call = 1 << 22
     batches = 128
@@ -250,9 +294,18 @@ def main():
     ap.add_argument("--matrix", action="store_true", help="one m = 4 group against the six pairs it replaces")
     ap.add_argument("--only-a", action="store_true", help="with --matrix: leg A (six pairs) alone")
     ap.add_argument("--reps", type=int, default=5, help="with --matrix: turns of A, B, A")
+    ap.add_argument("--zoom", action="store_true", help="ZoomCascadeBank fed x against CsdCascadeBank fed the pre-mixed (I, Q)")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.zoom:
+        line = json.dumps({"metric": "zoom_gsamples_s", "unit": "1e9 samples a second of one real stream",
+                           "legs": zoom_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)})
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.matrix:
         if a.frames:
             out = {"metric": "csm_frames_gsampletimes_s", "legs": matrix_frames_legs(pkg, torch, a.seconds, a.reps)}

@@ -6,7 +6,10 @@ as `SourceOpts` (file-backed subset, src/source.rs:16-48) and `AcqOpts` (src/bin
 usage: tools/psd_cli.py (--file FRAMES [--frame-size N] | --raw RAW) [AcqOpts ...] [--max-bytes B] [--csv DIR]
 Prints one line per trace: name, stages, averages of the top stage, bins, integrated RMS; --csv writes DIR/<trace>.csv (the plot points).
 --pair X:Y (repeatable; trace labels or indices, frames only) also feeds the frames to a CsdCascadeBank(512, ...) and prints, per
-pair, its bins and median coherence; with --csv it writes DIR/<x>__<y>.csv (f, |H1|, arg H1, coherence; H1 = Sxy / Sxx)."""
+pair, its bins and median coherence; with --csv it writes DIR/<x>__<y>.csv (f, |H1|, arg H1, coherence; H1 = Sxy / Sxx).
+--zoom F0[:TRACE] (repeatable; F0 in cycles per sample, TRACE a label or index, default the first trace) also feeds that trace to a
+ZoomCascade(512) around the carrier F0 and prints, or with --csv writes to DIR/zoom_<trace>_<F0>.csv, the lines offset,upper,lower
+(the offset from the carrier in units of fs; upper / lower the density at F0 + offset / F0 - offset)."""
 import argparse
 import os
 import sys
@@ -36,6 +39,7 @@ def main(argv=None):
     ap.add_argument("--max-bytes", type=int, default=None, help="stop after this many input bytes (needed with --repeat)")
     ap.add_argument("--csv", default=None, help="directory for the plot points of every trace")
     ap.add_argument("--pair", action="append", default=[], help="X:Y -- cross spectrum of traces X and Y (repeatable)")
+    ap.add_argument("--zoom", action="append", default=[], help="F0[:TRACE] -- two-sided spectrum around the carrier F0 (repeatable)")
     a = ap.parse_args(argv)
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
@@ -80,6 +84,8 @@ def main(argv=None):
                 f.writelines(f"{x:.9g},{y:.9g}\n" for x, y in xy)
     if a.pair:
         cross_pairs(pkg, source, a, merge)
+    if a.zoom:
+        zoom_traces(pkg, source, a, merge, names)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
@@ -125,6 +131,63 @@ def cross_pairs(pkg, source, a, merge):
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(f"{fr:.9g},{abs(h):.9g},{np.angle(h):.9g},{c:.9g}\n" for fr, h, c in zip(freqs, h1, coh))
     cross.close()
+
+
+def zoom_traces(pkg, source, a, merge, names):
+    """--zoom: the source once more through Source's host traces (raw files and frame files alike), the named trace of every read
+    into one zoom cascade per carrier"""
+    want = []
+    for z in a.zoom:
+        f0, _, tr = z.partition(":")
+        idx = 0 if tr == "" else int(tr) if tr.isdigit() else (names.index(tr) if tr in names else -1)
+        if not 0 <= idx < len(names):
+            raise SystemExit(f"--zoom: unknown trace {tr!r}")
+        want.append((float(f0), idx))
+    bank = pkg.ZoomCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _) in enumerate(want)]
+    src = source.Source(source.SourceOpts(file=a.file, frame_size=a.frame_size, repeat=a.repeat, raw=a.raw), pkg)
+    total, held, pend = 0, 0, [[] for _ in want]
+
+    def flush():
+        for i, chunks in enumerate(pend):
+            if chunks:
+                bank.process(i, np.concatenate(chunks))
+                chunks.clear()
+
+    while a.max_bytes is None or total < a.max_bytes:
+        try:
+            traces = src.get()  # [(label, samples)] of one frame, or one chunk of a raw file
+        except EOFError:
+            break
+        if src.eof:
+            break
+        for i, (_, idx) in enumerate(want):
+            pend[i].append(traces[idx][1])
+        total += a.frame_size if a.file else traces[0][1].nbytes
+        held += traces[0][1].size
+        if held >= 1 << 20:
+            flush()
+            held = 0
+    flush()
+    src.close()
+    for i, (_, idx) in enumerate(want):
+        label = f"zoom {names[idx]} @ {used[i]:.12g}"
+        if bank.num_stages(i) == 0:
+            print(f"{label}: no samples")
+            continue
+        up, lo, breaks = bank.psd(i, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        print(f"{label}: stages {bank.num_stages(i)} bins {up.size} breaks {len(breaks)}")
+        lines = [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"zoom_{names[idx]}_{used[i]:.9g}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+    bank.close()
 
 
 if __name__ == "__main__":
