@@ -700,6 +700,43 @@ int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t
 int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len);
 /* the same from device memory (any 4-byte aligned address and any length); producer_event: hipEvent_t or NULL */
 int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+/* Stream frames into zoom channels (mirrors psdc_csd_process_frames).  The three frames calls of a psdc_zoom object carry the
+ * prefix psdc_zoomcascade_, after ZoomCascade, the object's name in the mirrors, as a psdc_cross object's carry psdc_csd_
+ * after CsdCascade: the psdc_zoom_ set is the sample-fed object's and stays as it was.  The map has n_channels entries; channel c takes trace
+ * channel_traces[c] of every frame, in Payload::traces order (see "stream frames into a cross object").  PSDC_TRACE_NONE: the
+ * channel is not fed by this call and its stream index does not move.  A trace may feed any number of channels (a carrier
+ * and its harmonics on one input).  The map belongs to the call and is not stored.
+ * Map errors: PSDC_ERR_ARG without ingesting anything for a NULL map, a trace index >= 4 or a map that feeds no channel.  A
+ * run whose format carries fewer traces than the map names is PSDC_ERR_ARG at the run's first frame: the frames before it
+ * are ingested and *n_ok counts them.
+ * Frames: headers, runs of one format, de::Error codes, *n_ok, header-only frames (Loss only) and Loss are those of
+ * psdc_csd_process_frames, from the same scanner.  A call is cut into pieces of whole frames of at most 2^22 samples a trace,
+ * in runs of one format, as the pair object's is; each piece is ONE decode-and-mix launch per 16 fed channels
+ * (zoom_frames_kernel: a cell is read and converted once, mixed in registers with every channel's carrier that takes it and
+ * stored to the channel's I and Q streams; the f32 trace never exists in memory) and then one round.  The launch stands
+ * where the mixer of psdc_zoom_process_device stands: on the side stream, behind a grown buffer and round R - 2, in front of
+ * round R.  Host frames go up through the pinned staging into a 16 MB device landing buffer (a zoom object's staging slots
+ * are 16 MB, half the pair object's: made by the first host-frames call), one decode-and-mix launch a slot.
+ * Carrier rule: unchanged -- psdc_zoom_set_carrier is PSDC_ERR_ARG once the channel has taken a sample, by either route.
+ * samples_in of psdc_zoom_stats_read counts the samples accepted over all fed channels.  A reset zeroes Loss.
+ * Invariants:
+ *  (a) a call that is one piece gives the same bits as psdc_zoom_process fed Payload::traces of the same frames in one call
+ *      (the decode is bit-identical to Payload::traces, a sample's phase comes from its 64-bit stream index, and the round
+ *      is the same);
+ *  (b) the same frames in host and in device memory give the same bits (the cut depends on the headers alone);
+ *  (c) sample and frame calls may be mixed on one channel: the stream index, and so the phase, continues across them;
+ *  (d) a steady-state call of one piece that feeds up to 16 channels is 1 + 3 kernel launches on the side and compute
+ *      streams (decode-and-mix; segments, decimators, fold + tails), for host frames that fit one staging slot.  The device
+ *      call's header gather on its own stream is one more launch and psdc_zoom_stats_read counts it, as the pair object's
+ *      statistics do: such a device call reads 5. */
+int psdc_zoomcascade_process_frames(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size,
+                             size_t n_frames, size_t *n_ok);
+/* the same for frames in device memory (mirrors psdc_csd_process_frames_device): the side-stream header gather, the host
+ * wait for that launch alone, producer_event, the keep-unchanged rule and "any base address" are that call's */
+int psdc_zoomcascade_process_frames_device(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *d_frames,
+                                    size_t frame_size, size_t n_frames, size_t *n_ok, void *producer_event);
+/* the Loss counters of the frames the object ingested (mirrors psdc_csd_loss_read); reset != 0 zeroes them after reading */
+int psdc_zoomcascade_loss_read(psdc_zoom *h, psdc_loss *out, int reset);
 int psdc_zoom_sync(psdc_zoom *h);
 int psdc_zoom_num_stages(psdc_zoom *h, uint32_t channel);
 /* raw accumulators of one stage: upper, lower n/2 + 1 floats each; any may be NULL */

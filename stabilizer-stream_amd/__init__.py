@@ -356,6 +356,9 @@ def lib():
     f("psdc_zoom_set_carrier", i32, [H, u32, u64, u64])
     f("psdc_zoom_process", i32, [H, u32, fp, sz])
     f("psdc_zoom_process_device", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
+    f("psdc_zoomcascade_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_zoomcascade_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_zoomcascade_loss_read", i32, [H, C.POINTER(_CLoss), i32])
     f("psdc_zoom_sync", i32, [H])
     f("psdc_zoom_num_stages", i32, [H, u32])
     f("psdc_zoom_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp])
@@ -391,6 +394,7 @@ EXPORTS = [
     "psdc_zoom_create", "psdc_zoom_create_window", "psdc_zoom_destroy", "psdc_zoom_reset", "psdc_zoom_set_detrend",
     "psdc_zoom_set_avg", "psdc_zoom_set_carrier", "psdc_zoom_process", "psdc_zoom_process_device", "psdc_zoom_sync",
     "psdc_zoom_num_stages", "psdc_zoom_stage_spectra", "psdc_zoom_psd", "psdc_zoom_stats_read", "psdc_zoom_last_error",
+    "psdc_zoomcascade_process_frames", "psdc_zoomcascade_process_frames_device", "psdc_zoomcascade_loss_read",
 ]
 
 
@@ -1096,7 +1100,28 @@ def two_sided(upper, lower, breaks):
 
 def _raise_zoom(code, h=None):
     msg = lib().psdc_zoom_last_error(h)
-    raise PsdError(code, msg.decode() if msg else "")
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
+
+
+def channel_map(traces, n_channels):
+    """The map psdc_zoomcascade_process_frames[_device] take, from `traces`: entry c is the trace channel c takes -- an index or a TRACE_NAMES label (trace_index, as
+    pair_map resolves its pairs) -- or None (channel c not fed); channels past the end of the list are not fed.  A map that
+    feeds no channel, an index outside 0 ... 3 and an unknown label are ERR_ARG here, before the library sees the call."""
+    traces = list(traces)
+    if len(traces) > n_channels:
+        raise PsdError(ERR_ARG, f"{len(traces)} traces for a bank of {n_channels}")
+    m = np.full(n_channels, TRACE_NONE, np.uint32)
+    for c, t in enumerate(traces):
+        if t is None:
+            continue
+        i = trace_index(t)
+        if not 0 <= i < 4:
+            raise PsdError(ERR_ARG, f"channel {c} names trace {i} (frames carry at most 4)")
+        m[c] = i
+    if not np.any(m != TRACE_NONE):
+        raise PsdError(ERR_ARG, "the map feeds no channel")
+    return m
 
 
 class ZoomCascadeBank:
@@ -1168,6 +1193,35 @@ class ZoomCascadeBank:
         self._ck(self._L.psdc_zoom_process_device(self._h, channel, C.c_void_p(ptr), length,
                                                   C.c_void_p(after) if after else None))
 
+    def process_frames(self, data, frame_size, traces):
+        """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the channels: traces[c] is the
+        trace channel c takes of every frame (an index or a TRACE_NAMES label), None leaves it unfed; a trace may feed several
+        channels.  The frames are decoded and mixed on the device in one kernel.  Returns the number of frames ingested; a bad
+        frame raises FrameError after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = channel_map(traces, self.n_channels)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_zoomcascade_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
+                                              frame_size, buf.size // frame_size, C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, traces, after=None):
+        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
+        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
+        m = channel_map(traces, self.n_channels)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_zoomcascade_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
+                                                     frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(self._L.psdc_zoomcascade_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
     def sync(self):
         self._ck(self._L.psdc_zoom_sync(self._h))
 
@@ -1228,6 +1282,16 @@ class ZoomCascade:
 
     def process_device(self, ptr, length, after=None):
         self._b.process_device(0, ptr, length, after)
+
+    def process_frames(self, data, frame_size, trace):
+        """trace: the trace of the frames the stream is (ZoomCascadeBank.process_frames)"""
+        return self._b.process_frames(data, frame_size, [trace])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, trace, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [trace], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
 
     def psd(self, opts=MergeOpts()):
         return self._b.psd(0, opts)

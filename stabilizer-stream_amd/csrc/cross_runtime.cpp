@@ -35,7 +35,6 @@ namespace {
 constexpr uint32_t X_MAX_STAGES = 16;
 constexpr uint32_t X_MAX_PAIRS = 65536;
 constexpr size_t STAGING = (size_t)1 << 22; // host-fed samples a channel per pinned staging slot
-constexpr size_t FRAMES_CHUNK = 2 * STAGING * sizeof(float); // host-memory frame bytes a pinned staging slot takes at once
 constexpr size_t PIECE_SAMPLES = (size_t)1 << 22;            // a frames call is cut into pieces of <= this many samples a trace
 
 thread_local std::string x_last_error;
@@ -63,6 +62,10 @@ struct XObj {
     bool zoom = false;   // psdc_zoom: the streams are I and Q of one mixed channel, zoom_kernel and its two rows
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
     uint32_t rows() const { return zoom ? 2 : matrix ? m * m : 4; }
+    uint32_t map_w() const { return zoom ? 1 : m; } // entries a unit has in a frames call's map: a zoom channel takes one trace
+    // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
+    // channel's STAGING floats, the others' at least two
+    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? 1 : 2); }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -91,9 +94,9 @@ struct XObj {
     std::vector<void *> retired; // replaced device buffers, freed at the next sync point
     bool idle = true;            // every stage drained
     uint64_t launches = 0, pairs_in = 0;
-    // frames (psdc_csd_process_frames[_device]): Loss over every frame either call ingested; host-memory frames go up through
-    // h_stage into d_frames (FRAMES_CHUNK bytes, made by the first host-frames call); device frames' headers come to the host
-    // through `hdr`
+    // frames (psdc_csd_ / psdc_csm_ / psdc_zoomcascade_process_frames[_device]): Loss over every frame either call ingested; host-memory
+    // frames go up through h_stage into d_frames (frames_chunk() bytes, made by the first host-frames call); device frames' headers
+    // come to the host through `hdr`
     psdc_loss loss{};
     uint8_t *d_frames = nullptr;
     psdrt::HeaderGather hdr;
@@ -623,8 +626,8 @@ struct FedPair {
     uint32_t tr[CSM_MAX_M]; // the trace of each channel
 };
 
-// the pairs a call feeds, from its map; PSDC_ERR_ARG for a NULL map, an entry with exactly one PSDC_TRACE_NONE or a trace no
-// format carries
+// the pairs a call feeds, from its map (map_w() entries a unit); PSDC_ERR_ARG for a NULL map, an entry with exactly one
+// PSDC_TRACE_NONE or a trace no format carries
 int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair> *fed)
 {
     if (!map)
@@ -634,14 +637,15 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
         FedPair fp{};
         fp.pair = p;
         uint32_t none = 0, top = 0;
-        for (uint32_t c = 0; c < h->m; ++c) {
-            fp.tr[c] = map[h->m * p + c];
+        const uint32_t w = h->map_w();
+        for (uint32_t c = 0; c < w; ++c) {
+            fp.tr[c] = map[w * p + c];
             if (fp.tr[c] == PSDC_TRACE_NONE)
                 ++none;
             else
                 top = std::max(top, fp.tr[c]);
         }
-        if (none == h->m)
+        if (none == w)
             continue;
         if (none)
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) +
@@ -652,6 +656,8 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
                                               std::to_string(top) + " (frames carry at most 4)");
         fed->push_back(fp);
     }
+    if (h->zoom && fed->empty()) // (a pair object takes such a call for its Loss)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the map feeds no channel");
     return PSDC_OK;
 }
 
@@ -663,7 +669,8 @@ struct FrameSrc {
 };
 
 // decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[m i + c] (pair fed[i], channel
-// c), one launch per 32 / m pairs, on the copy stream
+// c), one launch per 32 / m pairs, on the copy stream.  A zoom channel's two buffers are its I and Q streams: zoom_frames_kernel
+// decodes the channel's trace and mixes it with the channel's carrier, the first sample at stream index total + dst_off.
 int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
@@ -671,7 +678,7 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
     if (!src.dev) { // host memory: up through a pinned staging slot into d_frames (the decode of the chunk before has read it:
                     // both are on the copy stream)
         if (!h->d_frames)
-            XCHK(h, hipMalloc(&h->d_frames, FRAMES_CHUNK));
+            XCHK(h, hipMalloc(&h->d_frames, h->frames_chunk()));
         const int slot = h->stage_cur;
         if (h->ev_pending[slot])
             XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
@@ -683,22 +690,44 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
         h->stage_cur ^= 1;
         frames = h->d_frames;
     }
-    const size_t per_launch = CROSS_FRAMES_MAX_DST / h->m;
-    for (size_t i0 = 0; i0 < fed.size(); i0 += per_launch) {
-        CrossFramesBatch b{};
-        b.frames = frames;
-        b.frame_size = frame_size;
-        b.n_frames = (unsigned)cnt;
-        b.batches = batches;
-        b.fmt = wf->id;
-        for (size_t i = i0; i < std::min(fed.size(), i0 + per_launch); ++i)
-            for (uint32_t c = 0; c < h->m; ++c) {
-                b.trace[b.ndst] = (int)fed[i].tr[c];
-                b.dst[b.ndst] = dst[h->m * i + c] + dst_off;
-                ++b.ndst;
+    // what both kinds of launch say about the frames
+    auto describe = [&](auto *b) {
+        b->frames = frames;
+        b->frame_size = frame_size;
+        b->n_frames = (unsigned)cnt;
+        b->batches = batches;
+        b->fmt = wf->id;
+    };
+    if (h->zoom) {
+        for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_FRAMES_MAX_CH) {
+            ZoomFramesBatch b{};
+            describe(&b);
+            for (size_t i = i0; i < std::min<size_t>(fed.size(), i0 + ZOOM_FRAMES_MAX_CH); ++i, ++b.nch) {
+                const uint32_t ch = fed[i].pair;
+                b.trace[b.nch] = (int)fed[i].tr[0];
+                b.dst_i[b.nch] = dst[2 * i] + dst_off;
+                b.dst_q[b.nch] = dst[2 * i + 1] + dst_off;
+                b.ftw[b.nch] = h->ftw[ch];
+                b.phase0[b.nch] = h->phase0[ch];
+                b.j0[b.nch] = h->pairs[ch][0].total + dst_off; // the stream index, as zoom_feed counts it
             }
-        XCHK(h, launch_cross_frames(b, h->copy_stream));
-        ++h->launches;
+            XCHK(h, launch_zoom_frames(b, h->copy_stream));
+            ++h->launches;
+        }
+    } else {
+        const size_t per_launch = CROSS_FRAMES_MAX_DST / h->m;
+        for (size_t i0 = 0; i0 < fed.size(); i0 += per_launch) {
+            CrossFramesBatch b{};
+            describe(&b);
+            for (size_t i = i0; i < std::min(fed.size(), i0 + per_launch); ++i)
+                for (uint32_t c = 0; c < h->m; ++c) {
+                    b.trace[b.ndst] = (int)fed[i].tr[c];
+                    b.dst[b.ndst] = dst[h->m * i + c] + dst_off;
+                    ++b.ndst;
+                }
+            XCHK(h, launch_cross_frames(b, h->copy_stream));
+            ++h->launches;
+        }
     }
     return PSDC_OK;
 }
@@ -720,7 +749,7 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
         if (bad != PSDC_OK)
             break;
         for (const FedPair &fp : fed) {
-            const uint32_t top = *std::max_element(fp.tr, fp.tr + h->m);
+            const uint32_t top = *std::max_element(fp.tr, fp.tr + h->map_w());
             if ((int)top >= wf->ntraces)
                 return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(fp.pair) + " names trace " +
                                                   std::to_string(top) + " but " + wf->name + " frames carry " +
@@ -756,7 +785,7 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
                 const int slot = (int)(h->rounds & 1);
                 if (h->round_recorded[slot])
                     XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
-                const size_t chunk = src.dev ? cnt : std::max<size_t>(1, FRAMES_CHUNK / frame_size);
+                const size_t chunk = src.dev ? cnt : std::max<size_t>(1, h->frames_chunk() / frame_size);
                 for (size_t c0 = 0; c0 < cnt; c0 += chunk) {
                     int rc = decode_frames(h, src, frame_size, wf, batches, f0 + c0, std::min(chunk, cnt - c0), fed, dst,
                                            c0 * per_frame);
@@ -1539,6 +1568,20 @@ int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, s
     return zoom_feed(h, channel, d_x, len, true, producer_event, "psdc_zoom_process_device");
 }
 
+int psdc_zoomcascade_process_frames(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                             size_t *n_ok)
+{
+    return frames_host_impl(h, channel_traces, frames, frame_size, n_frames, n_ok, "psdc_zoomcascade_process_frames");
+}
+
+int psdc_zoomcascade_process_frames_device(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *d_frames, size_t frame_size,
+                                    size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, channel_traces, d_frames, frame_size, n_frames, n_ok, producer_event,
+                              "psdc_zoomcascade_process_frames_device");
+}
+
+int psdc_zoomcascade_loss_read(psdc_zoom *h, psdc_loss *out, int reset) { return loss_impl(h, out, reset, "psdc_zoomcascade_loss_read"); }
 int psdc_zoom_sync(psdc_zoom *h) { return sync_impl(h, "psdc_zoom_sync"); }
 int psdc_zoom_num_stages(psdc_zoom *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_zoom_num_stages"); }
 

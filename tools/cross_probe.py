@@ -15,6 +15,13 @@ CsmCascadeBank(n, 4) (one call a step); unit: sample times a second (one sample 
 are timed in turn --reps times in one session: the ratio B / A per turn, and |A' - A| / A as the session's spread.  Also one
 m = 2 group against one pair.  --matrix --only-a times leg A alone (for a run on another build of the library through PSDC_LIB).
 --matrix --frames: the four traces of device-resident AdcDac frames as one m = 4 group against the two-pair frames leg above.
+--zoom --frames: stream frames into a zoom object.  AdcDac (128 batches a frame) and Mpll (255 batches) frames of 2^22 samples a
+trace a call at N = 512, 1024, 4096.  Leg A is the route tools/psd_cli.py --zoom takes: every frame decoded on the host
+(source.decode_frame), the trace through psdc_zoom_process from host memory.  Leg B is psdc_zoomcascade_process_frames_device on the same
+frames resident in device memory.  Leg C (a ceiling, not a gate) is psdc_zoom_process_device on the pre-decoded f32 trace resident
+in device memory.  A, B, A, C in turn --reps times in one session; B beats A when every B / A exceeds 1 + the largest |A' - A| / A.
+Also four carriers on trace 0: one B call feeding four channels against four C calls.  Clocks and power from rocm-smi (read only)
+before and after.  Writes profiles/zoom_frames_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -252,6 +259,111 @@ def zoom_legs(pkg, torch, seconds, reps, call):
     return legs
 
 
+def gpu_state():
+    """sclk / mclk / power as rocm-smi prints them (read only); None where the tool is missing"""
+    import subprocess
+    try:
+        out = subprocess.run(["rocm-smi", "-d", "0", "--showclocks", "--showpower", "--json"], capture_output=True, text=True, timeout=30)
+        card = next(iter(json.loads(out.stdout).values()))
+        return {k: v for k, v in card.items() if any(w in k.lower() for w in ("sclk", "mclk", "power"))}
+    except Exception:  # noqa: BLE001
+        return None
+
+
+def timed_calls(step, sync, calls):
+    """samples a second of `calls` back-to-back step() calls behind one warm-up call (the host-bound leg: a call takes 0.1 ... 1 s)"""
+    step()
+    sync()
+    t0 = time.perf_counter()
+    fed = sum(step() for _ in range(calls))
+    sync()
+    return fed / (time.perf_counter() - t0)
+
+
+def zoom_frames_legs(pkg, torch, seconds, reps):
+    from test_gpu_payload_formats import make_frames, random_payloads  # the frame builders of the test suite
+    from stabilizer_stream_amd import source as src  # decode_frame: the host decode of Source (load_package has registered the package)
+    call = 1 << 22
+    rng = np.random.default_rng(7)
+    inputs = []
+    w = rng.integers(-20000, 20000, size=(4, call), dtype=np.int64).astype(np.int16)
+    data, fs = pkg.make_adcdac_frames(w, 128)
+    inputs.append(("AdcDac", data, fs, 0))
+    nf = call // 255  # whole frames of at most 2^22 samples: a call is one piece
+    data, fs = make_frames(4, 255, random_payloads(rng, 4, 255, nf, wild=False))
+    inputs.append(("Mpll", data, fs, 0))
+    legs = []
+    for name, data, fs, trace in inputs:
+        nf = len(data) // fs
+        frames = [data[k * fs:(k + 1) * fs] for k in range(nf)]
+        x = np.concatenate([src.decode_frame(f)[3][trace][1] for f in frames]).astype(np.float32)
+        per_call = x.size
+        d = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
+        dx = torch.from_numpy(x).cuda()
+        torch.cuda.synchronize()
+        for n in (512, 1024, 4096):
+            za, zb, zc = (pkg.ZoomCascadeBank(n, 1) for _ in range(3))
+            for z in (za, zb, zc):
+                z.set_carrier(0, f0=0.2)
+
+            def a_step():
+                za.process(0, np.concatenate([src.decode_frame(f)[3][trace][1] for f in frames]))
+                return per_call
+
+            def b_step():
+                zb.process_frames_device(d.data_ptr(), fs, nf, [trace])
+                return per_call
+
+            def c_step():
+                zc.process_device(0, dx.data_ptr(), per_call)
+                return per_call
+
+            a1, b, a2, c = [], [], [], []
+            for _ in range(reps):
+                a1.append(timed_calls(a_step, za.sync, 2) / 1e9)
+                b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+                a2.append(timed_calls(a_step, za.sync, 2) / 1e9)
+                c.append(timed(c_step, zc.sync, seconds)[0] / 1e9)
+            zb.stats_read(reset=True)
+            for _ in range(8):
+                b_step()
+            launches = zb.stats_read()["launches"] / 8
+            zb.sync()
+            # four carriers on the one trace: one fused call against four calls of the pre-decoded trace
+            z4b, z4c = pkg.ZoomCascadeBank(n, 4), pkg.ZoomCascadeBank(n, 4)
+            for ch in range(4):
+                z4b.set_carrier(ch, f0=0.05 * (ch + 1))
+                z4c.set_carrier(ch, f0=0.05 * (ch + 1))
+
+            def b4_step():
+                z4b.process_frames_device(d.data_ptr(), fs, nf, [trace] * 4)
+                return 4 * per_call
+
+            def c4_step():
+                for ch in range(4):
+                    z4c.process_device(ch, dx.data_ptr(), per_call)
+                return 4 * per_call
+
+            b4, c4 = [], []
+            for _ in range(reps):
+                b4.append(timed(b4_step, z4b.sync, seconds)[0] / 1e9)
+                c4.append(timed(c4_step, z4c.sync, seconds)[0] / 1e9)
+            ba = [y / u for u, y in zip(a1, b)]
+            bc = [y / u for u, y in zip(c, b)]
+            spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+            r3 = lambda v: [round(t, 4) for t in v]  # noqa: E731
+            legs.append({"format": name, "n": n, "call_samples": per_call, "frame_size": fs, "frames": nf,
+                         "a_host_decode_gs_s": r3(a1), "b_frames_device_gs_s": r3(b), "a_again_gs_s": r3(a2),
+                         "c_f32_device_gs_s": r3(c), "ratio_b_over_a": [round(r, 2) for r in ba], "ratio_b_over_a_min": round(min(ba), 2),
+                         "aa_spread_max": round(spread, 4), "b_beats_a": bool(min(ba) > 1 + spread),
+                         "ratio_b_over_c": [round(r, 3) for r in bc], "b_launches_per_call": launches,
+                         "four_carriers_b_gs_s": r3(b4), "four_carriers_4c_gs_s": r3(c4),
+                         "four_carriers_ratio_b_over_4c": [round(y / u, 3) for u, y in zip(c4, b4)]})
+            for o in (za, zb, zc, z4b, z4c):
+                o.close()
+    return legs
+
+
 def matrix_frames_legs(pkg, torch, seconds, reps):
     call = 1 << 22
     batches = 128
@@ -298,6 +410,19 @@ def main():
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.zoom and a.frames:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        before = gpu_state()
+        legs = zoom_frames_legs(pkg, torch, a.seconds, a.reps)
+        line = json.dumps({"metric": "zoom_frames_gsamples_s", "unit": "1e9 samples a second and channel-sample for the four-carrier legs",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "leg A's samples go up through the zoom object's 16 MB pinned staging slots (psdc_zoom_process); host FRAMES "
+                                   "(not measured here) would go up in 16 MB slots too, half the pair object's 32 MB",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "zoom_frames_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.zoom:
         line = json.dumps({"metric": "zoom_gsamples_s", "unit": "1e9 samples a second of one real stream",
                            "legs": zoom_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)})
