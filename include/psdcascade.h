@@ -750,6 +750,81 @@ int psdc_zoom_psd(psdc_zoom *h, uint32_t channel, int keep_overlap, uint32_t min
 int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in, int reset);
 const char *psdc_zoom_last_error(const psdc_zoom *h);
 
+/* ---- zoom cross cascade: two streams around a carrier ------------------------------------------------------------
+ * The cross spectrum of two receivers that watch the same carrier, at the cascade's log resolution: their own noise is
+ * uncorrelated and averages out of S_ab; what stays is the source's noise at f0 +- f.  A zoom cross object holds `n_pairs`
+ * independent pairs.  A pair is two real f32 streams a and b, always fed together with equal lengths.  Each of the two has
+ * its own carrier, a tuning word and start phase exactly as psdc_zoom_set_carrier's (2^-64 turn, the phase of sample j
+ * from its 64-bit stream index in integers, however the stream is cut into calls); both default to ftw = 0, phase0 = 0.  A
+ * carrier may be set only while the pair has taken no sample since create or reset; a reset puts both back to the default.
+ * Stages: every one of the four streams (I_a, Q_a, I_b, Q_b) the two mixers make is a Psd<N> stage in lockstep with the
+ * others, exactly as a zoom channel's two are: segmentation, Window<N>, Detrend of each separately, /8 half-band decimation
+ * of each (four decimator jobs a (pair, stage)) with the drain of 35 outputs, lazy stages, EWMA factor g, 64-bit counts.  A
+ * pair has exactly the stages, counts, pendings and Breaks of a PsdCascade (or a psdc_zoom channel) fed a.
+ * Rows: per segment Z_a and Z_b are the N-point complex transforms of the detrended, windowed I + i Q of the SAME segment of
+ * the two channels.  A stage keeps eight f64 rows of n/2 + 1 bins, k = 0 ... N/2, each accumulated as row = g row + value:
+ *     value                 row `upper`: bin k      row `lower`: bin (N - k) mod N
+ *     S_aa = |Z_a|^2             0                       1
+ *     S_bb = |Z_b|^2             2                       3
+ *     Re S_ab                    4                       5
+ *     Im S_ab                    6                       7
+ * Sign: S_ab[j] = conj(Z_a[j]) Z_b[j], that of the pair object (conj(X) Y, scipy.signal.csd): the transfer function from a to
+ * b is S_ab / S_aa, the coherence |S_ab|^2 / (S_aa S_bb).  lower[k] is the value AT bin N - k, not conjugated: the spectrum
+ * at f0 - f, as `upper` is that at f0 + f (bins 0 and N/2 appear in both).  The products are formed per bin from the two
+ * transforms' registers; nothing is separated and nothing is subtracted across bins or rows, so a single sideband leaks into
+ * its image by the transform's own rounding only (a matrix object fed the four mixed streams rebuilds these rows from sums
+ * and differences of sixteen rows f32 has already rounded).
+ * Rows 0 ... 3 are the rows of two psdc_zoom channels fed a and b with the same carriers (within the chunking bound below:
+ * the partial sums are ordered differently).  With ftw = 0 on both sides Q is 0 and S_ab upper is psdc_cross_csd's Sxy of (a, b).
+ * Recipe, AM / PM separation: feed the SAME stream to both sides with the carriers ftw and -ftw (phase0 = 0).  Then Z_b[k] =
+ * conj(Z_a[-k]) for a real input, S_bb upper is S_aa lower, and S_ab upper = conj(Z_a[k] Z_a[-k]): the term whose real part
+ * (relative to the carrier's own phase) separates amplitude from phase noise.  No helper is built on it.
+ * Read-out: PsdCascade::psd (src/psd.rs:479-543) applied to each of the eight real rows with the same bins, Breaks and
+ * 1 / (gain() decimation), as psdc_zoom_psd does for its two: the auto rows read as psdc_zoom_psd's.
+ * Sizes: n a power of two 64 ... 4096 (psdc_zcsd_supported; every size builds without scratch memory); a refused size is
+ * PSDC_ERR_ARG with a text that names n.  Windows as for pairs.  Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere.
+ * Stream ordering, the caller-keeps-memory rule, errors, the device rule, determinism and the bank rule (a pair equals a
+ * single object bit for bit when fed and read out in turn, within 2e-6 interleaved or when the stream is cut into other calls)
+ * are those of psdc_zoom_*.  The two mixers stand where the zoom object's one stands; host samples go up through the pinned
+ * staging into a 32 MB device landing buffer.  A steady-state call on one pair is 2 + 3 kernel launches whatever the depth
+ * (PSDC_ZCSD_STEADY_LAUNCHES: two mixers; segments, decimators, fold + tails), with the matrix object's table limits at
+ * m = 4.  Host and device calls of the same samples run the same launches on the same data and give the same bits.
+ * Memory: per (pair, stage) two ping-pong buffers for each of the four streams, plus 64 MB of pinned staging.
+ * Stream frames do not feed this object. */
+#define PSDC_ZCSD_STEADY_LAUNCHES 5
+typedef struct psdc_zcsd psdc_zcsd;
+/* 1 if an object of size n can be created, else 0.  Pure host code. */
+int psdc_zcsd_supported(uint32_t n);
+/* n_pairs pairs; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_zcsd *psdc_zcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device);
+/* the same with a caller-built Window<N> (src/psd.rs:12-20), as psdc_create_window */
+psdc_zcsd *psdc_zcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap,
+                                   uint32_t n_pairs, int device);
+void psdc_zcsd_destroy(psdc_zcsd *h);
+/* back to the state of a fresh object: stages, buffers, settings, carriers and statistics */
+int psdc_zcsd_reset(psdc_zcsd *h);
+int psdc_zcsd_set_detrend(psdc_zcsd *h, int detrend_kind);
+int psdc_zcsd_set_avg(psdc_zcsd *h, uint32_t limit, uint32_t count);
+/* the carrier of one side of a pair (side 0: channel a, 1: channel b); PSDC_ERR_ARG once the pair has taken a sample */
+int psdc_zcsd_set_carrier(psdc_zcsd *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0);
+/* len real samples of each channel from host memory */
+int psdc_zcsd_process(psdc_zcsd *h, uint32_t pair, const float *x, const float *y, size_t len);
+/* the same from device memory (any 4-byte aligned addresses and any length); producer_event: hipEvent_t or NULL */
+int psdc_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
+                             void *producer_event);
+int psdc_zcsd_sync(psdc_zcsd *h);
+int psdc_zcsd_num_stages(psdc_zcsd *h, uint32_t pair);
+/* raw accumulators of one stage: rows 8 (n/2 + 1) floats in the row layout above; stat and rows may be NULL */
+int psdc_zcsd_stage_spectra(psdc_zcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows);
+/* PsdCascade::psd of every row, with the arguments of psdc_zoom_psd: the auto rows `cap` floats each, sab_upper and sab_lower
+ * 2 cap floats (re, im); any may be NULL */
+int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                  float *saa_upper, float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper,
+                  float *sab_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and sample pairs accepted since creation or the last reset of the statistics */
+int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset);
+const char *psdc_zcsd_last_error(const psdc_zcsd *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

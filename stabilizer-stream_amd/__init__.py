@@ -365,6 +365,22 @@ def lib():
     f("psdc_zoom_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_zoom_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_zoom_last_error", C.c_char_p, [H])
+    f("psdc_zcsd_supported", i32, [u32])
+    f("psdc_zcsd_create", H, [u32, i32, u32, i32])
+    f("psdc_zcsd_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_zcsd_destroy", None, [H])
+    f("psdc_zcsd_reset", i32, [H])
+    f("psdc_zcsd_set_detrend", i32, [H, i32])
+    f("psdc_zcsd_set_avg", i32, [H, u32, u32])
+    f("psdc_zcsd_set_carrier", i32, [H, u32, u32, u64, u64])
+    f("psdc_zcsd_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_zcsd_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_zcsd_sync", i32, [H])
+    f("psdc_zcsd_num_stages", i32, [H, u32])
+    f("psdc_zcsd_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
+    f("psdc_zcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_zcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_zcsd_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -395,6 +411,10 @@ EXPORTS = [
     "psdc_zoom_set_avg", "psdc_zoom_set_carrier", "psdc_zoom_process", "psdc_zoom_process_device", "psdc_zoom_sync",
     "psdc_zoom_num_stages", "psdc_zoom_stage_spectra", "psdc_zoom_psd", "psdc_zoom_stats_read", "psdc_zoom_last_error",
     "psdc_zoomcascade_process_frames", "psdc_zoomcascade_process_frames_device", "psdc_zoomcascade_loss_read",
+    "psdc_zcsd_supported", "psdc_zcsd_create", "psdc_zcsd_create_window", "psdc_zcsd_destroy", "psdc_zcsd_reset",
+    "psdc_zcsd_set_detrend", "psdc_zcsd_set_avg", "psdc_zcsd_set_carrier", "psdc_zcsd_process", "psdc_zcsd_process_device",
+    "psdc_zcsd_sync", "psdc_zcsd_num_stages", "psdc_zcsd_stage_spectra", "psdc_zcsd_csd", "psdc_zcsd_stats_read",
+    "psdc_zcsd_last_error",
 ]
 
 
@@ -1305,6 +1325,187 @@ class ZoomCascade:
     def reset(self):
         self._b.reset()
         self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+ZCSD_STEADY_LAUNCHES = 5  # PSDC_ZCSD_STEADY_LAUNCHES: two mixers; segments, decimators, fold + tails
+
+
+def zcsd_supported(n):
+    """True if a ZoomCsdCascadeBank of size n can be created (psdc_zcsd_supported).  Needs no GPU."""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_zcsd_supported(n))
+
+
+def _raise_zcsd(code, h=None):
+    msg = lib().psdc_zcsd_last_error(h)
+    raise PsdError(code, msg.decode() if msg else "")
+
+
+class ZoomCsdCascadeBank:
+    """`n_pairs` independent zoom cross cascades (psdc_zcsd_*): a pair is two real streams a and b, each mixed down from a
+    carrier of its own (ZoomCascadeBank's tuning word and start phase) to I + i Q in front of the cascade.  Every stage keeps the
+    two-sided auto spectra of both and their cross spectrum S_ab = conj(Z_a) Z_b (CsdCascade's sign), each as an `upper` row
+    (f0 + f) and a `lower` row (f0 - f, the value at bin N - k, not conjugated).  Two receivers on one carrier: their own noise
+    averages out of S_ab, the source's stays.  coherence(), transfer() and two_sided() take the rows of csd() as they are.
+
+    Recipe (AM / PM separation): feed the SAME stream to both sides with the carriers ftw and -ftw, phase0 = 0.  S_bb upper is
+    then S_aa lower and S_ab upper is conj(Z_k Z_-k), the term that separates amplitude from phase noise."""
+
+    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
+        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_zcsd_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
+        else:
+            self._h = self._L.psdc_zcsd_create(n, int(window), n_pairs, device)
+        # (ftw, phase0) of both sides of every pair, as set
+        self.carriers = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
+        if not self._h:
+            msg = self._L.psdc_zcsd_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_zcsd_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_zcsd(rc, self._h)
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        self._ck(self._L.psdc_zcsd_reset(self._h))
+        self.carriers = {k: (0, 0) for k in self.carriers}
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_zcsd_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_zcsd_set_avg(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
+        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as f0 (cycles per sample, through
+        zoom_ftw) or as the tuning word itself; phase0 in 2^-64 turn.  Only before the pair's first sample.  Returns the f0
+        actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        if side is not None and side not in (0, 1):
+            raise PsdError(ERR_ARG, f"side {side} out of range (0: channel a, 1: channel b)")
+        for s in ((0, 1) if side is None else (side,)):
+            self._ck(self._L.psdc_zcsd_set_carrier(self._h, pair, s, ftw, phase0))
+            self.carriers[(pair, s)] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, pair, x, y):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        if x.size != y.size:
+            raise PsdError(ERR_ARG, "x and y must have equal lengths")
+        self._ck(self._L.psdc_zcsd_process(self._h, pair, _fptr(x), _fptr(y), x.size))
+
+    def process_device(self, pair, px, py, length, after=None):
+        """px, py: device addresses of `length` f32 samples each; after: a hipEvent_t handle recorded behind their producer, or
+        None when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zcsd_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
+                                                  C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._L.psdc_zcsd_sync(self._h))
+
+    def num_stages(self, pair=0):
+        return self._ck(self._L.psdc_zcsd_num_stages(self._h, pair))
+
+    def stage_spectra(self, pair, stage):
+        """(info, rows) of one stage's raw accumulators: rows (8, n/2 + 1) in the layout of include/psdcascade.h -- S_aa upper,
+        lower; S_bb upper, lower; Re S_ab upper, lower; Im S_ab upper, lower."""
+        st = _CStageStat()
+        rows = np.empty((8, self.n // 2 + 1), np.float32)
+        self._ck(self._L.psdc_zcsd_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(rows)))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
+
+    def csd(self, pair=0, opts=MergeOpts()):
+        """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): PsdCascade::psd of every row, sab complex;
+        Break.frequencies(breaks) are the offsets of all."""
+        ns = self.num_stages(pair)
+        cap = max(1, ns * (self.n // 2 + 1))
+        real = [np.empty(cap, np.float32) for _ in range(4)]
+        cplx = [np.empty(2 * cap, np.float32) for _ in range(2)]
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_zcsd_csd(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                       *[_fptr(a) for a in real + cplx], cap, C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        out = [a[:m].copy() for a in real] + [(a[0:2 * m:2] + 1j * a[1:2 * m:2]).astype(np.complex64) for a in cplx]
+        return (*out, [Break._from_c(br[i]) for i in range(nb.value)])
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_zcsd_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "pairs_in": si.value}
+
+
+class ZoomCsdCascade:
+    """One pair around a carrier: ZoomCsdCascade(n, f0=0.2) or ZoomCsdCascade(n, ftw=...) sets both sides; set_carrier(side=...)
+    sets one.  reset() keeps the object's carriers."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = ZoomCsdCascadeBank(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
+        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
+        self.carriers = [self._b.carriers[(0, 0)], self._b.carriers[(0, 1)]]
+        return f
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x, y):
+        self._b.process(0, x, y)
+
+    def process_device(self, px, py, length, after=None):
+        self._b.process_device(0, px, py, length, after)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        car = list(self.carriers)
+        self._b.reset()
+        for s, (ftw, ph) in enumerate(car):
+            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
 
     def sync(self):
         self._b.sync()

@@ -1,8 +1,8 @@
 // cross_channel.h -- one channel of the cross-spectral kernels, shared by cross.hip (pairs), csm.hip (groups of m channels) and
-// zoom.hip (the I / Q pair of a mixed-down channel):
+// zoom.hip / zoom_cross.hip (the I / Q pair of a mixed-down channel):
 // load, detrend and window two consecutive segments of a channel, transform them as one complex signal and leave the spectrum
-// in natural order in an LDS frame (cross_fft.h) -- or, for the zoom kernel, leave nothing in the frame and add |Z|^2 of the
-// thread's bins to its registers.  Device code only.
+// in natural order in an LDS frame (cross_fft.h) -- or, for the zoom kernels, leave nothing in the frame and add |Z|^2 of the
+// thread's bins to its registers, or hand the bins themselves back.  Device code only.
 #pragma once
 #include "cross_fft.h"
 
@@ -61,12 +61,14 @@ __device__ __forceinline__ void xfft_run(int t, cf *v, cf *frame, const cf *__re
 // z = a + i b in natural order in `frame`.
 // ZOOM = true (zoom.hip): segment b is read from the stream srcq in place of src -- a and b are the I and Q of ONE segment --
 // and the spectrum is not stored: |Z|^2 of the thread's bins is added to pw, pw[s] being bin freq_of_slot<N>(t, s).
-template <int N, bool ZOOM = false>
+// KEEP = true (zoom_cross.hip, with ZOOM): nothing is summed; the thread's bins are handed back in zout, in the order of pw.
+template <int N, bool ZOOM = false, bool KEEP = false>
 __device__ __forceinline__ void cross_channel(const float *__restrict__ src, long long ofs_la, long long ofs_lb, bool act_a,
                                               bool act_b, int detrend, float ampa, float ampb, int t, int team, cf *frame,
                                               float *red, const float *__restrict__ win, const cf *__restrict__ tw,
-                                              const float *srcq = nullptr, float *pw = nullptr)
+                                              const float *srcq = nullptr, float *pw = nullptr, cf *zout = nullptr)
 {
+    static_assert(ZOOM || !KEEP, "the bins are handed back by the zoom kernels only");
     const float *srcb = ZOOM ? srcq : src;
     using Cfg = CrossCfg<N>;
     using P0 = PassInfo<N, 0>;
@@ -160,7 +162,11 @@ __device__ __forceinline__ void cross_channel(const float *__restrict__ src, lon
             v[s].im = b * w * ampb;
         }
     xfft_run<N, 0>(t, v, frame, tw);
-    if constexpr (ZOOM) {
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int s = 0; s < E; ++s)
+            zout[s] = v[s];
+    } else if constexpr (ZOOM) {
 #pragma unroll
         for (int s = 0; s < E; ++s)
             pw[s] += v[s].re * v[s].re + v[s].im * v[s].im;

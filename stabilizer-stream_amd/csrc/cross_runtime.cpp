@@ -1,9 +1,11 @@
 // cross_runtime.cpp -- the cross-spectral cascades behind psdc_cross_* / psdc_csd_* (pairs), psdc_csm_* (groups of m = 2 ... 4
-// channels with their full spectral matrix) and psdc_zoom_* (channels mixed down from a carrier) of include/psdcascade.h.  One
+// channels with their full spectral matrix), psdc_zoom_* (channels mixed down from a carrier) and psdc_zcsd_* (pairs of channels
+// mixed down from a carrier each, with their cross spectrum) of include/psdcascade.h.  One
 // runtime over the channel count: a pair object is m = 2 on cross_kernel with the rows xx, yy, re, im; a matrix object runs
 // csm_kernel<N, M> with m * m rows (csm_fft.h); a zoom object's unit is one real channel whose m = 2 streams are the I and Q the
-// mixer (zoom_mix_kernel, in place of the input copy) makes of it, on zoom_kernel with the rows upper, lower.  Below, "pair"
-// stands for any of these units.
+// mixer (zoom_mix_kernel, in place of the input copy) makes of it, on zoom_kernel with the rows upper, lower; a zoom cross
+// object's unit is two such channels, m = 4 streams (I_a, Q_a, I_b, Q_b), on zoom_cross_kernel with the eight rows of
+// zoom_cross_fft.h.  Below, "pair" stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -17,7 +19,7 @@
 // count (more only when a round's job tables overflow a launch).  Read-outs drain: rounds until no stage has work.
 // There is no CPU compute path.
 #include "csm.h"
-#include "zoom.h"
+#include "zoom_cross.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -59,9 +61,11 @@ struct XObj {
     uint32_t n = 0, n_pairs = 0;
     uint32_t m = 2;      // channels of a pair / group
     bool matrix = false; // psdc_csm: csm_kernel and its row layout
-    bool zoom = false;   // psdc_zoom: the streams are I and Q of one mixed channel, zoom_kernel and its two rows
+    bool zoom = false;   // psdc_zoom / psdc_zcsd: the streams are I and Q of mixed channels, fed through the mixer
+    bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return zoom ? 2 : matrix ? m * m : 4; }
+    uint32_t rows() const { return zcross ? 8 : zoom ? 2 : matrix ? m * m : 4; }
+    uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     uint32_t map_w() const { return zoom ? 1 : m; } // entries a unit has in a frames call's map: a zoom channel takes one trace
     // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
     // channel's STAGING floats, the others' at least two
@@ -100,7 +104,8 @@ struct XObj {
     psdc_loss loss{};
     uint8_t *d_frames = nullptr;
     psdrt::HeaderGather hdr;
-    // zoom: a channel's carrier (2^-64 turn a sample, start phase) and the device buffer host samples land in before the mixer
+    // zoom: a channel's carrier (2^-64 turn a sample, start phase; channel `side` of unit u at reals() u + side) and the device
+    // buffer host samples land in before the mixer (reals() x STAGING floats)
     std::vector<uint64_t> ftw, phase0;
     float *d_land = nullptr;
     int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
@@ -112,6 +117,7 @@ struct XObj {
 struct psdc_cross : XObj {};
 struct psdc_csm : XObj {};
 struct psdc_zoom : XObj {};
+struct psdc_zcsd : XObj {};
 
 namespace {
 
@@ -237,9 +243,10 @@ CrossJob pair_job(const CsmJob &j)
 int run_round(XObj *h, bool *did)
 {
     const Geometry &g = h->geo;
-    const int spt = h->matrix ? csm_segments_per_tile((int)h->n, (int)h->m)
-                    : h->zoom ? zoom_segments_per_tile((int)h->n)
-                              : cross_segments_per_tile((int)h->n);
+    const int spt = h->matrix   ? csm_segments_per_tile((int)h->n, (int)h->m)
+                    : h->zcross ? zoom_cross_segments_per_tile((int)h->n)
+                    : h->zoom   ? zoom_segments_per_tile((int)h->n)
+                                : cross_segments_per_tile((int)h->n);
     const int nch = (int)h->m;
     std::vector<PlannedCross> cross;
     std::vector<DecJob> decs;
@@ -372,10 +379,11 @@ int run_round(XObj *h, bool *did)
                 cb->jobs[cb->njobs++] = conv(cross[i].job);
         };
         hipError_t e;
-        if (h->matrix) {
+        if (h->matrix || h->zcross) {
             CsmBatch *cb = new CsmBatch();
             fill(cb, [](const CsmJob &j) { return j; });
-            e = launch_csm((int)h->n, (int)h->m, *cb, h->d_win, h->d_tw, h->stream);
+            e = h->zcross ? launch_zoom_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                          : launch_csm((int)h->n, (int)h->m, *cb, h->d_win, h->d_tw, h->stream);
             delete cb;
         } else {
             CrossBatch *cb = new CrossBatch();
@@ -512,7 +520,7 @@ std::string csm_size_text(uint32_t n, uint32_t m)
 }
 
 const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, bool matrix,
-                       bool zoom)
+                       bool zoom, bool zcross = false)
 {
     if (!matrix && (n < 64 || n > 4096 || (n & (n - 1)) != 0))
         return "n must be a power of two in [64, 4096]";
@@ -523,24 +531,37 @@ const char *check_args(uint32_t n, const float *win, float power, float nenbw, s
     if (!(power > 0.0f) || !(nenbw > 0.0f))
         return "window power and nenbw must be > 0";
     if (n_pairs < 1 || n_pairs > X_MAX_PAIRS)
-        return matrix ? "n_groups must be in [1, 65536]" : zoom ? "n_channels must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
+        return matrix ? "n_groups must be in [1, 65536]" : zoom && !zcross ? "n_channels must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
     return nullptr;
 }
 
 void destroy_impl(XObj *h);
 
-// T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel) or psdc_zoom (m = 2: I and Q, zoom_kernel)
+// the size of a zoom cross object, as text for a refusal
+std::string zcsd_size_text(uint32_t n)
+{
+    return "n = " + std::to_string(n) + " is not supported: n must be a power of two in [64, " +
+           (zoom_cross_supported(4096) ? "4096]" : "2048]");
+}
+
+// T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
+// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel)
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
 {
     constexpr bool matrix = std::is_same<T, psdc_csm>::value;
-    constexpr bool zoom = std::is_same<T, psdc_zoom>::value;
+    constexpr bool zcross = std::is_same<T, psdc_zcsd>::value;
+    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
         return nullptr;
     }
-    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom)) {
+    if (zcross && !zoom_cross_supported(n <= 4096 ? (int)n : 0)) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + zcsd_size_text(n));
+        return nullptr;
+    }
+    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom, zcross)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
         return nullptr;
     }
@@ -574,8 +595,14 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         h->tag = "psdc_zoom";
         h->unit = "channel";
         h->units = "n_channels";
-        h->ftw.assign(n_pairs, 0);
-        h->phase0.assign(n_pairs, 0);
+        if (zcross) {
+            h->zcross = true;
+            h->tag = "psdc_zcsd";
+            h->unit = "pair";
+            h->units = "n_pairs";
+        }
+        h->ftw.assign((size_t)n_pairs * h->reals(), 0);
+        h->phase0.assign((size_t)n_pairs * h->reals(), 0);
     }
     h->n_pairs = n_pairs;
     h->device = device;
@@ -607,7 +634,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
               hipMemcpy(h->d_win, win, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_tw, tw.data(), sizeof(cf) * n, hipMemcpyHostToDevice) == hipSuccess;
     for (int i = 0; ok && i < 2; ++i)
-        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * (zoom ? 1 : m) * STAGING) == hipSuccess &&
+        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * h->reals() * STAGING) == hipSuccess &&
              hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": device allocation failed");
@@ -1015,11 +1042,11 @@ int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t 
     return run_round(h, &did);
 }
 
-// A zoom channel takes len real samples, from host memory (dev == false: up through the pinned staging into the landing buffer,
+// A zoom unit takes len real samples of each of its reals() channels (xs: that many pointers), from host memory (dev == false: up through the pinned staging into the landing buffer,
 // as host frames go) or from device memory.  The mixer stands where psdc_cross_process_device has its copies and under the same
 // event rules: on the copy stream, behind a buffer's growth and round R - 2, and round R waits for it.  Both sources make the
 // same launches on the same data, so the same calls give the same bits from either.
-int zoom_feed(XObj *h, uint32_t ch, const float *x, size_t len, bool dev, void *producer_event, const char *who)
+int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev, void *producer_event, const char *who)
 {
     X_HANDLE(h, who);
     int rc = check_pair(h, ch);
@@ -1027,15 +1054,18 @@ int zoom_feed(XObj *h, uint32_t ch, const float *x, size_t len, bool dev, void *
         return rc;
     if (len == 0)
         return PSDC_OK;
-    if (!x)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-    if ((uintptr_t)x % sizeof(float))
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to 4 bytes");
+    const uint32_t nx = h->reals();
+    for (uint32_t c = 0; c < nx; ++c) {
+        if (!xs[c])
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+        if ((uintptr_t)xs[c] % sizeof(float))
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to 4 bytes");
+    }
     X_ON_DEVICE(h);
     if (producer_event)
         XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
     if (!dev && !h->d_land)
-        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * STAGING));
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * nx * STAGING));
     XStage *s = nullptr;
     h->grew = false;
     if ((rc = stage0_room(h, ch, len, &s)))
@@ -1050,28 +1080,32 @@ int zoom_feed(XObj *h, uint32_t ch, const float *x, size_t len, bool dev, void *
     const size_t piece = dev ? len : STAGING;
     for (size_t done = 0; done < len;) {
         const size_t cnt = std::min(piece, len - done);
-        ZoomMixJob mj{};
-        mj.x = x + done;
-        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
+        if (!dev) { // (the mixers of the piece before have read the landing buffer: all are on the copy stream)
             const int slot = h->stage_cur;
             if (h->ev_pending[slot])
                 XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-            memcpy(h->h_stage[slot], x + done, sizeof(float) * cnt);
-            XCHK(h, hipMemcpyAsync(h->d_land, h->h_stage[slot], sizeof(float) * cnt, hipMemcpyHostToDevice, h->copy_stream));
+            for (uint32_t c = 0; c < nx; ++c) {
+                memcpy(h->h_stage[slot] + c * STAGING, xs[c] + done, sizeof(float) * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, h->h_stage[slot] + c * STAGING, sizeof(float) * cnt,
+                                       hipMemcpyHostToDevice, h->copy_stream));
+            }
             XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
             h->ev_pending[slot] = true;
             h->stage_cur ^= 1;
-            mj.x = h->d_land;
         }
         const size_t at = (size_t)(s->total + done - s->buf.base);
-        mj.dst_i = s->buf.p[0][s->buf.cur] + at;
-        mj.dst_q = s->buf.p[1][s->buf.cur] + at;
-        mj.len = cnt;
-        mj.j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
-        mj.ftw = h->ftw[ch];
-        mj.phase0 = h->phase0[ch];
-        XCHK(h, launch_zoom_mix(mj, h->copy_stream));
-        ++h->launches;
+        for (uint32_t c = 0; c < nx; ++c) { // one mixer a channel
+            ZoomMixJob mj{};
+            mj.x = dev ? xs[c] + done : h->d_land + c * STAGING;
+            mj.dst_i = s->buf.p[2 * c][s->buf.cur] + at;
+            mj.dst_q = s->buf.p[2 * c + 1][s->buf.cur] + at;
+            mj.len = cnt;
+            mj.j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
+            mj.ftw = h->ftw[(size_t)nx * ch + c];
+            mj.phase0 = h->phase0[(size_t)nx * ch + c];
+            XCHK(h, launch_zoom_mix(mj, h->copy_stream));
+            ++h->launches;
+        }
         done += cnt;
     }
     XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
@@ -1560,12 +1594,12 @@ int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t
 
 int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len)
 {
-    return zoom_feed(h, channel, x, len, false, nullptr, "psdc_zoom_process");
+    return zoom_feed(h, channel, &x, len, false, nullptr, "psdc_zoom_process");
 }
 
 int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
 {
-    return zoom_feed(h, channel, d_x, len, true, producer_event, "psdc_zoom_process_device");
+    return zoom_feed(h, channel, &d_x, len, true, producer_event, "psdc_zoom_process_device");
 }
 
 int psdc_zoomcascade_process_frames(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
@@ -1627,5 +1661,124 @@ int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in,
 }
 
 const char *psdc_zoom_last_error(const psdc_zoom *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- zoom cross: two real channels a unit, each mixed to I and Q in front of stage 0; zoom_cross_kernel, the eight rows of
+// zoom_cross_fft.h ----
+
+int psdc_zcsd_supported(uint32_t n) { return n <= 4096 && zoom_cross_supported((int)n) ? 1 : 0; }
+
+psdc_zcsd *psdc_zcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                   int device)
+{
+    return create_impl<psdc_zcsd>(n, win, power, nenbw, overlap, 4, n_pairs, device, "psdc_zcsd_create_window");
+}
+
+psdc_zcsd *psdc_zcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    if (!psdc_zcsd_supported(n)) { // (before the window: a refused size names itself)
+        xfail(nullptr, PSDC_ERR_ARG, "psdc_zcsd_create: " + zcsd_size_text(n));
+        return nullptr;
+    }
+    return create_kind<psdc_zcsd>(n, window_kind, 4, n_pairs, device, "psdc_zcsd_create");
+}
+
+void psdc_zcsd_destroy(psdc_zcsd *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_zcsd_reset(psdc_zcsd *h) { return reset_impl(h, "psdc_zcsd_reset"); }
+int psdc_zcsd_set_detrend(psdc_zcsd *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zcsd_set_detrend"); }
+int psdc_zcsd_set_avg(psdc_zcsd *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zcsd_set_avg"); }
+
+int psdc_zcsd_set_carrier(psdc_zcsd *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0)
+{
+    X_HANDLE(h, "psdc_zcsd_set_carrier");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    if (side > 1)
+        return xfail(h, PSDC_ERR_ARG, "psdc_zcsd_set_carrier: side " + std::to_string(side) + " out of range (0: channel a, 1: channel b)");
+    const auto &st = h->pairs[pair];
+    if (!st.empty() && st[0].total)
+        return xfail(h, PSDC_ERR_ARG, "psdc_zcsd_set_carrier: pair " + std::to_string(pair) + " has taken " +
+                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
+    h->ftw[2 * (size_t)pair + side] = ftw;
+    h->phase0[2 * (size_t)pair + side] = phase0;
+    return PSDC_OK;
+}
+
+int psdc_zcsd_process(psdc_zcsd *h, uint32_t pair, const float *x, const float *y, size_t len)
+{
+    const float *xs[2] = {x, y};
+    return zoom_feed(h, pair, xs, len, false, nullptr, "psdc_zcsd_process");
+}
+
+int psdc_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const float *d_x, const float *d_y, size_t len, void *producer_event)
+{
+    const float *xs[2] = {d_x, d_y};
+    return zoom_feed(h, pair, xs, len, true, producer_event, "psdc_zcsd_process_device");
+}
+
+int psdc_zcsd_sync(psdc_zcsd *h) { return sync_impl(h, "psdc_zcsd_sync"); }
+int psdc_zcsd_num_stages(psdc_zcsd *h, uint32_t pair) { return num_stages_impl(h, pair, "psdc_zcsd_num_stages"); }
+
+int psdc_zcsd_stage_spectra(psdc_zcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, "psdc_zcsd_stage_spectra");
+    if (rc)
+        return rc;
+    for (size_t e = 0; e < acc.size(); ++e)
+        rows[e] = (float)acc[e];
+    return PSDC_OK;
+}
+
+int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
+                  float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap, size_t *len,
+                  psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    X_HANDLE(h, "psdc_zcsd_csd");
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, pair, &in)))
+        return rc;
+    // the complex rows are stitched as their real and imaginary rows and interleaved afterwards, as psdc_cross_stitch does
+    std::vector<float> tmp(4 * (cap ? cap : 1));
+    float *outs[8] = {saa_upper, saa_lower, sbb_upper, sbb_lower, sab_upper ? &tmp[0] : nullptr, sab_lower ? &tmp[cap] : nullptr,
+                      sab_upper ? &tmp[2 * cap] : nullptr, sab_lower ? &tmp[3 * cap] : nullptr};
+    size_t plen = 0;
+    rc = stitch_rows_impl("psdc_zcsd_csd", h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(),
+                          in.pend.data(), in.rows.data(), 8, keep_overlap, min_count, keep_transition_band, outs, cap, &plen, breaks,
+                          breaks_cap, n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    for (size_t k = 0; k < plen; ++k) {
+        if (sab_upper) {
+            sab_upper[2 * k] = tmp[k];
+            sab_upper[2 * k + 1] = tmp[2 * cap + k];
+        }
+        if (sab_lower) {
+            sab_lower[2 * k] = tmp[cap + k];
+            sab_lower[2 * k + 1] = tmp[3 * cap + k];
+        }
+    }
+    if (len)
+        *len = plen;
+    return PSDC_OK;
+}
+
+int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    return stats_impl(h, launches, pairs_in, reset, "psdc_zcsd_stats_read");
+}
+
+const char *psdc_zcsd_last_error(const psdc_zcsd *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

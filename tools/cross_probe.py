@@ -22,6 +22,12 @@ frames resident in device memory.  Leg C (a ceiling, not a gate) is psdc_zoom_pr
 in device memory.  A, B, A, C in turn --reps times in one session; B beats A when every B / A exceeds 1 + the largest |A' - A| / A.
 Also four carriers on trace 0: one B call feeding four channels against four C calls.  Clocks and power from rocm-smi (read only)
 before and after.  Writes profiles/zoom_frames_probe.json unless --out names another file.
+--zoom --pair: two streams around a carrier.  Two device-resident f32 streams (b = 0.6 a delayed by 3 samples + noise) of 2^24
+samples a call at N = 512, 1024, 2048; leg A is CsmCascadeBank(n, 4) fed the pre-mixed (I_a, Q_a, I_b, Q_b) -- four transforms and
+sixteen rows a segment pair --, leg B is ZoomCsdCascadeBank(n, 1) fed (a, b) -- two mixers, two transforms and eight rows a segment;
+A / B / A in turn --reps times in one session, idle clocks and power before and after.  Also the tone-image figure of the cross
+row: a tone at f0 + delta on both channels, |S_ab lower| / |S_ab upper| at the tone's bin from B and rebuilt from A's sixteen rows.
+Writes profiles/zoom_cross_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -259,6 +265,83 @@ def zoom_legs(pkg, torch, seconds, reps, call):
     return legs
 
 
+def zoom_pair_image(pkg, torch, n=1024, k=2, b=100, f0=0.2, length=1 << 20):
+    """A tone at f0 + delta (delta the centre of bin b of stage k) on both channels, b's at 0.7 of a's and 1 rad behind:
+    |S_ab lower[b]| / |S_ab upper[b]| at stage k from the zoom cross object, and the same rebuilt from a matrix object fed the
+    pre-mixed (I_a, Q_a, I_b, Q_b): with S[c, d] = conj(X_c) X_d of the four real streams, bin k of
+    S_ab upper = S[0,2] + i S[0,3] - i S[1,2] + S[1,3] and S_ab lower = the same sum of the conjugated entries."""
+    ftw, f0 = pkg.zoom_ftw(f0)
+    delta = b / (n * 8.0 ** k)
+    j = np.arange(length, dtype=np.float64)
+    xa = np.cos(2 * np.pi * (((f0 + delta) * j) % 1.0)).astype(np.float32)
+    xb = (0.7 * np.cos(2 * np.pi * (((f0 + delta) * j) % 1.0) - 1.0)).astype(np.float32)
+    z = pkg.ZoomCsdCascade(n, ftw=ftw)
+    z.process(xa, xb)
+    _, r = z.stage_spectra(k)
+    r = r.astype(np.float64)
+    native = float(np.hypot(r[5][b], r[7][b]) / np.hypot(r[4][b], r[6][b]))
+    z.close()
+    ph = 2 * np.pi * ((f0 * j) % 1.0)
+    c, sn = np.cos(ph), np.sin(ph)
+    four = [(xa * c).astype(np.float32), (-xa * sn).astype(np.float32), (xb * c).astype(np.float32), (-xb * sn).astype(np.float32)]
+    m = pkg.CsmCascade(n, 4)
+    m.process(four)
+    S = m.stage_spectra(k)[1].astype(np.complex128)[:, :, b]  # (m, m, bins) Hermitian, from the f32 rows
+    m.close()
+    up = S[0, 2] + 1j * S[0, 3] - 1j * S[1, 2] + S[1, 3]
+    lo = np.conj(S[0, 2]) + 1j * np.conj(S[0, 3]) - 1j * np.conj(S[1, 2]) + np.conj(S[1, 3])
+    return {"n": n, "stage": k, "bin": b, "image_over_peak_zoom_cross": native, "image_over_peak_rebuilt_from_matrix_rows": float(abs(lo) / abs(up))}
+
+
+def zoom_pair_legs(pkg, torch, seconds, reps, call):
+    """Two device-resident f32 streams.  A: CsmCascadeBank(n, 4) fed the pre-mixed (I_a, Q_a, I_b, Q_b).  B: ZoomCsdCascadeBank(n, 1)
+    fed (a, b).  A / B / A in turn; unit: sample pairs a second (one sample of a and one of b)."""
+    xa = torch.randn(call + 3, device="cuda")
+    xb = (0.6 * xa[:-3] + 0.8 * torch.randn(call, device="cuda")).contiguous()
+    xa = xa[3:].contiguous()
+    ph = 2 * np.pi * 0.2 * torch.arange(call, device="cuda", dtype=torch.float64)
+    c, sn = torch.cos(ph).float(), torch.sin(ph).float()
+    del ph
+    four = [(xa * c).contiguous(), (-xa * sn).contiguous(), (xb * c).contiguous(), (-xb * sn).contiguous()]
+    del c, sn
+    torch.cuda.synchronize()
+    ptrs = [t.data_ptr() for t in four]
+    legs = []
+    for n in (512, 1024, 2048):
+        ma = pkg.CsmCascadeBank(n, 4, 1)
+        zb = pkg.ZoomCsdCascadeBank(n, 1)
+        zb.set_carrier(0, f0=0.2)
+
+        def a_step():
+            ma.process_device(0, ptrs, call)
+            return call
+
+        def b_step():
+            zb.process_device(0, xa.data_ptr(), xb.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, ma.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, ma.sync, seconds)[0] / 1e9)
+        zb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = zb.stats_read()["launches"] / 8
+        zb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        legs.append({"n": n, "call": call, "a_matrix_fed_iq_gpairs_s": [round(v, 3) for v in a1],
+                     "b_zoom_cross_gpairs_s": [round(v, 3) for v in b], "a_again_gpairs_s": [round(v, 3) for v in a2],
+                     "ratio_b_over_a": [round(r, 3) for r in ratios], "ratio_min": round(min(ratios), 3),
+                     "aa_spread_max": round(spread, 4), "b_beats_a": bool(min(ratios) > 1 + spread),
+                     "b_launches_per_call": launches, "stages": zb.num_stages(0)})
+        ma.close()
+        zb.close()
+    return legs
+
+
 def gpu_state():
     """sclk / mclk / power as rocm-smi prints them (read only); None where the tool is missing"""
     import subprocess
@@ -407,6 +490,8 @@ def main():
     ap.add_argument("--only-a", action="store_true", help="with --matrix: leg A (six pairs) alone")
     ap.add_argument("--reps", type=int, default=5, help="with --matrix: turns of A, B, A")
     ap.add_argument("--zoom", action="store_true", help="ZoomCascadeBank fed x against CsdCascadeBank fed the pre-mixed (I, Q)")
+    ap.add_argument("--pair", action="store_true", help="with --zoom: ZoomCsdCascadeBank fed (a, b) against CsmCascadeBank(n, 4) fed the "
+                                                        "pre-mixed (I_a, Q_a, I_b, Q_b)")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
@@ -421,6 +506,16 @@ def main():
                            "legs": legs})
         print(line)
         with open(a.out or os.path.join(ROOT, "profiles", "zoom_frames_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
+    if a.zoom and a.pair:
+        before = gpu_state()
+        legs = zoom_pair_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)
+        after = gpu_state()
+        line = json.dumps({"metric": "zoom_cross_gpairs_s", "unit": "1e9 sample pairs a second (one sample of each of the two real streams)",
+                           "gpu_before": before, "gpu_after": after, "legs": legs, "tone_image": zoom_pair_image(pkg, torch)})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "zoom_cross_probe.json"), "w") as f:
             f.write(line + "\n")
         return
     if a.zoom:

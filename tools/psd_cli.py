@@ -9,7 +9,10 @@ Prints one line per trace: name, stages, averages of the top stage, bins, integr
 pair, its bins and median coherence; with --csv it writes DIR/<x>__<y>.csv (f, |H1|, arg H1, coherence; H1 = Sxy / Sxx).
 --zoom F0[:TRACE] (repeatable; F0 in cycles per sample, TRACE a label or index, default the first trace) also feeds that trace to a
 ZoomCascade(512) around the carrier F0 and prints, or with --csv writes to DIR/zoom_<trace>_<F0>.csv, the lines offset,upper,lower
-(the offset from the carrier in units of fs; upper / lower the density at F0 + offset / F0 - offset)."""
+(the offset from the carrier in units of fs; upper / lower the density at F0 + offset / F0 - offset).
+--zoom-pair F0:X:Y (repeatable; X, Y trace labels or indices) feeds the traces X and Y to a ZoomCsdCascade(512) with the carrier F0 on
+both sides and prints, or with --csv writes to DIR/zoompair_<x>__<y>_<F0>.csv, the lines
+offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b."""
 import argparse
 import os
 import sys
@@ -40,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--csv", default=None, help="directory for the plot points of every trace")
     ap.add_argument("--pair", action="append", default=[], help="X:Y -- cross spectrum of traces X and Y (repeatable)")
     ap.add_argument("--zoom", action="append", default=[], help="F0[:TRACE] -- two-sided spectrum around the carrier F0 (repeatable)")
+    ap.add_argument("--zoom-pair", action="append", default=[],
+                    help="F0:X:Y -- two-sided auto and cross spectra of traces X and Y around the carrier F0 (repeatable)")
     a = ap.parse_args(argv)
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
@@ -86,6 +91,8 @@ def main(argv=None):
         cross_pairs(pkg, source, a, merge)
     if a.zoom:
         zoom_traces(pkg, source, a, merge, names)
+    if a.zoom_pair:
+        zoom_pairs(pkg, source, a, merge, names)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
@@ -133,28 +140,26 @@ def cross_pairs(pkg, source, a, merge):
     cross.close()
 
 
-def zoom_traces(pkg, source, a, merge, names):
-    """--zoom: the source once more through Source's host traces (raw files and frame files alike), the named trace of every read
-    into one zoom cascade per carrier"""
-    want = []
-    for z in a.zoom:
-        f0, _, tr = z.partition(":")
-        idx = 0 if tr == "" else int(tr) if tr.isdigit() else (names.index(tr) if tr in names else -1)
-        if not 0 <= idx < len(names):
-            raise SystemExit(f"--zoom: unknown trace {tr!r}")
-        want.append((float(f0), idx))
-    bank = pkg.ZoomCascadeBank(1 << 9, len(want))
-    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
-    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
-    used = [bank.set_carrier(i, f0=f0) for i, (f0, _) in enumerate(want)]
+def trace_arg(tr, names, opt):
+    """a trace given as a label or an index ("" is the first trace)"""
+    idx = 0 if tr == "" else int(tr) if tr.isdigit() else (names.index(tr) if tr in names else -1)
+    if not 0 <= idx < len(names):
+        raise SystemExit(f"{opt}: unknown trace {tr!r}")
+    return idx
+
+
+def host_traces(source, pkg, a, units, process):
+    """The source once more through Source's host traces (raw files and frame files alike): unit i takes the traces units[i] (a
+    tuple of indices) of every read; process(i, [samples of each]) is called about every 2^20 samples"""
     src = source.Source(source.SourceOpts(file=a.file, frame_size=a.frame_size, repeat=a.repeat, raw=a.raw), pkg)
-    total, held, pend = 0, 0, [[] for _ in want]
+    total, held, pend = 0, 0, [[[] for _ in u] for u in units]
 
     def flush():
         for i, chunks in enumerate(pend):
-            if chunks:
-                bank.process(i, np.concatenate(chunks))
-                chunks.clear()
+            if chunks[0]:
+                process(i, [np.concatenate(c) for c in chunks])
+                for c in chunks:
+                    c.clear()
 
     while a.max_bytes is None or total < a.max_bytes:
         try:
@@ -163,8 +168,9 @@ def zoom_traces(pkg, source, a, merge, names):
             break
         if src.eof:
             break
-        for i, (_, idx) in enumerate(want):
-            pend[i].append(traces[idx][1])
+        for i, u in enumerate(units):
+            for c, idx in enumerate(u):
+                pend[i][c].append(traces[idx][1])
         total += a.frame_size if a.file else traces[0][1].nbytes
         held += traces[0][1].size
         if held >= 1 << 20:
@@ -172,6 +178,19 @@ def zoom_traces(pkg, source, a, merge, names):
             held = 0
     flush()
     src.close()
+
+
+def zoom_traces(pkg, source, a, merge, names):
+    """--zoom: the named trace of every read (host_traces) into one zoom cascade per carrier"""
+    want = []
+    for z in a.zoom:
+        f0, _, tr = z.partition(":")
+        want.append((float(f0), trace_arg(tr, names, "--zoom")))
+    bank = pkg.ZoomCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _) in enumerate(want)]
+    host_traces(source, pkg, a, [(idx,) for _, idx in want], lambda i, xs: bank.process(i, xs[0]))
     for i, (_, idx) in enumerate(want):
         label = f"zoom {names[idx]} @ {used[i]:.12g}"
         if bank.num_stages(i) == 0:
@@ -183,6 +202,39 @@ def zoom_traces(pkg, source, a, merge, names):
         lines = [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)]
         if a.csv:
             safe = "".join(ch if ch.isalnum() else "_" for ch in f"zoom_{names[idx]}_{used[i]:.9g}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+    bank.close()
+
+
+def zoom_pairs(pkg, source, a, merge, names):
+    """--zoom-pair: the two named traces of every read (host_traces) into one zoom cross cascade per pair, one carrier on both sides"""
+    want = []
+    for z in a.zoom_pair:
+        parts = z.split(":")
+        if len(parts) != 3:
+            raise SystemExit("--zoom-pair takes F0:X:Y")
+        want.append((float(parts[0]), trace_arg(parts[1], names, "--zoom-pair"), trace_arg(parts[2], names, "--zoom-pair")))
+    bank = pkg.ZoomCsdCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _, _) in enumerate(want)]
+    host_traces(source, pkg, a, [(x, y) for _, x, y in want], lambda i, xs: bank.process(i, xs[0], xs[1]))
+    for i, (_, x, y) in enumerate(want):
+        label = f"zoom pair {names[x]}:{names[y]} @ {used[i]:.12g}"
+        if bank.num_stages(i) == 0:
+            print(f"{label}: no samples")
+            continue
+        aup, alo, bup, blo, xup, xlo, breaks = bank.csd(i, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        coh = pkg.coherence(aup, bup, xup)
+        print(f"{label}: stages {bank.num_stages(i)} bins {aup.size} breaks {len(breaks)} median coherence (upper) {np.nanmedian(coh):.6g}")
+        lines = [f"{o:.9g},{p:.9g},{q:.9g},{u.real:.9g},{u.imag:.9g},{r:.9g},{t:.9g},{w.real:.9g},{w.imag:.9g}\n"
+                 for o, p, q, u, r, t, w in zip(off, aup, bup, xup, alo, blo, xlo)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"zoompair_{names[x]}__{names[y]}_{used[i]:.9g}")
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(lines)
         else:
