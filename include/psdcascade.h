@@ -790,7 +790,7 @@ const char *psdc_zoom_last_error(const psdc_zoom *h);
  * (PSDC_ZCSD_STEADY_LAUNCHES: two mixers; segments, decimators, fold + tails), with the matrix object's table limits at
  * m = 4.  Host and device calls of the same samples run the same launches on the same data and give the same bits.
  * Memory: per (pair, stage) two ping-pong buffers for each of the four streams, plus 64 MB of pinned staging.
- * Stream frames do not feed this object. */
+ * Stream frames feed this object through the three psdc_zoomcsdcascade_ calls below ("Stream frames into zoom cross pairs"). */
 #define PSDC_ZCSD_STEADY_LAUNCHES 5
 typedef struct psdc_zcsd psdc_zcsd;
 /* 1 if an object of size n can be created, else 0.  Pure host code. */
@@ -812,6 +812,50 @@ int psdc_zcsd_process(psdc_zcsd *h, uint32_t pair, const float *x, const float *
 /* the same from device memory (any 4-byte aligned addresses and any length); producer_event: hipEvent_t or NULL */
 int psdc_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
                              void *producer_event);
+/* Stream frames into zoom cross pairs (mirrors psdc_csd_process_frames).  The three frames calls of a psdc_zcsd object carry the
+ * prefix psdc_zoomcsdcascade_, after ZoomCsdCascade, the object's name in the mirrors, as a psdc_zoom object's carry
+ * psdc_zoomcascade_ after ZoomCascade: the psdc_zcsd_ set is the sample-fed object's and stays as it was.  The map is
+ * psdc_csd_process_frames's, 2 * n_pairs entries: pair p takes a = trace pair_traces[2p] and b = trace pair_traces[2p + 1] of every
+ * frame, in Payload::traces order (see "stream frames into a cross object").  Both entries PSDC_TRACE_NONE: the pair is not fed
+ * by this call and its stream index does not move.  A trace may feed any number of sides; a == b is allowed (the AM / PM
+ * recipe above: one trace, carriers +-ftw).  The map belongs to the call and is not stored.
+ * Map errors: PSDC_ERR_ARG without ingesting anything, *n_ok = 0, for a NULL map, a pair with exactly one PSDC_TRACE_NONE, a
+ * trace index >= 4 or a map that feeds no pair (the zoom kind's rule, not the pair object's: a call for Loss alone is refused).
+ * A run whose format carries fewer traces than the map names is PSDC_ERR_ARG at the run's first frame, with a text that names
+ * the trace: the frames before it are ingested and *n_ok counts them.
+ * Frames: headers, runs of one format, de::Error codes, *n_ok, header-only frames (Loss only) and Loss are those of
+ * psdc_csd_process_frames, from the same scanner; one psdc_loss an object, zeroed by psdc_zcsd_reset.  A call is cut into pieces
+ * of whole frames of at most 2^22 samples a trace, in runs of one format, and the cut depends on the headers alone; each piece
+ * is ONE decode-and-mix launch per 8 fed pairs (zoom_cross_frames_kernel: a cell is read and converted once, handed to every
+ * side of every pair that takes it, mixed in registers with the side's carrier and stored to the side's I and Q streams; the
+ * f32 trace never exists in memory) and then one round.  Where both sides of a pair have the same ftw and the same phase0 --
+ * two receivers on one carrier -- the oscillator is evaluated once a sample for both, with the bits of two evaluations (I = x c
+ * and Q = -(x s) are formed separately from the same (c, s)); equal ftw with different phase0, and the +-ftw recipe, are two
+ * oscillators.  The launch stands where the two mixers of psdc_zcsd_process_device stand: on the side stream, behind a grown
+ * buffer and round R - 2, in front of round R.
+ * Memory: host frames go up through the pinned staging into a 32 MB device buffer made by the first host-frames call -- one
+ * staging slot of this object, twice the zoom object's 16 MB --, one decode-and-mix launch (per 8 fed pairs) a slot.
+ * Carrier rule: unchanged -- psdc_zcsd_set_carrier is PSDC_ERR_ARG once the pair has taken a sample, by either route; a pair
+ * the map left out is still free.  pairs_in of psdc_zcsd_stats_read counts the sample pairs accepted over all fed pairs.
+ * Invariants:
+ *  (a) a call that is one piece gives the same bits as psdc_zcsd_process fed Payload::traces of the same frames in one call:
+ *      all eight rows of every stage, the stats and psdc_zcsd_csd (the decode is bit-identical to Payload::traces, a sample's
+ *      phase comes from its 64-bit stream index, and the round is the same);
+ *  (b) the same frames in host and in device memory give the same bits (the cut depends on the headers alone);
+ *  (c) sample and frame calls may be mixed on one pair: the 64-bit stream index, and so both phases, continues across them;
+ *  (d) a steady-state call of one piece that feeds up to 8 pairs is 1 + 3 kernel launches on the side and compute streams
+ *      (decode-and-mix; segments, decimators, fold + tails), for host frames that fit one staging slot, where the sample route
+ *      needs 2 + 3 for ONE pair.  The device call's header gather on its own stream is one more launch and
+ *      psdc_zcsd_stats_read counts it, as the pair object's statistics do: such a device call reads 5. */
+int psdc_zoomcsdcascade_process_frames(psdc_zcsd *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size,
+                                       size_t n_frames, size_t *n_ok);
+/* the same for frames in device memory (mirrors psdc_csd_process_frames_device): the side-stream header gather, the host
+ * wait for that launch alone, producer_event, the keep-payload-unchanged rule and "any base address" are that call's; header
+ * bytes may be rewritten once the call has returned */
+int psdc_zoomcsdcascade_process_frames_device(psdc_zcsd *h, const uint32_t *pair_traces, const uint8_t *d_frames,
+                                              size_t frame_size, size_t n_frames, size_t *n_ok, void *producer_event);
+/* the Loss counters of the frames the object ingested (mirrors psdc_csd_loss_read); reset != 0 zeroes them after reading */
+int psdc_zoomcsdcascade_loss_read(psdc_zcsd *h, psdc_loss *out, int reset);
 int psdc_zcsd_sync(psdc_zcsd *h);
 int psdc_zcsd_num_stages(psdc_zcsd *h, uint32_t pair);
 /* raw accumulators of one stage: rows 8 (n/2 + 1) floats in the row layout above; stat and rows may be NULL */

@@ -375,6 +375,9 @@ def lib():
     f("psdc_zcsd_set_carrier", i32, [H, u32, u32, u64, u64])
     f("psdc_zcsd_process", i32, [H, u32, fp, fp, sz])
     f("psdc_zcsd_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_zoomcsdcascade_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_zoomcsdcascade_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_zoomcsdcascade_loss_read", i32, [H, C.POINTER(_CLoss), i32])
     f("psdc_zcsd_sync", i32, [H])
     f("psdc_zcsd_num_stages", i32, [H, u32])
     f("psdc_zcsd_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
@@ -415,6 +418,7 @@ EXPORTS = [
     "psdc_zcsd_set_detrend", "psdc_zcsd_set_avg", "psdc_zcsd_set_carrier", "psdc_zcsd_process", "psdc_zcsd_process_device",
     "psdc_zcsd_sync", "psdc_zcsd_num_stages", "psdc_zcsd_stage_spectra", "psdc_zcsd_csd", "psdc_zcsd_stats_read",
     "psdc_zcsd_last_error",
+    "psdc_zoomcsdcascade_process_frames", "psdc_zoomcsdcascade_process_frames_device", "psdc_zoomcsdcascade_loss_read",
 ]
 
 
@@ -1346,7 +1350,8 @@ def zcsd_supported(n):
 
 def _raise_zcsd(code, h=None):
     msg = lib().psdc_zcsd_last_error(h)
-    raise PsdError(code, msg.decode() if msg else "")
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
 
 
 class ZoomCsdCascadeBank:
@@ -1429,6 +1434,38 @@ class ZoomCsdCascadeBank:
         self._ck(self._L.psdc_zcsd_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
                                                   C.c_void_p(after) if after else None))
 
+    def process_frames(self, data, frame_size, pairs):
+        """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] is (x, y),
+        the traces sides a and b of pair p take of every frame (indices or TRACE_NAMES labels, pair_map), or None to leave the
+        pair unfed; a trace may feed several sides, both sides of one pair included.  The frames are decoded and mixed on the
+        device in one kernel; two sides with one carrier share the oscillator.  Returns the number of frames ingested; a bad
+        frame raises FrameError after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_zoomcsdcascade_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        buf.ctypes.data_as(C.c_void_p), frame_size, buf.size // frame_size,
+                                                        C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
+        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
+        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
+        m = pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_zoomcsdcascade_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
+                                                               frame_size, n_frames, C.byref(ok),
+                                                               C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(self._L.psdc_zoomcsdcascade_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
     def sync(self):
         self._ck(self._L.psdc_zcsd_sync(self._h))
 
@@ -1491,6 +1528,16 @@ class ZoomCsdCascade:
 
     def process_device(self, px, py, length, after=None):
         self._b.process_device(0, px, py, length, after)
+
+    def process_frames(self, data, frame_size, pair):
+        """pair: (x, y), the traces of the frames the two streams are (ZoomCsdCascadeBank.process_frames)"""
+        return self._b.process_frames(data, frame_size, [pair])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
 
     def csd(self, opts=MergeOpts()):
         return self._b.csd(0, opts)

@@ -66,10 +66,11 @@ struct XObj {
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
     uint32_t rows() const { return zcross ? 8 : zoom ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
-    uint32_t map_w() const { return zoom ? 1 : m; } // entries a unit has in a frames call's map: a zoom channel takes one trace
+    // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
+    uint32_t map_w() const { return zoom ? reals() : m; }
     // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
-    // channel's STAGING floats, the others' at least two
-    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? 1 : 2); }
+    // channel's STAGING floats (16 MB), a zoom cross object's two (32 MB), the others' at least two
+    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? reals() : 2); }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -98,7 +99,7 @@ struct XObj {
     std::vector<void *> retired; // replaced device buffers, freed at the next sync point
     bool idle = true;            // every stage drained
     uint64_t launches = 0, pairs_in = 0;
-    // frames (psdc_csd_ / psdc_csm_ / psdc_zoomcascade_process_frames[_device]): Loss over every frame either call ingested; host-memory
+    // frames (psdc_csd_ / psdc_csm_ / psdc_zoomcascade_ / psdc_zoomcsdcascade_process_frames[_device]): Loss over every frame either call ingested; host-memory
     // frames go up through h_stage into d_frames (frames_chunk() bytes, made by the first host-frames call); device frames' headers
     // come to the host through `hdr`
     psdc_loss loss{};
@@ -660,11 +661,11 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
     if (!map)
         return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null " + h->unit + " map");
     fed->clear();
+    const uint32_t w = h->map_w();
     for (uint32_t p = 0; p < h->n_pairs; ++p) {
         FedPair fp{};
         fp.pair = p;
         uint32_t none = 0, top = 0;
-        const uint32_t w = h->map_w();
         for (uint32_t c = 0; c < w; ++c) {
             fp.tr[c] = map[w * p + c];
             if (fp.tr[c] == PSDC_TRACE_NONE)
@@ -676,7 +677,7 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
             continue;
         if (none)
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) +
-                                              (h->m == 2 ? " names one trace and PSDC_TRACE_NONE"
+                                              (w == 2 ? " names one trace and PSDC_TRACE_NONE"
                                                          : " names PSDC_TRACE_NONE for some of its traces only"));
         if (top >= 4)
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) + " names trace " +
@@ -684,7 +685,7 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
         fed->push_back(fp);
     }
     if (h->zoom && fed->empty()) // (a pair object takes such a call for its Loss)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the map feeds no channel");
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the map feeds no " + h->unit);
     return PSDC_OK;
 }
 
@@ -697,7 +698,9 @@ struct FrameSrc {
 
 // decode frames [f, f + cnt) of src (format wf, `batches` a frame) into the stage-0 buffers at dst[m i + c] (pair fed[i], channel
 // c), one launch per 32 / m pairs, on the copy stream.  A zoom channel's two buffers are its I and Q streams: zoom_frames_kernel
-// decodes the channel's trace and mixes it with the channel's carrier, the first sample at stream index total + dst_off.
+// decodes the channel's trace and mixes it with the channel's carrier, the first sample at stream index total + dst_off.  A zoom
+// cross pair's four are I_a, Q_a, I_b, Q_b: zoom_cross_frames_kernel does the same for both sides of 8 pairs a launch, where
+// psdc_zcsd_process_device has its two mixers.
 int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
@@ -725,7 +728,25 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
         b->batches = batches;
         b->fmt = wf->id;
     };
-    if (h->zoom) {
+    if (h->zcross) {
+        for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_CROSS_FRAMES_MAX_PAIRS) {
+            ZoomCrossFramesBatch b{};
+            describe(&b);
+            for (size_t i = i0; i < std::min<size_t>(fed.size(), i0 + ZOOM_CROSS_FRAMES_MAX_PAIRS); ++i, ++b.npairs) {
+                const uint32_t p = fed[i].pair;
+                for (int side = 0; side < 2; ++side) {
+                    b.trace[b.npairs][side] = (int)fed[i].tr[side];
+                    b.ftw[b.npairs][side] = h->ftw[2 * (size_t)p + side];
+                    b.phase0[b.npairs][side] = h->phase0[2 * (size_t)p + side];
+                }
+                for (int c = 0; c < 4; ++c) // I_a, Q_a, I_b, Q_b: the order zoom_feed's mixers write them in
+                    b.dst[b.npairs][c] = dst[4 * i + c] + dst_off;
+                b.j0[b.npairs] = h->pairs[p][0].total + dst_off; // the stream index of both sides, as zoom_feed counts it
+            }
+            XCHK(h, launch_zoom_cross_frames(b, h->copy_stream));
+            ++h->launches;
+        }
+    } else if (h->zoom) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_FRAMES_MAX_CH) {
             ZoomFramesBatch b{};
             describe(&b);
@@ -1777,6 +1798,25 @@ int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_co
 int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
 {
     return stats_impl(h, launches, pairs_in, reset, "psdc_zcsd_stats_read");
+}
+
+// the frames calls of a zoom cross object (the prefix follows ZoomCsdCascade, as psdc_zoomcascade_ follows ZoomCascade)
+int psdc_zoomcsdcascade_process_frames(psdc_zcsd *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size,
+                                       size_t n_frames, size_t *n_ok)
+{
+    return frames_host_impl(h, pair_traces, frames, frame_size, n_frames, n_ok, "psdc_zoomcsdcascade_process_frames");
+}
+
+int psdc_zoomcsdcascade_process_frames_device(psdc_zcsd *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
+                                              size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, pair_traces, d_frames, frame_size, n_frames, n_ok, producer_event,
+                              "psdc_zoomcsdcascade_process_frames_device");
+}
+
+int psdc_zoomcsdcascade_loss_read(psdc_zcsd *h, psdc_loss *out, int reset)
+{
+    return loss_impl(h, out, reset, "psdc_zoomcsdcascade_loss_read");
 }
 
 const char *psdc_zcsd_last_error(const psdc_zcsd *h) { return h ? h->err.c_str() : x_last_error.c_str(); }

@@ -28,6 +28,15 @@ sixteen rows a segment pair --, leg B is ZoomCsdCascadeBank(n, 1) fed (a, b) -- 
 A / B / A in turn --reps times in one session, idle clocks and power before and after.  Also the tone-image figure of the cross
 row: a tone at f0 + delta on both channels, |S_ab lower| / |S_ab upper| at the tone's bin from B and rebuilt from A's sixteen rows.
 Writes profiles/zoom_cross_probe.json unless --out names another file.
+--zoom --pair --frames: stream frames into a zoom cross object.  AdcDac (128 batches a frame, the pair (ADC0, DAC0)) and Mpll (255
+batches, the pair (phase, frequency)) frames of 2^22 samples a trace a call, one piece each, at N = 512, 1024, 4096.  Leg A is the
+route tools/psd_cli.py --zoom-pair takes: every frame decoded on the host (source.decode_frame), both traces through
+psdc_zcsd_process from host memory.  Leg B is psdc_zoomcsdcascade_process_frames_device on the same frames resident in device
+memory with ONE carrier on both sides (the shared oscillator); leg B' is the same call with two different carriers (two
+oscillators a sample).  Leg C (a ceiling, not a gate) is psdc_zcsd_process_device on the pre-decoded f32 traces resident in device
+memory.  A, B, A, C, B' in turn --reps times in one session; B beats A when every B / A exceeds 1 + the largest |A' - A| / A.
+B / C and B / B' are recorded, not gated.  Clocks and power from rocm-smi (read only) before and after.  Writes
+profiles/zoom_cross_frames_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -447,6 +456,83 @@ def zoom_frames_legs(pkg, torch, seconds, reps):
     return legs
 
 
+def zoom_pair_frames_legs(pkg, torch, seconds, reps):
+    from test_gpu_payload_formats import make_frames, random_payloads  # the frame builders of the test suite
+    from stabilizer_stream_amd import source as src  # decode_frame: the host decode of Source
+    call = 1 << 22
+    rng = np.random.default_rng(7)
+    inputs = []
+    w = rng.integers(-20000, 20000, size=(4, call), dtype=np.int64).astype(np.int16)
+    data, fs = pkg.make_adcdac_frames(w, 128)
+    inputs.append(("AdcDac", data, fs, (0, 2)))
+    nf = call // 255  # whole frames of at most 2^22 samples: a call is one piece
+    data, fs = make_frames(4, 255, random_payloads(rng, 4, 255, nf, wild=False))
+    inputs.append(("Mpll", data, fs, (0, 1)))
+    legs = []
+    for name, data, fs, pair in inputs:
+        nf = len(data) // fs
+        frames = [data[k * fs:(k + 1) * fs] for k in range(nf)]
+
+        def host_decode():
+            tr = [src.decode_frame(f)[3] for f in frames]
+            return [np.concatenate([t[side][1] for t in tr]).astype(np.float32) for side in pair]
+
+        xa, xb = host_decode()
+        per_call = xa.size
+        d = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
+        dxa, dxb = torch.from_numpy(xa).cuda(), torch.from_numpy(xb).cuda()
+        torch.cuda.synchronize()
+        for n in (512, 1024, 4096):
+            za, zb, zc, z2 = (pkg.ZoomCsdCascadeBank(n, 1) for _ in range(4))
+            for z in (za, zb, zc):
+                z.set_carrier(0, f0=0.2)
+            z2.set_carrier(0, f0=0.2, side=0)
+            z2.set_carrier(0, f0=0.21, side=1)
+
+            def a_step():
+                za.process(0, *host_decode())
+                return per_call
+
+            def b_step():
+                zb.process_frames_device(d.data_ptr(), fs, nf, [pair])
+                return per_call
+
+            def b2_step():
+                z2.process_frames_device(d.data_ptr(), fs, nf, [pair])
+                return per_call
+
+            def c_step():
+                zc.process_device(0, dxa.data_ptr(), dxb.data_ptr(), per_call)
+                return per_call
+
+            a1, b, a2, c, b2 = [], [], [], [], []
+            for _ in range(reps):
+                a1.append(timed_calls(a_step, za.sync, 2) / 1e9)
+                b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+                a2.append(timed_calls(a_step, za.sync, 2) / 1e9)
+                c.append(timed(c_step, zc.sync, seconds)[0] / 1e9)
+                b2.append(timed(b2_step, z2.sync, seconds)[0] / 1e9)
+            zb.stats_read(reset=True)
+            for _ in range(8):
+                b_step()
+            launches = zb.stats_read()["launches"] / 8
+            zb.sync()
+            ba = [y / u for u, y in zip(a1, b)]
+            spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+            r3 = lambda v: [round(t, 4) for t in v]  # noqa: E731
+            legs.append({"format": name, "n": n, "pair": list(pair), "call_pairs": per_call, "frame_size": fs, "frames": nf,
+                         "a_host_decode_gpairs_s": r3(a1), "b_frames_device_one_carrier_gpairs_s": r3(b), "a_again_gpairs_s": r3(a2),
+                         "c_f32_device_gpairs_s": r3(c), "b2_frames_device_two_carriers_gpairs_s": r3(b2),
+                         "ratio_b_over_a": [round(r, 2) for r in ba], "ratio_b_over_a_min": round(min(ba), 2),
+                         "aa_spread_max": round(spread, 4), "b_beats_a": bool(min(ba) > 1 + spread),
+                         "ratio_b_over_c": [round(y / u, 3) for u, y in zip(c, b)],
+                         "ratio_b_over_b2": [round(y / u, 3) for u, y in zip(b2, b)], "b_launches_per_call": launches,
+                         "stages": zb.num_stages(0)})
+            for o in (za, zb, zc, z2):
+                o.close()
+    return legs
+
+
 def matrix_frames_legs(pkg, torch, seconds, reps):
     call = 1 << 22
     batches = 128
@@ -491,10 +577,26 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="with --matrix: turns of A, B, A")
     ap.add_argument("--zoom", action="store_true", help="ZoomCascadeBank fed x against CsdCascadeBank fed the pre-mixed (I, Q)")
     ap.add_argument("--pair", action="store_true", help="with --zoom: ZoomCsdCascadeBank fed (a, b) against CsmCascadeBank(n, 4) fed the "
-                                                        "pre-mixed (I_a, Q_a, I_b, Q_b)")
+                                                        "pre-mixed (I_a, Q_a, I_b, Q_b); with --zoom --frames: stream frames into a "
+                                                        "ZoomCsdCascadeBank against the host decode")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.zoom and a.pair and a.frames:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        before = gpu_state()
+        legs = zoom_pair_frames_legs(pkg, torch, a.seconds, a.reps)
+        line = json.dumps({"metric": "zoom_cross_frames_gpairs_s",
+                           "unit": "1e9 sample pairs a second (one sample of each of the two traces of a pair)",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "not measured here: frames in HOST memory (they go up through the object's 32 MB pinned staging slots "
+                                   "into a 32 MB device buffer), the dword-store path (every call here starts 16-byte aligned), banks "
+                                   "(more than one pair a launch)",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "zoom_cross_frames_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.zoom and a.frames:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         before = gpu_state()
