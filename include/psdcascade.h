@@ -869,6 +869,95 @@ int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_co
 int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset);
 const char *psdc_zcsd_last_error(const psdc_zcsd *h);
 
+/* ---- IQ cascade: complex baseband streams, with an optional retune ---------------------------------------------
+ * The zoom objects take a REAL stream and mix it to I + i Q themselves.  An IQ object takes streams that are complex already:
+ * the demodulated quadratures of an Fls payload (traces BI / BQ), the I/Q of a lock-in or SDR front end, a complex64 array.  It
+ * holds `n_channels` independent complex f32 streams z_j = I_j + i Q_j and keeps the two-sided spectrum of each.
+ * Carrier: every channel has one, a tuning word `ftw` and a start phase `phase0` (uint64_t, units of 2^-64 turn; default 0, 0),
+ * under the zoom object's rules: sample j of the channel's stream, counted from create or reset in 64 bits, has the phase
+ * phi_j = phase0 + ftw j mod 2^64, exact in integer arithmetic however the stream is cut into calls; a carrier may be set only
+ * while the channel has taken no sample since create or reset (else PSDC_ERR_ARG with a text); a reset puts every carrier back
+ * to the default.  With the default the object analyses z as it is; with a carrier it is a second-stage zoom: a coarse
+ * down-conversion elsewhere, the fine retune and the log-resolution spectrum here.
+ * Mixing: z'_j = z_j exp(-2 pi i phi_j / 2^64).  (c, s) are the f32 cosine and sine of the zoom object's oscillator
+ * (csrc/zoom_lo.h, unchanged), and the f32 operations are fixed (csrc/iq_lo.h):
+ *     I' = fmaf(Q, s,  I * c)
+ *     Q' = fmaf(Q, c, -(I * s))
+ * one stand-alone product and one explicit fused multiply-add each, the same bits on host and device.  Two consequences: with
+ * Q = 0 these are exactly the zoom mixer's x c and -(x s) -- an IQ channel fed (x, 0) is the zoom channel fed x, bit for bit;
+ * with ftw = phase0 = 0 they return (I, Q) unchanged for finite input (up to the sign of a zero).
+ * Stages, rows, read-out: everything behind the mixer is the zoom object's, bit for bit (see "zoom cascade" above):
+ * segmentation, Window<N>, Detrend applied to I' and Q' separately, /8 half-band decimation of each with the drain of 35
+ * outputs, lazy stages, the EWMA factor g and 64-bit counts; each segment is ONE N-point complex transform Z of I' + i Q' and
+ * a stage keeps the rows upper[k] = g upper[k] + |Z[k]|^2 and lower[k] = g lower[k] + |Z[(N - k) mod N]|^2, k = 0 ... N/2;
+ * the read-out is PsdCascade::psd on each row with the unchanged gain.  A channel has exactly the stages, counts, pendings and
+ * Breaks of a PsdCascade fed a real stream of the same length.
+ * Scale: under the unchanged gain complex white noise with E|z|^2 = 1 reads 2 in every bin of both rows.  row / 2 is the
+ * two-sided density of z: over the offsets (-0.5, 0.5] -- `lower` mirrored, then `upper` -- it integrates to E|z|^2.
+ * Sizes and windows are those of the zoom object: n a power of two 64 ... 4096; Window::hann(), Window::rectangular(), or a
+ * caller's table with (n - overlap) % 8 == 0.  Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere.  There is no CPU
+ * fallback.
+ * Sample routes: planar (two f32 streams, each 4-byte aligned) and interleaved ((re, im) pairs, 8-byte aligned: the memory of
+ * a complex64 array), each from host or from device memory, any length.  The complex mixer stands where the zoom object's
+ * mixer stands: on the side stream, behind a grown buffer and round R - 2, in front of round R; host samples go up through the
+ * pinned staging into a 32 MB device landing buffer first (made by the first host call), so host and device calls run the
+ * same launches.  A steady-state call is 1 + 3 kernel launches (mixer; segments, decimators, fold + tails) whatever the depth.
+ * All four sample routes and the frames route may be mixed on one channel: the stream index, and so the phase, continues
+ * across them, and the same calls give the same bits by every route.  Stream ordering, the caller-keeps-memory rule, errors,
+ * the device rule and what holds for a bank's channels against single objects are those of the zoom object.
+ * Memory: per (channel, stage) two ping-pong buffers for each of I and Q, plus 64 MB of pinned staging. */
+typedef struct psdc_iq psdc_iq;
+/* n_channels complex channels; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_iq *psdc_iq_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+/* the same with a caller-built Window<N> (src/psd.rs:12-20), as psdc_create_window */
+psdc_iq *psdc_iq_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                               int device);
+void psdc_iq_destroy(psdc_iq *h);
+/* back to the state of a fresh object: stages, buffers, settings, carriers and statistics */
+int psdc_iq_reset(psdc_iq *h);
+int psdc_iq_set_detrend(psdc_iq *h, int detrend_kind);
+int psdc_iq_set_avg(psdc_iq *h, uint32_t limit, uint32_t count);
+/* the channel's carrier (see Carrier above); PSDC_ERR_ARG once the channel has taken a sample */
+int psdc_iq_set_carrier(psdc_iq *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* len complex samples of a channel from host memory, planar: i[j] + i q[j] */
+int psdc_iq_process(psdc_iq *h, uint32_t channel, const float *i, const float *q, size_t len);
+/* the same from device memory (any 4-byte aligned addresses and any length); producer_event: hipEvent_t or NULL */
+int psdc_iq_process_device(psdc_iq *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event);
+/* len complex samples as (re, im) pairs, 2 len floats, 8-byte aligned, from host memory */
+int psdc_iq_process_interleaved(psdc_iq *h, uint32_t channel, const float *iq, size_t len);
+/* the same from device memory */
+int psdc_iq_process_interleaved_device(psdc_iq *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event);
+/* Stream frames into IQ channels (mirrors psdc_csd_process_frames).  The map has 2 n_channels entries: channel c takes trace
+ * channel_traces[2 c] of every frame as I and trace channel_traces[2 c + 1] as Q, in Payload::traces order (Fls: BI = 2,
+ * BQ = 3).  PSDC_TRACE_NONE in both entries: the channel is not fed by this call and its stream index does not move; in only one
+ * of them it is PSDC_ERR_ARG.  A trace may feed any number of channels and both sides of one.  The map belongs to the call.
+ * Map errors: PSDC_ERR_ARG without ingesting anything for a NULL map, a trace index >= 4, a channel with one PSDC_TRACE_NONE
+ * or a map that feeds no channel.  A run whose format carries fewer traces than the map names is PSDC_ERR_ARG at the run's
+ * first frame: the frames before it are ingested and *n_ok counts them.
+ * Frames: headers, runs of one format, de::Error codes, *n_ok, header-only frames (Loss only), the cut into pieces of whole
+ * frames of at most 2^22 samples a trace and Loss committed piece by piece are those of psdc_csd_process_frames, from the same
+ * scanner.  Each piece is ONE decode-and-mix launch per 16 fed channels (iq_frames_kernel: a cell is read and converted once,
+ * the two samples of every channel it feeds are mixed in registers and stored to the channel's I and Q streams; the f32
+ * traces never exist in memory) and then one round.  A one-piece call gives the same bits as the planar sample call fed
+ * Payload::traces of the same frames; host and device frames give the same bits; a steady-state one-piece call is 1 + 3
+ * launches, and the device call's header gather is a fifth that psdc_iq_stats_read counts. */
+int psdc_iq_process_frames(psdc_iq *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                           size_t *n_ok);
+int psdc_iq_process_frames_device(psdc_iq *h, const uint32_t *channel_traces, const uint8_t *d_frames, size_t frame_size,
+                                  size_t n_frames, size_t *n_ok, void *producer_event);
+/* the Loss counters of the frames the object ingested; reset != 0 zeroes them after reading */
+int psdc_iq_loss_read(psdc_iq *h, psdc_loss *out, int reset);
+int psdc_iq_sync(psdc_iq *h);
+int psdc_iq_num_stages(psdc_iq *h, uint32_t channel);
+/* raw accumulators of one stage: upper, lower n/2 + 1 floats each; any may be NULL */
+int psdc_iq_stage_spectra(psdc_iq *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower);
+/* PsdCascade::psd (src/psd.rs:479-543) of both rows: upper, lower `cap` floats each (either may be NULL) */
+int psdc_iq_psd(psdc_iq *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and complex samples accepted since creation or the last reset of the statistics */
+int psdc_iq_stats_read(psdc_iq *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_iq_last_error(const psdc_iq *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

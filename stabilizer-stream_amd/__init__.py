@@ -384,6 +384,26 @@ def lib():
     f("psdc_zcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_zcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_zcsd_last_error", C.c_char_p, [H])
+    f("psdc_iq_create", H, [u32, i32, u32, i32])
+    f("psdc_iq_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_iq_destroy", None, [H])
+    f("psdc_iq_reset", i32, [H])
+    f("psdc_iq_set_detrend", i32, [H, i32])
+    f("psdc_iq_set_avg", i32, [H, u32, u32])
+    f("psdc_iq_set_carrier", i32, [H, u32, u64, u64])
+    f("psdc_iq_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_iq_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_iq_process_interleaved", i32, [H, u32, fp, sz])
+    f("psdc_iq_process_interleaved_device", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
+    f("psdc_iq_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_iq_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_iq_loss_read", i32, [H, C.POINTER(_CLoss), i32])
+    f("psdc_iq_sync", i32, [H])
+    f("psdc_iq_num_stages", i32, [H, u32])
+    f("psdc_iq_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp])
+    f("psdc_iq_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_iq_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_iq_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -419,6 +439,10 @@ EXPORTS = [
     "psdc_zcsd_sync", "psdc_zcsd_num_stages", "psdc_zcsd_stage_spectra", "psdc_zcsd_csd", "psdc_zcsd_stats_read",
     "psdc_zcsd_last_error",
     "psdc_zoomcsdcascade_process_frames", "psdc_zoomcsdcascade_process_frames_device", "psdc_zoomcsdcascade_loss_read",
+    "psdc_iq_create", "psdc_iq_create_window", "psdc_iq_destroy", "psdc_iq_reset", "psdc_iq_set_detrend", "psdc_iq_set_avg",
+    "psdc_iq_set_carrier", "psdc_iq_process", "psdc_iq_process_device", "psdc_iq_process_interleaved",
+    "psdc_iq_process_interleaved_device", "psdc_iq_process_frames", "psdc_iq_process_frames_device", "psdc_iq_loss_read",
+    "psdc_iq_sync", "psdc_iq_num_stages", "psdc_iq_stage_spectra", "psdc_iq_psd", "psdc_iq_stats_read", "psdc_iq_last_error",
 ]
 
 
@@ -1313,6 +1337,251 @@ class ZoomCascade:
 
     def process_frames_device(self, ptr, frame_size, n_frames, trace, after=None):
         return self._b.process_frames_device(ptr, frame_size, n_frames, [trace], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
+
+    def psd(self, opts=MergeOpts()):
+        return self._b.psd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        self._b.reset()
+        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+def _raise_iq(code, h=None):
+    msg = lib().psdc_iq_last_error(h)
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
+
+
+def iq_map(pairs, n_channels):
+    """The map psdc_iq_process_frames[_device] take, from `pairs`: entry c is the (i_trace, q_trace) channel c takes -- indices or
+    TRACE_NAMES labels (trace_index, as channel_map resolves its traces), e.g. ("BI", "BQ") -- or None (channel c not fed);
+    channels past the end of the list are not fed.  A map that feeds no channel, a pair with one None, an index outside 0 ... 3
+    and an unknown label are ERR_ARG here, before the library sees the call."""
+    pairs = list(pairs)
+    if len(pairs) > n_channels:
+        raise PsdError(ERR_ARG, f"{len(pairs)} trace pairs for a bank of {n_channels}")
+    m = np.full(2 * n_channels, TRACE_NONE, np.uint32)
+    for c, pq in enumerate(pairs):
+        if pq is None:
+            continue
+        if not isinstance(pq, (tuple, list)) or len(pq) != 2 or pq[0] is None or pq[1] is None:
+            raise PsdError(ERR_ARG, f"channel {c} needs a pair (i_trace, q_trace)")
+        for side, t in enumerate(pq):
+            i = trace_index(t)
+            if not 0 <= i < 4:
+                raise PsdError(ERR_ARG, f"channel {c} names trace {i} (frames carry at most 4)")
+            m[2 * c + side] = i
+    if not np.any(m != TRACE_NONE):
+        raise PsdError(ERR_ARG, "the map feeds no channel")
+    return m
+
+
+class IqCascadeBank:
+    """`n_channels` independent IQ cascades (psdc_iq_*): each stream is complex already, z = I + i Q, and is turned by its own
+    carrier (default none: ftw = 0, phase0 = 0) in front of the zoom object's cascade.  Every stage keeps the two-sided |Z|^2 as
+    two rows, `upper` at offsets f >= 0 and `lower` at -f, scaled as PsdCascade::psd scales its one-sided spectrum: complex
+    white noise with E|z|^2 = 1 reads 2, and row / 2 is the two-sided density of z (two_sided() lays the rows out)."""
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_iq_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
+        else:
+            self._h = self._L.psdc_iq_create(n, int(window), n_channels, device)
+        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
+        if not self._h:
+            msg = self._L.psdc_iq_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_iq_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_iq(rc, self._h)
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        self._ck(self._L.psdc_iq_reset(self._h))
+        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_iq_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_iq_set_avg(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
+        """The channel's carrier, as f0 (cycles per sample, through zoom_ftw) or as the tuning word itself; phase0 in 2^-64
+        turn.  Only before the channel's first sample.  Returns the f0 actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        self._ck(self._L.psdc_iq_set_carrier(self._h, channel, ftw, phase0))
+        self.carriers[channel] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, channel, z):
+        """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
+        real arrays of one length (the planar route)."""
+        if isinstance(z, (tuple, list)):
+            if len(z) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
+            i = np.ascontiguousarray(z[0], dtype=np.float32)
+            q = np.ascontiguousarray(z[1], dtype=np.float32)
+            if i.ndim != 1 or i.shape != q.shape:
+                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
+            self._ck(self._L.psdc_iq_process(self._h, channel, _fptr(i), _fptr(q), i.size))
+            return
+        z = np.asarray(z)
+        if not np.iscomplexobj(z):
+            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
+        z = np.ascontiguousarray(z, dtype=np.complex64)
+        self._ck(self._L.psdc_iq_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); after: a hipEvent_t
+        handle recorded behind their producer, or None when it has completed.  The samples must stay unchanged until sync() or a
+        read-out returns."""
+        self._ck(self._L.psdc_iq_process_interleaved_device(self._h, channel, C.c_void_p(ptr), length,
+                                                            C.c_void_p(after) if after else None))
+
+    def process_device_planar(self, channel, pi, pq, length, after=None):
+        """pi, pq: device addresses of `length` f32 samples each, the I and the Q stream (process_device's rules)"""
+        self._ck(self._L.psdc_iq_process_device(self._h, channel, C.c_void_p(pi), C.c_void_p(pq), length,
+                                                C.c_void_p(after) if after else None))
+
+    def process_frames(self, data, frame_size, pairs):
+        """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the channels: pairs[c] is the
+        (i_trace, q_trace) channel c takes of every frame (indices or TRACE_NAMES labels, e.g. ("BI", "BQ")), None leaves it
+        unfed; a trace may feed several channels.  The frames are decoded and mixed on the device in one kernel.  Returns the
+        number of frames ingested; a bad frame raises FrameError after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = iq_map(pairs, self.n_channels)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_iq_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
+                                            frame_size, buf.size // frame_size, C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
+        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
+        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
+        m = iq_map(pairs, self.n_channels)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_iq_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr), frame_size,
+                                                   n_frames, C.byref(ok), C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(self._L.psdc_iq_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
+    def sync(self):
+        self._ck(self._L.psdc_iq_sync(self._h))
+
+    def num_stages(self, channel=0):
+        return self._ck(self._L.psdc_iq_num_stages(self._h, channel))
+
+    def stage_spectra(self, channel, stage):
+        """(info, upper, lower) of one stage's raw accumulators."""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        up, lo = np.empty(b, np.float32), np.empty(b, np.float32)
+        self._ck(self._L.psdc_iq_stage_spectra(self._h, channel, stage, C.byref(st), _fptr(up), _fptr(lo)))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, up, lo
+
+    def psd(self, channel=0, opts=MergeOpts()):
+        """(upper, lower, breaks): PsdCascade::psd of each row; Break.frequencies(breaks) are the offsets of both, and
+        two_sided(upper, lower, breaks) is the spectrum over (-0.5, 0.5]."""
+        ns = self.num_stages(channel)
+        cap = max(1, ns * (self.n // 2 + 1))
+        up, lo = np.empty(cap, np.float32), np.empty(cap, np.float32)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_iq_psd(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                     _fptr(up), _fptr(lo), cap, C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_iq_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+
+class IqCascade:
+    """One complex stream: IqCascade(n) analyses it as it is, IqCascade(n, f0=0.2) or IqCascade(n, ftw=...) retunes it first.
+    `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = IqCascadeBank(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0):
+        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
+        self.ftw, self.phase0 = self._b.carriers[0]
+        return self.f0
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, z):
+        """z: a complex array, or a pair (i, q) (IqCascadeBank.process)"""
+        self._b.process(0, z)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def process_device_planar(self, pi, pq, length, after=None):
+        self._b.process_device_planar(0, pi, pq, length, after)
+
+    def process_frames(self, data, frame_size, pair):
+        """pair: the (i_trace, q_trace) of the frames the stream is (IqCascadeBank.process_frames)"""
+        return self._b.process_frames(data, frame_size, [pair])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
 
     def loss(self, reset=False):
         return self._b.loss(reset)

@@ -5,7 +5,9 @@
 // csm_kernel<N, M> with m * m rows (csm_fft.h); a zoom object's unit is one real channel whose m = 2 streams are the I and Q the
 // mixer (zoom_mix_kernel, in place of the input copy) makes of it, on zoom_kernel with the rows upper, lower; a zoom cross
 // object's unit is two such channels, m = 4 streams (I_a, Q_a, I_b, Q_b), on zoom_cross_kernel with the eight rows of
-// zoom_cross_fft.h.  Below, "pair" stands for any of these units.
+// zoom_cross_fft.h; an IQ object (psdc_iq_*) is the zoom kind with a different feed: its unit is one COMPLEX channel whose I and Q
+// arrive from the caller and go through the complex mixer (iq_mix_kernel, iq_frames_kernel) into the same two streams.  Below, "pair"
+// stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -20,6 +22,7 @@
 // There is no CPU compute path.
 #include "csm.h"
 #include "zoom_cross.h"
+#include "iq.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -63,14 +66,18 @@ struct XObj {
     bool matrix = false; // psdc_csm: csm_kernel and its row layout
     bool zoom = false;   // psdc_zoom / psdc_zcsd: the streams are I and Q of mixed channels, fed through the mixer
     bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
+    bool iq = false;     // psdc_iq (with zoom): the channel's I and Q come from the caller, through the complex mixer
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
     uint32_t rows() const { return zcross ? 8 : zoom ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
-    uint32_t map_w() const { return zoom ? reals() : m; }
+    // (an IQ channel two: its I and its Q)
+    uint32_t map_w() const { return iq ? 2 : zoom ? reals() : m; }
+    // f32 streams of STAGING samples a pinned staging slot and the landing buffer hold: an IQ channel's I and Q, else reals()
+    uint32_t lanes() const { return iq ? 2 : reals(); }
     // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
     // channel's STAGING floats (16 MB), a zoom cross object's two (32 MB), the others' at least two
-    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? reals() : 2); }
+    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? lanes() : 2); }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -119,6 +126,7 @@ struct psdc_cross : XObj {};
 struct psdc_csm : XObj {};
 struct psdc_zoom : XObj {};
 struct psdc_zcsd : XObj {};
+struct psdc_iq : XObj {};
 
 namespace {
 
@@ -553,7 +561,8 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
 {
     constexpr bool matrix = std::is_same<T, psdc_csm>::value;
     constexpr bool zcross = std::is_same<T, psdc_zcsd>::value;
-    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross;
+    constexpr bool iq = std::is_same<T, psdc_iq>::value;
+    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
         return nullptr;
@@ -602,6 +611,10 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
             h->unit = "pair";
             h->units = "n_pairs";
         }
+        if (iq) {
+            h->iq = true;
+            h->tag = "psdc_iq";
+        }
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
     }
@@ -635,7 +648,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
               hipMemcpy(h->d_win, win, sizeof(float) * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(h->d_tw, tw.data(), sizeof(cf) * n, hipMemcpyHostToDevice) == hipSuccess;
     for (int i = 0; ok && i < 2; ++i)
-        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * h->reals() * STAGING) == hipSuccess &&
+        ok = hipHostMalloc(&h->h_stage[i], sizeof(float) * h->lanes() * STAGING) == hipSuccess &&
              hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": device allocation failed");
@@ -700,7 +713,7 @@ struct FrameSrc {
 // c), one launch per 32 / m pairs, on the copy stream.  A zoom channel's two buffers are its I and Q streams: zoom_frames_kernel
 // decodes the channel's trace and mixes it with the channel's carrier, the first sample at stream index total + dst_off.  A zoom
 // cross pair's four are I_a, Q_a, I_b, Q_b: zoom_cross_frames_kernel does the same for both sides of 8 pairs a launch, where
-// psdc_zcsd_process_device has its two mixers.
+// psdc_zcsd_process_device has its two mixers.  An IQ channel's two are its I and Q as well, made of two traces by iq_frames_kernel.
 int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
@@ -744,6 +757,23 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
                 b.j0[b.npairs] = h->pairs[p][0].total + dst_off; // the stream index of both sides, as zoom_feed counts it
             }
             XCHK(h, launch_zoom_cross_frames(b, h->copy_stream));
+            ++h->launches;
+        }
+    } else if (h->iq) {
+        for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_FRAMES_MAX_CH) {
+            IqFramesBatch b{};
+            describe(&b);
+            for (size_t i = i0; i < std::min<size_t>(fed.size(), i0 + ZOOM_FRAMES_MAX_CH); ++i, ++b.nch) {
+                const uint32_t ch = fed[i].pair;
+                b.trace_i[b.nch] = (int)fed[i].tr[0];
+                b.trace_q[b.nch] = (int)fed[i].tr[1];
+                b.dst_i[b.nch] = dst[2 * i] + dst_off;
+                b.dst_q[b.nch] = dst[2 * i + 1] + dst_off;
+                b.ftw[b.nch] = h->ftw[ch];
+                b.phase0[b.nch] = h->phase0[ch];
+                b.j0[b.nch] = h->pairs[ch][0].total + dst_off; // the stream index, as iq_feed counts it
+            }
+            XCHK(h, launch_iq_frames(b, h->copy_stream));
             ++h->launches;
         }
     } else if (h->zoom) {
@@ -1138,6 +1168,90 @@ int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev
     return run_round(h, &did);
 }
 
+// An IQ channel takes len complex samples: planar (src_q != NULL: two f32 streams, each 4-byte aligned) or interleaved (src_q ==
+// NULL: src_i points to (re, im) pairs, 8-byte aligned), from host memory (up through the pinned staging into the landing buffer)
+// or from device memory.  zoom_feed with the complex mixer in place of the real one: the same stream, the same events, and the
+// same launches on the same data from either memory, so all four routes give the same bits for the same calls.
+int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool interleaved, size_t len, bool dev, void *producer_event,
+            const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, ch);
+    if (rc)
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    if (!src_i || (!interleaved && !src_q))
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if (interleaved ? (uintptr_t)src_i % (2 * sizeof(float)) != 0
+                    : (uintptr_t)src_i % sizeof(float) != 0 || (uintptr_t)src_q % sizeof(float) != 0)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to 8 bytes"
+                                                                      : ": the samples are not aligned to 4 bytes"));
+    X_ON_DEVICE(h);
+    if (producer_event)
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    if (!dev && !h->d_land)
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * 2 * STAGING));
+    XStage *s = nullptr;
+    h->grew = false;
+    if ((rc = stage0_room(h, ch, len, &s)))
+        return rc;
+    if (h->grew) {
+        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+    }
+    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
+    if (h->round_recorded[rslot])
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
+    const size_t piece = dev ? len : STAGING;
+    for (size_t done = 0; done < len;) {
+        const size_t cnt = std::min(piece, len - done);
+        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
+            const int slot = h->stage_cur;
+            if (h->ev_pending[slot])
+                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+            float *stg = h->h_stage[slot];
+            if (interleaved) { // the pairs as they are: 2 cnt floats at the front of the slot and of the landing buffer
+                memcpy(stg, src_i + 2 * done, sizeof(float) * 2 * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land, stg, sizeof(float) * 2 * cnt, hipMemcpyHostToDevice, h->copy_stream));
+            } else {
+                memcpy(stg, src_i + done, sizeof(float) * cnt);
+                memcpy(stg + STAGING, src_q + done, sizeof(float) * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land, stg, sizeof(float) * cnt, hipMemcpyHostToDevice, h->copy_stream));
+                XCHK(h, hipMemcpyAsync(h->d_land + STAGING, stg + STAGING, sizeof(float) * cnt, hipMemcpyHostToDevice,
+                                       h->copy_stream));
+            }
+            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
+            h->ev_pending[slot] = true;
+            h->stage_cur ^= 1;
+        }
+        const size_t at = (size_t)(s->total + done - s->buf.base);
+        IqMixJob mj{};
+        if (interleaved) {
+            mj.src_i = dev ? src_i + 2 * done : h->d_land;
+        } else {
+            mj.src_i = dev ? src_i + done : h->d_land;
+            mj.src_q = dev ? src_q + done : h->d_land + STAGING;
+        }
+        mj.dst_i = s->buf.p[0][s->buf.cur] + at;
+        mj.dst_q = s->buf.p[1][s->buf.cur] + at;
+        mj.len = cnt;
+        mj.j0 = s->total + done; // the stream index: complex samples the channel has taken since create or reset
+        mj.ftw = h->ftw[ch];
+        mj.phase0 = h->phase0[ch];
+        XCHK(h, launch_iq_mix(mj, interleaved, h->copy_stream));
+        ++h->launches;
+        done += cnt;
+    }
+    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+    s->total += len;
+    h->pairs_in += len;
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
 int sync_impl(XObj *h, const char *who)
 {
     X_HANDLE(h, who);
@@ -1323,6 +1437,59 @@ int frames_device_impl(XObj *h, const uint32_t *map, const uint8_t *d_frames, si
     src.dev = d_frames;
     src.hdr = {h->hdr.h_hdr, 8};
     return ingest_frames(h, fed, src, frame_size, n_frames, &good, who);
+}
+
+// the carrier of a channel of a one-channel-a-unit object (psdc_zoom, psdc_iq)
+int set_carrier_impl(XObj *h, uint32_t channel, uint64_t ftw, uint64_t phase0, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    const auto &st = h->pairs[channel];
+    if (!st.empty() && st[0].total)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": channel " + std::to_string(channel) + " has taken " +
+                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
+    h->ftw[channel] = ftw;
+    h->phase0[channel] = phase0;
+    return PSDC_OK;
+}
+
+// the two rows of one stage / the stitched two rows of a channel (psdc_zoom, psdc_iq)
+int two_rows_stage_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower, const char *who)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, channel, stage, stat, upper || lower ? &acc : nullptr, who);
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    for (size_t k = 0; k < b; ++k) {
+        if (upper)
+            upper[k] = (float)acc[k];
+        if (lower)
+            lower[k] = (float)acc[b + k];
+    }
+    return PSDC_OK;
+}
+
+int two_rows_psd_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                      float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, channel, &in)))
+        return rc;
+    float *outs[2] = {upper, lower};
+    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                          in.rows.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap,
+                          n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    return PSDC_OK;
 }
 
 int loss_impl(XObj *h, psdc_loss *out, int reset, const char *who)
@@ -1600,17 +1767,7 @@ int psdc_zoom_set_avg(psdc_zoom *h, uint32_t limit, uint32_t count) { return set
 
 int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
 {
-    X_HANDLE(h, "psdc_zoom_set_carrier");
-    int rc = check_pair(h, channel);
-    if (rc)
-        return rc;
-    const auto &st = h->pairs[channel];
-    if (!st.empty() && st[0].total)
-        return xfail(h, PSDC_ERR_ARG, "psdc_zoom_set_carrier: channel " + std::to_string(channel) + " has taken " +
-                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
-    h->ftw[channel] = ftw;
-    h->phase0[channel] = phase0;
-    return PSDC_OK;
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_zoom_set_carrier");
 }
 
 int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len)
@@ -1642,38 +1799,14 @@ int psdc_zoom_num_stages(psdc_zoom *h, uint32_t channel) { return num_stages_imp
 
 int psdc_zoom_stage_spectra(psdc_zoom *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, channel, stage, stat, upper || lower ? &acc : nullptr, "psdc_zoom_stage_spectra");
-    if (rc || acc.empty())
-        return rc;
-    const size_t b = bins(h);
-    for (size_t k = 0; k < b; ++k) {
-        if (upper)
-            upper[k] = (float)acc[k];
-        if (lower)
-            lower[k] = (float)acc[b + k];
-    }
-    return PSDC_OK;
+    return two_rows_stage_impl(h, channel, stage, stat, upper, lower, "psdc_zoom_stage_spectra");
 }
 
 int psdc_zoom_psd(psdc_zoom *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
                   float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    X_HANDLE(h, "psdc_zoom_psd");
-    int rc = check_pair(h, channel);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, channel, &in)))
-        return rc;
-    float *outs[2] = {upper, lower};
-    rc = stitch_rows_impl("psdc_zoom_psd", h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(),
-                          in.pend.data(), in.rows.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks,
-                          breaks_cap, n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    return PSDC_OK;
+    return two_rows_psd_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, cap, len, breaks, breaks_cap,
+                             n_breaks, "psdc_zoom_psd");
 }
 
 int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -1682,6 +1815,92 @@ int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in,
 }
 
 const char *psdc_zoom_last_error(const psdc_zoom *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- IQ: one complex channel a unit, its I and Q through the complex mixer in front of stage 0; everything behind is the zoom
+// object's (zoom_kernel, rows upper, lower) ----
+
+psdc_iq *psdc_iq_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_iq>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iq_create_window");
+}
+
+psdc_iq *psdc_iq_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_iq>(n, window_kind, 2, n_channels, device, "psdc_iq_create");
+}
+
+void psdc_iq_destroy(psdc_iq *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_iq_reset(psdc_iq *h) { return reset_impl(h, "psdc_iq_reset"); }
+int psdc_iq_set_detrend(psdc_iq *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iq_set_detrend"); }
+int psdc_iq_set_avg(psdc_iq *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iq_set_avg"); }
+
+int psdc_iq_set_carrier(psdc_iq *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_iq_set_carrier");
+}
+
+int psdc_iq_process(psdc_iq *h, uint32_t channel, const float *i, const float *q, size_t len)
+{
+    return iq_feed(h, channel, i, q, false, len, false, nullptr, "psdc_iq_process");
+}
+
+int psdc_iq_process_device(psdc_iq *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_i, d_q, false, len, true, producer_event, "psdc_iq_process_device");
+}
+
+int psdc_iq_process_interleaved(psdc_iq *h, uint32_t channel, const float *iq, size_t len)
+{
+    return iq_feed(h, channel, iq, nullptr, true, len, false, nullptr, "psdc_iq_process_interleaved");
+}
+
+int psdc_iq_process_interleaved_device(psdc_iq *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_iq, nullptr, true, len, true, producer_event, "psdc_iq_process_interleaved_device");
+}
+
+int psdc_iq_process_frames(psdc_iq *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                           size_t *n_ok)
+{
+    return frames_host_impl(h, channel_traces, frames, frame_size, n_frames, n_ok, "psdc_iq_process_frames");
+}
+
+int psdc_iq_process_frames_device(psdc_iq *h, const uint32_t *channel_traces, const uint8_t *d_frames, size_t frame_size,
+                                  size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, channel_traces, d_frames, frame_size, n_frames, n_ok, producer_event,
+                              "psdc_iq_process_frames_device");
+}
+
+int psdc_iq_loss_read(psdc_iq *h, psdc_loss *out, int reset) { return loss_impl(h, out, reset, "psdc_iq_loss_read"); }
+int psdc_iq_sync(psdc_iq *h) { return sync_impl(h, "psdc_iq_sync"); }
+int psdc_iq_num_stages(psdc_iq *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_iq_num_stages"); }
+
+int psdc_iq_stage_spectra(psdc_iq *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower)
+{
+    return two_rows_stage_impl(h, channel, stage, stat, upper, lower, "psdc_iq_stage_spectra");
+}
+
+int psdc_iq_psd(psdc_iq *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return two_rows_psd_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, cap, len, breaks, breaks_cap,
+                             n_breaks, "psdc_iq_psd");
+}
+
+int psdc_iq_stats_read(psdc_iq *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_iq_stats_read");
+}
+
+const char *psdc_iq_last_error(const psdc_iq *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 // ---- zoom cross: two real channels a unit, each mixed to I and Q in front of stage 0; zoom_cross_kernel, the eight rows of
 // zoom_cross_fft.h ----

@@ -37,6 +37,11 @@ oscillators a sample).  Leg C (a ceiling, not a gate) is psdc_zcsd_process_devic
 memory.  A, B, A, C, B' in turn --reps times in one session; B beats A when every B / A exceeds 1 + the largest |A' - A| / A.
 B / C and B / B' are recorded, not gated.  Clocks and power from rocm-smi (read only) before and after.  Writes
 profiles/zoom_cross_frames_probe.json unless --out names another file.
+--iq: a complex stream that is complex already.  One device-resident complex64 stream of 2^24 samples a call at N = 512, 1024, 4096.
+Leg A (a ceiling: the same round, 4 bytes a sample read instead of 8) is ZoomCascadeBank(n, 1) fed a real stream; leg B is
+IqCascadeBank(n, 1) fed the interleaved complex64; leg C is what a user did before: CsdCascadeBank(n, 1) fed the planar (I, Q).
+A, B, A, C in turn --reps times in one session; B / A, B / C and the largest |A' - A| / A are recorded as findings, none is a gate.
+Clocks and power from rocm-smi (read only) before and after.  Writes profiles/iq_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -271,6 +276,58 @@ def zoom_legs(pkg, torch, seconds, reps, call):
                      "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": zb.num_stages(0)})
         pa.close()
         zb.close()
+    return legs
+
+
+def iq_legs(pkg, torch, seconds, reps, call):
+    """One device-resident complex64 stream z, its planar copies (I, Q) and a real stream x.  A: ZoomCascadeBank fed x (carrier
+    0.2); B: IqCascadeBank fed z interleaved (carrier 0.2); C: CsdCascadeBank fed (I, Q).  A / B / A / C in turn."""
+    x = torch.randn(call, device="cuda")
+    z = torch.randn(call, dtype=torch.complex64, device="cuda")
+    zi, zq = z.real.contiguous(), z.imag.contiguous()
+    torch.cuda.synchronize()
+    legs = []
+    for n in (512, 1024, 4096):
+        za = pkg.ZoomCascadeBank(n, 1)
+        za.set_carrier(0, f0=0.2)
+        qb = pkg.IqCascadeBank(n, 1)
+        qb.set_carrier(0, f0=0.2)
+        pc = pkg.CsdCascadeBank(n, 1)
+
+        def a_step():
+            za.process_device(0, x.data_ptr(), call)
+            return call
+
+        def b_step():
+            qb.process_device(0, z.data_ptr(), call)
+            return call
+
+        def c_step():
+            pc.process_device(0, zi.data_ptr(), zq.data_ptr(), call)
+            return call
+
+        a1, b, a2, c = [], [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, qb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+            c.append(timed(c_step, pc.sync, seconds)[0] / 1e9)
+        qb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = qb.stats_read()["launches"] / 8
+        qb.sync()
+        ba = [v / u for u, v in zip(a1, b)]
+        bc = [v / u for u, v in zip(c, b)]
+        spread = max(abs(v - u) / u for u, v in zip(a1, a2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "call": call, "a_zoom_real_gs_s": r3(a1), "b_iq_interleaved_gs_s": r3(b), "a_again_gs_s": r3(a2),
+                     "c_pair_fed_iq_gs_s": r3(c), "ratio_b_over_a": r3(ba), "ratio_b_over_c": r3(bc),
+                     "b_over_a_min": round(min(ba), 3), "b_over_c_min": round(min(bc), 3), "aa_spread_max": round(spread, 4),
+                     "b_launches_per_call": launches, "stages": qb.num_stages(0)})
+        za.close()
+        qb.close()
+        pc.close()
     return legs
 
 
@@ -579,9 +636,23 @@ def main():
     ap.add_argument("--pair", action="store_true", help="with --zoom: ZoomCsdCascadeBank fed (a, b) against CsmCascadeBank(n, 4) fed the "
                                                         "pre-mixed (I_a, Q_a, I_b, Q_b); with --zoom --frames: stream frames into a "
                                                         "ZoomCsdCascadeBank against the host decode")
+    ap.add_argument("--iq", action="store_true", help="IqCascadeBank fed complex64 against ZoomCascadeBank fed a real stream (a ceiling) "
+                                                      "and CsdCascadeBank fed the planar (I, Q)")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.iq:
+        before = gpu_state()
+        legs = iq_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)
+        line = json.dumps({"metric": "iq_gsamples_s", "unit": "1e9 samples a second of one stream (complex for B and C, real for A)",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "findings, no gate: A reads 4 bytes a sample where B reads 8; not measured here: the planar route, host "
+                                   "memory, frames, banks",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "iq_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.zoom and a.pair and a.frames:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         before = gpu_state()

@@ -12,7 +12,11 @@ ZoomCascade(512) around the carrier F0 and prints, or with --csv writes to DIR/z
 (the offset from the carrier in units of fs; upper / lower the density at F0 + offset / F0 - offset).
 --zoom-pair F0:X:Y (repeatable; X, Y trace labels or indices) feeds the traces X and Y to a ZoomCsdCascade(512) with the carrier F0 on
 both sides and prints, or with --csv writes to DIR/zoompair_<x>__<y>_<F0>.csv, the lines
-offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b."""
+offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b.
+--iq I:Q[:F0] (repeatable) feeds a complex stream I + i Q to an IqCascade(512), retuned by F0 (cycles per sample, default 0: as it
+is).  With --file, I and Q are traces of the frames (labels or indices, e.g. BI:BQ); without it they are two raw f32 files of equal
+length (the planar pair; no --file / --raw is needed then).  Prints, or with --csv writes to DIR/iq_<i>__<q>_<F0>.csv, the lines
+offset,upper,lower (the density of z at F0 + offset / F0 - offset; half of it is the two-sided density)."""
 import argparse
 import os
 import sys
@@ -45,12 +49,21 @@ def main(argv=None):
     ap.add_argument("--zoom", action="append", default=[], help="F0[:TRACE] -- two-sided spectrum around the carrier F0 (repeatable)")
     ap.add_argument("--zoom-pair", action="append", default=[],
                     help="F0:X:Y -- two-sided auto and cross spectra of traces X and Y around the carrier F0 (repeatable)")
+    ap.add_argument("--iq", action="append", default=[],
+                    help="I:Q[:F0] -- two-sided spectrum of the complex stream I + i Q, retuned by F0 (repeatable)")
     a = ap.parse_args(argv)
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
+    if a.iq and not a.file:  # the planar raw pair: the only input this option needs
+        merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
+        if a.csv:
+            os.makedirs(a.csv, exist_ok=True)
+        iq_streams(pkg, source, a, merge, None)
+        if not a.raw:
+            return 0
     integral_start, integral_end = a.integral_start * a.fs, a.integral_end * a.fs  # src/bin/psd.rs:161-162
     src = source.Source(source.SourceOpts(file=a.file, frame_size=a.frame_size, repeat=a.repeat, raw=a.raw), pkg)
     if a.raw:
@@ -93,6 +106,8 @@ def main(argv=None):
         zoom_traces(pkg, source, a, merge, names)
     if a.zoom_pair:
         zoom_pairs(pkg, source, a, merge, names)
+    if a.iq and a.file:
+        iq_streams(pkg, source, a, merge, names)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
@@ -235,6 +250,53 @@ def zoom_pairs(pkg, source, a, merge, names):
                  for o, p, q, u, r, t, w in zip(off, aup, bup, xup, alo, blo, xlo)]
         if a.csv:
             safe = "".join(ch if ch.isalnum() else "_" for ch in f"zoompair_{names[x]}__{names[y]}_{used[i]:.9g}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+    bank.close()
+
+
+def iq_streams(pkg, source, a, merge, names):
+    """--iq: two traces of every read (host_traces), or two raw f32 files (names None), into one IQ cascade per stream"""
+    want = []
+    for z in a.iq:
+        parts = z.split(":")
+        if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
+            raise SystemExit("--iq takes I:Q[:F0]")
+        want.append((parts[0], parts[1], float(parts[2]) if len(parts) == 3 else 0.0))
+    bank = pkg.IqCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (_, _, f0) in enumerate(want)]
+    if names is None:
+        labels = [(os.path.basename(i), os.path.basename(q)) for i, q, _ in want]
+        for c, (pi, pq, _) in enumerate(want):
+            if os.path.getsize(pi) != os.path.getsize(pq):
+                raise SystemExit(f"--iq: {pi} and {pq} differ in length")
+            with open(pi, "rb") as fi, open(pq, "rb") as fq:
+                fed = 0
+                while a.max_bytes is None or fed < a.max_bytes:
+                    xi, xq = np.fromfile(fi, "<f4", 1 << 20), np.fromfile(fq, "<f4", 1 << 20)
+                    if xi.size == 0:
+                        break
+                    bank.process(c, (xi, xq))
+                    fed += xi.nbytes
+    else:
+        idx = [(trace_arg(i, names, "--iq"), trace_arg(q, names, "--iq")) for i, q, _ in want]
+        labels = [(names[i], names[q]) for i, q in idx]
+        host_traces(source, pkg, a, idx, lambda c, xs: bank.process(c, (xs[0], xs[1])))
+    for c, (li, lq) in enumerate(labels):
+        label = f"iq {li}:{lq} @ {used[c]:.12g}"
+        if bank.num_stages(c) == 0:
+            print(f"{label}: no samples")
+            continue
+        up, lo, breaks = bank.psd(c, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        print(f"{label}: stages {bank.num_stages(c)} bins {up.size} breaks {len(breaks)}")
+        lines = [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"iq_{li}__{lq}_{used[c]:.9g}")
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(lines)
         else:
