@@ -958,6 +958,101 @@ int psdc_iq_psd(psdc_iq *h, uint32_t channel, int keep_overlap, uint32_t min_cou
 int psdc_iq_stats_read(psdc_iq *h, uint64_t *launches, uint64_t *samples_in, int reset);
 const char *psdc_iq_last_error(const psdc_iq *h);
 
+/* ---- IQ cross cascade: two complex baseband streams, one transform each ------------------------------------------
+ * The cross spectrum of two streams that are complex already: two lock-ins or two SDR front ends on one source (their own
+ * noise averages out of S_ab, the source's stays), a second-stage zoom on both outputs of a coarse down-conversion done
+ * elsewhere, or -- by the zoom cross section's +-ftw recipe with the SAME complex stream on both sides -- the AM / PM
+ * separation of a stream that arrives as I/Q.  An IQ cross object holds `n_pairs` independent pairs.  A pair is two complex
+ * f32 streams a = I_a + i Q_a and b = I_b + i Q_b, always fed together with equal lengths.
+ * Carrier: each side has one, a tuning word and start phase under the zoom cross object's rule (psdc_zcsd_set_carrier): units
+ * of 2^-64 turn, default 0, 0; sample j of the pair's stream, counted from create or reset in 64 bits, has the phase
+ * phase0 + ftw j mod 2^64 of its side, exact in integers however the stream is cut into calls and by whichever route it came;
+ * a carrier may be set only while the pair has taken no sample, by any route, since create or reset (else PSDC_ERR_ARG); a
+ * reset puts both back to the default.
+ * Mixing: each side is turned by csrc/iq_lo.h's fixed formula, unchanged: I' = fmaf(Q, s, I * c), Q' = fmaf(Q, c, -(I * s))
+ * with the (c, s) of csrc/zoom_lo.h at the side's phase.  Where both sides have the same ftw AND the same phase0 the
+ * oscillator is evaluated once a sample and used for both, with the bits of two evaluations; equal ftw with different phase0,
+ * and the +-ftw recipe, are two oscillators.  With Q_a = Q_b = 0 the four mixed streams are the zoom cross object's of (I_a,
+ * I_b), bit for bit (up to the sign of a zero).
+ * Everything behind the mixer is the zoom cross object's, bit for bit (see "zoom cross cascade" above): the four streams in
+ * lockstep, segmentation, Window<N>, Detrend of each separately, the /8 decimators with the drain of 35 outputs, lazy stages,
+ * the EWMA factor g and 64-bit counts; ONE N-point complex transform a side and segment; the eight f64 rows S_aa, S_bb,
+ * Re S_ab, Im S_ab, `upper` and `lower` of each, in that section's layout; the sign S_ab = conj(Z_a) Z_b; lower[k] the value AT
+ * bin N - k, not conjugated; the read-out PsdCascade::psd on each row with the unchanged gain; the sizes 64 ... 4096
+ * (psdc_iqcsd_supported equals psdc_zcsd_supported); the windows; Detrend::Linear PSDC_ERR_UNIMPLEMENTED.  There is no CPU
+ * fallback.  Rows 0 ... 3 are the rows of two psdc_iq channels fed the sides with the same carriers (within the chunking bound:
+ * the partial sums are ordered differently).
+ * Sample routes: planar (four f32 streams I_a, Q_a, I_b, Q_b, each 4-byte aligned) and interleaved (the (re, im) pairs of each
+ * side, 8-byte aligned: two complex64 arrays), each from host or from device memory, any length; the contracts are those of the
+ * psdc_iq_process calls, per side.  ONE pair mixer launch (iq_pair_mix_kernel) turns both sides, where the zoom cross object
+ * runs a mixer a side: on the side stream, behind a grown buffer and round R - 2, in front of round R.  Host samples go up
+ * through the pinned staging into a 64 MB device landing buffer first (four streams of 2^22 samples, made by the first host
+ * call), so host and device calls run the same launches.  A steady-state call on one pair is 1 + 3 kernel launches whatever
+ * the depth (PSDC_IQCSD_STEADY_LAUNCHES: pair mixer; segments, decimators, fold + tails).
+ * All four sample routes and the frames route may be mixed on one pair: the stream index, and so both phases, continues across
+ * them, and the same calls give the same bits by every route.  Stream ordering, the caller-keeps-memory rule, errors, the
+ * device rule, determinism and the bank rule are those of the zoom cross object.
+ * Memory: per (pair, stage) two ping-pong buffers for each of the four streams, plus 128 MB of pinned staging. */
+#define PSDC_IQCSD_STEADY_LAUNCHES 4
+typedef struct psdc_iqcsd psdc_iqcsd;
+/* 1 if an object of size n can be created, else 0.  Pure host code. */
+int psdc_iqcsd_supported(uint32_t n);
+/* n_pairs pairs; window_kind PSDC_WINDOW_HANN / _RECTANGULAR */
+psdc_iqcsd *psdc_iqcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device);
+/* the same with a caller-built Window<N> (src/psd.rs:12-20), as psdc_create_window */
+psdc_iqcsd *psdc_iqcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                     int device);
+void psdc_iqcsd_destroy(psdc_iqcsd *h);
+/* back to the state of a fresh object: stages, buffers, settings, carriers and statistics */
+int psdc_iqcsd_reset(psdc_iqcsd *h);
+int psdc_iqcsd_set_detrend(psdc_iqcsd *h, int detrend_kind);
+int psdc_iqcsd_set_avg(psdc_iqcsd *h, uint32_t limit, uint32_t count);
+/* the carrier of one side of a pair (side 0: stream a, 1: stream b); PSDC_ERR_ARG once the pair has taken a sample */
+int psdc_iqcsd_set_carrier(psdc_iqcsd *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0);
+/* len complex samples of each side from host memory, planar: ia[j] + i qa[j] and ib[j] + i qb[j] */
+int psdc_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const float *ia, const float *qa, const float *ib, const float *qb,
+                       size_t len);
+/* the same from device memory (any 4-byte aligned addresses and any length); producer_event: hipEvent_t or NULL */
+int psdc_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const float *d_ia, const float *d_qa, const float *d_ib,
+                              const float *d_qb, size_t len, void *producer_event);
+/* len complex samples of each side as (re, im) pairs, 2 len floats a side, 8-byte aligned, from host memory */
+int psdc_iqcsd_process_interleaved(psdc_iqcsd *h, uint32_t pair, const float *za, const float *zb, size_t len);
+/* the same from device memory */
+int psdc_iqcsd_process_interleaved_device(psdc_iqcsd *h, uint32_t pair, const float *d_za, const float *d_zb, size_t len,
+                                          void *producer_event);
+/* Stream frames into IQ cross pairs (mirrors psdc_zoomcsdcascade_process_frames).  The map has 4 n_pairs entries: pair p takes
+ * the traces pair_traces[4 p ... 4 p + 3] of every frame as I_a, Q_a, I_b, Q_b, in Payload::traces order (Fls: BI = 2, BQ = 3).
+ * All four entries PSDC_TRACE_NONE: the pair is not fed by this call and its stream index does not move; one to three of them
+ * is PSDC_ERR_ARG.  A trace may feed any number of sides and entries.  The map belongs to the call and is not stored.
+ * Every other map, format, cut, Loss and *n_ok rule is that call's: PSDC_ERR_ARG without ingesting anything for a NULL map, a
+ * trace index >= 4 or a map that feeds no pair; a run whose format carries fewer traces than the map names is PSDC_ERR_ARG at
+ * the run's first frame, the frames before it ingested and counted in *n_ok; pieces of whole frames of at most 2^22 samples a
+ * trace, cut by the headers alone; Loss committed piece by piece; one psdc_loss an object, zeroed by a reset.
+ * Each piece is ONE decode-and-mix launch per 8 fed pairs (iq_cross_frames_kernel: a cell is read and converted once, handed to
+ * every entry of every pair that takes it, each side turned in registers and stored to its I and Q streams; the f32 traces never
+ * exist in memory) and then one round.  A one-piece call gives the same bits as the planar sample call fed Payload::traces of
+ * the same frames; host and device frames give the same bits; a steady-state one-piece call that feeds up to 8 pairs is 1 + 3
+ * launches, and the device call's header gather is a fifth that psdc_iqcsd_stats_read counts.  Host frames go up through the
+ * pinned staging into a 64 MB device buffer made by the first host-frames call. */
+int psdc_iqcsd_process_frames(psdc_iqcsd *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size,
+                              size_t n_frames, size_t *n_ok);
+int psdc_iqcsd_process_frames_device(psdc_iqcsd *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
+                                     size_t n_frames, size_t *n_ok, void *producer_event);
+/* the Loss counters of the frames the object ingested; reset != 0 zeroes them after reading */
+int psdc_iqcsd_loss_read(psdc_iqcsd *h, psdc_loss *out, int reset);
+int psdc_iqcsd_sync(psdc_iqcsd *h);
+int psdc_iqcsd_num_stages(psdc_iqcsd *h, uint32_t pair);
+/* raw accumulators of one stage: rows 8 (n/2 + 1) floats in the zoom cross object's row layout; stat and rows may be NULL */
+int psdc_iqcsd_stage_spectra(psdc_iqcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows);
+/* PsdCascade::psd of every row, with the arguments of psdc_zcsd_csd: the auto rows `cap` floats each, sab_upper and sab_lower
+ * 2 cap floats (re, im); any may be NULL */
+int psdc_iqcsd_csd(psdc_iqcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                   float *saa_upper, float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper,
+                   float *sab_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and complex sample pairs accepted since creation or the last reset of the statistics */
+int psdc_iqcsd_stats_read(psdc_iqcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset);
+const char *psdc_iqcsd_last_error(const psdc_iqcsd *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -404,6 +404,27 @@ def lib():
     f("psdc_iq_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_iq_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_iq_last_error", C.c_char_p, [H])
+    f("psdc_iqcsd_supported", i32, [u32])
+    f("psdc_iqcsd_create", H, [u32, i32, u32, i32])
+    f("psdc_iqcsd_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_iqcsd_destroy", None, [H])
+    f("psdc_iqcsd_reset", i32, [H])
+    f("psdc_iqcsd_set_detrend", i32, [H, i32])
+    f("psdc_iqcsd_set_avg", i32, [H, u32, u32])
+    f("psdc_iqcsd_set_carrier", i32, [H, u32, u32, u64, u64])
+    f("psdc_iqcsd_process", i32, [H, u32, fp, fp, fp, fp, sz])
+    f("psdc_iqcsd_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_iqcsd_process_interleaved", i32, [H, u32, fp, fp, sz])
+    f("psdc_iqcsd_process_interleaved_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    f("psdc_iqcsd_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
+    f("psdc_iqcsd_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
+    f("psdc_iqcsd_loss_read", i32, [H, C.POINTER(_CLoss), i32])
+    f("psdc_iqcsd_sync", i32, [H])
+    f("psdc_iqcsd_num_stages", i32, [H, u32])
+    f("psdc_iqcsd_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
+    f("psdc_iqcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_iqcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_iqcsd_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -443,6 +464,11 @@ EXPORTS = [
     "psdc_iq_set_carrier", "psdc_iq_process", "psdc_iq_process_device", "psdc_iq_process_interleaved",
     "psdc_iq_process_interleaved_device", "psdc_iq_process_frames", "psdc_iq_process_frames_device", "psdc_iq_loss_read",
     "psdc_iq_sync", "psdc_iq_num_stages", "psdc_iq_stage_spectra", "psdc_iq_psd", "psdc_iq_stats_read", "psdc_iq_last_error",
+    "psdc_iqcsd_supported", "psdc_iqcsd_create", "psdc_iqcsd_create_window", "psdc_iqcsd_destroy", "psdc_iqcsd_reset",
+    "psdc_iqcsd_set_detrend", "psdc_iqcsd_set_avg", "psdc_iqcsd_set_carrier", "psdc_iqcsd_process", "psdc_iqcsd_process_device",
+    "psdc_iqcsd_process_interleaved", "psdc_iqcsd_process_interleaved_device", "psdc_iqcsd_process_frames",
+    "psdc_iqcsd_process_frames_device", "psdc_iqcsd_loss_read", "psdc_iqcsd_sync", "psdc_iqcsd_num_stages",
+    "psdc_iqcsd_stage_spectra", "psdc_iqcsd_csd", "psdc_iqcsd_stats_read", "psdc_iqcsd_last_error",
 ]
 
 
@@ -1828,6 +1854,289 @@ class ZoomCsdCascade:
 
     def stats_read(self, reset=False):
         return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+IQCSD_STEADY_LAUNCHES = 4  # PSDC_IQCSD_STEADY_LAUNCHES: pair mixer; segments, decimators, fold + tails
+
+
+def iqcsd_supported(n):
+    """True if an IqCsdCascadeBank of size n can be created (psdc_iqcsd_supported: the zoom cross object's sizes).  Needs no GPU."""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_iqcsd_supported(n))
+
+
+def _raise_iqcsd(code, h=None):
+    msg = lib().psdc_iqcsd_last_error(h)
+    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+    raise cls(code, msg.decode() if msg else "")
+
+
+def iq_pair_map(pairs, n_pairs):
+    """The map psdc_iqcsd_process_frames[_device] take, from `pairs`: entry p is ((ia, qa), (ib, qb)), the traces the two sides of
+    pair p take as I and Q -- indices or TRACE_NAMES labels (trace_index), e.g. (("BI", "BQ"), ("AR", "AP")) --, or None, or a
+    pair whose four entries are all None (pair p not fed); pairs past the end of the list are not fed.  A map that feeds no pair,
+    a pair with one to three None, an index outside 0 ... 3 and an unknown label are ERR_ARG here, before the library sees the
+    call."""
+    pairs = list(pairs)
+    if len(pairs) > n_pairs:
+        raise PsdError(ERR_ARG, f"{len(pairs)} entries for a bank of {n_pairs} pairs")
+    m = np.full(4 * n_pairs, TRACE_NONE, np.uint32)
+    for p, ab in enumerate(pairs):
+        if ab is None:
+            continue
+        ok = isinstance(ab, (tuple, list)) and len(ab) == 2 and all(isinstance(s, (tuple, list)) and len(s) == 2 for s in ab)
+        if not ok:
+            raise PsdError(ERR_ARG, f"pair {p} needs ((ia, qa), (ib, qb))")
+        four = [ab[0][0], ab[0][1], ab[1][0], ab[1][1]]
+        none = sum(t is None for t in four)
+        if none == 4:
+            continue
+        if none:
+            raise PsdError(ERR_ARG, f"pair {p} names None for some of its traces only")
+        for c, t in enumerate(four):
+            i = trace_index(t)
+            if not 0 <= i < 4:
+                raise PsdError(ERR_ARG, f"pair {p} names trace {i} (frames carry at most 4)")
+            m[4 * p + c] = i
+    if not np.any(m != TRACE_NONE):
+        raise PsdError(ERR_ARG, "the map feeds no pair")
+    return m
+
+
+class IqCsdCascadeBank:
+    """`n_pairs` independent IQ cross cascades (psdc_iqcsd_*): a pair is two streams that are complex already, a = I_a + i Q_a
+    and b = I_b + i Q_b, each turned by a carrier of its own (default none: ftw = 0, phase0 = 0) in one pair mixer launch in front
+    of the zoom cross object's cascade.  Every stage keeps the two-sided auto spectra of both and their cross spectrum
+    S_ab = conj(Z_a) Z_b, each as an `upper` row (offsets f >= 0) and a `lower` row (-f, the value at bin N - k, not
+    conjugated), exactly as ZoomCsdCascadeBank does.  coherence(), transfer() and two_sided() take the rows of csd() as they are."""
+
+    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
+        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_iqcsd_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
+        else:
+            self._h = self._L.psdc_iqcsd_create(n, int(window), n_pairs, device)
+        # (ftw, phase0) of both sides of every pair, as set
+        self.carriers = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
+        if not self._h:
+            msg = self._L.psdc_iqcsd_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_iqcsd_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_iqcsd(rc, self._h)
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        self._ck(self._L.psdc_iqcsd_reset(self._h))
+        self.carriers = {k: (0, 0) for k in self.carriers}
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_iqcsd_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_iqcsd_set_avg(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
+        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as f0 (cycles per sample, through
+        zoom_ftw) or as the tuning word itself; phase0 in 2^-64 turn.  Only before the pair's first sample.  Returns the f0
+        actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        if side is not None and side not in (0, 1):
+            raise PsdError(ERR_ARG, f"side {side} out of range (0: stream a, 1: stream b)")
+        for s in ((0, 1) if side is None else (side,)):
+            self._ck(self._L.psdc_iqcsd_set_carrier(self._h, pair, s, ftw, phase0))
+            self.carriers[(pair, s)] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, pair, za, zb):
+        """za, zb: two complex arrays of one length (converted to complex64 and fed as (re, im) pairs: the interleaved route), or
+        two pairs (ia, qa), (ib, qb) of real arrays of one length (the planar route)."""
+        planar = [isinstance(z, (tuple, list)) for z in (za, zb)]
+        if all(planar):
+            if len(za) != 2 or len(zb) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (ia, qa), (ib, qb)")
+            x = [np.ascontiguousarray(v, dtype=np.float32) for v in (*za, *zb)]
+            if any(v.ndim != 1 or v.shape != x[0].shape for v in x):
+                raise PsdError(ERR_ARG, "the four streams differ in length (" + ", ".join(str(v.size) for v in x) + ")")
+            self._ck(self._L.psdc_iqcsd_process(self._h, pair, *[_fptr(v) for v in x], x[0].size))
+            return
+        if any(planar):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q), not one of each")
+        za, zb = np.asarray(za), np.asarray(zb)
+        if not (np.iscomplexobj(za) and np.iscomplexobj(zb)):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q)")
+        za = np.ascontiguousarray(za, dtype=np.complex64)
+        zb = np.ascontiguousarray(zb, dtype=np.complex64)
+        if za.ndim != 1 or za.shape != zb.shape:
+            raise PsdError(ERR_ARG, f"za and zb differ in length ({za.size} and {zb.size})")
+        self._ck(self._L.psdc_iqcsd_process_interleaved(self._h, pair, za.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        zb.ctypes.data_as(C.POINTER(C.c_float)), za.size))
+
+    def process_device(self, pair, pa, pb, length, after=None):
+        """pa, pb: device addresses of `length` (re, im) pairs of f32 each (two complex64 tensors' memory; 8-byte aligned); after:
+        a hipEvent_t handle recorded behind their producer, or None when it has completed.  The samples must stay unchanged
+        until sync() or a read-out returns."""
+        self._ck(self._L.psdc_iqcsd_process_interleaved_device(self._h, pair, C.c_void_p(pa), C.c_void_p(pb), length,
+                                                               C.c_void_p(after) if after else None))
+
+    def process_device_planar(self, pair, pia, pqa, pib, pqb, length, after=None):
+        """pia, pqa, pib, pqb: device addresses of `length` f32 samples each, the I and Q streams of side a and of side b
+        (process_device's rules)"""
+        self._ck(self._L.psdc_iqcsd_process_device(self._h, pair, C.c_void_p(pia), C.c_void_p(pqa), C.c_void_p(pib),
+                                                   C.c_void_p(pqb), length, C.c_void_p(after) if after else None))
+
+    def process_frames(self, data, frame_size, pairs):
+        """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] is
+        ((ia, qa), (ib, qb)), the traces the two sides of pair p take as I and Q of every frame (indices or TRACE_NAMES labels,
+        iq_pair_map), or None to leave the pair unfed; a trace may feed any number of sides.  The frames are decoded and mixed on
+        the device in one kernel; two sides with one carrier share the oscillator.  Returns the number of frames ingested; a
+        bad frame raises FrameError after the frames before it were ingested."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = iq_pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_iqcsd_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
+                                               frame_size, buf.size // frame_size, C.byref(ok))
+        self._ck(rc)
+        return ok.value
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
+        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
+        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
+        m = iq_pair_map(pairs, self.n_pairs)
+        ok = C.c_size_t(0)
+        rc = self._L.psdc_iqcsd_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
+                                                      frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
+        self._ck(rc)
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(self._L.psdc_iqcsd_loss_read(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
+    def sync(self):
+        self._ck(self._L.psdc_iqcsd_sync(self._h))
+
+    def num_stages(self, pair=0):
+        return self._ck(self._L.psdc_iqcsd_num_stages(self._h, pair))
+
+    def stage_spectra(self, pair, stage):
+        """(info, rows) of one stage's raw accumulators: rows (8, n/2 + 1) in the layout of include/psdcascade.h -- S_aa upper,
+        lower; S_bb upper, lower; Re S_ab upper, lower; Im S_ab upper, lower."""
+        st = _CStageStat()
+        rows = np.empty((8, self.n // 2 + 1), np.float32)
+        self._ck(self._L.psdc_iqcsd_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(rows)))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
+
+    def csd(self, pair=0, opts=MergeOpts()):
+        """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): PsdCascade::psd of every row, sab complex;
+        Break.frequencies(breaks) are the offsets of all."""
+        ns = self.num_stages(pair)
+        cap = max(1, ns * (self.n // 2 + 1))
+        real = [np.empty(cap, np.float32) for _ in range(4)]
+        cplx = [np.empty(2 * cap, np.float32) for _ in range(2)]
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._L.psdc_iqcsd_csd(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                        *[_fptr(a) for a in real + cplx], cap, C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        out = [a[:m].copy() for a in real] + [(a[0:2 * m:2] + 1j * a[1:2 * m:2]).astype(np.complex64) for a in cplx]
+        return (*out, [Break._from_c(br[i]) for i in range(nb.value)])
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_iqcsd_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "pairs_in": si.value}
+
+    stats = stats_read
+
+
+class IqCsdCascade:
+    """One pair of complex streams: IqCsdCascade(n) analyses them as they are, IqCsdCascade(n, f0=0.2) or IqCsdCascade(n, ftw=...)
+    retunes both sides first; set_carrier(side=...) sets one.  reset() keeps the object's carriers."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = IqCsdCascadeBank(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
+        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
+        self.carriers = [self._b.carriers[(0, 0)], self._b.carriers[(0, 1)]]
+        return f
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, za, zb):
+        """za, zb: two complex arrays, or two pairs (i, q) (IqCsdCascadeBank.process)"""
+        self._b.process(0, za, zb)
+
+    def process_device(self, pa, pb, length, after=None):
+        self._b.process_device(0, pa, pb, length, after)
+
+    def process_device_planar(self, pia, pqa, pib, pqb, length, after=None):
+        self._b.process_device_planar(0, pia, pqa, pib, pqb, length, after)
+
+    def process_frames(self, data, frame_size, pair):
+        """pair: ((ia, qa), (ib, qb)), the traces of the frames the two streams are (IqCsdCascadeBank.process_frames)"""
+        return self._b.process_frames(data, frame_size, [pair])
+
+    def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
+        return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
+
+    def loss(self, reset=False):
+        return self._b.loss(reset)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_spectra(self, i):
+        return self._b.stage_spectra(0, i)
+
+    def reset(self):
+        car = list(self.carriers)
+        self._b.reset()
+        for s, (ftw, ph) in enumerate(car):
+            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    stats = stats_read
 
     def close(self):
         self._b.close()

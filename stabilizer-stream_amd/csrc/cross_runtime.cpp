@@ -6,8 +6,10 @@
 // mixer (zoom_mix_kernel, in place of the input copy) makes of it, on zoom_kernel with the rows upper, lower; a zoom cross
 // object's unit is two such channels, m = 4 streams (I_a, Q_a, I_b, Q_b), on zoom_cross_kernel with the eight rows of
 // zoom_cross_fft.h; an IQ object (psdc_iq_*) is the zoom kind with a different feed: its unit is one COMPLEX channel whose I and Q
-// arrive from the caller and go through the complex mixer (iq_mix_kernel, iq_frames_kernel) into the same two streams.  Below, "pair"
-// stands for any of these units.
+// arrive from the caller and go through the complex mixer (iq_mix_kernel, iq_frames_kernel) into the same two streams; an IQ cross
+// object (psdc_iqcsd_*) is the zoom cross kind with that feed for both sides at once: its unit is two complex channels, turned by
+// one pair mixer (iq_pair_mix_kernel, iq_cross_frames_kernel) into the same four streams.  Below, "pair" stands for any of these
+// units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -23,6 +25,7 @@
 #include "csm.h"
 #include "zoom_cross.h"
 #include "iq.h"
+#include "iq_cross.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -66,17 +69,17 @@ struct XObj {
     bool matrix = false; // psdc_csm: csm_kernel and its row layout
     bool zoom = false;   // psdc_zoom / psdc_zcsd: the streams are I and Q of mixed channels, fed through the mixer
     bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
-    bool iq = false;     // psdc_iq (with zoom): the channel's I and Q come from the caller, through the complex mixer
+    bool iq = false;     // psdc_iq (with zoom), psdc_iqcsd (with zoom and zcross): I and Q come from the caller, through the complex mixer
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
     uint32_t rows() const { return zcross ? 8 : zoom ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
-    // (an IQ channel two: its I and its Q)
-    uint32_t map_w() const { return iq ? 2 : zoom ? reals() : m; }
-    // f32 streams of STAGING samples a pinned staging slot and the landing buffer hold: an IQ channel's I and Q, else reals()
-    uint32_t lanes() const { return iq ? 2 : reals(); }
+    // (an IQ channel two: its I and its Q; an IQ cross pair four)
+    uint32_t map_w() const { return iq ? m : zoom ? reals() : m; }
+    // f32 streams of STAGING samples a pinned staging slot and the landing buffer hold: an IQ unit's I and Q streams, else reals()
+    uint32_t lanes() const { return iq ? m : reals(); }
     // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
-    // channel's STAGING floats (16 MB), a zoom cross object's two (32 MB), the others' at least two
+    // channel's STAGING floats (16 MB), a zoom cross object's two (32 MB), an IQ cross object's four (64 MB), the others' at least two
     size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? lanes() : 2); }
     int device = 0;
     Geometry geo;
@@ -127,6 +130,7 @@ struct psdc_csm : XObj {};
 struct psdc_zoom : XObj {};
 struct psdc_zcsd : XObj {};
 struct psdc_iq : XObj {};
+struct psdc_iqcsd : XObj {};
 
 namespace {
 
@@ -554,14 +558,15 @@ std::string zcsd_size_text(uint32_t n)
 }
 
 // T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
-// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel)
+// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
 {
     constexpr bool matrix = std::is_same<T, psdc_csm>::value;
-    constexpr bool zcross = std::is_same<T, psdc_zcsd>::value;
-    constexpr bool iq = std::is_same<T, psdc_iq>::value;
+    constexpr bool iqcsd = std::is_same<T, psdc_iqcsd>::value;
+    constexpr bool zcross = std::is_same<T, psdc_zcsd>::value || iqcsd;
+    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd;
     constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
@@ -613,7 +618,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         }
         if (iq) {
             h->iq = true;
-            h->tag = "psdc_iq";
+            h->tag = iqcsd ? "psdc_iqcsd" : "psdc_iq";
         }
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
@@ -713,7 +718,8 @@ struct FrameSrc {
 // c), one launch per 32 / m pairs, on the copy stream.  A zoom channel's two buffers are its I and Q streams: zoom_frames_kernel
 // decodes the channel's trace and mixes it with the channel's carrier, the first sample at stream index total + dst_off.  A zoom
 // cross pair's four are I_a, Q_a, I_b, Q_b: zoom_cross_frames_kernel does the same for both sides of 8 pairs a launch, where
-// psdc_zcsd_process_device has its two mixers.  An IQ channel's two are its I and Q as well, made of two traces by iq_frames_kernel.
+// psdc_zcsd_process_device has its two mixers.  An IQ channel's two are its I and Q as well, made of two traces by iq_frames_kernel;
+// an IQ cross pair's four are made of four traces by iq_cross_frames_kernel, 8 pairs a launch.
 int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt *wf, int batches, size_t f, size_t cnt,
                   const std::vector<FedPair> &fed, const std::vector<float *> &dst, size_t dst_off)
 {
@@ -741,7 +747,26 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
         b->batches = batches;
         b->fmt = wf->id;
     };
-    if (h->zcross) {
+    if (h->zcross && h->iq) {
+        for (size_t i0 = 0; i0 < fed.size(); i0 += IQ_CROSS_FRAMES_MAX_PAIRS) {
+            IqCrossFramesBatch b{};
+            describe(&b);
+            for (size_t i = i0; i < std::min<size_t>(fed.size(), i0 + IQ_CROSS_FRAMES_MAX_PAIRS); ++i, ++b.npairs) {
+                const uint32_t p = fed[i].pair;
+                for (int side = 0; side < 2; ++side) {
+                    b.ftw[b.npairs][side] = h->ftw[2 * (size_t)p + side];
+                    b.phase0[b.npairs][side] = h->phase0[2 * (size_t)p + side];
+                }
+                for (int c = 0; c < 4; ++c) { // I_a, Q_a, I_b, Q_b: the map's order and the order iq_pair_feed's mixer writes them in
+                    b.trace[b.npairs][c] = (int)fed[i].tr[c];
+                    b.dst[b.npairs][c] = dst[4 * i + c] + dst_off;
+                }
+                b.j0[b.npairs] = h->pairs[p][0].total + dst_off; // the stream index of both sides, as iq_pair_feed counts it
+            }
+            XCHK(h, launch_iq_cross_frames(b, h->copy_stream));
+            ++h->launches;
+        }
+    } else if (h->zcross) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_CROSS_FRAMES_MAX_PAIRS) {
             ZoomCrossFramesBatch b{};
             describe(&b);
@@ -1252,6 +1277,88 @@ int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool i
     return run_round(h, &did);
 }
 
+// An IQ cross pair takes len complex samples of each side: planar (src: I_a, Q_a, I_b, Q_b, four f32 streams, each 4-byte
+// aligned) or interleaved (src[0], src[2]: the (re, im) pairs of side a and side b, 8-byte aligned; src[1], src[3] unused), from
+// host memory (up through the pinned staging into the landing buffer) or from device memory.  iq_feed with the pair mixer in place
+// of the complex one: the same stream, the same events, ONE mixer launch a piece for both sides, and the same launches on the same
+// data from either memory, so all four routes give the same bits for the same calls.
+int iq_pair_feed(XObj *h, uint32_t pair, const float *const (&src)[4], bool interleaved, size_t len, bool dev, void *producer_event,
+                 const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
+        if (!src[c])
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+        if ((uintptr_t)src[c] % (interleaved ? 2 * sizeof(float) : sizeof(float)) != 0)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to 8 bytes"
+                                                                          : ": the samples are not aligned to 4 bytes"));
+    }
+    X_ON_DEVICE(h);
+    if (producer_event)
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    if (!dev && !h->d_land)
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * 4 * STAGING));
+    XStage *s = nullptr;
+    h->grew = false;
+    if ((rc = stage0_room(h, pair, len, &s)))
+        return rc;
+    if (h->grew) {
+        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+    }
+    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
+    if (h->round_recorded[rslot])
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
+    const size_t piece = dev ? len : STAGING;
+    for (size_t done = 0; done < len;) {
+        const size_t cnt = std::min(piece, len - done);
+        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
+            const int slot = h->stage_cur;
+            if (h->ev_pending[slot])
+                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+            float *stg = h->h_stage[slot];
+            // planar: stream c in lane c; interleaved: side a's pairs in lanes 0 and 1, side b's in lanes 2 and 3, as they are
+            for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
+                const size_t w = interleaved ? 2 : 1;
+                memcpy(stg + c * STAGING, src[c] + w * done, sizeof(float) * w * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, stg + c * STAGING, sizeof(float) * w * cnt, hipMemcpyHostToDevice,
+                                       h->copy_stream));
+            }
+            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
+            h->ev_pending[slot] = true;
+            h->stage_cur ^= 1;
+        }
+        const size_t at = (size_t)(s->total + done - s->buf.base);
+        IqPairMixJob mj{};
+        for (int c = 0; c < 4; ++c) {
+            if (!interleaved || !(c & 1))
+                mj.src[c] = dev ? src[c] + (interleaved ? 2 : 1) * done : h->d_land + c * STAGING;
+            mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
+        }
+        mj.len = cnt;
+        mj.j0 = s->total + done; // the stream index: complex samples each side has taken since create or reset
+        for (int side = 0; side < 2; ++side) {
+            mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
+            mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
+        }
+        XCHK(h, launch_iq_pair_mix(mj, interleaved, h->copy_stream));
+        ++h->launches;
+        done += cnt;
+    }
+    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+    s->total += len;
+    h->pairs_in += len;
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
 int sync_impl(XObj *h, const char *who)
 {
     X_HANDLE(h, who);
@@ -1489,6 +1596,73 @@ int two_rows_psd_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_
                           n_breaks);
     if (rc)
         return xfail(h, rc, x_last_error);
+    return PSDC_OK;
+}
+
+// the carrier of one side of a pair of a two-channels-a-unit object (psdc_zcsd, psdc_iqcsd)
+int pair_carrier_impl(XObj *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    if (side > 1)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": side " + std::to_string(side) + " out of range (0: channel a, 1: channel b)");
+    const auto &st = h->pairs[pair];
+    if (!st.empty() && st[0].total)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": pair " + std::to_string(pair) + " has taken " +
+                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
+    h->ftw[2 * (size_t)pair + side] = ftw;
+    h->phase0[2 * (size_t)pair + side] = phase0;
+    return PSDC_OK;
+}
+
+// the eight rows of one stage / the stitched rows of a pair (psdc_zcsd, psdc_iqcsd)
+int eight_rows_stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows, const char *who)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, who);
+    if (rc)
+        return rc;
+    for (size_t e = 0; e < acc.size(); ++e)
+        rows[e] = (float)acc[e];
+    return PSDC_OK;
+}
+
+int eight_rows_csd_impl(XObj *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
+                        float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap,
+                        size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, pair);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    StitchIn in;
+    if ((rc = stitch_in(h, pair, &in)))
+        return rc;
+    // the complex rows are stitched as their real and imaginary rows and interleaved afterwards, as psdc_cross_stitch does
+    std::vector<float> tmp(4 * (cap ? cap : 1));
+    float *outs[8] = {saa_upper, saa_lower, sbb_upper, sbb_lower, sab_upper ? &tmp[0] : nullptr, sab_lower ? &tmp[cap] : nullptr,
+                      sab_upper ? &tmp[2 * cap] : nullptr, sab_lower ? &tmp[3 * cap] : nullptr};
+    size_t plen = 0;
+    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                          in.rows.data(), 8, keep_overlap, min_count, keep_transition_band, outs, cap, &plen, breaks, breaks_cap,
+                          n_breaks);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    for (size_t k = 0; k < plen; ++k) {
+        if (sab_upper) {
+            sab_upper[2 * k] = tmp[k];
+            sab_upper[2 * k + 1] = tmp[2 * cap + k];
+        }
+        if (sab_lower) {
+            sab_lower[2 * k] = tmp[cap + k];
+            sab_lower[2 * k + 1] = tmp[3 * cap + k];
+        }
+    }
+    if (len)
+        *len = plen;
     return PSDC_OK;
 }
 
@@ -1936,19 +2110,7 @@ int psdc_zcsd_set_avg(psdc_zcsd *h, uint32_t limit, uint32_t count) { return set
 
 int psdc_zcsd_set_carrier(psdc_zcsd *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0)
 {
-    X_HANDLE(h, "psdc_zcsd_set_carrier");
-    int rc = check_pair(h, pair);
-    if (rc)
-        return rc;
-    if (side > 1)
-        return xfail(h, PSDC_ERR_ARG, "psdc_zcsd_set_carrier: side " + std::to_string(side) + " out of range (0: channel a, 1: channel b)");
-    const auto &st = h->pairs[pair];
-    if (!st.empty() && st[0].total)
-        return xfail(h, PSDC_ERR_ARG, "psdc_zcsd_set_carrier: pair " + std::to_string(pair) + " has taken " +
-                                          std::to_string(st[0].total) + " samples: a carrier is set before the first one (or after a reset)");
-    h->ftw[2 * (size_t)pair + side] = ftw;
-    h->phase0[2 * (size_t)pair + side] = phase0;
-    return PSDC_OK;
+    return pair_carrier_impl(h, pair, side, ftw, phase0, "psdc_zcsd_set_carrier");
 }
 
 int psdc_zcsd_process(psdc_zcsd *h, uint32_t pair, const float *x, const float *y, size_t len)
@@ -1968,50 +2130,15 @@ int psdc_zcsd_num_stages(psdc_zcsd *h, uint32_t pair) { return num_stages_impl(h
 
 int psdc_zcsd_stage_spectra(psdc_zcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, "psdc_zcsd_stage_spectra");
-    if (rc)
-        return rc;
-    for (size_t e = 0; e < acc.size(); ++e)
-        rows[e] = (float)acc[e];
-    return PSDC_OK;
+    return eight_rows_stage_impl(h, pair, stage, stat, rows, "psdc_zcsd_stage_spectra");
 }
 
 int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
                   float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap, size_t *len,
                   psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    X_HANDLE(h, "psdc_zcsd_csd");
-    int rc = check_pair(h, pair);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, pair, &in)))
-        return rc;
-    // the complex rows are stitched as their real and imaginary rows and interleaved afterwards, as psdc_cross_stitch does
-    std::vector<float> tmp(4 * (cap ? cap : 1));
-    float *outs[8] = {saa_upper, saa_lower, sbb_upper, sbb_lower, sab_upper ? &tmp[0] : nullptr, sab_lower ? &tmp[cap] : nullptr,
-                      sab_upper ? &tmp[2 * cap] : nullptr, sab_lower ? &tmp[3 * cap] : nullptr};
-    size_t plen = 0;
-    rc = stitch_rows_impl("psdc_zcsd_csd", h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(),
-                          in.pend.data(), in.rows.data(), 8, keep_overlap, min_count, keep_transition_band, outs, cap, &plen, breaks,
-                          breaks_cap, n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    for (size_t k = 0; k < plen; ++k) {
-        if (sab_upper) {
-            sab_upper[2 * k] = tmp[k];
-            sab_upper[2 * k + 1] = tmp[2 * cap + k];
-        }
-        if (sab_lower) {
-            sab_lower[2 * k] = tmp[cap + k];
-            sab_lower[2 * k + 1] = tmp[3 * cap + k];
-        }
-    }
-    if (len)
-        *len = plen;
-    return PSDC_OK;
+    return eight_rows_csd_impl(h, pair, keep_overlap, min_count, keep_transition_band, saa_upper, saa_lower, sbb_upper, sbb_lower,
+                               sab_upper, sab_lower, cap, len, breaks, breaks_cap, n_breaks, "psdc_zcsd_csd");
 }
 
 int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -2039,5 +2166,104 @@ int psdc_zoomcsdcascade_loss_read(psdc_zcsd *h, psdc_loss *out, int reset)
 }
 
 const char *psdc_zcsd_last_error(const psdc_zcsd *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- IQ cross: two complex channels a unit, both turned by one pair mixer in front of stage 0; everything behind the mixer is
+// the zoom cross object's ----
+
+int psdc_iqcsd_supported(uint32_t n) { return psdc_zcsd_supported(n); }
+
+psdc_iqcsd *psdc_iqcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                     int device)
+{
+    return create_impl<psdc_iqcsd>(n, win, power, nenbw, overlap, 4, n_pairs, device, "psdc_iqcsd_create_window");
+}
+
+psdc_iqcsd *psdc_iqcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    if (!psdc_iqcsd_supported(n)) { // (before the window: a refused size names itself)
+        xfail(nullptr, PSDC_ERR_ARG, "psdc_iqcsd_create: " + zcsd_size_text(n));
+        return nullptr;
+    }
+    return create_kind<psdc_iqcsd>(n, window_kind, 4, n_pairs, device, "psdc_iqcsd_create");
+}
+
+void psdc_iqcsd_destroy(psdc_iqcsd *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_iqcsd_reset(psdc_iqcsd *h) { return reset_impl(h, "psdc_iqcsd_reset"); }
+int psdc_iqcsd_set_detrend(psdc_iqcsd *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqcsd_set_detrend"); }
+int psdc_iqcsd_set_avg(psdc_iqcsd *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqcsd_set_avg"); }
+
+int psdc_iqcsd_set_carrier(psdc_iqcsd *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0)
+{
+    return pair_carrier_impl(h, pair, side, ftw, phase0, "psdc_iqcsd_set_carrier");
+}
+
+int psdc_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const float *ia, const float *qa, const float *ib, const float *qb, size_t len)
+{
+    const float *const src[4] = {ia, qa, ib, qb};
+    return iq_pair_feed(h, pair, src, false, len, false, nullptr, "psdc_iqcsd_process");
+}
+
+int psdc_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const float *d_ia, const float *d_qa, const float *d_ib, const float *d_qb,
+                              size_t len, void *producer_event)
+{
+    const float *const src[4] = {d_ia, d_qa, d_ib, d_qb};
+    return iq_pair_feed(h, pair, src, false, len, true, producer_event, "psdc_iqcsd_process_device");
+}
+
+int psdc_iqcsd_process_interleaved(psdc_iqcsd *h, uint32_t pair, const float *za, const float *zb, size_t len)
+{
+    const float *const src[4] = {za, nullptr, zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, len, false, nullptr, "psdc_iqcsd_process_interleaved");
+}
+
+int psdc_iqcsd_process_interleaved_device(psdc_iqcsd *h, uint32_t pair, const float *d_za, const float *d_zb, size_t len,
+                                          void *producer_event)
+{
+    const float *const src[4] = {d_za, nullptr, d_zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, len, true, producer_event, "psdc_iqcsd_process_interleaved_device");
+}
+
+int psdc_iqcsd_process_frames(psdc_iqcsd *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
+                              size_t *n_ok)
+{
+    return frames_host_impl(h, pair_traces, frames, frame_size, n_frames, n_ok, "psdc_iqcsd_process_frames");
+}
+
+int psdc_iqcsd_process_frames_device(psdc_iqcsd *h, const uint32_t *pair_traces, const uint8_t *d_frames, size_t frame_size,
+                                     size_t n_frames, size_t *n_ok, void *producer_event)
+{
+    return frames_device_impl(h, pair_traces, d_frames, frame_size, n_frames, n_ok, producer_event, "psdc_iqcsd_process_frames_device");
+}
+
+int psdc_iqcsd_loss_read(psdc_iqcsd *h, psdc_loss *out, int reset) { return loss_impl(h, out, reset, "psdc_iqcsd_loss_read"); }
+int psdc_iqcsd_sync(psdc_iqcsd *h) { return sync_impl(h, "psdc_iqcsd_sync"); }
+int psdc_iqcsd_num_stages(psdc_iqcsd *h, uint32_t pair) { return num_stages_impl(h, pair, "psdc_iqcsd_num_stages"); }
+
+int psdc_iqcsd_stage_spectra(psdc_iqcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows)
+{
+    return eight_rows_stage_impl(h, pair, stage, stat, rows, "psdc_iqcsd_stage_spectra");
+}
+
+int psdc_iqcsd_csd(psdc_iqcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
+                   float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap, size_t *len,
+                   psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return eight_rows_csd_impl(h, pair, keep_overlap, min_count, keep_transition_band, saa_upper, saa_lower, sbb_upper, sbb_lower,
+                               sab_upper, sab_lower, cap, len, breaks, breaks_cap, n_breaks, "psdc_iqcsd_csd");
+}
+
+int psdc_iqcsd_stats_read(psdc_iqcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    return stats_impl(h, launches, pairs_in, reset, "psdc_iqcsd_stats_read");
+}
+
+const char *psdc_iqcsd_last_error(const psdc_iqcsd *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

@@ -42,6 +42,11 @@ Leg A (a ceiling: the same round, 4 bytes a sample read instead of 8) is ZoomCas
 IqCascadeBank(n, 1) fed the interleaved complex64; leg C is what a user did before: CsdCascadeBank(n, 1) fed the planar (I, Q).
 A, B, A, C in turn --reps times in one session; B / A, B / C and the largest |A' - A| / A are recorded as findings, none is a gate.
 Clocks and power from rocm-smi (read only) before and after.  Writes profiles/iq_probe.json unless --out names another file.
+--iq --pair: two complex streams.  One device-resident pair of 2^24 sample pairs a call at N = 512, 1024, 2048, 4096.  Leg A (a
+ceiling: the same round, half the bytes read) is ZoomCsdCascadeBank(n, 1) fed two real streams; leg B is IqCsdCascadeBank(n, 1) fed
+two interleaved complex64 streams; leg C is what a user did before: CsmCascadeBank(n, 4, 1) fed the four planar streams (N <= 2048
+only, and it cannot retune).  A, B, A, C in turn --reps times in one session; B / A, B / C, the largest |A' - A| / A and B's launches
+a call are recorded as findings, none is a gate.  Writes profiles/iq_cross_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -328,6 +333,66 @@ def iq_legs(pkg, torch, seconds, reps, call):
         za.close()
         qb.close()
         pc.close()
+    return legs
+
+
+def iq_pair_legs(pkg, torch, seconds, reps, call):
+    """One device-resident pair: two real streams (xa, xb), two complex64 streams (za, zb) and their four planar copies.  A:
+    ZoomCsdCascadeBank fed (xa, xb) -- half the bytes of B, a ceiling; B: IqCsdCascadeBank fed (za, zb) interleaved; C:
+    CsmCascadeBank(n, 4) fed the four planar streams, what a user does today (N <= 2048 only).  Carrier 0.2 on both sides of A
+    and B (C cannot retune).  A / B / A / C in turn; unit: sample pairs a second (one sample of each side)."""
+    xa, xb = torch.randn(call, device="cuda"), torch.randn(call, device="cuda")
+    za = torch.randn(call, dtype=torch.complex64, device="cuda")
+    zb = (0.6 * za + 0.8 * torch.randn(call, dtype=torch.complex64, device="cuda")).contiguous()
+    four = [za.real.contiguous(), za.imag.contiguous(), zb.real.contiguous(), zb.imag.contiguous()]
+    torch.cuda.synchronize()
+    ptrs = [t.data_ptr() for t in four]
+    legs = []
+    for n in (512, 1024, 2048, 4096):
+        zc = pkg.ZoomCsdCascadeBank(n, 1)
+        zc.set_carrier(0, f0=0.2)
+        qb = pkg.IqCsdCascadeBank(n, 1)
+        qb.set_carrier(0, f0=0.2)
+        mc = pkg.CsmCascadeBank(n, 4, 1) if pkg.csm_supported(n, 4) else None
+
+        def a_step():
+            zc.process_device(0, xa.data_ptr(), xb.data_ptr(), call)
+            return call
+
+        def b_step():
+            qb.process_device(0, za.data_ptr(), zb.data_ptr(), call)
+            return call
+
+        def c_step():
+            mc.process_device(0, ptrs, call)
+            return call
+
+        a1, b, a2, c = [], [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, zc.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, qb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, zc.sync, seconds)[0] / 1e9)
+            if mc is not None:
+                c.append(timed(c_step, mc.sync, seconds)[0] / 1e9)
+        qb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = qb.stats_read()["launches"] / 8
+        qb.sync()
+        ba = [v / u for u, v in zip(a1, b)]
+        bc = [v / u for u, v in zip(c, b)]
+        spread = max(abs(v - u) / u for u, v in zip(a1, a2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "call": call, "a_zoom_cross_real_gpairs_s": r3(a1), "b_iq_cross_interleaved_gpairs_s": r3(b),
+                     "a_again_gpairs_s": r3(a2), "c_matrix_fed_planar_gpairs_s": r3(c) if c else None, "ratio_b_over_a": r3(ba),
+                     "ratio_b_over_c": r3(bc) if c else None, "b_over_a_min": round(min(ba), 3),
+                     "b_over_c_min": round(min(bc), 3) if c else None, "aa_spread_max": round(spread, 4),
+                     "b_beats_c": bool(min(bc) > 1 + spread) if c else None, "b_launches_per_call": launches,
+                     "stages": qb.num_stages(0)})
+        zc.close()
+        qb.close()
+        if mc is not None:
+            mc.close()
     return legs
 
 
@@ -637,10 +702,26 @@ def main():
                                                         "pre-mixed (I_a, Q_a, I_b, Q_b); with --zoom --frames: stream frames into a "
                                                         "ZoomCsdCascadeBank against the host decode")
     ap.add_argument("--iq", action="store_true", help="IqCascadeBank fed complex64 against ZoomCascadeBank fed a real stream (a ceiling) "
-                                                      "and CsdCascadeBank fed the planar (I, Q)")
+                                                      "and CsdCascadeBank fed the planar (I, Q); with --pair: IqCsdCascadeBank fed two "
+                                                      "complex64 streams against ZoomCsdCascadeBank fed two real streams (a ceiling) "
+                                                      "and CsmCascadeBank(n, 4) fed the four planar streams")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.iq and a.pair:
+        before = gpu_state()
+        legs = iq_pair_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)
+        line = json.dumps({"metric": "iq_cross_gpairs_s", "unit": "1e9 sample pairs a second (one sample of each side; complex for B and C, "
+                                                                  "real for A)",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "findings, no gate: A reads 8 bytes a sample pair where B and C read 16; no kernel trace was taken, so "
+                                   "nothing is said about the split between the mixer and the round; not measured here: the planar route, "
+                                   "host memory, frames, banks, two different carriers (B runs the shared-oscillator branch)",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "iq_cross_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.iq:
         before = gpu_state()
         legs = iq_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)

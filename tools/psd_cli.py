@@ -16,7 +16,11 @@ offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - off
 --iq I:Q[:F0] (repeatable) feeds a complex stream I + i Q to an IqCascade(512), retuned by F0 (cycles per sample, default 0: as it
 is).  With --file, I and Q are traces of the frames (labels or indices, e.g. BI:BQ); without it they are two raw f32 files of equal
 length (the planar pair; no --file / --raw is needed then).  Prints, or with --csv writes to DIR/iq_<i>__<q>_<F0>.csv, the lines
-offset,upper,lower (the density of z at F0 + offset / F0 - offset; half of it is the two-sided density)."""
+offset,upper,lower (the density of z at F0 + offset / F0 - offset; half of it is the two-sided density).
+--iq-pair IA:QA:IB:QB[:F0] (repeatable) feeds the two complex streams IA + i QA and IB + i QB to an IqCsdCascade(512), both retuned by
+the one carrier F0 (default 0).  Traces of the frames with --file, four raw f32 files of equal length without it, as for --iq.
+Prints, or with --csv writes to DIR/iqpair_<ia>__<qa>__<ib>__<qb>_<F0>.csv, the lines of --zoom-pair:
+offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b."""
 import argparse
 import os
 import sys
@@ -51,17 +55,22 @@ def main(argv=None):
                     help="F0:X:Y -- two-sided auto and cross spectra of traces X and Y around the carrier F0 (repeatable)")
     ap.add_argument("--iq", action="append", default=[],
                     help="I:Q[:F0] -- two-sided spectrum of the complex stream I + i Q, retuned by F0 (repeatable)")
+    ap.add_argument("--iq-pair", action="append", default=[],
+                    help="IA:QA:IB:QB[:F0] -- two-sided auto and cross spectra of two complex streams, retuned by F0 (repeatable)")
     a = ap.parse_args(argv)
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
-    if a.iq and not a.file:  # the planar raw pair: the only input this option needs
+    if (a.iq or a.iq_pair) and not a.file:  # the planar raw files: the only input these options need
         merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
         if a.csv:
             os.makedirs(a.csv, exist_ok=True)
-        iq_streams(pkg, source, a, merge, None)
+        if a.iq:
+            iq_streams(pkg, source, a, merge, None)
+        if a.iq_pair:
+            iq_pairs(pkg, source, a, merge, None)
         if not a.raw:
             return 0
     integral_start, integral_end = a.integral_start * a.fs, a.integral_end * a.fs  # src/bin/psd.rs:161-162
@@ -108,6 +117,8 @@ def main(argv=None):
         zoom_pairs(pkg, source, a, merge, names)
     if a.iq and a.file:
         iq_streams(pkg, source, a, merge, names)
+    if a.iq_pair and a.file:
+        iq_pairs(pkg, source, a, merge, names)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
@@ -297,6 +308,58 @@ def iq_streams(pkg, source, a, merge, names):
         lines = [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)]
         if a.csv:
             safe = "".join(ch if ch.isalnum() else "_" for ch in f"iq_{li}__{lq}_{used[c]:.9g}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+    bank.close()
+
+
+def iq_pairs(pkg, source, a, merge, names):
+    """--iq-pair: four traces of every read (host_traces), or four raw f32 files (names None), into one IQ cross cascade per pair,
+    one carrier on both sides"""
+    want = []
+    for z in a.iq_pair:
+        parts = z.split(":")
+        if len(parts) not in (4, 5) or not all(parts[:4]):
+            raise SystemExit("--iq-pair takes IA:QA:IB:QB[:F0]")
+        want.append((tuple(parts[:4]), float(parts[4]) if len(parts) == 5 else 0.0))
+    bank = pkg.IqCsdCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (_, f0) in enumerate(want)]
+    if names is None:
+        labels = [tuple(os.path.basename(f) for f in files) for files, _ in want]
+        for p, (files, _) in enumerate(want):
+            if len({os.path.getsize(f) for f in files}) != 1:
+                raise SystemExit("--iq-pair: " + ", ".join(files) + " differ in length")
+            fh = [open(f, "rb") for f in files]
+            fed = 0
+            while a.max_bytes is None or fed < a.max_bytes:
+                xs = [np.fromfile(f, "<f4", 1 << 20) for f in fh]
+                if xs[0].size == 0:
+                    break
+                bank.process(p, (xs[0], xs[1]), (xs[2], xs[3]))
+                fed += xs[0].nbytes
+            for f in fh:
+                f.close()
+    else:
+        idx = [tuple(trace_arg(t, names, "--iq-pair") for t in tr) for tr, _ in want]
+        labels = [tuple(names[i] for i in four) for four in idx]
+        host_traces(source, pkg, a, idx, lambda p, xs: bank.process(p, (xs[0], xs[1]), (xs[2], xs[3])))
+    for p, lab in enumerate(labels):
+        label = f"iq pair {lab[0]}:{lab[1]}:{lab[2]}:{lab[3]} @ {used[p]:.12g}"
+        if bank.num_stages(p) == 0:
+            print(f"{label}: no samples")
+            continue
+        aup, alo, bup, blo, xup, xlo, breaks = bank.csd(p, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        coh = pkg.coherence(aup, bup, xup)
+        print(f"{label}: stages {bank.num_stages(p)} bins {aup.size} breaks {len(breaks)} median coherence (upper) {np.nanmedian(coh):.6g}")
+        lines = [f"{o:.9g},{u:.9g},{v:.9g},{x.real:.9g},{x.imag:.9g},{r:.9g},{t:.9g},{w.real:.9g},{w.imag:.9g}\n"
+                 for o, u, v, x, r, t, w in zip(off, aup, bup, xup, alo, blo, xlo)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"iqpair_{lab[0]}__{lab[1]}__{lab[2]}__{lab[3]}_{used[p]:.9g}")
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(lines)
         else:
