@@ -18,7 +18,8 @@
  *     moved between threads (Send, not Sync).  Distinct handles are independent.
  *   - one handle holds `n_channels` independent cascades (one `PsdCascade` per
  *     trace, src/bin/psd.rs:174-182) that are batched onto one GPU.
- *   - all sample data is IEEE f32, native endian (src/bin/stream_to_raw.rs:24-25).
+ *   - all sample data is IEEE f32, native endian (src/bin/stream_to_raw.rs:24-25), except the integer feeds below
+ *     ("integer sample feeds").
  *   - there is NO CPU fallback: without a usable HIP device `psdc_create` fails.
  *   - call chunking: like the reference (src/psd.rs:196-208) every result is a function of the CONCATENATED stream of a
  *     channel.  Counters (stage count, count, pending, processed, Break fields, frequencies, Loss) are exactly independent of
@@ -1052,6 +1053,50 @@ int psdc_iqcsd_csd(psdc_iqcsd *h, uint32_t pair, int keep_overlap, uint32_t min_
 /* kernel launches issued and complex sample pairs accepted since creation or the last reset of the statistics */
 int psdc_iqcsd_stats_read(psdc_iqcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset);
 const char *psdc_iqcsd_last_error(const psdc_iqcsd *h);
+
+/* ---- integer sample feeds: int16 / int8 samples into the zoom and IQ objects (s16 / s8, sc16 / sc8) -----------------------
+ * Hardware does not deliver f32: an SDR delivers interleaved 16-bit or 8-bit integer pairs, a capture card a real int16
+ * stream.  The four mixer-fronted objects (zoom, zoom cross, IQ, IQ cross) take such a stream as it is; the mixer in front of
+ * stage 0 reads the integers where it reads floats on the f32 routes, so there is no widened copy and no extra launch.
+ * Kinds: PSDC_SAMPLE_S16 (int16, native endian) and PSDC_SAMPLE_S8 (int8).  Unit: for the real-input objects (zoom, zoom
+ * cross) one integer; for the complex-input objects (IQ, IQ cross) one interleaved (re, im) pair of that type -- sc16 (4
+ * bytes) or sc8 (2 bytes).  There is no planar integer route.  `len` counts units.
+ * Conversion: every call carries a `float scale`, and the f32 sample the mixer sees is (float)v * scale: the int-to-float
+ * conversion is exact, and the product is one stand-alone f32 product rounded to nearest (__fmul_rn on the device; nothing is
+ * contracted into the mix formulas of csrc/zoom_lo.h and csrc/iq_lo.h).  scale must be finite, else PSDC_ERR_ARG.  2^-15 for
+ * s16 and 2^-7 for s8 map full scale into [-1, 1) (the Python mirror's defaults).
+ * The defining property: an integer call gives bit for bit what the object's existing f32 call of the same length -- the
+ * interleaved call of the complex objects, the plain call of the real ones -- gives when that call is fed
+ * float32(v) * float32(scale), on the same object state and from the same memory side (host or device).  Integer, f32 and
+ * frames calls may be mixed on one channel or pair in any order; the stream index, and so the phase, continues across them.
+ * Arguments: pointers aligned to the unit (2 bytes for s16, 1 for s8, 4 for sc16, 2 for sc8), else PSDC_ERR_ARG; an unknown
+ * kind is PSDC_ERR_ARG; NULL with len > 0 is PSDC_ERR_ARG; len == 0 is PSDC_OK.  A failed call leaves the object as it was.
+ * Stream ordering, the producer_event meaning, the caller-keeps-memory rule and lifetimes are exactly those of the object's
+ * f32 device call; the error text goes through the object's *_last_error.  Host calls go up through the same pinned staging
+ * into the front of the same landing buffer as raw integers, cut into pieces of 2^22 units as the f32 calls are cut into pieces
+ * of 2^22 samples, so an integer call makes the launches and rounds of the f32 call of the same length (1 + 3 a steady call for
+ * zoom, IQ and IQ cross, 2 + 3 for zoom cross) and *_stats_read counts as before; device calls read the caller's memory in place.
+ * Kernels: csrc/sample_int.hip (zoom_mix_int_kernel, iq_mix_int_kernel, iq_pair_mix_int_kernel, each for int16_t and int8_t),
+ * siblings of the f32 mixers with their access scheme and, on a pair, their shared oscillator; csrc/sample_int.h holds the
+ * index map and the unpack-and-scale, and runs on the host in tests/host/sample_int_emul.cpp.  The ABI stays at version 3. */
+#define PSDC_SAMPLE_S16 1 /* int16, native endian */
+#define PSDC_SAMPLE_S8 2  /* int8 */
+/* len real integers into one zoom channel, from host memory / from device memory */
+int psdc_int_zoom_process(psdc_zoom *h, uint32_t channel, const void *x, int kind, float scale, size_t len);
+int psdc_int_zoom_process_device(psdc_zoom *h, uint32_t channel, const void *d_x, int kind, float scale, size_t len,
+                                 void *producer_event);
+/* len real integers of each side into one zoom cross pair (both sides of one kind and scale) */
+int psdc_int_zcsd_process(psdc_zcsd *h, uint32_t pair, const void *xa, const void *xb, int kind, float scale, size_t len);
+int psdc_int_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const void *d_xa, const void *d_xb, int kind, float scale,
+                                 size_t len, void *producer_event);
+/* len interleaved (re, im) integer pairs into one IQ channel */
+int psdc_int_iq_process(psdc_iq *h, uint32_t channel, const void *z, int kind, float scale, size_t len);
+int psdc_int_iq_process_device(psdc_iq *h, uint32_t channel, const void *d_z, int kind, float scale, size_t len,
+                               void *producer_event);
+/* len interleaved (re, im) integer pairs of each side into one IQ cross pair (both sides of one kind and scale) */
+int psdc_int_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const void *za, const void *zb, int kind, float scale, size_t len);
+int psdc_int_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const void *d_za, const void *d_zb, int kind, float scale,
+                                  size_t len, void *producer_event);
 
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */

@@ -425,6 +425,15 @@ def lib():
     f("psdc_iqcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_iqcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_iqcsd_last_error", C.c_char_p, [H])
+    vp, fl = C.c_void_p, C.c_float
+    f("psdc_int_zoom_process", i32, [H, u32, vp, i32, fl, sz])
+    f("psdc_int_zoom_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
+    f("psdc_int_zcsd_process", i32, [H, u32, vp, vp, i32, fl, sz])
+    f("psdc_int_zcsd_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
+    f("psdc_int_iq_process", i32, [H, u32, vp, i32, fl, sz])
+    f("psdc_int_iq_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
+    f("psdc_int_iqcsd_process", i32, [H, u32, vp, vp, i32, fl, sz])
+    f("psdc_int_iqcsd_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
     _lib = L
     return L
 
@@ -469,11 +478,70 @@ EXPORTS = [
     "psdc_iqcsd_process_interleaved", "psdc_iqcsd_process_interleaved_device", "psdc_iqcsd_process_frames",
     "psdc_iqcsd_process_frames_device", "psdc_iqcsd_loss_read", "psdc_iqcsd_sync", "psdc_iqcsd_num_stages",
     "psdc_iqcsd_stage_spectra", "psdc_iqcsd_csd", "psdc_iqcsd_stats_read", "psdc_iqcsd_last_error",
+    "psdc_int_zoom_process", "psdc_int_zoom_process_device", "psdc_int_zcsd_process", "psdc_int_zcsd_process_device",
+    "psdc_int_iq_process", "psdc_int_iq_process_device", "psdc_int_iqcsd_process", "psdc_int_iqcsd_process_device",
 ]
 
 
 def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+class SampleKind(enum.IntEnum):
+    """The integer sample kinds of the psdc_int_* calls (PSDC_SAMPLE_*).  For the complex objects a unit is an interleaved
+    (re, im) pair of the kind's integers: sc16, sc8."""
+    S16 = 1
+    S8 = 2
+
+
+def sample_kind(dtype):
+    """(SampleKind, default scale) of an integer dtype: int16 -> (S16, 2^-15), int8 -> (S8, 2^-7), so full scale maps into
+    [-1, 1).  The one place that maps a dtype to a kind; any other dtype raises ValueError."""
+    dt = np.dtype(dtype)
+    if dt == np.dtype(np.int16):
+        return SampleKind.S16, 2.0 ** -15
+    if dt == np.dtype(np.int8):
+        return SampleKind.S8, 2.0 ** -7
+    raise ValueError(f"integer samples are int16 or int8, not {dt}")
+
+
+def int_samples(x):
+    """(array, kind, default scale) of a real integer stream for process_int: a 1-D C-contiguous int16 or int8 array, taken as
+    it is (never converted or copied); anything else raises ValueError."""
+    if not isinstance(x, np.ndarray):
+        raise ValueError("integer samples are a numpy array of int16 or int8")
+    kind, scale = sample_kind(x.dtype)
+    if x.ndim != 1:
+        raise ValueError(f"a real integer stream is 1-D, not of shape {x.shape}")
+    if not x.flags.c_contiguous:
+        raise ValueError("the integer samples are not contiguous")
+    return x, kind, scale
+
+
+def int_pairs(z):
+    """(array, kind, default scale) of a complex integer stream for process_int: a C-contiguous int16 or int8 array of shape
+    (len, 2) holding (re, im) rows (sc16, sc8), taken as it is; anything else raises ValueError."""
+    if not isinstance(z, np.ndarray):
+        raise ValueError("integer samples are a numpy array of int16 or int8")
+    kind, scale = sample_kind(z.dtype)
+    if z.ndim != 2 or z.shape[1] != 2:
+        raise ValueError(f"a complex integer stream has the shape (len, 2), not {z.shape}")
+    if not z.flags.c_contiguous:
+        raise ValueError("the (re, im) integer pairs are not contiguous")
+    return z, kind, scale
+
+
+def _int_scale(kind, scale):
+    """the kind as the C ABI takes it and the scale (None: the kind's default)"""
+    if scale is None:
+        kind = SampleKind(kind)
+        scale = 2.0 ** -15 if kind == SampleKind.S16 else 2.0 ** -7
+    return int(kind), float(scale)
+
+
+def _same_kind(a, b):
+    if a[0].dtype != b[0].dtype or a[0].shape != b[0].shape:
+        raise ValueError(f"the two sides differ in dtype or shape ({a[0].dtype} {a[0].shape} and {b[0].dtype} {b[0].shape})")
 
 
 def _raise(code, h=None):
@@ -1267,6 +1335,19 @@ class ZoomCascadeBank:
         self._ck(self._L.psdc_zoom_process_device(self._h, channel, C.c_void_p(ptr), length,
                                                   C.c_void_p(after) if after else None))
 
+    def process_int(self, channel, x, scale=None):
+        """x: a 1-D int16 or int8 array, fed as it is; the mixer sees float32(v) * float32(scale) (scale None: 2^-15 for int16,
+        2^-7 for int8) and gives the bits process() gives for that stream."""
+        x, kind, dflt = int_samples(x)
+        self._ck(self._L.psdc_int_zoom_process(self._h, channel, x.ctypes.data_as(C.c_void_p), int(kind),
+                                               dflt if scale is None else float(scale), x.size))
+
+    def process_int_device(self, channel, ptr, length, kind, scale=None, after=None):
+        """ptr: device address of `length` integers of SampleKind `kind`, aligned to the integer; the rest as process_device"""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_int_zoom_process_device(self._h, channel, C.c_void_p(ptr), kind, scale, length,
+                                                      C.c_void_p(after) if after else None))
+
     def process_frames(self, data, frame_size, traces):
         """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the channels: traces[c] is the
         trace channel c takes of every frame (an index or a TRACE_NAMES label), None leaves it unfed; a trace may feed several
@@ -1356,6 +1437,12 @@ class ZoomCascade:
 
     def process_device(self, ptr, length, after=None):
         self._b.process_device(0, ptr, length, after)
+
+    def process_int(self, x, scale=None):
+        self._b.process_int(0, x, scale)
+
+    def process_int_device(self, ptr, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, ptr, length, kind, scale, after)
 
     def process_frames(self, data, frame_size, trace):
         """trace: the trace of the frames the stream is (ZoomCascadeBank.process_frames)"""
@@ -1503,6 +1590,21 @@ class IqCascadeBank:
         self._ck(self._L.psdc_iq_process_interleaved_device(self._h, channel, C.c_void_p(ptr), length,
                                                             C.c_void_p(after) if after else None))
 
+    def process_int(self, channel, z, scale=None):
+        """z: a C-contiguous int16 or int8 array of shape (len, 2), the (re, im) rows of sc16 / sc8, fed as it is; the mixer sees
+        float32(v) * float32(scale) (scale None: 2^-15 for int16, 2^-7 for int8) and gives the bits process() gives for that
+        complex64 stream."""
+        z, kind, dflt = int_pairs(z)
+        self._ck(self._L.psdc_int_iq_process(self._h, channel, z.ctypes.data_as(C.c_void_p), int(kind),
+                                             dflt if scale is None else float(scale), z.shape[0]))
+
+    def process_int_device(self, channel, ptr, length, kind, scale=None, after=None):
+        """ptr: device address of `length` (re, im) integer pairs of SampleKind `kind`, aligned to the pair; the rest as
+        process_device"""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_int_iq_process_device(self._h, channel, C.c_void_p(ptr), kind, scale, length,
+                                                    C.c_void_p(after) if after else None))
+
     def process_device_planar(self, channel, pi, pq, length, after=None):
         """pi, pq: device addresses of `length` f32 samples each, the I and the Q stream (process_device's rules)"""
         self._ck(self._L.psdc_iq_process_device(self._h, channel, C.c_void_p(pi), C.c_void_p(pq), length,
@@ -1598,6 +1700,12 @@ class IqCascade:
 
     def process_device(self, ptr, length, after=None):
         self._b.process_device(0, ptr, length, after)
+
+    def process_int(self, z, scale=None):
+        self._b.process_int(0, z, scale)
+
+    def process_int_device(self, ptr, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, ptr, length, kind, scale, after)
 
     def process_device_planar(self, pi, pq, length, after=None):
         self._b.process_device_planar(0, pi, pq, length, after)
@@ -1729,6 +1837,19 @@ class ZoomCsdCascadeBank:
         self._ck(self._L.psdc_zcsd_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
                                                   C.c_void_p(after) if after else None))
 
+    def process_int(self, pair, x, y, scale=None):
+        """x, y: 1-D int16 or int8 arrays of one dtype and length, fed as they are (ZoomCascadeBank.process_int, a side each)"""
+        a, b = int_samples(x), int_samples(y)
+        _same_kind(a, b)
+        self._ck(self._L.psdc_int_zcsd_process(self._h, pair, a[0].ctypes.data_as(C.c_void_p), b[0].ctypes.data_as(C.c_void_p),
+                                               int(a[1]), a[2] if scale is None else float(scale), a[0].size))
+
+    def process_int_device(self, pair, px, py, length, kind, scale=None, after=None):
+        """px, py: device addresses of `length` integers of SampleKind `kind` each; the rest as process_device"""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_int_zcsd_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), kind, scale, length,
+                                                      C.c_void_p(after) if after else None))
+
     def process_frames(self, data, frame_size, pairs):
         """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] is (x, y),
         the traces sides a and b of pair p take of every frame (indices or TRACE_NAMES labels, pair_map), or None to leave the
@@ -1823,6 +1944,12 @@ class ZoomCsdCascade:
 
     def process_device(self, px, py, length, after=None):
         self._b.process_device(0, px, py, length, after)
+
+    def process_int(self, x, y, scale=None):
+        self._b.process_int(0, x, y, scale)
+
+    def process_int_device(self, px, py, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, px, py, length, kind, scale, after)
 
     def process_frames(self, data, frame_size, pair):
         """pair: (x, y), the traces of the frames the two streams are (ZoomCsdCascadeBank.process_frames)"""
@@ -2000,6 +2127,20 @@ class IqCsdCascadeBank:
         self._ck(self._L.psdc_iqcsd_process_interleaved_device(self._h, pair, C.c_void_p(pa), C.c_void_p(pb), length,
                                                                C.c_void_p(after) if after else None))
 
+    def process_int(self, pair, za, zb, scale=None):
+        """za, zb: C-contiguous int16 or int8 arrays of shape (len, 2) of one dtype and length, the (re, im) rows of each side, fed
+        as they are (IqCascadeBank.process_int, a side each)"""
+        a, b = int_pairs(za), int_pairs(zb)
+        _same_kind(a, b)
+        self._ck(self._L.psdc_int_iqcsd_process(self._h, pair, a[0].ctypes.data_as(C.c_void_p), b[0].ctypes.data_as(C.c_void_p),
+                                                int(a[1]), a[2] if scale is None else float(scale), a[0].shape[0]))
+
+    def process_int_device(self, pair, pa, pb, length, kind, scale=None, after=None):
+        """pa, pb: device addresses of `length` (re, im) integer pairs of SampleKind `kind` each; the rest as process_device"""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_int_iqcsd_process_device(self._h, pair, C.c_void_p(pa), C.c_void_p(pb), kind, scale, length,
+                                                       C.c_void_p(after) if after else None))
+
     def process_device_planar(self, pair, pia, pqa, pib, pqb, length, after=None):
         """pia, pqa, pib, pqb: device addresses of `length` f32 samples each, the I and Q streams of side a and of side b
         (process_device's rules)"""
@@ -2101,6 +2242,12 @@ class IqCsdCascade:
 
     def process_device(self, pa, pb, length, after=None):
         self._b.process_device(0, pa, pb, length, after)
+
+    def process_int(self, za, zb, scale=None):
+        self._b.process_int(0, za, zb, scale)
+
+    def process_int_device(self, pa, pb, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, pa, pb, length, kind, scale, after)
 
     def process_device_planar(self, pia, pqa, pib, pqb, length, after=None):
         self._b.process_device_planar(0, pia, pqa, pib, pqb, length, after)

@@ -26,6 +26,7 @@
 #include "zoom_cross.h"
 #include "iq.h"
 #include "iq_cross.h"
+#include "sample_int.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -475,10 +476,11 @@ int sync_all(XObj *h)
     return free_retired(h);
 }
 
-int check_pair(XObj *h, uint32_t pair)
+// who: the call to name in the text (the integer feeds do); NULL: the object's family
+int check_pair(XObj *h, uint32_t pair, const char *who = nullptr)
 {
     if (pair >= h->n_pairs)
-        return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": " + h->unit + " " + std::to_string(pair) + " out of range (" +
+        return xfail(h, PSDC_ERR_ARG, std::string(who ? who : h->tag) + ": " + h->unit + " " + std::to_string(pair) + " out of range (" +
                                           h->units + " " + std::to_string(h->n_pairs) + ")");
     return PSDC_OK;
 }
@@ -1040,6 +1042,32 @@ int set_avg_impl(XObj *h, uint32_t limit, uint32_t count, const char *who)
     return PSDC_OK;
 }
 
+// The number format of a sample call: f32 (every psdc_*_process call) or the integers of the psdc_int_* calls, which the mixer
+// converts as (float)v * scale (sample_int.h).
+struct SampleFmt {
+    int kind = SAMPLE_F32;
+    float scale = 1.0f;
+    size_t bytes() const { return kind == SAMPLE_F32 ? sizeof(float) : (size_t)sint_bytes(kind); } // of one number
+};
+
+// the psdc_int_* calls' format; the kind and the scale are checked by check_fmt
+SampleFmt int_fmt(int kind, float scale)
+{
+    SampleFmt f;
+    f.kind = kind == PSDC_SAMPLE_S16 ? SAMPLE_S16 : kind == PSDC_SAMPLE_S8 ? SAMPLE_S8 : -1;
+    f.scale = scale;
+    return f;
+}
+
+int check_fmt(XObj *h, const SampleFmt &fmt, const char *who)
+{
+    if (fmt.kind != SAMPLE_F32 && !sint_bytes(fmt.kind))
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": unknown sample kind (PSDC_SAMPLE_S16 or PSDC_SAMPLE_S8)");
+    if (!std::isfinite(fmt.scale))
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the scale is not finite");
+    return PSDC_OK;
+}
+
 // x: h->m pointers (host memory)
 int process_impl(XObj *h, uint32_t pair, const float *const *x, size_t len, const char *who)
 {
@@ -1122,20 +1150,26 @@ int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t 
 // as host frames go) or from device memory.  The mixer stands where psdc_cross_process_device has its copies and under the same
 // event rules: on the copy stream, behind a buffer's growth and round R - 2, and round R waits for it.  Both sources make the
 // same launches on the same data, so the same calls give the same bits from either.
-int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev, void *producer_event, const char *who)
+// fmt: f32 samples, or integers (psdc_int_*: sample_int.h) -- the raw integers take the f32 samples' way (the front of each
+// staging lane and landing lane, pieces of STAGING samples) and the integer mixer converts them in registers, so an integer
+// call makes the launches of the f32 call of the same length.
+int zoom_feed(XObj *h, uint32_t ch, const void *const *xs, SampleFmt fmt, size_t len, bool dev, void *producer_event, const char *who)
 {
     X_HANDLE(h, who);
-    int rc = check_pair(h, ch);
+    int rc = check_pair(h, ch, fmt.kind == SAMPLE_F32 ? nullptr : who);
     if (rc)
+        return rc;
+    if ((rc = check_fmt(h, fmt, who)))
         return rc;
     if (len == 0)
         return PSDC_OK;
     const uint32_t nx = h->reals();
+    const size_t unit = fmt.bytes(); // of one sample
     for (uint32_t c = 0; c < nx; ++c) {
         if (!xs[c])
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-        if ((uintptr_t)xs[c] % sizeof(float))
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to 4 bytes");
+        if ((uintptr_t)xs[c] % unit)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to " + std::to_string(unit) + " bytes");
     }
     X_ON_DEVICE(h);
     if (producer_event)
@@ -1161,8 +1195,8 @@ int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev
             if (h->ev_pending[slot])
                 XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
             for (uint32_t c = 0; c < nx; ++c) {
-                memcpy(h->h_stage[slot] + c * STAGING, xs[c] + done, sizeof(float) * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, h->h_stage[slot] + c * STAGING, sizeof(float) * cnt,
+                memcpy(h->h_stage[slot] + c * STAGING, static_cast<const uint8_t *>(xs[c]) + unit * done, unit * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, h->h_stage[slot] + c * STAGING, unit * cnt,
                                        hipMemcpyHostToDevice, h->copy_stream));
             }
             XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
@@ -1171,15 +1205,17 @@ int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev
         }
         const size_t at = (size_t)(s->total + done - s->buf.base);
         for (uint32_t c = 0; c < nx; ++c) { // one mixer a channel
-            ZoomMixJob mj{};
-            mj.x = dev ? xs[c] + done : h->d_land + c * STAGING;
-            mj.dst_i = s->buf.p[2 * c][s->buf.cur] + at;
-            mj.dst_q = s->buf.p[2 * c + 1][s->buf.cur] + at;
-            mj.len = cnt;
-            mj.j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
-            mj.ftw = h->ftw[(size_t)nx * ch + c];
-            mj.phase0 = h->phase0[(size_t)nx * ch + c];
-            XCHK(h, launch_zoom_mix(mj, h->copy_stream));
+            const void *src = dev ? static_cast<const void *>(static_cast<const uint8_t *>(xs[c]) + unit * done) : h->d_land + c * STAGING;
+            float *dst_i = s->buf.p[2 * c][s->buf.cur] + at, *dst_q = s->buf.p[2 * c + 1][s->buf.cur] + at;
+            const uint64_t j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
+            const uint64_t ftw = h->ftw[(size_t)nx * ch + c], phase0 = h->phase0[(size_t)nx * ch + c];
+            if (fmt.kind == SAMPLE_F32) {
+                const ZoomMixJob mj{static_cast<const float *>(src), dst_i, dst_q, cnt, j0, ftw, phase0};
+                XCHK(h, launch_zoom_mix(mj, h->copy_stream));
+            } else {
+                const SintMixJob mj{src, dst_i, dst_q, cnt, j0, ftw, phase0, fmt.scale};
+                XCHK(h, launch_zoom_mix_int(mj, fmt.kind, h->copy_stream));
+            }
             ++h->launches;
         }
         done += cnt;
@@ -1197,21 +1233,25 @@ int zoom_feed(XObj *h, uint32_t ch, const float *const *xs, size_t len, bool dev
 // NULL: src_i points to (re, im) pairs, 8-byte aligned), from host memory (up through the pinned staging into the landing buffer)
 // or from device memory.  zoom_feed with the complex mixer in place of the real one: the same stream, the same events, and the
 // same launches on the same data from either memory, so all four routes give the same bits for the same calls.
-int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool interleaved, size_t len, bool dev, void *producer_event,
-            const char *who)
+// fmt: f32, or integers (psdc_int_*: always interleaved, src_i points to the (re, im) integer pairs) as in zoom_feed.
+int iq_feed(XObj *h, uint32_t ch, const void *src_i_, const float *src_q, bool interleaved, SampleFmt fmt, size_t len, bool dev,
+            void *producer_event, const char *who)
 {
     X_HANDLE(h, who);
-    int rc = check_pair(h, ch);
+    int rc = check_pair(h, ch, fmt.kind == SAMPLE_F32 ? nullptr : who);
     if (rc)
+        return rc;
+    if ((rc = check_fmt(h, fmt, who)))
         return rc;
     if (len == 0)
         return PSDC_OK;
-    if (!src_i || (!interleaved && !src_q))
+    const float *src_i = static_cast<const float *>(src_i_); // (f32 only)
+    const size_t unit = 2 * fmt.bytes();                     // of one interleaved complex sample
+    if (!src_i_ || (!interleaved && !src_q))
         return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-    if (interleaved ? (uintptr_t)src_i % (2 * sizeof(float)) != 0
-                    : (uintptr_t)src_i % sizeof(float) != 0 || (uintptr_t)src_q % sizeof(float) != 0)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to 8 bytes"
-                                                                      : ": the samples are not aligned to 4 bytes"));
+    if (interleaved ? (uintptr_t)src_i_ % unit != 0 : (uintptr_t)src_i % sizeof(float) != 0 || (uintptr_t)src_q % sizeof(float) != 0)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to " + std::to_string(unit) + " bytes"
+                                                                      : std::string(": the samples are not aligned to 4 bytes")));
     X_ON_DEVICE(h);
     if (producer_event)
         XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
@@ -1236,9 +1276,9 @@ int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool i
             if (h->ev_pending[slot])
                 XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
             float *stg = h->h_stage[slot];
-            if (interleaved) { // the pairs as they are: 2 cnt floats at the front of the slot and of the landing buffer
-                memcpy(stg, src_i + 2 * done, sizeof(float) * 2 * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land, stg, sizeof(float) * 2 * cnt, hipMemcpyHostToDevice, h->copy_stream));
+            if (interleaved) { // the pairs as they are: cnt units at the front of the slot and of the landing buffer
+                memcpy(stg, static_cast<const uint8_t *>(src_i_) + unit * done, unit * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land, stg, unit * cnt, hipMemcpyHostToDevice, h->copy_stream));
             } else {
                 memcpy(stg, src_i + done, sizeof(float) * cnt);
                 memcpy(stg + STAGING, src_q + done, sizeof(float) * cnt);
@@ -1251,6 +1291,15 @@ int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool i
             h->stage_cur ^= 1;
         }
         const size_t at = (size_t)(s->total + done - s->buf.base);
+        if (fmt.kind != SAMPLE_F32) {
+            const void *src = dev ? static_cast<const void *>(static_cast<const uint8_t *>(src_i_) + unit * done) : h->d_land;
+            const SintMixJob ij{src, s->buf.p[0][s->buf.cur] + at, s->buf.p[1][s->buf.cur] + at, cnt, s->total + done, h->ftw[ch],
+                                h->phase0[ch], fmt.scale};
+            XCHK(h, launch_iq_mix_int(ij, fmt.kind, h->copy_stream));
+            ++h->launches;
+            done += cnt;
+            continue;
+        }
         IqMixJob mj{};
         if (interleaved) {
             mj.src_i = dev ? src_i + 2 * done : h->d_land;
@@ -1282,21 +1331,26 @@ int iq_feed(XObj *h, uint32_t ch, const float *src_i, const float *src_q, bool i
 // host memory (up through the pinned staging into the landing buffer) or from device memory.  iq_feed with the pair mixer in place
 // of the complex one: the same stream, the same events, ONE mixer launch a piece for both sides, and the same launches on the same
 // data from either memory, so all four routes give the same bits for the same calls.
-int iq_pair_feed(XObj *h, uint32_t pair, const float *const (&src)[4], bool interleaved, size_t len, bool dev, void *producer_event,
-                 const char *who)
+// fmt: f32, or integers (psdc_int_*: always interleaved, src[0] and src[2] point to the sides' (re, im) integer pairs) as in
+// zoom_feed.
+int iq_pair_feed(XObj *h, uint32_t pair, const void *const (&src)[4], bool interleaved, SampleFmt fmt, size_t len, bool dev,
+                 void *producer_event, const char *who)
 {
     X_HANDLE(h, who);
-    int rc = check_pair(h, pair);
+    int rc = check_pair(h, pair, fmt.kind == SAMPLE_F32 ? nullptr : who);
     if (rc)
+        return rc;
+    if ((rc = check_fmt(h, fmt, who)))
         return rc;
     if (len == 0)
         return PSDC_OK;
+    const size_t unit = (interleaved ? 2 : 1) * fmt.bytes(); // of one sample of a stream: a pair, or one f32
     for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
         if (!src[c])
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-        if ((uintptr_t)src[c] % (interleaved ? 2 * sizeof(float) : sizeof(float)) != 0)
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to 8 bytes"
-                                                                          : ": the samples are not aligned to 4 bytes"));
+        if ((uintptr_t)src[c] % unit != 0)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to " + std::to_string(unit) + " bytes"
+                                                                          : std::string(": the samples are not aligned to 4 bytes")));
     }
     X_ON_DEVICE(h);
     if (producer_event)
@@ -1324,29 +1378,45 @@ int iq_pair_feed(XObj *h, uint32_t pair, const float *const (&src)[4], bool inte
             float *stg = h->h_stage[slot];
             // planar: stream c in lane c; interleaved: side a's pairs in lanes 0 and 1, side b's in lanes 2 and 3, as they are
             for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
-                const size_t w = interleaved ? 2 : 1;
-                memcpy(stg + c * STAGING, src[c] + w * done, sizeof(float) * w * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, stg + c * STAGING, sizeof(float) * w * cnt, hipMemcpyHostToDevice,
-                                       h->copy_stream));
+                memcpy(stg + c * STAGING, static_cast<const uint8_t *>(src[c]) + unit * done, unit * cnt);
+                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, stg + c * STAGING, unit * cnt, hipMemcpyHostToDevice, h->copy_stream));
             }
             XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
             h->ev_pending[slot] = true;
             h->stage_cur ^= 1;
         }
         const size_t at = (size_t)(s->total + done - s->buf.base);
-        IqPairMixJob mj{};
-        for (int c = 0; c < 4; ++c) {
-            if (!interleaved || !(c & 1))
-                mj.src[c] = dev ? src[c] + (interleaved ? 2 : 1) * done : h->d_land + c * STAGING;
-            mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
+        const void *from[4] = {};
+        for (int c = 0; c < 4; c += interleaved ? 2 : 1)
+            from[c] = dev ? static_cast<const void *>(static_cast<const uint8_t *>(src[c]) + unit * done) : h->d_land + c * STAGING;
+        const uint64_t j0 = s->total + done; // the stream index: complex samples each side has taken since create or reset
+        if (fmt.kind == SAMPLE_F32) {
+            IqPairMixJob mj{};
+            for (int c = 0; c < 4; ++c) {
+                mj.src[c] = static_cast<const float *>(from[c]);
+                mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
+            }
+            mj.len = cnt;
+            mj.j0 = j0;
+            for (int side = 0; side < 2; ++side) {
+                mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
+                mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
+            }
+            XCHK(h, launch_iq_pair_mix(mj, interleaved, h->copy_stream));
+        } else {
+            SintPairMixJob mj{};
+            for (int c = 0; c < 4; ++c)
+                mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
+            mj.len = cnt;
+            mj.j0 = j0;
+            mj.scale = fmt.scale;
+            for (int side = 0; side < 2; ++side) {
+                mj.src[side] = from[2 * side];
+                mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
+                mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
+            }
+            XCHK(h, launch_iq_pair_mix_int(mj, fmt.kind, h->copy_stream));
         }
-        mj.len = cnt;
-        mj.j0 = s->total + done; // the stream index: complex samples each side has taken since create or reset
-        for (int side = 0; side < 2; ++side) {
-            mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
-            mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
-        }
-        XCHK(h, launch_iq_pair_mix(mj, interleaved, h->copy_stream));
         ++h->launches;
         done += cnt;
     }
@@ -1946,12 +2016,14 @@ int psdc_zoom_set_carrier(psdc_zoom *h, uint32_t channel, uint64_t ftw, uint64_t
 
 int psdc_zoom_process(psdc_zoom *h, uint32_t channel, const float *x, size_t len)
 {
-    return zoom_feed(h, channel, &x, len, false, nullptr, "psdc_zoom_process");
+    const void *xs[1] = {x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, false, nullptr, "psdc_zoom_process");
 }
 
 int psdc_zoom_process_device(psdc_zoom *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
 {
-    return zoom_feed(h, channel, &d_x, len, true, producer_event, "psdc_zoom_process_device");
+    const void *xs[1] = {d_x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, true, producer_event, "psdc_zoom_process_device");
 }
 
 int psdc_zoomcascade_process_frames(psdc_zoom *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
@@ -2022,22 +2094,22 @@ int psdc_iq_set_carrier(psdc_iq *h, uint32_t channel, uint64_t ftw, uint64_t pha
 
 int psdc_iq_process(psdc_iq *h, uint32_t channel, const float *i, const float *q, size_t len)
 {
-    return iq_feed(h, channel, i, q, false, len, false, nullptr, "psdc_iq_process");
+    return iq_feed(h, channel, i, q, false, SampleFmt{}, len, false, nullptr, "psdc_iq_process");
 }
 
 int psdc_iq_process_device(psdc_iq *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event)
 {
-    return iq_feed(h, channel, d_i, d_q, false, len, true, producer_event, "psdc_iq_process_device");
+    return iq_feed(h, channel, d_i, d_q, false, SampleFmt{}, len, true, producer_event, "psdc_iq_process_device");
 }
 
 int psdc_iq_process_interleaved(psdc_iq *h, uint32_t channel, const float *iq, size_t len)
 {
-    return iq_feed(h, channel, iq, nullptr, true, len, false, nullptr, "psdc_iq_process_interleaved");
+    return iq_feed(h, channel, iq, nullptr, true, SampleFmt{}, len, false, nullptr, "psdc_iq_process_interleaved");
 }
 
 int psdc_iq_process_interleaved_device(psdc_iq *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event)
 {
-    return iq_feed(h, channel, d_iq, nullptr, true, len, true, producer_event, "psdc_iq_process_interleaved_device");
+    return iq_feed(h, channel, d_iq, nullptr, true, SampleFmt{}, len, true, producer_event, "psdc_iq_process_interleaved_device");
 }
 
 int psdc_iq_process_frames(psdc_iq *h, const uint32_t *channel_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
@@ -2115,14 +2187,14 @@ int psdc_zcsd_set_carrier(psdc_zcsd *h, uint32_t pair, uint32_t side, uint64_t f
 
 int psdc_zcsd_process(psdc_zcsd *h, uint32_t pair, const float *x, const float *y, size_t len)
 {
-    const float *xs[2] = {x, y};
-    return zoom_feed(h, pair, xs, len, false, nullptr, "psdc_zcsd_process");
+    const void *xs[2] = {x, y};
+    return zoom_feed(h, pair, xs, SampleFmt{}, len, false, nullptr, "psdc_zcsd_process");
 }
 
 int psdc_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const float *d_x, const float *d_y, size_t len, void *producer_event)
 {
-    const float *xs[2] = {d_x, d_y};
-    return zoom_feed(h, pair, xs, len, true, producer_event, "psdc_zcsd_process_device");
+    const void *xs[2] = {d_x, d_y};
+    return zoom_feed(h, pair, xs, SampleFmt{}, len, true, producer_event, "psdc_zcsd_process_device");
 }
 
 int psdc_zcsd_sync(psdc_zcsd *h) { return sync_impl(h, "psdc_zcsd_sync"); }
@@ -2206,28 +2278,28 @@ int psdc_iqcsd_set_carrier(psdc_iqcsd *h, uint32_t pair, uint32_t side, uint64_t
 
 int psdc_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const float *ia, const float *qa, const float *ib, const float *qb, size_t len)
 {
-    const float *const src[4] = {ia, qa, ib, qb};
-    return iq_pair_feed(h, pair, src, false, len, false, nullptr, "psdc_iqcsd_process");
+    const void *const src[4] = {ia, qa, ib, qb};
+    return iq_pair_feed(h, pair, src, false, SampleFmt{}, len, false, nullptr, "psdc_iqcsd_process");
 }
 
 int psdc_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const float *d_ia, const float *d_qa, const float *d_ib, const float *d_qb,
                               size_t len, void *producer_event)
 {
-    const float *const src[4] = {d_ia, d_qa, d_ib, d_qb};
-    return iq_pair_feed(h, pair, src, false, len, true, producer_event, "psdc_iqcsd_process_device");
+    const void *const src[4] = {d_ia, d_qa, d_ib, d_qb};
+    return iq_pair_feed(h, pair, src, false, SampleFmt{}, len, true, producer_event, "psdc_iqcsd_process_device");
 }
 
 int psdc_iqcsd_process_interleaved(psdc_iqcsd *h, uint32_t pair, const float *za, const float *zb, size_t len)
 {
-    const float *const src[4] = {za, nullptr, zb, nullptr};
-    return iq_pair_feed(h, pair, src, true, len, false, nullptr, "psdc_iqcsd_process_interleaved");
+    const void *const src[4] = {za, nullptr, zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, SampleFmt{}, len, false, nullptr, "psdc_iqcsd_process_interleaved");
 }
 
 int psdc_iqcsd_process_interleaved_device(psdc_iqcsd *h, uint32_t pair, const float *d_za, const float *d_zb, size_t len,
                                           void *producer_event)
 {
-    const float *const src[4] = {d_za, nullptr, d_zb, nullptr};
-    return iq_pair_feed(h, pair, src, true, len, true, producer_event, "psdc_iqcsd_process_interleaved_device");
+    const void *const src[4] = {d_za, nullptr, d_zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, SampleFmt{}, len, true, producer_event, "psdc_iqcsd_process_interleaved_device");
 }
 
 int psdc_iqcsd_process_frames(psdc_iqcsd *h, const uint32_t *pair_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
@@ -2265,5 +2337,55 @@ int psdc_iqcsd_stats_read(psdc_iqcsd *h, uint64_t *launches, uint64_t *pairs_in,
 }
 
 const char *psdc_iqcsd_last_error(const psdc_iqcsd *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- integer sample feeds (include/psdcascade.h, "integer sample feeds"): the objects' feeds with an integer SampleFmt ----
+
+int psdc_int_zoom_process(psdc_zoom *h, uint32_t channel, const void *x, int kind, float scale, size_t len)
+{
+    const void *xs[1] = {x};
+    return zoom_feed(h, channel, xs, int_fmt(kind, scale), len, false, nullptr, "psdc_int_zoom_process");
+}
+
+int psdc_int_zoom_process_device(psdc_zoom *h, uint32_t channel, const void *d_x, int kind, float scale, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return zoom_feed(h, channel, xs, int_fmt(kind, scale), len, true, producer_event, "psdc_int_zoom_process_device");
+}
+
+int psdc_int_zcsd_process(psdc_zcsd *h, uint32_t pair, const void *xa, const void *xb, int kind, float scale, size_t len)
+{
+    const void *xs[2] = {xa, xb};
+    return zoom_feed(h, pair, xs, int_fmt(kind, scale), len, false, nullptr, "psdc_int_zcsd_process");
+}
+
+int psdc_int_zcsd_process_device(psdc_zcsd *h, uint32_t pair, const void *d_xa, const void *d_xb, int kind, float scale, size_t len,
+                                 void *producer_event)
+{
+    const void *xs[2] = {d_xa, d_xb};
+    return zoom_feed(h, pair, xs, int_fmt(kind, scale), len, true, producer_event, "psdc_int_zcsd_process_device");
+}
+
+int psdc_int_iq_process(psdc_iq *h, uint32_t channel, const void *z, int kind, float scale, size_t len)
+{
+    return iq_feed(h, channel, z, nullptr, true, int_fmt(kind, scale), len, false, nullptr, "psdc_int_iq_process");
+}
+
+int psdc_int_iq_process_device(psdc_iq *h, uint32_t channel, const void *d_z, int kind, float scale, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_z, nullptr, true, int_fmt(kind, scale), len, true, producer_event, "psdc_int_iq_process_device");
+}
+
+int psdc_int_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const void *za, const void *zb, int kind, float scale, size_t len)
+{
+    const void *const src[4] = {za, nullptr, zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, int_fmt(kind, scale), len, false, nullptr, "psdc_int_iqcsd_process");
+}
+
+int psdc_int_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const void *d_za, const void *d_zb, int kind, float scale, size_t len,
+                                  void *producer_event)
+{
+    const void *const src[4] = {d_za, nullptr, d_zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, int_fmt(kind, scale), len, true, producer_event, "psdc_int_iqcsd_process_device");
+}
 
 } // extern "C"

@@ -47,6 +47,12 @@ ceiling: the same round, half the bytes read) is ZoomCsdCascadeBank(n, 1) fed tw
 two interleaved complex64 streams; leg C is what a user did before: CsmCascadeBank(n, 4, 1) fed the four planar streams (N <= 2048
 only, and it cannot retune).  A, B, A, C in turn --reps times in one session; B / A, B / C, the largest |A' - A| / A and B's launches
 a call are recorded as findings, none is a gate.  Writes profiles/iq_cross_probe.json unless --out names another file.
+--iq --int [--pair]: the integer feed against the f32 feed of the same stream (sc16, scale 2^-15) at N = 512, 1024, 4096.  Host
+memory, 2^22 units a call: leg A is IqCascadeBank(n, 1) (--pair: IqCsdCascadeBank(n, 1)) fed interleaved complex64, leg B the same
+object kind fed the sc16 stream whose conversion A's is -- half the bytes over the host link.  Device memory, 2^24 units a call:
+legs C (complex64) and D (sc16).  A, B, A and C, D, C in turn --reps times in one session; the rates, B / A, D / C, the largest
+|A' - A| / A and |C' - C| / C and the launches a call of B and D are recorded as findings, none is a gate.  Writes
+profiles/iq_int_probe.json (--pair: its "pair" entry; the file holds one entry a flavour) unless --out names another file.
 """
 import argparse
 import json
@@ -396,6 +402,74 @@ def iq_pair_legs(pkg, torch, seconds, reps, call):
     return legs
 
 
+def iq_int_legs(pkg, torch, seconds, reps, pair):
+    """The sc16 feed against the complex64 feed of the same stream, from host memory (2^22 units a call) and from device memory
+    (2^24 units a call): A / B / A and C / D / C in turn.  pair: IqCsdCascadeBank and two streams, else IqCascadeBank and one."""
+    host_call, dev_call = 1 << 22, 1 << 24
+    rng = np.random.default_rng(7)
+    sides = 2 if pair else 1
+    kind, scale = pkg.sample_kind(np.int16)
+    ints = [np.clip(np.rint(rng.standard_normal((dev_call, 2)) * 6000.0), -32768, 32767).astype(np.int16) for _ in range(sides)]
+    f32 = [np.ascontiguousarray(v.astype(np.float32) * np.float32(scale)).view(np.complex64).reshape(-1) for v in ints]
+    d_int = [torch.from_numpy(v).cuda() for v in ints]
+    d_f32 = [torch.from_numpy(z).cuda() for z in f32]
+    torch.cuda.synchronize()
+    h_int, h_f32 = [v[:host_call] for v in ints], [z[:host_call] for z in f32]
+    cls = pkg.IqCsdCascadeBank if pair else pkg.IqCascadeBank
+    legs = []
+    for n in (512, 1024, 4096):
+        objs = {k: cls(n, 1) for k in "abcd"}
+        for o in objs.values():
+            o.set_carrier(0, f0=0.2)
+
+        def a_step():
+            objs["a"].process(0, *h_f32)
+            return host_call
+
+        def b_step():
+            objs["b"].process_int(0, *h_int)
+            return host_call
+
+        def c_step():
+            objs["c"].process_device(0, *[t.data_ptr() for t in d_f32], dev_call)
+            return dev_call
+
+        def d_step():
+            objs["d"].process_int_device(0, *[t.data_ptr() for t in d_int], dev_call, kind)
+            return dev_call
+
+        a1, b, a2, c1, d, c2 = [], [], [], [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, objs["a"].sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, objs["b"].sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, objs["a"].sync, seconds)[0] / 1e9)
+        for _ in range(reps):
+            c1.append(timed(c_step, objs["c"].sync, seconds)[0] / 1e9)
+            d.append(timed(d_step, objs["d"].sync, seconds)[0] / 1e9)
+            c2.append(timed(c_step, objs["c"].sync, seconds)[0] / 1e9)
+        launches = {}
+        for k, step in (("a", a_step), ("b", b_step), ("c", c_step), ("d", d_step)):
+            objs[k].stats_read(reset=True)
+            for _ in range(8):
+                step()
+            launches[k] = objs[k].stats_read()["launches"] / 8
+            objs[k].sync()
+        ba = [v / u for u, v in zip(a1, b)]
+        dc = [v / u for u, v in zip(c1, d)]
+        aa = max(abs(v - u) / u for u, v in zip(a1, a2))
+        cc = max(abs(v - u) / u for u, v in zip(c1, c2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "host_call": host_call, "device_call": dev_call, "a_host_complex64_gs_s": r3(a1), "b_host_sc16_gs_s": r3(b),
+                     "a_again_gs_s": r3(a2), "c_device_complex64_gs_s": r3(c1), "d_device_sc16_gs_s": r3(d), "c_again_gs_s": r3(c2),
+                     "ratio_b_over_a": r3(ba), "ratio_d_over_c": r3(dc), "b_over_a_min": round(min(ba), 3),
+                     "d_over_c_min": round(min(dc), 3), "d_over_c_max": round(max(dc), 3), "aa_spread_max": round(aa, 4),
+                     "cc_spread_max": round(cc, 4), "b_beats_a": bool(min(ba) > 1 + aa), "d_beats_c": bool(min(dc) > 1 + cc),
+                     "launches_per_call": launches, "stages": objs["d"].num_stages(0)})
+        for o in objs.values():
+            o.close()
+    return legs
+
+
 def zoom_pair_image(pkg, torch, n=1024, k=2, b=100, f0=0.2, length=1 << 20):
     """A tone at f0 + delta (delta the centre of bin b of stage k) on both channels, b's at 0.7 of a's and 1 rad behind:
     |S_ab lower[b]| / |S_ab upper[b]| at stage k from the zoom cross object, and the same rebuilt from a matrix object fed the
@@ -705,9 +779,33 @@ def main():
                                                       "and CsdCascadeBank fed the planar (I, Q); with --pair: IqCsdCascadeBank fed two "
                                                       "complex64 streams against ZoomCsdCascadeBank fed two real streams (a ceiling) "
                                                       "and CsmCascadeBank(n, 4) fed the four planar streams")
+    ap.add_argument("--int", dest="int_feed", action="store_true", help="with --iq [--pair]: the sc16 feed against the complex64 feed of "
+                                                                        "the same stream, host-fed and device-resident")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.iq and a.int_feed:
+        before = gpu_state()
+        legs = iq_int_legs(pkg, torch, a.seconds, a.reps, a.pair)
+        entry_ = {"metric": "iq_int_gsamples_s", "object": "IqCsdCascadeBank" if a.pair else "IqCascadeBank",
+                  "unit": "1e9 complex samples a second" + (" of each side" if a.pair else ""),
+                  "gpu_before": before, "gpu_after": gpu_state(),
+                  "note": "findings, no gate: B moves 4 bytes a complex sample over the host link where A moves 8, so B / A can be at most "
+                          "about 2; the mixer runs beside the previous round, so D / C is expected near 1; not measured here: s8, the "
+                          "real objects, banks, two different carriers with --pair (the shared-oscillator branch runs)",
+                  "legs": legs}
+        path = a.out or os.path.join(ROOT, "profiles", "iq_int_probe.json")
+        try:
+            with open(path) as f:
+                record = json.load(f)
+        except (OSError, ValueError):
+            record = {}
+        record["pair" if a.pair else "single"] = entry_
+        line = json.dumps(record)
+        print(json.dumps(entry_))
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.iq and a.pair:
         before = gpu_state()
         legs = iq_pair_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)

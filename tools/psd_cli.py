@@ -20,7 +20,12 @@ offset,upper,lower (the density of z at F0 + offset / F0 - offset; half of it is
 --iq-pair IA:QA:IB:QB[:F0] (repeatable) feeds the two complex streams IA + i QA and IB + i QB to an IqCsdCascade(512), both retuned by
 the one carrier F0 (default 0).  Traces of the frames with --file, four raw f32 files of equal length without it, as for --iq.
 Prints, or with --csv writes to DIR/iqpair_<ia>__<qa>__<ib>__<qb>_<F0>.csv, the lines of --zoom-pair:
-offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b."""
+offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b.
+--sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
+integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
+then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
+FILE[:F0] and --iq-pair FILEA:FILEB[:F0] files of interleaved (re, im) integer pairs (sc16 / sc8, an SDR's native output).  The
+printed lines and the --csv files are those of the f32 options."""
 import argparse
 import os
 import sys
@@ -57,7 +62,18 @@ def main(argv=None):
                     help="I:Q[:F0] -- two-sided spectrum of the complex stream I + i Q, retuned by F0 (repeatable)")
     ap.add_argument("--iq-pair", action="append", default=[],
                     help="IA:QA:IB:QB[:F0] -- two-sided auto and cross spectra of two complex streams, retuned by F0 (repeatable)")
+    ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
+                    help="s16 / s8: --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
+    ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
     a = ap.parse_args(argv)
+    if a.sample_format != "f32":
+        if a.file or a.raw or a.pair or not (a.zoom or a.zoom_pair or a.iq or a.iq_pair):
+            raise SystemExit("--sample-format s16 / s8 takes --zoom, --zoom-pair, --iq or --iq-pair with raw integer files, and no "
+                             "--file, --raw or --pair")
+        import __graft_entry__ as entry
+        return int_feeds(entry.load_package(), a)
+    if a.scale is not None:
+        raise SystemExit("--scale needs --sample-format s16 or s8")
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
     import __graft_entry__ as entry
@@ -365,6 +381,104 @@ def iq_pairs(pkg, source, a, merge, names):
         else:
             sys.stdout.writelines(lines)
     bank.close()
+
+
+def int_feeds(pkg, a):
+    """--sample-format s16 / s8: raw integer files through process_int, 2^20 units a call; one object per option given"""
+    dtype = np.dtype("<i2" if a.sample_format == "s16" else "i1")
+    merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
+    if a.csv:
+        os.makedirs(a.csv, exist_ok=True)
+
+    def settle(bank):
+        bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+        bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+        return bank
+
+    def feed(files, per_unit, opt, process):
+        """the files in step, 2^20 units a read; per_unit integers a unit (2: interleaved pairs)"""
+        if len({os.path.getsize(f) for f in files}) != 1:
+            raise SystemExit(f"{opt}: " + ", ".join(files) + " differ in length")
+        if os.path.getsize(files[0]) % (per_unit * dtype.itemsize):
+            raise SystemExit(f"{opt}: {files[0]} does not hold whole units of {per_unit * dtype.itemsize} bytes")
+        fh = [open(f, "rb") for f in files]
+        fed = 0
+        while a.max_bytes is None or fed < a.max_bytes:
+            xs = [np.fromfile(f, dtype, per_unit << 20) for f in fh]
+            if xs[0].size == 0:
+                break
+            process([x.reshape(-1, 2) if per_unit == 2 else x for x in xs])
+            fed += xs[0].nbytes
+        for f in fh:
+            f.close()
+
+    def emit(name, lines):
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in name)
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+
+    def single(bank, label, stem):
+        if bank.num_stages(0) == 0:
+            print(f"{label}: no samples")
+            return
+        up, lo, breaks = bank.psd(0, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        print(f"{label}: stages {bank.num_stages(0)} bins {up.size} breaks {len(breaks)}")
+        emit(stem, [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)])
+
+    def pair(bank, label, stem):
+        if bank.num_stages(0) == 0:
+            print(f"{label}: no samples")
+            return
+        aup, alo, bup, blo, xup, xlo, breaks = bank.csd(0, merge)
+        off = pkg.Break.frequencies(breaks) * a.fs
+        coh = pkg.coherence(aup, bup, xup)
+        print(f"{label}: stages {bank.num_stages(0)} bins {aup.size} breaks {len(breaks)} median coherence (upper) {np.nanmedian(coh):.6g}")
+        emit(stem, [f"{o:.9g},{p:.9g},{q:.9g},{u.real:.9g},{u.imag:.9g},{r:.9g},{t:.9g},{w.real:.9g},{w.imag:.9g}\n"
+                    for o, p, q, u, r, t, w in zip(off, aup, bup, xup, alo, blo, xlo)])
+
+    for z in a.zoom:
+        f0, _, path = z.partition(":")
+        if not path:
+            raise SystemExit("--zoom takes F0:FILE with --sample-format s16 / s8")
+        bank = settle(pkg.ZoomCascadeBank(1 << 9, 1))
+        used = bank.set_carrier(0, f0=float(f0))
+        feed([path], 1, "--zoom", lambda xs: bank.process_int(0, xs[0], a.scale))
+        base = os.path.basename(path)
+        single(bank, f"zoom {base} @ {used:.12g}", f"zoom_{base}_{used:.9g}")
+        bank.close()
+    for z in a.zoom_pair:
+        parts = z.split(":")
+        if len(parts) != 3 or not all(parts):
+            raise SystemExit("--zoom-pair takes F0:FILEA:FILEB with --sample-format s16 / s8")
+        bank = settle(pkg.ZoomCsdCascadeBank(1 << 9, 1))
+        used = bank.set_carrier(0, f0=float(parts[0]))
+        feed(parts[1:], 1, "--zoom-pair", lambda xs: bank.process_int(0, xs[0], xs[1], a.scale))
+        x, y = (os.path.basename(f) for f in parts[1:])
+        pair(bank, f"zoom pair {x}:{y} @ {used:.12g}", f"zoompair_{x}__{y}_{used:.9g}")
+        bank.close()
+    for z in a.iq:
+        path, _, f0 = z.partition(":")
+        bank = settle(pkg.IqCascadeBank(1 << 9, 1))
+        used = bank.set_carrier(0, f0=float(f0) if f0 else 0.0)
+        feed([path], 2, "--iq", lambda xs: bank.process_int(0, xs[0], a.scale))
+        base = os.path.basename(path)
+        single(bank, f"iq {base} @ {used:.12g}", f"iq_{base}_{used:.9g}")
+        bank.close()
+    for z in a.iq_pair:
+        parts = z.split(":")
+        if len(parts) not in (2, 3) or not all(parts[:2]):
+            raise SystemExit("--iq-pair takes FILEA:FILEB[:F0] with --sample-format s16 / s8")
+        bank = settle(pkg.IqCsdCascadeBank(1 << 9, 1))
+        used = bank.set_carrier(0, f0=float(parts[2]) if len(parts) == 3 else 0.0)
+        feed(parts[:2], 2, "--iq-pair", lambda xs: bank.process_int(0, xs[0], xs[1], a.scale))
+        x, y = (os.path.basename(f) for f in parts[:2])
+        pair(bank, f"iq pair {x}:{y} @ {used:.12g}", f"iqpair_{x}__{y}_{used:.9g}")
+        bank.close()
+    return 0
 
 
 if __name__ == "__main__":
