@@ -1098,6 +1098,48 @@ int psdc_int_iqcsd_process(psdc_iqcsd *h, uint32_t pair, const void *za, const v
 int psdc_int_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const void *d_za, const void *d_zb, int kind, float scale,
                                   size_t len, void *producer_event);
 
+/* ---- integer sample feeds of the real-input objects: int16 / int8 samples into the PSD, pair and matrix objects (s16 / s8) --
+ * The three objects with no mixer in front of stage 0 (psdc_handle, psdc_cross, psdc_csm) take the same integers under the rule
+ * of the section above: kinds PSDC_SAMPLE_S16 / PSDC_SAMPLE_S8, one integer a unit, `len` counts units, the f32 sample the
+ * object sees is (float)v * scale as defined there, and the arguments behave as stated there (pointers aligned to the integer,
+ * a finite scale, an unknown kind, NULL with len > 0: PSDC_ERR_ARG; len == 0: PSDC_OK; a failed call leaves the object as it
+ * was; the error text names the call and goes through psdc_last_error / psdc_cross_last_error / psdc_csm_last_error).
+ * With no mixer to read the integers, a converter (csrc/sample_int.hip, sample_cvt_int_kernel for int16_t and int8_t: the
+ * mixers' access scheme without the oscillator, one launch for the 1 ... 4 channels of a call) writes the f32 samples into the
+ * stage-0 stream buffers exactly where the f32 call's copy writes them.
+ * Pair and matrix: an integer call gives bit for bit what the f32 call (psdc_cross_process[_device], psdc_csm_process[_device])
+ * of float32(v) * float32(scale) gives, from the same memory side, on the same object state, in every row of every stage;
+ * integer, f32 and frames calls mix on one pair or group in any order.  Host calls carry the raw integers through the pinned
+ * staging into a landing buffer (m 2^22 floats, made by the first such call) in the f32 call's pieces of 2^22 units: per piece
+ * the m copies and ONE converter launch, so a steady host call makes the f32 call's launches (3 a round) + 1 a piece, 4 for a
+ * call of at most 2^22 units.  A device call has ONE converter launch on the copy stream where the f32 call has its m copies,
+ * under the same event rules (3 + 1 launches a steady call); the caller's memory is read by that launch alone, so stream ordering,
+ * producer_event and lifetimes are those of the f32 device call.  psdc_cross_stats_read / psdc_csm_stats_read count the converter.
+ * PSD object, host: psdc_sint_process follows psdc_process step for step -- the same pinned staging holding the raw integers,
+ * the same quantum counted in samples, the same fast path (a bounds check and a memcpy while the staged samples stay below the
+ * quantum).  A staged fill of integers is uploaded into a landing buffer of the handle (2 quantum bytes, made by the first such
+ * upload) and converted on the copy stream into the place the f32 upload writes.  A call whose (kind, scale) differs from what
+ * the channel's staging holds -- f32 against integers, s16 against s8, another scale -- submits the staged samples first.  So
+ * a stream fed with ONE (kind, scale) gives the BITS of psdc_process fed float32(v) * float32(scale) in the same call sizes;
+ * where kinds change inside a quantum the chunk-invariance statement of psdc_process holds: counters exact, spectra to rounding.
+ * PSD object, device: psdc_sint_process_device takes the route of a SHORT f32 span: producer_event is waited for on the handle's
+ * stream, earlier spans and staged host samples of the channel go out first, and the converter writes the stage-0 stream buffer
+ * (calls longer than 2^26 units in pieces of that many).  The integers are NOT read in place by the fused kernels: the route
+ * costs one extra pass over the stream compared with an in-place f32 span.  The caller's buffer is read by the converter
+ * launches only and must stay valid and unmodified until psdc_sync, a read-out or a psdc_record_consumed event, as an f32 span.
+ * The thread function runs on the host in tests/host/sample_cvt_emul.cpp.  The ABI stays at version 3. */
+int psdc_sint_process(psdc_handle *h, uint32_t channel, const void *x, int kind, float scale, size_t len);
+int psdc_sint_process_device(psdc_handle *h, uint32_t channel, const void *d_x, int kind, float scale, size_t len,
+                             void *producer_event);
+/* len integers of each side into one pair (both sides of one kind and scale) */
+int psdc_sint_cross_process(psdc_cross *h, uint32_t pair, const void *x, const void *y, int kind, float scale, size_t len);
+int psdc_sint_cross_process_device(psdc_cross *h, uint32_t pair, const void *d_x, const void *d_y, int kind, float scale,
+                                   size_t len, void *producer_event);
+/* len integers of each of the m channels of one group (x: m pointers, the array itself in host memory) */
+int psdc_sint_csm_process(psdc_csm *h, uint32_t group, const void *const *x, int kind, float scale, size_t len);
+int psdc_sint_csm_process_device(psdc_csm *h, uint32_t group, const void *const *d_x, int kind, float scale, size_t len,
+                                 void *producer_event);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

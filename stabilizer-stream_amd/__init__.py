@@ -434,6 +434,12 @@ def lib():
     f("psdc_int_iq_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
     f("psdc_int_iqcsd_process", i32, [H, u32, vp, vp, i32, fl, sz])
     f("psdc_int_iqcsd_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
+    f("psdc_sint_process", i32, [H, u32, vp, i32, fl, sz])
+    f("psdc_sint_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
+    f("psdc_sint_cross_process", i32, [H, u32, vp, vp, i32, fl, sz])
+    f("psdc_sint_cross_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
+    f("psdc_sint_csm_process", i32, [H, u32, pp, i32, fl, sz])
+    f("psdc_sint_csm_process_device", i32, [H, u32, pp, i32, fl, sz, vp])
     _lib = L
     return L
 
@@ -480,6 +486,8 @@ EXPORTS = [
     "psdc_iqcsd_stage_spectra", "psdc_iqcsd_csd", "psdc_iqcsd_stats_read", "psdc_iqcsd_last_error",
     "psdc_int_zoom_process", "psdc_int_zoom_process_device", "psdc_int_zcsd_process", "psdc_int_zcsd_process_device",
     "psdc_int_iq_process", "psdc_int_iq_process_device", "psdc_int_iqcsd_process", "psdc_int_iqcsd_process_device",
+    "psdc_sint_process", "psdc_sint_process_device", "psdc_sint_cross_process", "psdc_sint_cross_process_device",
+    "psdc_sint_csm_process", "psdc_sint_csm_process_device",
 ]
 
 
@@ -644,6 +652,22 @@ class PsdCascadeBank:
         else:
             self._ck(self._L.psdc_process_device_after(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after)))
 
+    def process_int(self, channel, x, scale=None):
+        """x: a 1-D C-contiguous int16 or int8 array, fed as it is (psdc_sint_process): the library sees float32(v) *
+        float32(scale), scale None = the dtype's default (2^-15, 2^-7: full scale into [-1, 1)).  The same staging, quantum and
+        fast path as process; one (kind, scale) in the same call sizes gives the bits of process fed the converted stream."""
+        x, kind, dflt = int_samples(x)
+        self._ck(self._L.psdc_sint_process(self._h, channel, x.ctypes.data_as(C.c_void_p), int(kind),
+                                           dflt if scale is None else float(scale), x.size))
+
+    def process_int_device(self, channel, ptr, length, kind, scale=None, after=None):
+        """ptr: device address of `length` integers of SampleKind `kind`; after as process_device.  The integers are converted
+        into the stage-0 stream buffer (one extra pass: they are not read in place as a long f32 span is); they must stay
+        unchanged until sync(), a read-out or a record_consumed event."""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_sint_process_device(self._h, channel, C.c_void_p(ptr), kind, scale, length,
+                                                  C.c_void_p(after) if after else None))
+
     def record_consumed(self, event):
         """Record the hipEvent_t handle `event` behind the last read of every span handed over so far."""
         self._ck(self._L.psdc_record_consumed(self._h, C.c_void_p(event)))
@@ -775,6 +799,12 @@ class PsdCascade:
     def process_device(self, ptr, length, after=None):
         self._b.process_device(0, ptr, length, after)
 
+    def process_int(self, x, scale=None):
+        self._b.process_int(0, x, scale)
+
+    def process_int_device(self, ptr, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, ptr, length, kind, scale, after)
+
     def psd(self, opts=MergeOpts()):
         return self._b.psd(0, opts)
 
@@ -895,6 +925,20 @@ class CsdCascadeBank:
         self._ck(self._L.psdc_cross_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
                                                    C.c_void_p(after) if after else None))
 
+    def process_int(self, pair, x, y, scale=None):
+        """x, y: 1-D int16 or int8 arrays of one dtype and length, fed as they are (psdc_sint_cross_process): the bits of
+        process fed float32(v) * float32(scale); scale None = the dtype's default"""
+        a, b = int_samples(x), int_samples(y)
+        _same_kind(a, b)
+        self._ck(self._L.psdc_sint_cross_process(self._h, pair, a[0].ctypes.data_as(C.c_void_p), b[0].ctypes.data_as(C.c_void_p),
+                                                 int(a[1]), a[2] if scale is None else float(scale), a[0].size))
+
+    def process_int_device(self, pair, px, py, length, kind, scale=None, after=None):
+        """px, py: device addresses of `length` integers of SampleKind `kind` each; the rest as process_device"""
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_sint_cross_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), kind, scale, length,
+                                                        C.c_void_p(after) if after else None))
+
     def process_frames(self, data, frame_size, pairs):
         """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] = (x, y)
         feeds pair p with traces x and y of every frame (indices or TRACE_NAMES labels), None leaves it unfed.  Returns the
@@ -976,6 +1020,12 @@ class CsdCascade:
 
     def process_device(self, px, py, length, after=None):
         self._b.process_device(0, px, py, length, after)
+
+    def process_int(self, x, y, scale=None):
+        self._b.process_int(0, x, y, scale)
+
+    def process_int_device(self, px, py, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, px, py, length, kind, scale, after)
 
     def process_frames(self, data, frame_size, pair):
         """pair: (x, y) traces of the frames (CsdCascadeBank.process_frames)"""
@@ -1113,6 +1163,26 @@ class CsmCascadeBank:
         self._ck(self._L.psdc_csm_process_device(self._h, group, self._ptrs([int(p) for p in ptrs]), length,
                                                  C.c_void_p(after) if after else None))
 
+    def process_int(self, group, xs, scale=None):
+        """xs: m 1-D int16 or int8 arrays of one dtype and length, fed as they are (psdc_sint_csm_process): the bits of process
+        fed float32(v) * float32(scale); scale None = the dtype's default"""
+        if isinstance(xs, np.ndarray) or len(xs) != self.m:
+            raise ValueError(f"a group takes a list of m = {self.m} integer arrays")
+        a = [int_samples(x) for x in xs]
+        for b in a[1:]:
+            _same_kind(a[0], b)
+        arr = (C.c_void_p * self.m)(*[x[0].ctypes.data for x in a])
+        self._ck(self._L.psdc_sint_csm_process(self._h, group, arr, int(a[0][1]), a[0][2] if scale is None else float(scale),
+                                               a[0][0].size))
+
+    def process_int_device(self, group, ptrs, length, kind, scale=None, after=None):
+        """ptrs: m device addresses of `length` integers of SampleKind `kind` each; the rest as process_device"""
+        if len(ptrs) != self.m:
+            raise ValueError(f"{len(ptrs)} channels for m = {self.m}")
+        kind, scale = _int_scale(kind, scale)
+        self._ck(self._L.psdc_sint_csm_process_device(self._h, group, (C.c_void_p * self.m)(*[int(p) for p in ptrs]), kind, scale,
+                                                      length, C.c_void_p(after) if after else None))
+
     def process_frames(self, data, frame_size, groups):
         """Stream frames (bytes-like holding whole frames) into the groups: groups[g] = m traces (indices or TRACE_NAMES
         labels) feeds group g, None leaves it unfed.  Returns the number of frames ingested; a bad frame raises FrameError
@@ -1188,6 +1258,12 @@ class CsmCascade:
 
     def process_device(self, ptrs, length, after=None):
         self._b.process_device(0, ptrs, length, after)
+
+    def process_int(self, xs, scale=None):
+        self._b.process_int(0, xs, scale)
+
+    def process_int_device(self, ptrs, length, kind, scale=None, after=None):
+        self._b.process_int_device(0, ptrs, length, kind, scale, after)
 
     def process_frames(self, data, frame_size, group):
         return self._b.process_frames(data, frame_size, [group])

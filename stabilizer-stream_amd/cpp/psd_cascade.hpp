@@ -213,6 +213,16 @@ public:
     void set_detrend(Detrend d) { check(psdc_set_detrend(h_, static_cast<int>(d))); }
     void process(std::span<const float> x) { check(psdc_process(h_, 0, x.data(), x.size())); }
     void process_device(const float *d_x, size_t len) { check(psdc_process_device(h_, 0, d_x, len)); }
+    // integer samples as hardware delivers them (psdc_sint_process): the cascade sees float(v) * scale; the defaults map full scale
+    // into [-1, 1).  One (kind, scale) in the same call sizes gives the bits of process() fed the converted stream
+    void process_int(std::span<const int16_t> x, float scale = 0x1p-15f)
+    {
+        check(psdc_sint_process(h_, 0, x.data(), PSDC_SAMPLE_S16, scale, x.size()));
+    }
+    void process_int(std::span<const int8_t> x, float scale = 0x1p-7f)
+    {
+        check(psdc_sint_process(h_, 0, x.data(), PSDC_SAMPLE_S8, scale, x.size()));
+    }
     // how device spans share rounds (include/psdcascade.h): held until `n` spans / 2^29 samples or a call that cannot join -- a function
     // of the calls alone, so the same calls give the same bits; eager(true): also sent out when the device is seen idle (timing-dependent);
     // merge(false): a span that continues the held one in memory becomes a span of its own instead of extending it

@@ -1068,22 +1068,64 @@ int check_fmt(XObj *h, const SampleFmt &fmt, const char *who)
     return PSDC_OK;
 }
 
-// x: h->m pointers (host memory)
-int process_impl(XObj *h, uint32_t pair, const float *const *x, size_t len, const char *who)
+// the sample pointers of a psdc_sint_* call: none null, each aligned to the integer
+int check_int_ptrs(XObj *h, const void *const *x, const SampleFmt &fmt, const char *who)
+{
+    for (uint32_t c = 0; c < h->m; ++c) {
+        if (!x || !x[c])
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+        if ((uintptr_t)x[c] % fmt.bytes())
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to " + std::to_string(fmt.bytes()) + " bytes");
+    }
+    return PSDC_OK;
+}
+
+// the converter of one piece of an integer call: cnt integers of each of the m channels at src[c], written where the f32 call's
+// copies write (sample_int.h, sample_cvt_int_kernel) -- ONE launch for the m channels, whose stream buffers share their phase
+int convert_piece(XObj *h, XStage *s, const void *const *src, const SampleFmt &fmt, size_t at, size_t cnt, hipStream_t stream)
+{
+    SintCvtJob job{};
+    for (uint32_t c = 0; c < h->m; ++c) {
+        job.src[c] = src[c];
+        job.dst[c] = s->buf.p[c][s->buf.cur] + at;
+    }
+    job.nch = h->m;
+    job.len = cnt;
+    job.scale = fmt.scale;
+    XCHK(h, launch_cvt_int(job, fmt.kind, stream));
+    ++h->launches;
+    return PSDC_OK;
+}
+
+// x: h->m pointers (host memory).  fmt: f32 (psdc_cross_process, psdc_csm_process), or integers (psdc_sint_*): the raw integers
+// go up through the front of each staging lane into the front of each landing lane, in the f32 call's pieces, and one converter a
+// piece writes the bytes the f32 call's copies write -- so run_round sees the same streams and gives the same bits.
+int process_impl(XObj *h, uint32_t pair, const void *const *x, SampleFmt fmt, size_t len, const char *who)
 {
     X_HANDLE(h, who);
-    int rc = check_pair(h, pair);
+    const bool ints = fmt.kind != SAMPLE_F32;
+    int rc = check_pair(h, pair, ints ? who : nullptr);
     if (rc)
+        return rc;
+    if (ints && (rc = check_fmt(h, fmt, who)))
         return rc;
     if (len == 0)
         return PSDC_OK;
-    for (uint32_t c = 0; c < h->m; ++c)
-        if (!x || !x[c])
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if (ints) {
+        if ((rc = check_int_ptrs(h, x, fmt, who)))
+            return rc;
+    } else {
+        for (uint32_t c = 0; c < h->m; ++c)
+            if (!x || !x[c])
+                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    }
     X_ON_DEVICE(h);
+    if (ints && !h->d_land)
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * h->m * STAGING));
     XStage *s = nullptr;
     if ((rc = stage0_room(h, pair, len, &s)))
         return rc;
+    const size_t unit = fmt.bytes();
     for (size_t done = 0; done < len;) {
         const size_t m = std::min(STAGING, len - done);
         const int slot = h->stage_cur;
@@ -1091,14 +1133,21 @@ int process_impl(XObj *h, uint32_t pair, const float *const *x, size_t len, cons
             XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
         float *stg = h->h_stage[slot];
         for (uint32_t c = 0; c < h->m; ++c)
-            memcpy(stg + c * STAGING, x[c] + done, sizeof(float) * m);
+            memcpy(stg + c * STAGING, static_cast<const uint8_t *>(x[c]) + unit * done, unit * m);
         const size_t at = (size_t)(s->total + done - s->buf.base);
         for (uint32_t c = 0; c < h->m; ++c)
-            XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, stg + c * STAGING, sizeof(float) * m, hipMemcpyHostToDevice,
-                                   h->stream));
+            XCHK(h, hipMemcpyAsync(ints ? h->d_land + c * STAGING : s->buf.p[c][s->buf.cur] + at, stg + c * STAGING, unit * m,
+                                   hipMemcpyHostToDevice, h->stream));
         XCHK(h, hipEventRecord(h->stage_ev[slot], h->stream));
         h->ev_pending[slot] = true;
         h->stage_cur ^= 1;
+        if (ints) { // (the next piece's copies into the landing lanes run behind it: one stream)
+            const void *from[CSM_MAX_M] = {};
+            for (uint32_t c = 0; c < h->m; ++c)
+                from[c] = h->d_land + c * STAGING;
+            if ((rc = convert_piece(h, s, from, fmt, at, m, h->stream)))
+                return rc;
+        }
         done += m;
     }
     s->total += len;
@@ -1108,18 +1157,27 @@ int process_impl(XObj *h, uint32_t pair, const float *const *x, size_t len, cons
     return run_round(h, &did);
 }
 
-// d_x: h->m device pointers (the array itself is host memory)
-int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t len, void *producer_event, const char *who)
+// d_x: h->m device pointers (the array itself is host memory).  fmt as in process_impl: an integer call has ONE converter launch
+// on the copy stream where the f32 call has its m copies, under the same event rules.
+int process_device_impl(XObj *h, uint32_t pair, const void *const *d_x, SampleFmt fmt, size_t len, void *producer_event, const char *who)
 {
     X_HANDLE(h, who);
-    int rc = check_pair(h, pair);
+    const bool ints = fmt.kind != SAMPLE_F32;
+    int rc = check_pair(h, pair, ints ? who : nullptr);
     if (rc)
+        return rc;
+    if (ints && (rc = check_fmt(h, fmt, who)))
         return rc;
     if (len == 0)
         return PSDC_OK;
-    for (uint32_t c = 0; c < h->m; ++c)
-        if (!d_x || !d_x[c])
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if (ints) {
+        if ((rc = check_int_ptrs(h, d_x, fmt, who)))
+            return rc;
+    } else {
+        for (uint32_t c = 0; c < h->m; ++c)
+            if (!d_x || !d_x[c])
+                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    }
     X_ON_DEVICE(h);
     if (producer_event)
         XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
@@ -1135,8 +1193,13 @@ int process_device_impl(XObj *h, uint32_t pair, const float *const *d_x, size_t 
     if (h->round_recorded[slot])
         XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
     const size_t at = (size_t)(s->total - s->buf.base);
-    for (uint32_t c = 0; c < h->m; ++c)
-        XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, d_x[c], sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    if (ints) {
+        if ((rc = convert_piece(h, s, d_x, fmt, at, len, h->copy_stream)))
+            return rc;
+    } else {
+        for (uint32_t c = 0; c < h->m; ++c)
+            XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, d_x[c], sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
+    }
     XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
     XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
     s->total += len;
@@ -1778,15 +1841,15 @@ int psdc_cross_set_avg(psdc_cross *h, uint32_t limit, uint32_t count) { return s
 
 int psdc_cross_process(psdc_cross *h, uint32_t pair, const float *x, const float *y, size_t len)
 {
-    const float *xs[2] = {x, y};
-    return process_impl(h, pair, xs, len, "psdc_cross_process");
+    const void *xs[2] = {x, y};
+    return process_impl(h, pair, xs, SampleFmt{}, len, "psdc_cross_process");
 }
 
 int psdc_cross_process_device(psdc_cross *h, uint32_t pair, const float *d_x, const float *d_y, size_t len,
                               void *producer_event)
 {
-    const float *xs[2] = {d_x, d_y};
-    return process_device_impl(h, pair, xs, len, producer_event, "psdc_cross_process_device");
+    const void *xs[2] = {d_x, d_y};
+    return process_device_impl(h, pair, xs, SampleFmt{}, len, producer_event, "psdc_cross_process_device");
 }
 
 int psdc_cross_sync(psdc_cross *h) { return sync_impl(h, "psdc_cross_sync"); }
@@ -1909,12 +1972,12 @@ int psdc_csm_set_avg(psdc_csm *h, uint32_t limit, uint32_t count) { return set_a
 
 int psdc_csm_process(psdc_csm *h, uint32_t group, const float *const *x, size_t len)
 {
-    return process_impl(h, group, x, len, "psdc_csm_process");
+    return process_impl(h, group, reinterpret_cast<const void *const *>(x), SampleFmt{}, len, "psdc_csm_process");
 }
 
 int psdc_csm_process_device(psdc_csm *h, uint32_t group, const float *const *d_x, size_t len, void *producer_event)
 {
-    return process_device_impl(h, group, d_x, len, producer_event, "psdc_csm_process_device");
+    return process_device_impl(h, group, reinterpret_cast<const void *const *>(d_x), SampleFmt{}, len, producer_event, "psdc_csm_process_device");
 }
 
 int psdc_csm_process_frames(psdc_csm *h, const uint32_t *group_traces, const uint8_t *frames, size_t frame_size, size_t n_frames,
@@ -2386,6 +2449,32 @@ int psdc_int_iqcsd_process_device(psdc_iqcsd *h, uint32_t pair, const void *d_za
 {
     const void *const src[4] = {d_za, nullptr, d_zb, nullptr};
     return iq_pair_feed(h, pair, src, true, int_fmt(kind, scale), len, true, producer_event, "psdc_int_iqcsd_process_device");
+}
+
+// ---- integer sample feeds of the real-input objects (include/psdcascade.h): the pair and the matrix object; psdc_sint_process[_device]
+// of the PSD object are in runtime.cpp ----
+
+int psdc_sint_cross_process(psdc_cross *h, uint32_t pair, const void *x, const void *y, int kind, float scale, size_t len)
+{
+    const void *xs[2] = {x, y};
+    return process_impl(h, pair, xs, int_fmt(kind, scale), len, "psdc_sint_cross_process");
+}
+
+int psdc_sint_cross_process_device(psdc_cross *h, uint32_t pair, const void *d_x, const void *d_y, int kind, float scale, size_t len,
+                                   void *producer_event)
+{
+    const void *xs[2] = {d_x, d_y};
+    return process_device_impl(h, pair, xs, int_fmt(kind, scale), len, producer_event, "psdc_sint_cross_process_device");
+}
+
+int psdc_sint_csm_process(psdc_csm *h, uint32_t group, const void *const *x, int kind, float scale, size_t len)
+{
+    return process_impl(h, group, x, int_fmt(kind, scale), len, "psdc_sint_csm_process");
+}
+
+int psdc_sint_csm_process_device(psdc_csm *h, uint32_t group, const void *const *d_x, int kind, float scale, size_t len, void *producer_event)
+{
+    return process_device_impl(h, group, d_x, int_fmt(kind, scale), len, producer_event, "psdc_sint_csm_process_device");
 }
 
 } // extern "C"

@@ -85,6 +85,10 @@ struct Channel {
     bool ev_pending[2] = {false, false};
     int cur_stage = 0;
     size_t fill = 0;
+    // what the `fill` staged samples are (psdc_sint_process): SAMPLE_F32, or raw integers of this kind to be converted with
+    // this scale (sample_int.h) when they are uploaded; a call of another (kind, scale) submits the staged samples first
+    int stage_kind = 0;
+    float stage_scale = 1.0f;
     bool submitted = false; // device holds samples that advance() has not looked at yet
     // zero-copy spans registered but not enqueued yet, in stream order.  More than one is held
     // while the device is still busy with earlier rounds (PSDC_OPT_COALESCE): they go out as ONE
@@ -226,6 +230,9 @@ struct psdc_handle {
     size_t frames_cap = 0; // bytes per buffer
     int frames_cur = 0;
     size_t quantum = (size_t)1 << 22;
+    // integer host feeds (psdc_sint_process): the device buffer a staged fill of raw integers lands in before the converter
+    // writes it into the stage-0 stream (2 * quantum bytes, made by the first integer upload, released with the staging)
+    void *d_land = nullptr;
     uint32_t coalesce = 8; // zero-copy spans per channel held back while the device is busy (1 = none)
     bool coalesce_auto = true; // PSDC_OPT_COALESCE not set: `coalesce`, or 16 ... MAX_COALESCE for one channel fed in short spans (coalesce_limit)
     uint32_t stage_limit = psdrt::MAX_STAGES; // stages that analyse their stream; 1 for a single Psd<N> (psdc_stage_*)

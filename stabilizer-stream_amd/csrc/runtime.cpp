@@ -1,6 +1,7 @@
 // runtime.cpp -- the host runtime behind include/psdcascade.h: handle lifecycle, per-stream device buffers, pinned staging and
 // uploads, the feed calls (psdc_process, psdc_process_device) and the flush / sync points.  See host_runtime.h for the parts.
 #include "host_runtime.h"
+#include "sample_int.h"
 
 #include <cmath>
 #include <complex>
@@ -14,6 +15,14 @@
 #include <thread>
 
 using namespace psdrt;
+
+#if !defined(__HIPCC__)
+// A host build of this file (tests/host/round_plan_check: the HIP runtime modelled on the CPU, no device code) has no
+// sample_int.o and so no converter: the integer feeds fail there with a device error, every other path is as in the library.
+namespace psdk {
+inline hipError_t launch_cvt_int(const SintCvtJob &, int, hipStream_t) { return hipErrorInvalidValue; }
+} // namespace psdk
+#endif
 
 namespace psdrt {
 
@@ -581,12 +590,27 @@ int submit_host(psdc_handle *h, Channel &c)
     if (rc)
         return rc;
     const int b = c.cur_stage;
+    if (c.stage_kind != SAMPLE_F32 && !h->d_land)
+        HIPCHK(h, hipMalloc(&h->d_land, 2 * h->quantum));
     rc = order_upload(h);
     if (rc)
         return rc;
-    HIPCHK(h, hipMemcpyAsync(s0.buf.p[s0.buf.cur] + (s0.total - s0.buf.base), c.stage_host[b],
-                             sizeof(float) * c.fill, hipMemcpyHostToDevice, h->copy_stream));
-    HIPCHK(h, hipEventRecord(c.stage_ev[b], h->copy_stream));
+    float *dst = s0.buf.p[s0.buf.cur] + (s0.total - s0.buf.base);
+    if (c.stage_kind == SAMPLE_F32) {
+        HIPCHK(h, hipMemcpyAsync(dst, c.stage_host[b], sizeof(float) * c.fill, hipMemcpyHostToDevice, h->copy_stream));
+        HIPCHK(h, hipEventRecord(c.stage_ev[b], h->copy_stream));
+    } else { // raw integers: up into the landing buffer, and the converter writes what the f32 upload writes (sample_int.h)
+        HIPCHK(h, hipMemcpyAsync(h->d_land, c.stage_host[b], (size_t)sint_bytes(c.stage_kind) * c.fill, hipMemcpyHostToDevice,
+                                 h->copy_stream));
+        HIPCHK(h, hipEventRecord(c.stage_ev[b], h->copy_stream));
+        SintCvtJob job{};
+        job.src[0] = h->d_land;
+        job.dst[0] = dst;
+        job.nch = 1;
+        job.len = c.fill;
+        job.scale = c.stage_scale;
+        HIPCHK(h, launch_cvt_int(job, c.stage_kind, h->copy_stream));
+    }
     {
         int rc2 = mark_upload(h);
         if (rc2)
@@ -630,6 +654,86 @@ int free_staging(psdc_handle *h, Channel &c)
         }
         c.ev_pending[i] = false;
     }
+    if (h->d_land) { // (sized by the quantum, as the staging is)
+        HIPCHK(h, hipFree(h->d_land));
+        h->d_land = nullptr;
+    }
+    return PSDC_OK;
+}
+
+// A host call of `len` samples of one number format: psdc_process past its fast path, and psdc_sint_process.  x: f32 samples
+// (kind SAMPLE_F32) or integers of `kind` (sample_int.h); the staging holds them as they are, `quantum` samples a slot.
+int host_feed(psdc_handle *h, Channel &c, const void *x, int kind, float scale, size_t len)
+{
+    int rc;
+    if (c.has_span()) { // keep the stream in order behind a pending zero-copy span
+        rc = advance(h);
+        if (rc)
+            return rc;
+    }
+    rc = ensure_staging(h, c);
+    if (rc)
+        return rc;
+    if (c.st.empty()) {
+        rc = add_stage(h, c);
+        if (rc)
+            return rc;
+    }
+    if (c.stage_kind != kind || memcmp(&c.stage_scale, &scale, sizeof(float)) != 0) {
+        if (c.fill) { // the staged samples are of another format: they go out as a fill of their own
+            if (c.submitted) {
+                rc = advance(h);
+                if (rc)
+                    return rc;
+            }
+            rc = submit_host(h, c);
+            if (rc)
+                return rc;
+        }
+        c.stage_kind = kind;
+        c.stage_scale = scale;
+    }
+    h->idle = false;
+    const size_t unit = kind == SAMPLE_F32 ? sizeof(float) : (size_t)sint_bytes(kind);
+    const uint8_t *src = static_cast<const uint8_t *>(x);
+    while (len > 0) {
+        const size_t take = std::min(len, h->quantum - c.fill);
+        CopyPool::get().copy(reinterpret_cast<uint8_t *>(c.stage_host[c.cur_stage]) + unit * c.fill, src, unit * take);
+        c.fill += take;
+        src += unit * take;
+        len -= take;
+        if (c.fill == h->quantum) {
+            if (c.submitted) { // a full round of channels is on the device: run it as one batch
+                rc = advance(h);
+                if (rc)
+                    return rc;
+            }
+            rc = submit_host(h, c);
+            if (rc)
+                return rc;
+            if (h->n_channels == 1) {
+                rc = advance(h);
+                if (rc)
+                    return rc;
+            }
+        }
+    }
+    return PSDC_OK;
+}
+
+// the arguments of a psdc_sint_* call (the pointer only where len > 0): *kind becomes the sample_int.h kind
+int check_sint(psdc_handle *h, const char *who, const void *x, int *kind, float scale, size_t len)
+{
+    const int k = *kind == PSDC_SAMPLE_S16 ? SAMPLE_S16 : *kind == PSDC_SAMPLE_S8 ? SAMPLE_S8 : -1;
+    if (k < 0)
+        return fail(h, PSDC_ERR_ARG, std::string(who) + ": unknown sample kind (PSDC_SAMPLE_S16 or PSDC_SAMPLE_S8)");
+    if (!std::isfinite(scale))
+        return fail(h, PSDC_ERR_ARG, std::string(who) + ": the scale is not finite");
+    if (len && !x)
+        return fail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if (len && (uintptr_t)x % (size_t)sint_bytes(k))
+        return fail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to " + std::to_string(sint_bytes(k)) + " bytes");
+    *kind = k;
     return PSDC_OK;
 }
 
@@ -1067,6 +1171,8 @@ int psdc_reset(psdc_handle *h)
         }
         c.st.clear();
         c.fill = 0;
+        c.stage_kind = SAMPLE_F32; // (nothing staged: the next host call tags the staging anew)
+        c.stage_scale = 1.0f;
         c.submitted = false;
         c.spans.clear();
     }
@@ -1169,7 +1275,8 @@ int psdc_process(psdc_handle *h, uint32_t channel, const float *x, size_t len)
     // at these sizes).  Everything else takes the general path below.
     if (h && channel < h->n_channels && x && len && !h->knobs.no_fastpath) {
         Channel &cf_ = h->ch[channel];
-        if (cf_.stage_host[0] && !cf_.st.empty() && cf_.spans.empty() && len < h->quantum - cf_.fill && len < ((size_t)1 << 19)) { // (>= 2 MiB: the copy threads)
+        if (cf_.stage_host[0] && !cf_.st.empty() && cf_.spans.empty() && len < h->quantum - cf_.fill && len < ((size_t)1 << 19) && // (>= 2 MiB: the copy threads)
+            cf_.stage_kind == SAMPLE_F32) { // (integers staged by psdc_sint_process go out first: the general path)
             memcpy(cf_.stage_host[cf_.cur_stage] + cf_.fill, x, sizeof(float) * len);
             cf_.fill += len;
             h->idle = false;
@@ -1184,13 +1291,58 @@ int psdc_process(psdc_handle *h, uint32_t channel, const float *x, size_t len)
         return PSDC_OK; // x.chunks() yields nothing: no stage is created (src/psd.rs:459)
     if (!x)
         return fail(h, PSDC_ERR_ARG, "null input");
+    return host_feed(h, h->ch[channel], x, SAMPLE_F32, 1.0f, len);
+}
+
+// psdc_process on integers (include/psdcascade.h): the same staging memory holding the raw integers, the same quantum in samples,
+// the same fast path and the same submit_host calls -- which upload an integer fill into the landing buffer and convert it into
+// the stage-0 stream where the f32 upload writes
+int psdc_sint_process(psdc_handle *h, uint32_t channel, const void *x, int kind, float scale, size_t len)
+{
+    const int k = kind == PSDC_SAMPLE_S16 ? SAMPLE_S16 : kind == PSDC_SAMPLE_S8 ? SAMPLE_S8 : -1;
+    if (h && channel < h->n_channels && x && len && k > 0 && !h->knobs.no_fastpath) {
+        Channel &cf_ = h->ch[channel];
+        const size_t unit = (size_t)sint_bytes(k);
+        if (cf_.stage_host[0] && !cf_.st.empty() && cf_.spans.empty() && len < h->quantum - cf_.fill && len < ((size_t)1 << 19) &&
+            cf_.stage_kind == k && memcmp(&cf_.stage_scale, &scale, sizeof(float)) == 0 && (uintptr_t)x % unit == 0) {
+            memcpy(reinterpret_cast<uint8_t *>(cf_.stage_host[cf_.cur_stage]) + unit * cf_.fill, x, unit * len);
+            cf_.fill += len;
+            h->idle = false;
+            return PSDC_OK;
+        }
+    }
+    int rc = check_channel(h, channel);
+    if (rc)
+        return fail(h, rc, "psdc_sint_process: " + g_last_error);
+    if ((rc = check_sint(h, "psdc_sint_process", x, &kind, scale, len)))
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    ON_DEVICE(h, h->device);
+    return host_feed(h, h->ch[channel], x, kind, scale, len);
+}
+
+// The route of a SHORT f32 span (psdc_process_device_after, !in_place): the converter stands where that route's copy stands and
+// writes the stage-0 stream buffer on the compute stream.  Not read in place by the fused kernels: one extra pass over the stream.
+int psdc_sint_process_device(psdc_handle *h, uint32_t channel, const void *d_x, int kind, float scale, size_t len, void *producer_event)
+{
+    int rc = check_channel(h, channel);
+    if (rc)
+        return fail(h, rc, "psdc_sint_process_device: " + g_last_error);
+    if ((rc = check_sint(h, "psdc_sint_process_device", d_x, &kind, scale, len)))
+        return rc;
+    if (len == 0)
+        return PSDC_OK;
+    ON_DEVICE(h, h->device);
+    if (producer_event)
+        HIPCHK(h, hipStreamWaitEvent(h->stream, static_cast<hipEvent_t>(producer_event), 0));
     Channel &c = h->ch[channel];
-    if (c.has_span()) { // keep the stream in order behind a pending zero-copy span
+    if (c.has_span() || c.submitted) { // earlier spans of this channel go out first
         rc = advance(h);
         if (rc)
             return rc;
     }
-    rc = ensure_staging(h, c);
+    rc = submit_host(h, c); // host-fed samples staged earlier come first
     if (rc)
         return rc;
     if (c.st.empty()) {
@@ -1199,28 +1351,34 @@ int psdc_process(psdc_handle *h, uint32_t channel, const float *x, size_t len)
             return rc;
     }
     h->idle = false;
-    while (len > 0) {
-        const size_t take = std::min(len, h->quantum - c.fill);
-        CopyPool::get().copy(c.stage_host[c.cur_stage] + c.fill, x, sizeof(float) * take);
-        c.fill += take;
-        x += take;
-        len -= take;
-        if (c.fill == h->quantum) {
-            if (c.submitted) { // a full round of channels is on the device: run it as one batch
-                rc = advance(h);
-                if (rc)
-                    return rc;
-            }
-            rc = submit_host(h, c);
+    // pieces: the stream buffer holds a piece at a time (the round between two pieces carries the tail and frees the rest)
+    const size_t unit = (size_t)sint_bytes(kind), piece = (size_t)1 << 26;
+    const uint8_t *src = static_cast<const uint8_t *>(d_x);
+    for (size_t done = 0; done < len;) {
+        const size_t cnt = std::min(piece, len - done);
+        if (done) {
+            rc = advance(h);
             if (rc)
                 return rc;
-            if (h->n_channels == 1) {
-                rc = advance(h);
-                if (rc)
-                    return rc;
-            }
         }
+        StageState &s0 = c.st[0];
+        rc = ensure_room(h, s0, s0.total + cnt);
+        if (rc)
+            return rc;
+        SintCvtJob job{};
+        job.src[0] = src + unit * done;
+        job.dst[0] = s0.buf.p[s0.buf.cur] + (s0.total - s0.buf.base);
+        job.nch = 1;
+        job.len = cnt;
+        job.scale = scale;
+        HIPCHK(h, launch_cvt_int(job, kind, h->stream));
+        s0.total += cnt;
+        s0.buf.end = s0.total;
+        c.submitted = true;
+        done += cnt;
     }
+    if (h->n_channels == 1)
+        return advance(h);
     return PSDC_OK;
 }
 

@@ -1,5 +1,6 @@
 // sample_int.h -- the integer sample feeds of the four mixer-fronted objects (psdc_int_*, sample_int.hip): int16 / int8 samples
-// read where the f32 mixers (zoom.hip, iq.hip, iq_cross.hip) read floats, converted in registers and mixed by the same formulas.
+// read where the f32 mixers (zoom.hip, iq.hip, iq_cross.hip) read floats, converted in registers and mixed by the same formulas;
+// and of the three real-input objects (psdc_sint_*: PSD, pair, matrix): the same conversion with no mixer behind it (sint_cvt_thread).
 // Usable from host and device like iq_lo.h: tests/host/sample_int_emul.cpp runs everything below on the host.
 //
 // Conversion: the f32 sample the mixer sees is (float)v * scale -- the int-to-float conversion is exact (|v| <= 2^15), and the
@@ -292,12 +293,56 @@ ZOOM_HD void sint_iq_pair_thread(const SintPairMixJob &job, unsigned head, int s
     }
 }
 
+// ---- the converter, one thread ---------------------------------------------------------------------------------------------
+// The feeds of the objects with no mixer in front of stage 0 (psdc_sint_*: PSD, pair, matrix): nch (1 ... 4) equally long
+// channels of integers, each written as f32 where the f32 call's copy writes, dst[c][i] = sint_scale(src[c][i], scale).  The
+// mixers' access scheme without the oscillator; the destinations of a launch share their 16-byte phase.
+struct SintCvtJob {
+    const void *src[4];
+    float *dst[4];
+    unsigned nch;
+    unsigned long long len;
+    float scale;
+};
+
+// thread g of channel ch of sample_cvt_int_kernel.  src_aligned_mask: bit c -- channel c's source is aligned at the first group
+template <typename T>
+ZOOM_HD void sint_cvt_thread(const SintCvtJob &job, unsigned head, int src_aligned_mask, unsigned ch, unsigned long long g)
+{
+    if (ch >= job.nch)
+        return;
+    const SintSpan sp = sint_span(g, head, job.len, (src_aligned_mask >> ch) & 1);
+    if (sp.count == 0)
+        return;
+    const T *src = static_cast<const T *>(job.src[ch]);
+    float *dst = job.dst[ch];
+    if (sp.count == SINT_Q) { // a full group (thread 0's head is at most three units)
+        SintF4 v;
+        if (sp.wide) {
+            SintGroup<T, 1> grp;
+            sint_load_group<T, 1>(src + sp.first, grp);
+#pragma unroll
+            for (int u = 0; u < SINT_Q; ++u)
+                v.v[u] = grp.get(u, 0, job.scale);
+        } else {
+#pragma unroll
+            for (int u = 0; u < SINT_Q; ++u)
+                v.v[u] = sint_load1(src + sp.first + u, job.scale);
+        }
+        sint_store4(dst + sp.first, v);
+        return;
+    }
+    for (unsigned long long i = sp.first; i < sp.first + sp.count; ++i)
+        dst[i] = sint_load1(src + i, job.scale);
+}
+
 #if defined(__HIPCC__)
 // the launches (sample_int.hip); kind: SAMPLE_S16 or SAMPLE_S8.  hipErrorInvalidValue for another kind, a null or misaligned
 // pointer, or destinations that do not share their 16-byte phase.
 hipError_t launch_zoom_mix_int(const SintMixJob &j, int kind, hipStream_t s);
 hipError_t launch_iq_mix_int(const SintMixJob &j, int kind, hipStream_t s);
 hipError_t launch_iq_pair_mix_int(const SintPairMixJob &j, int kind, hipStream_t s);
+hipError_t launch_cvt_int(const SintCvtJob &j, int kind, hipStream_t s); // also for nch outside 1 ... 4
 #endif
 
 } // namespace psdk

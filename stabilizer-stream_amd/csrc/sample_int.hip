@@ -4,6 +4,7 @@
 //   zoom_mix_int_kernel<T>     zoom_mix_kernel (zoom.hip) on real integers
 //   iq_mix_int_kernel<T>       iq_mix_kernel<true> (iq.hip) on interleaved (re, im) integer pairs
 //   iq_pair_mix_int_kernel<T>  iq_pair_mix_kernel<true> (iq_cross.hip) on the integer pairs of both sides, shared oscillator included
+//   sample_cvt_int_kernel<T>   the converter of the objects with no mixer (psdc_sint_*): 1 ... 4 channels of real integers to f32
 // T = int16_t or int8_t.  A thread's work is sample_int.h's sint_*_thread (the same source the host check runs): the f32 mixers'
 // access scheme, a sample converted as __fmul_rn((float)v, scale) in registers and mixed by zoom_lo.h / iq_lo.h unchanged, so a
 // launch stores the bits the f32 kernel stores for the converted stream.  The f32 kernels and their TUs are untouched.
@@ -28,6 +29,13 @@ template <typename T>
 __global__ __launch_bounds__(SINT_BLOCK) void iq_pair_mix_int_kernel(const SintPairMixJob job, const unsigned head, const int src_aligned)
 {
     sint_iq_pair_thread<T>(job, head, src_aligned, (unsigned long long)blockIdx.x * SINT_BLOCK + threadIdx.x);
+}
+
+// grid: x -- the groups of a channel, y -- the channel
+template <typename T>
+__global__ __launch_bounds__(SINT_BLOCK) void sample_cvt_int_kernel(const SintCvtJob job, const unsigned head, const int src_aligned_mask)
+{
+    sint_cvt_thread<T>(job, head, src_aligned_mask, blockIdx.y, (unsigned long long)blockIdx.x * SINT_BLOCK + threadIdx.x);
 }
 
 namespace {
@@ -103,6 +111,29 @@ hipError_t launch_iq_pair_mix_int(const SintPairMixJob &j, int kind, hipStream_t
         hipLaunchKernelGGL(iq_pair_mix_int_kernel<int16_t>, dim3(blocks), dim3(SINT_BLOCK), 0, s, j, head, al);
     else
         hipLaunchKernelGGL(iq_pair_mix_int_kernel<int8_t>, dim3(blocks), dim3(SINT_BLOCK), 0, s, j, head, al);
+    return hipGetLastError();
+}
+
+hipError_t launch_cvt_int(const SintCvtJob &j, int kind, hipStream_t s)
+{
+    const size_t unit = (size_t)sint_bytes(kind);
+    if (!unit || j.nch < 1 || j.nch > 4)
+        return hipErrorInvalidValue;
+    if (j.len == 0)
+        return hipSuccess;
+    for (unsigned c = 0; c < j.nch; ++c)
+        if (!j.src[c] || (uintptr_t)j.src[c] % unit || !sint_dst_ok(j.dst[0], j.dst[c]))
+            return hipErrorInvalidValue;
+    const unsigned head = sint_head(j.dst[0], j.len), blocks = sint_blocks(head, j.len);
+    if (!blocks)
+        return hipErrorInvalidValue;
+    int al = 0;
+    for (unsigned c = 0; c < j.nch; ++c)
+        al |= (sint_src_aligned(j.src[c], head, unit) ? 1 : 0) << c;
+    if (kind == SAMPLE_S16)
+        hipLaunchKernelGGL(sample_cvt_int_kernel<int16_t>, dim3(blocks, j.nch), dim3(SINT_BLOCK), 0, s, j, head, al);
+    else
+        hipLaunchKernelGGL(sample_cvt_int_kernel<int8_t>, dim3(blocks, j.nch), dim3(SINT_BLOCK), 0, s, j, head, al);
     return hipGetLastError();
 }
 

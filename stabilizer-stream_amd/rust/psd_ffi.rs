@@ -70,6 +70,35 @@ extern "C" {
     fn psdc_last_error(h: *const PsdcHandle) -> *const c_char;
 }
 
+/// The pair and the matrix object of include/psdcascade.h (opaque; only their integer feeds are declared here).
+#[repr(C)]
+pub struct PsdcCross {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct PsdcCsm {
+    _private: [u8; 0],
+}
+/// `kind` of the integer feeds: PSDC_SAMPLE_S16, PSDC_SAMPLE_S8.
+pub const PSDC_SAMPLE_S16: c_int = 1;
+pub const PSDC_SAMPLE_S8: c_int = 2;
+
+// The integer sample feeds of the real-input objects (include/psdcascade.h): int16 / int8 samples as they are, seen as
+// `v as f32 * scale`.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    fn psdc_sint_process(h: *mut PsdcHandle, channel: u32, x: *const c_void, kind: c_int, scale: f32, len: usize) -> c_int;
+    fn psdc_sint_process_device(h: *mut PsdcHandle, channel: u32, d_x: *const c_void, kind: c_int, scale: f32, len: usize,
+                                producer_event: *mut c_void) -> c_int;
+    fn psdc_sint_cross_process(h: *mut PsdcCross, pair: u32, x: *const c_void, y: *const c_void, kind: c_int, scale: f32,
+                               len: usize) -> c_int;
+    fn psdc_sint_cross_process_device(h: *mut PsdcCross, pair: u32, d_x: *const c_void, d_y: *const c_void, kind: c_int,
+                                      scale: f32, len: usize, producer_event: *mut c_void) -> c_int;
+    fn psdc_sint_csm_process(h: *mut PsdcCsm, group: u32, x: *const *const c_void, kind: c_int, scale: f32, len: usize) -> c_int;
+    fn psdc_sint_csm_process_device(h: *mut PsdcCsm, group: u32, d_x: *const *const c_void, kind: c_int, scale: f32, len: usize,
+                                    producer_event: *mut c_void) -> c_int;
+}
+
 /// Online power spectral density estimation on one MI355X (drop-in for `psd::PsdCascade<N>`).
 pub struct PsdCascade<const N: usize>(NonNull<PsdcHandle>);
 

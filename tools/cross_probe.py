@@ -53,6 +53,11 @@ object kind fed the sc16 stream whose conversion A's is -- half the bytes over t
 legs C (complex64) and D (sc16).  A, B, A and C, D, C in turn --reps times in one session; the rates, B / A, D / C, the largest
 |A' - A| / A and |C' - C| / C and the launches a call of B and D are recorded as findings, none is a gate.  Writes
 profiles/iq_int_probe.json (--pair: its "pair" entry; the file holds one entry a flavour) unless --out names another file.
+--real-int: the integer feed of the objects with no mixer (s16, scale 2^-15) against the f32 feed of the converted stream on the
+same kind of object, at N = 512, 1024, 4096: PsdCascadeBank(n, 1) and CsdCascadeBank(n, 1), host-fed in 2^22-unit calls and
+device-resident in 2^24-unit calls.  A (f32), B (s16), A in turn --reps times for each of the four; the rates, B / A, the largest
+|A' - A| / A and the pair object's launches a steady call are recorded as findings, none is a gate.  Writes
+profiles/real_int_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -470,6 +475,60 @@ def iq_int_legs(pkg, torch, seconds, reps, pair):
     return legs
 
 
+def real_int_legs(pkg, torch, seconds, reps):
+    """The s16 feed (scale 2^-15) of the PSD and the pair object against the f32 feed of the converted stream on the same kind of
+    object: host-fed in 2^22-unit calls (legs psd_host, pair_host) and device-resident in 2^24-unit calls (psd_device, pair_device),
+    A / B / A in turn for each, and the launches of a steady call of the pair object."""
+    host_call, dev_call = 1 << 22, 1 << 24
+    rng = np.random.default_rng(7)
+    kind, scale = pkg.sample_kind(np.int16)
+    ints = [np.clip(np.rint(rng.standard_normal(dev_call) * 6000.0), -32768, 32767).astype(np.int16) for _ in range(2)]
+    f32 = [v.astype(np.float32) * np.float32(scale) for v in ints]
+    d_int = [torch.from_numpy(v).cuda() for v in ints]
+    d_f32 = [torch.from_numpy(x).cuda() for x in f32]
+    torch.cuda.synchronize()
+    h_int, h_f32 = [v[:host_call] for v in ints], [x[:host_call] for x in f32]
+    r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+    legs = []
+    for n in (512, 1024, 4096):
+        psd = {k: pkg.PsdCascadeBank(n, 1) for k in "ab"}
+        csd = {k: pkg.CsdCascadeBank(n, 1) for k in "ab"}
+        steps = {  # name -> (objects, f32 step, s16 step)
+            "psd_host": (psd, lambda: psd["a"].process(0, h_f32[0]) or host_call, lambda: psd["b"].process_int(0, h_int[0]) or host_call),
+            "pair_host": (csd, lambda: csd["a"].process(0, *h_f32) or host_call, lambda: csd["b"].process_int(0, *h_int) or host_call),
+            "psd_device": (psd, lambda: psd["a"].process_device(0, d_f32[0].data_ptr(), dev_call) or dev_call,
+                           lambda: psd["b"].process_int_device(0, d_int[0].data_ptr(), dev_call, kind) or dev_call),
+            "pair_device": (csd, lambda: csd["a"].process_device(0, *[t.data_ptr() for t in d_f32], dev_call) or dev_call,
+                            lambda: csd["b"].process_int_device(0, *[t.data_ptr() for t in d_int], dev_call, kind) or dev_call),
+        }
+        out = {"n": n, "host_call": host_call, "device_call": dev_call}
+        for name, (objs, a_step, b_step) in steps.items():
+            a1, b, a2 = [], [], []
+            for _ in range(reps):
+                a1.append(timed(a_step, objs["a"].sync, seconds)[0] / 1e9)
+                b.append(timed(b_step, objs["b"].sync, seconds)[0] / 1e9)
+                a2.append(timed(a_step, objs["a"].sync, seconds)[0] / 1e9)
+            ba = [v / u for u, v in zip(a1, b)]
+            aa = max(abs(v - u) / u for u, v in zip(a1, a2))
+            out[name] = {"a_f32_gs_s": r3(a1), "b_s16_gs_s": r3(b), "a_again_gs_s": r3(a2), "ratio_b_over_a": r3(ba),
+                         "b_over_a_min": round(min(ba), 3), "b_over_a_max": round(max(ba), 3), "aa_spread_max": round(aa, 4),
+                         "b_beats_a": bool(min(ba) > 1 + aa), "b_loses_to_a": bool(max(ba) < 1 - aa)}
+        launches = {}
+        for name in ("pair_host", "pair_device"):
+            objs, a_step, b_step = steps[name]
+            for k, step in (("a", a_step), ("b", b_step)):
+                objs[k].stats_read(reset=True)
+                for _ in range(8):
+                    step()
+                launches[f"{name}_{'f32' if k == 'a' else 's16'}"] = objs[k].stats_read()["launches"] / 8
+                objs[k].sync()
+        out["launches_per_call"] = launches
+        legs.append(out)
+        for o in list(psd.values()) + list(csd.values()):
+            o.close()
+    return legs
+
+
 def zoom_pair_image(pkg, torch, n=1024, k=2, b=100, f0=0.2, length=1 << 20):
     """A tone at f0 + delta (delta the centre of bin b of stage k) on both channels, b's at 0.7 of a's and 1 rad behind:
     |S_ab lower[b]| / |S_ab upper[b]| at stage k from the zoom cross object, and the same rebuilt from a matrix object fed the
@@ -781,9 +840,25 @@ def main():
                                                       "and CsmCascadeBank(n, 4) fed the four planar streams")
     ap.add_argument("--int", dest="int_feed", action="store_true", help="with --iq [--pair]: the sc16 feed against the complex64 feed of "
                                                                         "the same stream, host-fed and device-resident")
+    ap.add_argument("--real-int", action="store_true", help="the s16 feed of PsdCascadeBank and CsdCascadeBank against the f32 feed of "
+                                                            "the converted stream, host-fed and device-resident")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.real_int:
+        before = gpu_state()
+        legs = real_int_legs(pkg, torch, a.seconds, a.reps)
+        line = json.dumps({"metric": "real_int_gsamples_s", "unit": "1e9 samples a second (of each side for the pair object)",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "findings, no gate: host-fed, B moves 2 bytes a sample over the host link where A moves 4; "
+                                   "device-resident, the PSD object's s16 route converts into the stream buffer (one extra pass) where "
+                                   "its f32 route is read in place, and the pair object's converter stands where its copies stand; "
+                                   "not measured here: s8, the matrix object, banks, a wider converter",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "real_int_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.iq and a.int_feed:
         before = gpu_state()
         legs = iq_int_legs(pkg, torch, a.seconds, a.reps, a.pair)

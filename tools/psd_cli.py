@@ -24,8 +24,10 @@ offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - off
 --sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
 integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
 then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
-FILE[:F0] and --iq-pair FILEA:FILEB[:F0] files of interleaved (re, im) integer pairs (sc16 / sc8, an SDR's native output).  The
-printed lines and the --csv files are those of the f32 options."""
+FILE[:F0] and --iq-pair FILEA:FILEB[:F0] files of interleaved (re, im) integer pairs (sc16 / sc8, an SDR's native output); --raw
+FILE is the plain spectrum of a file of real integers (PsdCascade.process_int) and --pair FILEX:FILEY the cross spectrum of two
+such files (CsdCascade.process_int).  --file (frames) is refused.  The printed lines and the --csv files are those of the f32
+options."""
 import argparse
 import os
 import sys
@@ -63,13 +65,13 @@ def main(argv=None):
     ap.add_argument("--iq-pair", action="append", default=[],
                     help="IA:QA:IB:QB[:F0] -- two-sided auto and cross spectra of two complex streams, retuned by F0 (repeatable)")
     ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
-                    help="s16 / s8: --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
+                    help="s16 / s8: --raw, --pair, --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
     ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
     a = ap.parse_args(argv)
     if a.sample_format != "f32":
-        if a.file or a.raw or a.pair or not (a.zoom or a.zoom_pair or a.iq or a.iq_pair):
-            raise SystemExit("--sample-format s16 / s8 takes --zoom, --zoom-pair, --iq or --iq-pair with raw integer files, and no "
-                             "--file, --raw or --pair")
+        if a.file or not (a.raw or a.pair or a.zoom or a.zoom_pair or a.iq or a.iq_pair):
+            raise SystemExit("--sample-format s16 / s8 takes --raw, --pair, --zoom, --zoom-pair, --iq or --iq-pair with raw integer files, "
+                             "and no --file")
         import __graft_entry__ as entry
         return int_feeds(entry.load_package(), a)
     if a.scale is not None:
@@ -440,6 +442,37 @@ def int_feeds(pkg, a):
         emit(stem, [f"{o:.9g},{p:.9g},{q:.9g},{u.real:.9g},{u.imag:.9g},{r:.9g},{t:.9g},{w.real:.9g},{w.imag:.9g}\n"
                     for o, p, q, u, r, t, w in zip(off, aup, bup, xup, alo, blo, xlo)])
 
+    if a.raw:  # the plain spectrum: the lines of the f32 --raw
+        bank = settle(pkg.PsdCascadeBank(1 << 9, 1))
+        feed([a.raw], 1, "--raw", lambda xs: bank.process_int(0, xs[0], a.scale))
+        if bank.num_stages(0) == 0:
+            print("raw: no samples")
+        else:
+            psd, breaks = bank.psd(0, merge)
+            rms, xy = pkg.trace_plot(psd, pkg.Break.frequencies(breaks), fs=a.fs, integrate=a.integrate,
+                                     integral_start=a.integral_start * a.fs, integral_end=a.integral_end * a.fs)
+            top = bank.stage_info(0, 0)["count"]
+            print(f"raw: stages {bank.num_stages(0)} top-stage averages {top} bins {psd.size} breaks {len(breaks)} rms {rms:.9g}")
+            if a.csv:
+                emit("raw", [f"{x:.9g},{y:.9g}\n" for x, y in xy])
+        bank.close()
+    for z in a.pair:  # the lines of the f32 --pair
+        parts = z.split(":")
+        if len(parts) != 2 or not all(parts):
+            raise SystemExit("--pair takes FILEX:FILEY with --sample-format s16 / s8")
+        bank = settle(pkg.CsdCascadeBank(1 << 9, 1))
+        feed(parts, 1, "--pair", lambda xs: bank.process_int(0, xs[0], xs[1], a.scale))
+        x, y = (os.path.basename(f) for f in parts)
+        if bank.num_stages(0) == 0:
+            print(f"{x}:{y}: no samples")
+        else:
+            sxx, syy, sxy, breaks = bank.csd(0, merge)
+            freqs = pkg.Break.frequencies(breaks) * a.fs
+            coh, h1 = pkg.coherence(sxx, syy, sxy), pkg.transfer(sxx, sxy)
+            print(f"{x}:{y}: bins {sxx.size} median coherence {np.nanmedian(coh):.6g}")
+            if a.csv:
+                emit(f"pair_{x}__{y}", [f"{fr:.9g},{abs(h):.9g},{np.angle(h):.9g},{c:.9g}\n" for fr, h, c in zip(freqs, h1, coh)])
+        bank.close()
     for z in a.zoom:
         f0, _, path = z.partition(":")
         if not path:
