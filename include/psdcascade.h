@@ -1140,6 +1140,70 @@ int psdc_sint_csm_process(psdc_csm *h, uint32_t group, const void *const *x, int
 int psdc_sint_csm_process_device(psdc_csm *h, uint32_t group, const void *const *d_x, int kind, float scale, size_t len,
                                  void *producer_event);
 
+/* ---- spectral kurtosis cascade: per-bin Gaussianity beside the PSD ------------------------------------------------
+ * Every other object keeps first moments of the periodogram P_j[k] = |X_j[k]|^2: how much power a bin holds.  This one keeps
+ * the second moment beside it, which tells stationary Gaussian noise from a coherent line, a burst, or a source that is on
+ * part of the time -- all of which read the same in the PSD.
+ * Unit and stages: a unit is one real f32 stream; `n_channels` independent ones.  Per stage the segmentation, Window<N>,
+ * Detrend, /8 half-band decimation with the drain of 35 outputs, lazy stages and the averaging schedule (set_avg) are those of
+ * PsdCascade<N> fed the same stream -- what a pair object does per channel.  A channel has exactly the stages, counts,
+ * pendings and Breaks of a PsdCascade fed x.
+ * Rows: each (channel, stage) holds two f64 rows of n/2 + 1 bins,
+ *     row 0:  S1[k] = sum_j w_j P_j[k],        row 1:  S2[k] = sum_j w_j P_j[k]^2,
+ * with w_j the weights a pair object gives S_xx: 1 while the stage averages as a boxcar, then the EWMA weights of
+ * src/psd.rs:218-233; both rows are folded with the same factor.  Row 0 is therefore the pair object's S_xx row and
+ * PsdCascade's spectrum (to 1e-5 relative: the rounding order differs).
+ * Weights: the segment kernel transforms with amplitude 1 and weights both products afterwards, (w P) and (w P) P; the weight
+ * is never squared and never divided by (csrc/sk_fft.h).
+ * Estimator: with M = count, the stage's reported count (psdc_stage_stat.count),
+ *     SK[k] = (M + 1) / (M - 1) * (M S2[k] / S1[k]^2 - 1),
+ * computed on the host in f64 from the f64 rows.  It is defined for count >= 2; below that, and where S1[k] == 0, a bin reads
+ * NaN.  Readings: 1 for Gaussian noise of any colour (a linear filter keeps Gaussian noise Gaussian, so at every stage);
+ * 0 for a line of constant amplitude; about 2/d - 1 for noise present a fraction d of the time.  The real-valued bins 0 and N/2
+ * read 2 for Gaussian noise (their P is chi-squared with one degree of freedom, not two).  For Gaussian noise the standard
+ * deviation of a bin is about 2 / sqrt(M).
+ * EWMA regime: once count sits at the averaging limit the weights decay geometrically and M = count is an approximation: the
+ * effective number of averages is about 2 count - 1, so SK carries a bias of order 1 / count.
+ * Range: a workgroup's partial rows are f32, so P^2 summed over the segments a workgroup takes in one round must stay below
+ * f32 max (3.4e38); the accumulators themselves are f64.
+ * Merged read-out: psdc_sk_psd is PsdCascade::psd (src/psd.rs:479-543) of row 0, with the same MergeOpts, bins, Breaks and gain
+ * as psdc_psd.  psdc_sk_sk returns the same Breaks and bin selection: bin i of the merged array is the SK of the stage and bin
+ * that psdc_sk_psd took bin i from (no gain applies: SK is a ratio).  It is written in f64.
+ * Sizes and windows are those of pairs: n a power of two 64 ... 4096; Window::hann(), Window::rectangular(), or a caller's
+ * table with (n - overlap) % 8 == 0.  Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere.  There is no CPU fallback.
+ * Stream ordering, the caller-keeps-memory rule, errors and the device rule are those of the pair object: host samples go up
+ * through the pinned staging, device samples are copied on the side stream behind producer_event, a grown buffer and round
+ * R - 2.  A steady round is 3 kernel launches whatever the depth (segments, decimators, fold + tails).  Host and device
+ * calls of the same samples, and the same calls twice, give the same bits; a bank's channel equals a single object under the
+ * rule stated for the zoom object.  Stream frames and integer samples do not feed this object yet. */
+typedef struct psdc_sk psdc_sk;
+/* 1 where n is a size the object takes, else 0 */
+int psdc_sk_supported(uint32_t n);
+psdc_sk *psdc_sk_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+psdc_sk *psdc_sk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                               int device);
+void psdc_sk_destroy(psdc_sk *h);
+int psdc_sk_reset(psdc_sk *h);
+int psdc_sk_set_detrend(psdc_sk *h, int detrend_kind);
+int psdc_sk_set_avg(psdc_sk *h, uint32_t limit, uint32_t count);
+/* len real samples of a channel from host memory */
+int psdc_sk_process(psdc_sk *h, uint32_t channel, const float *x, size_t len);
+/* the same from device memory; producer_event: hipEvent_t or NULL */
+int psdc_sk_process_device(psdc_sk *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_sk_sync(psdc_sk *h);
+int psdc_sk_num_stages(psdc_sk *h, uint32_t channel);
+/* raw f64 accumulators of one stage: s1, s2 n/2 + 1 doubles each; any may be NULL */
+int psdc_sk_stage_moments(psdc_sk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1, double *s2);
+/* the merged PSD (row 0): psd `cap` floats, may be NULL to query sizes */
+int psdc_sk_psd(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *psd,
+                size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* the merged SK: sk `cap` doubles, may be NULL to query sizes; the Breaks and the length are those of psdc_sk_psd */
+int psdc_sk_sk(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk,
+               size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* kernel launches issued and samples accepted since creation or the last reset of the statistics */
+int psdc_sk_stats_read(psdc_sk *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_sk_last_error(const psdc_sk *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

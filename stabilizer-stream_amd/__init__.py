@@ -440,6 +440,23 @@ def lib():
     f("psdc_sint_cross_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
     f("psdc_sint_csm_process", i32, [H, u32, pp, i32, fl, sz])
     f("psdc_sint_csm_process_device", i32, [H, u32, pp, i32, fl, sz, vp])
+    dp = C.POINTER(C.c_double)
+    f("psdc_sk_supported", i32, [u32])
+    f("psdc_sk_create", H, [u32, i32, u32, i32])
+    f("psdc_sk_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+    f("psdc_sk_destroy", None, [H])
+    f("psdc_sk_reset", i32, [H])
+    f("psdc_sk_set_detrend", i32, [H, i32])
+    f("psdc_sk_set_avg", i32, [H, u32, u32])
+    f("psdc_sk_process", i32, [H, u32, fp, sz])
+    f("psdc_sk_process_device", i32, [H, u32, vp, sz, vp])
+    f("psdc_sk_sync", i32, [H])
+    f("psdc_sk_num_stages", i32, [H, u32])
+    f("psdc_sk_stage_moments", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp])
+    f("psdc_sk_psd", i32, [H, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_sk_sk", i32, [H, u32, i32, u32, i32, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+    f("psdc_sk_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+    f("psdc_sk_last_error", C.c_char_p, [H])
     _lib = L
     return L
 
@@ -488,6 +505,9 @@ EXPORTS = [
     "psdc_int_iq_process", "psdc_int_iq_process_device", "psdc_int_iqcsd_process", "psdc_int_iqcsd_process_device",
     "psdc_sint_process", "psdc_sint_process_device", "psdc_sint_cross_process", "psdc_sint_cross_process_device",
     "psdc_sint_csm_process", "psdc_sint_csm_process_device",
+    "psdc_sk_supported", "psdc_sk_create", "psdc_sk_create_window", "psdc_sk_destroy", "psdc_sk_reset", "psdc_sk_set_detrend",
+    "psdc_sk_set_avg", "psdc_sk_process", "psdc_sk_process_device", "psdc_sk_sync", "psdc_sk_num_stages",
+    "psdc_sk_stage_moments", "psdc_sk_psd", "psdc_sk_sk", "psdc_sk_stats_read", "psdc_sk_last_error",
 ]
 
 
@@ -1548,6 +1568,175 @@ class ZoomCascade:
 
     def stats_read(self, reset=False):
         return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+def sk_supported(n):
+    """Whether SkCascade[Bank] takes the size n: a power of two 64 ... 4096"""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_sk_supported(n))
+
+
+def sk_from_moments(count, s1, s2):
+    """The spectral kurtosis estimator over M = count averaged segments, in f64, from the moments S1 = sum P and S2 = sum P^2
+    of the periodogram:  SK = (M + 1) / (M - 1) * (M S2 / S1^2 - 1).  1 for Gaussian noise of any colour (2 at the real-valued
+    bins 0 and N/2), 0 for a line of constant amplitude, about 2/d - 1 for noise present a fraction d of the time.  NaN for
+    count < 2 and where S1 == 0."""
+    s1, s2 = np.asarray(s1, np.float64), np.asarray(s2, np.float64)
+    m = float(count)
+    if count < 2:
+        return np.full(np.broadcast(s1, s2).shape, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sk = (m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0)
+    return np.where(s1 == 0.0, np.nan, sk)
+
+
+def sk_sigma(count):
+    """2 / sqrt(count): the asymptotic standard deviation of a bin of sk_from_moments for Gaussian noise over `count` independent
+    segments.  It ignores the small correlation of 50 %-overlapped Hann segments (which widens the scatter slightly) and is
+    not meant below a few tens of averages."""
+    return 2.0 / float(np.sqrt(float(count)))
+
+
+def _raise_sk(code, h=None):
+    msg = lib().psdc_sk_last_error(h)
+    raise PsdError(code, msg.decode() if msg else "")
+
+
+class SkCascadeBank:
+    """`n_channels` independent spectral kurtosis cascades (psdc_sk_*): every stage of a real stream keeps S1 = sum P, the
+    spectrum PsdCascade keeps, and S2 = sum P^2 beside it.  psd() is PsdCascade's; sk() is the per-bin estimator
+    sk_from_moments of the same stages and bins: 1 where the bin holds stationary Gaussian noise."""
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._L.psdc_sk_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
+        else:
+            self._h = self._L.psdc_sk_create(n, int(window), n_channels, device)
+        if not self._h:
+            msg = self._L.psdc_sk_last_error(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psdc_sk_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            _raise_sk(rc, self._h)
+        return rc
+
+    def reset(self):
+        self._ck(self._L.psdc_sk_reset(self._h))
+
+    def set_detrend(self, d):
+        self._ck(self._L.psdc_sk_set_detrend(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._L.psdc_sk_set_avg(self._h, avg.limit, avg.count))
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._L.psdc_sk_process(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_sk_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._L.psdc_sk_sync(self._h))
+
+    def num_stages(self, channel=0):
+        return self._ck(self._L.psdc_sk_num_stages(self._h, channel))
+
+    def stage_moments(self, channel, stage):
+        """(info, s1, s2) of one stage: its raw f64 accumulators sum w P and sum w P^2"""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        s1, s2 = np.empty(b, np.float64), np.empty(b, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._ck(self._L.psdc_sk_stage_moments(self._h, channel, stage, C.byref(st), s1.ctypes.data_as(dp), s2.ctypes.data_as(dp)))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, s1, s2
+
+    def _merged(self, fn, dtype, ctype, channel, opts):
+        ns = self.num_stages(channel)
+        cap = max(1, ns * (self.n // 2 + 1))
+        out = np.empty(cap, dtype)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(fn(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                    out.ctypes.data_as(C.POINTER(ctype)), cap, C.byref(plen), br, ns, C.byref(nb)))
+        return out[:plen.value].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def psd(self, channel=0, opts=MergeOpts()):
+        """(psd, breaks): PsdCascade::psd of row 0, as PsdCascade.psd() returns it"""
+        return self._merged(self._L.psdc_sk_psd, np.float32, C.c_float, channel, opts)
+
+    def sk(self, channel=0, opts=MergeOpts()):
+        """(sk, breaks): float64 SK of every bin of psd(), from the stage and bin psd() took it from; the same breaks"""
+        return self._merged(self._L.psdc_sk_sk, np.float64, C.c_double, channel, opts)
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.psdc_sk_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+    stats = stats_read
+
+
+class SkCascade:
+    """One stream: SkCascade(n).  psd() beside sk(), the per-bin spectral kurtosis."""
+
+    def __init__(self, n, window=Window.HANN, device=0):
+        self.n = n
+        self._b = SkCascadeBank(n, 1, window, device)
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x):
+        self._b.process(0, x)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def psd(self, opts=MergeOpts()):
+        return self._b.psd(0, opts)
+
+    def sk(self, opts=MergeOpts()):
+        return self._b.sk(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_moments(self, i):
+        return self._b.stage_moments(0, i)
+
+    def reset(self):
+        self._b.reset()
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    stats = stats_read
 
     def close(self):
         self._b.close()

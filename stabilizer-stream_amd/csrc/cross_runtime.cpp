@@ -8,8 +8,9 @@
 // zoom_cross_fft.h; an IQ object (psdc_iq_*) is the zoom kind with a different feed: its unit is one COMPLEX channel whose I and Q
 // arrive from the caller and go through the complex mixer (iq_mix_kernel, iq_frames_kernel) into the same two streams; an IQ cross
 // object (psdc_iqcsd_*) is the zoom cross kind with that feed for both sides at once: its unit is two complex channels, turned by
-// one pair mixer (iq_pair_mix_kernel, iq_cross_frames_kernel) into the same four streams.  Below, "pair" stands for any of these
-// units.
+// one pair mixer (iq_pair_mix_kernel, iq_cross_frames_kernel) into the same four streams; a spectral kurtosis object (psdc_sk_*)
+// has one real channel a unit, m = 1 stream fed as a pair's are, on sk_kernel with the rows S1 = sum w P and S2 = sum w P^2 of
+// sk_fft.h.  Below, "pair" stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -27,6 +28,8 @@
 #include "iq.h"
 #include "iq_cross.h"
 #include "sample_int.h"
+#include "sk.h"
+#include "sk_fft.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -71,8 +74,9 @@ struct XObj {
     bool zoom = false;   // psdc_zoom / psdc_zcsd: the streams are I and Q of mixed channels, fed through the mixer
     bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
     bool iq = false;     // psdc_iq (with zoom), psdc_iqcsd (with zoom and zcross): I and Q come from the caller, through the complex mixer
+    bool sk = false;     // psdc_sk: one real stream a unit (m = 1), sk_kernel and its two rows S1, S2
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return zcross ? 8 : zoom ? 2 : matrix ? m * m : 4; }
+    uint32_t rows() const { return zcross ? 8 : zoom || sk ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
     // (an IQ channel two: its I and its Q; an IQ cross pair four)
@@ -132,6 +136,7 @@ struct psdc_zoom : XObj {};
 struct psdc_zcsd : XObj {};
 struct psdc_iq : XObj {};
 struct psdc_iqcsd : XObj {};
+struct psdc_sk : XObj {};
 
 namespace {
 
@@ -260,6 +265,7 @@ int run_round(XObj *h, bool *did)
     const int spt = h->matrix   ? csm_segments_per_tile((int)h->n, (int)h->m)
                     : h->zcross ? zoom_cross_segments_per_tile((int)h->n)
                     : h->zoom   ? zoom_segments_per_tile((int)h->n)
+                    : h->sk     ? sk_segments_per_tile((int)h->n)
                                 : cross_segments_per_tile((int)h->n);
     const int nch = (int)h->m;
     std::vector<PlannedCross> cross;
@@ -403,6 +409,7 @@ int run_round(XObj *h, bool *did)
             CrossBatch *cb = new CrossBatch();
             fill(cb, pair_job);
             e = h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                : h->sk ? launch_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
                         : launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
             delete cb;
         }
@@ -560,7 +567,8 @@ std::string zcsd_size_text(uint32_t n)
 }
 
 // T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
-// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed
+// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed;
+// psdc_sk (m = 1: one real stream, sk_kernel)
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
@@ -570,6 +578,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
     constexpr bool zcross = std::is_same<T, psdc_zcsd>::value || iqcsd;
     constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd;
     constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq;
+    constexpr bool sk = std::is_same<T, psdc_sk>::value;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
         return nullptr;
@@ -578,7 +587,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + zcsd_size_text(n));
         return nullptr;
     }
-    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom, zcross)) {
+    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom || sk, zcross)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
         return nullptr;
     }
@@ -624,6 +633,12 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         }
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
+    }
+    if (sk) {
+        h->sk = true;
+        h->tag = "psdc_sk";
+        h->unit = "channel";
+        h->units = "n_channels";
     }
     h->n_pairs = n_pairs;
     h->device = device;
@@ -2476,5 +2491,154 @@ int psdc_sint_csm_process_device(psdc_csm *h, uint32_t group, const void *const 
 {
     return process_device_impl(h, group, d_x, int_fmt(kind, scale), len, producer_event, "psdc_sint_csm_process_device");
 }
+
+} // extern "C"
+
+// ---- spectral kurtosis: one real stream a unit; sk_kernel, rows S1 = sum w P and S2 = sum w P^2 ----
+
+namespace {
+
+// SK of one bin from its moments (include/psdcascade.h, "spectral kurtosis cascade"): NaN below two averages and without power
+double sk_estimate(uint32_t count, double s1, double s2)
+{
+    if (count < 2 || s1 == 0.0)
+        return std::numeric_limits<double>::quiet_NaN();
+    const double m = (double)count;
+    return (m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0);
+}
+
+// the stitch of row 0 (psd != NULL: written) and, with sk != NULL, the SK of every bin the stitch takes, selected by its Breaks
+int sk_readout_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *psd, double *sk,
+                    size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    if ((rc = drain(h)) || (rc = sync_all(h)))
+        return rc;
+    const auto &st = h->pairs[channel];
+    const uint32_t ns = (uint32_t)st.size();
+    const size_t b = bins(h);
+    std::vector<uint64_t> c64(std::max<uint32_t>(ns, 1)), pend(std::max<uint32_t>(ns, 1));
+    std::vector<uint32_t> avgs(std::max<uint32_t>(ns, 1));
+    std::vector<double> acc((size_t)ns * SK_ROWS * b);
+    std::vector<float> row0(std::max<size_t>(1, (size_t)ns * b));
+    for (uint32_t i = 0; i < ns; ++i) {
+        c64[i] = st[i].count64;
+        pend[i] = pending_for(h->geo, st[i].total);
+        avgs[i] = cur_avg(h, i);
+        double *a = &acc[(size_t)i * SK_ROWS * b];
+        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * SK_ROWS * b, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < b; ++k)
+            row0[(size_t)i * b + k] = (float)a[k];
+    }
+    psdc_break own[X_MAX_STAGES];
+    size_t l = 0, nb = 0;
+    rc = psdc_stitch_window(h->n, h->power, h->nenbw, h->geo.overlap, ns, c64.data(), avgs.data(), pend.data(), row0.data(),
+                            keep_overlap, min_count, keep_transition_band, psd, psd ? cap : 0, &l, own, X_MAX_STAGES, &nb);
+    if (rc == PSDC_ERR_CAPACITY || ((psd || sk) && l > cap))
+        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
+    if (rc)
+        return xfail(h, rc, std::string(who) + ": " + psdc_last_error(nullptr));
+    if (len)
+        *len = l;
+    if (n_breaks)
+        *n_breaks = nb;
+    if (breaks) {
+        if (nb > breaks_cap)
+            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
+        std::copy(own, own + nb, breaks);
+    }
+    if (sk)
+        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
+            const psdc_break &br = own[i];
+            if (!br.include)
+                continue;
+            const double *a = &acc[(size_t)(ns - 1 - i) * SK_ROWS * b];
+            for (uint64_t k = br.bins_start; k < br.bins_end; ++k)
+                sk[br.start + (k - br.bins_start)] = sk_estimate(br.count, a[k], a[b + k]);
+        }
+    return PSDC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int psdc_sk_supported(uint32_t n) { return n <= 4096 && cross_supported((int)n) ? 1 : 0; }
+
+psdc_sk *psdc_sk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_sk>(n, win, power, nenbw, overlap, 1, n_channels, device, "psdc_sk_create_window");
+}
+
+psdc_sk *psdc_sk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_sk>(n, window_kind, 1, n_channels, device, "psdc_sk_create");
+}
+
+void psdc_sk_destroy(psdc_sk *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+int psdc_sk_reset(psdc_sk *h) { return reset_impl(h, "psdc_sk_reset"); }
+int psdc_sk_set_detrend(psdc_sk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_sk_set_detrend"); }
+int psdc_sk_set_avg(psdc_sk *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_sk_set_avg"); }
+
+int psdc_sk_process(psdc_sk *h, uint32_t channel, const float *x, size_t len)
+{
+    const void *xs[1] = {x};
+    return process_impl(h, channel, xs, SampleFmt{}, len, "psdc_sk_process");
+}
+
+int psdc_sk_process_device(psdc_sk *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return process_device_impl(h, channel, xs, SampleFmt{}, len, producer_event, "psdc_sk_process_device");
+}
+
+int psdc_sk_sync(psdc_sk *h) { return sync_impl(h, "psdc_sk_sync"); }
+int psdc_sk_num_stages(psdc_sk *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_sk_num_stages"); }
+
+int psdc_sk_stage_moments(psdc_sk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1, double *s2)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, channel, stage, stat, s1 || s2 ? &acc : nullptr, "psdc_sk_stage_moments");
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    if (s1)
+        std::copy(acc.begin(), acc.begin() + b, s1);
+    if (s2)
+        std::copy(acc.begin() + b, acc.begin() + 2 * b, s2);
+    return PSDC_OK;
+}
+
+int psdc_sk_psd(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *psd, size_t cap,
+                size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return sk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, psd, nullptr, cap, len, breaks, breaks_cap,
+                           n_breaks, "psdc_sk_psd");
+}
+
+int psdc_sk_sk(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk, size_t cap,
+               size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return sk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, sk, cap, len, breaks, breaks_cap,
+                           n_breaks, "psdc_sk_sk");
+}
+
+int psdc_sk_stats_read(psdc_sk *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_sk_stats_read");
+}
+
+const char *psdc_sk_last_error(const psdc_sk *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

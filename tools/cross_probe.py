@@ -58,6 +58,10 @@ same kind of object, at N = 512, 1024, 4096: PsdCascadeBank(n, 1) and CsdCascade
 device-resident in 2^24-unit calls.  A (f32), B (s16), A in turn --reps times for each of the four; the rates, B / A, the largest
 |A' - A| / A and the pair object's launches a steady call are recorded as findings, none is a gate.  Writes
 profiles/real_int_probe.json unless --out names another file.
+--sk: per-bin Gaussianity beside the PSD.  One device-resident f32 stream of 2^24 samples a call at N = 512, 1024, 4096.  Leg A:
+CsdCascadeBank(n, 1) fed (x, x), the nearest the other objects come (two transforms and decimations, S1 three times, no S2).  Leg B:
+SkCascadeBank(n, 1) fed x.  A, B, A in turn --reps times; the rates, B / A, the largest |A' - A| / A and B's launches a steady call
+are recorded as findings, none is a gate.  Writes profiles/sk_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -292,6 +296,46 @@ def zoom_legs(pkg, torch, seconds, reps, call):
                      "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": zb.num_stages(0)})
         pa.close()
         zb.close()
+    return legs
+
+
+def sk_legs(pkg, torch, seconds, reps, call):
+    """One device-resident f32 stream x.  A: CsdCascadeBank(n, 1) fed (x, x) -- the only way the other objects come near the
+    question, two transforms and two decimations a segment pair, four rows, S1 three times over and no S2.  B: SkCascadeBank(n, 1)
+    fed x (one transform and one decimation, two rows).  A / B / A in turn."""
+    x = torch.randn(call, device="cuda")
+    torch.cuda.synchronize()
+    legs = []
+    for n in (512, 1024, 4096):
+        pa = pkg.CsdCascadeBank(n, 1)
+        sb = pkg.SkCascadeBank(n, 1)
+
+        def a_step():
+            pa.process_device(0, x.data_ptr(), x.data_ptr(), call)
+            return call
+
+        def b_step():
+            sb.process_device(0, x.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, sb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, pa.sync, seconds)[0] / 1e9)
+        sb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = sb.stats_read()["launches"] / 8
+        sb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        legs.append({"n": n, "call": call, "a_pair_fed_xx_gs_s": [round(v, 3) for v in a1], "b_sk_gs_s": [round(v, 3) for v in b],
+                     "a_again_gs_s": [round(v, 3) for v in a2], "ratio_b_over_a": [round(r, 3) for r in ratios],
+                     "ratio_min": round(min(ratios), 3), "aa_spread_max": round(spread, 4),
+                     "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": sb.num_stages(0)})
+        pa.close()
+        sb.close()
     return legs
 
 
@@ -840,11 +884,24 @@ def main():
                                                       "and CsmCascadeBank(n, 4) fed the four planar streams")
     ap.add_argument("--int", dest="int_feed", action="store_true", help="with --iq [--pair]: the sc16 feed against the complex64 feed of "
                                                                         "the same stream, host-fed and device-resident")
+    ap.add_argument("--sk", action="store_true", help="SkCascadeBank fed x against CsdCascadeBank fed (x, x); writes profiles/sk_probe.json")
     ap.add_argument("--real-int", action="store_true", help="the s16 feed of PsdCascadeBank and CsdCascadeBank against the f32 feed of "
                                                             "the converted stream, host-fed and device-resident")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.sk:
+        before = gpu_state()
+        legs = sk_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)
+        line = json.dumps({"metric": "sk_gsamples_s", "unit": "1e9 samples a second of one real stream",
+                           "gpu_before": before, "gpu_after": gpu_state(),
+                           "note": "findings, no gate: A runs two transforms and two decimations where B runs one of each; not measured "
+                                   "here: host memory, banks, the EWMA regime (default averaging: every weight is 1)",
+                           "legs": legs})
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "sk_probe.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.real_int:
         before = gpu_state()
         legs = real_int_legs(pkg, torch, a.seconds, a.reps)

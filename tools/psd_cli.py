@@ -21,6 +21,10 @@ offset,upper,lower (the density of z at F0 + offset / F0 - offset; half of it is
 the one carrier F0 (default 0).  Traces of the frames with --file, four raw f32 files of equal length without it, as for --iq.
 Prints, or with --csv writes to DIR/iqpair_<ia>__<qa>__<ib>__<qb>_<F0>.csv, the lines of --zoom-pair:
 offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - offset); Sab = conj(Z_a) Z_b.
+--sk [TRACE] (repeatable; TRACE a label or index, default the first trace; with --raw the file) also feeds that trace to an
+SkCascade(512) and prints, or with --csv writes to DIR/sk_<trace>.csv, the lines frequency,psd,sk: the spectral kurtosis of every
+bin beside its density (1: stationary Gaussian noise; 0: a line of constant amplitude; above 1: power that comes and goes; NaN
+below two averages).  The summary line counts the bins more than 8 sk_sigma(count) away from 1.
 --sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
 integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
 then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
@@ -64,6 +68,8 @@ def main(argv=None):
                     help="I:Q[:F0] -- two-sided spectrum of the complex stream I + i Q, retuned by F0 (repeatable)")
     ap.add_argument("--iq-pair", action="append", default=[],
                     help="IA:QA:IB:QB[:F0] -- two-sided auto and cross spectra of two complex streams, retuned by F0 (repeatable)")
+    ap.add_argument("--sk", action="append", nargs="?", const="", default=[],
+                    help="[TRACE] -- spectral kurtosis of every bin beside the PSD of that trace (repeatable; default the first trace)")
     ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
                     help="s16 / s8: --raw, --pair, --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
     ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
@@ -133,6 +139,8 @@ def main(argv=None):
         zoom_traces(pkg, source, a, merge, names)
     if a.zoom_pair:
         zoom_pairs(pkg, source, a, merge, names)
+    if a.sk:
+        sk_traces(pkg, source, a, merge, names)
     if a.iq and a.file:
         iq_streams(pkg, source, a, merge, names)
     if a.iq_pair and a.file:
@@ -246,6 +254,36 @@ def zoom_traces(pkg, source, a, merge, names):
         lines = [f"{o:.9g},{u:.9g},{w:.9g}\n" for o, u, w in zip(off, up, lo)]
         if a.csv:
             safe = "".join(ch if ch.isalnum() else "_" for ch in f"zoom_{names[idx]}_{used[i]:.9g}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.writelines(lines)
+        else:
+            sys.stdout.writelines(lines)
+    bank.close()
+
+
+def sk_traces(pkg, source, a, merge, names):
+    """--sk: the named trace of every read (host_traces) into one spectral kurtosis cascade each"""
+    want = [trace_arg(tr, names, "--sk") for tr in a.sk]
+    bank = pkg.SkCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    host_traces(source, pkg, a, [(idx,) for idx in want], lambda i, xs: bank.process(i, xs[0]))
+    for i, idx in enumerate(want):
+        label = f"sk {names[idx]}"
+        if bank.num_stages(i) == 0:
+            print(f"{label}: no samples")
+            continue
+        psd, breaks = bank.psd(i, merge)
+        sk, _ = bank.sk(i, merge)
+        freqs = pkg.Break.frequencies(breaks) * a.fs
+        sigma = np.concatenate([np.full(b.bins.stop - b.bins.start, pkg.sk_sigma(max(b.count, 1))) for b in breaks if b.include] or [np.zeros(0)])
+        with np.errstate(invalid="ignore"):
+            odd = int(np.sum(np.abs(sk - 1.0) > 8.0 * sigma))
+        print(f"{label}: stages {bank.num_stages(i)} bins {psd.size} breaks {len(breaks)} median sk {np.nanmedian(sk) if sk.size else float('nan'):.6g} "
+              f"bins beyond 8 sigma of 1: {odd}")
+        lines = [f"{fr:.9g},{p:.9g},{k:.9g}\n" for fr, p, k in zip(freqs, psd, sk)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"sk_{names[idx]}")
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(lines)
         else:
