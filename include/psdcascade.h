@@ -1204,6 +1204,103 @@ int psdc_sk_sk(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_coun
 int psdc_sk_stats_read(psdc_sk *h, uint64_t *launches, uint64_t *samples_in, int reset);
 const char *psdc_sk_last_error(const psdc_sk *h);
 
+/* ---- zoom and IQ spectral kurtosis cascades: SK around a carrier ---------------------------------------------------
+ * The spectral kurtosis object takes real streams from DC upwards.  The streams SK is used on most are complex: I/Q from an
+ * SDR front end or a lock-in, the Fls BI / BQ traces, or a narrow band around a carrier of a real stream.  These two objects
+ * keep the second moment of the periodogram beside the first on the two-sided cascade: psdc_zsk_* is the zoom object (a real
+ * stream plus a carrier, fed as psdc_zoom_* is) and psdc_iqsk_* the IQ object (a complex stream plus an optional retune, fed
+ * as psdc_iq_* is).  Both share one segment kernel (csrc/zoom_sk.hip).
+ * Unit, carrier and stages: those of the zoom / IQ object fed the same stream and carrier -- segmentation, Window<N>, Detrend,
+ * /8 decimation of I and Q with the drain of 35 outputs, lazy stages, the averaging schedule (set_avg), counts, pendings and
+ * Breaks.
+ * Rows: each (channel, stage) holds four f64 rows of n/2 + 1 bins, in this order, Z the transform of the segment's I + i Q:
+ *     row 0:  s1_upper[k] = sum_j w_j |Z_j[k]|^2              row 1:  s1_lower[k] = sum_j w_j |Z_j[(N - k) mod N]|^2
+ *     row 2:  s2_upper[k] = sum_j w_j |Z_j[k]|^4              row 3:  s2_lower[k] = sum_j w_j |Z_j[(N - k) mod N]|^4
+ * with w_j the weights of the spectral kurtosis object: 1 while the stage averages as a boxcar, then the EWMA weights; all four
+ * rows are folded with the same factor.  Rows 0 and 1 are therefore the zoom / IQ object's `upper` and `lower` (to 1e-5
+ * relative: the weight goes on the products here, on the samples there).  The transform runs with amplitude 1 and the weight is
+ * applied as (w P) and (w P) P, never squared and never divided by (csrc/zoom_sk_fft.h, csrc/sk_fft.h).
+ * Estimator: SK = (M + 1) / (M - 1) * (M S2 / S1^2 - 1) with M = count, per side, in f64 on the host, in the operation order
+ * of the spectral kurtosis object; NaN below two averages and where S1 == 0.
+ * What SK reads on complex bins: every bin of a complex stream is complex, so circular Gaussian noise reads 1 at every bin,
+ * offset 0 and Nyquist included: the real object's "2 at the real-valued bins" does not occur.  A line of constant amplitude
+ * reads 0; power that is on a fraction d of the time reads about 2/d - 1.  A real stream mixed from f0 is not circular where
+ * its own DC and Nyquist fall: near offset f0 in `lower` and offset 0.5 - f0 in `upper` (for 0 < f0 < 0.5) SK rises towards 2.
+ * A numpy model (N = 512, f0 = 0.2, 2^21 samples, Hann) read 1.29 and 1.56 at upper bins 153 and 154 and 1.31 and 1.60 at
+ * lower bins 103 and 102, every other bin inside 16 / sqrt(count); circular complex Gaussian noise in the same model read
+ * 5.8 / sqrt(count) at its worst bin, 1.013 at bin 0 and 1.000 at bin N/2.  The EWMA regime and the f32 range of a workgroup's
+ * partial rows are as stated for the spectral kurtosis object.
+ * Merged read-out: psdc_zsk_psd / psdc_iqsk_psd are psdc_zoom_psd of rows 0 and 1.  psdc_zsk_sk / psdc_iqsk_sk return the same
+ * Breaks and bin selection: bin i of each merged array is the SK of the stage and bin the psd took bin i from (no gain: SK is
+ * a ratio; no new stitch).  Offsets are read as the zoom object's are.
+ * Sizes and windows are those of psdc_sk_supported and of the zoom object; Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as
+ * everywhere.  There is no CPU fallback.  Sample routes, stream ordering, the caller-keeps-memory rule, errors, the device
+ * rule and the bank rule are those of psdc_zoom_* / psdc_iq_*: a steady-state call is 1 + 3 kernel launches (mixer; segments,
+ * decimators, fold + tails); host and device calls of the same samples, and the same calls twice, give the same bits.  Only
+ * the f32 sample routes feed these objects yet. */
+typedef struct psdc_zsk psdc_zsk;
+/* 1 where n is a size the object takes, else 0 (psdc_sk_supported) */
+int psdc_zsk_supported(uint32_t n);
+/* mirrors psdc_zoom_create / psdc_zoom_create_window */
+psdc_zsk *psdc_zsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+psdc_zsk *psdc_zsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                 int device);
+void psdc_zsk_destroy(psdc_zsk *h);
+/* as psdc_zoom_reset: stages, buffers, settings, carriers and statistics */
+int psdc_zsk_reset(psdc_zsk *h);
+int psdc_zsk_set_detrend(psdc_zsk *h, int detrend_kind);
+int psdc_zsk_set_avg(psdc_zsk *h, uint32_t limit, uint32_t count);
+/* as psdc_zoom_set_carrier; PSDC_ERR_ARG once the channel has taken a sample */
+int psdc_zsk_set_carrier(psdc_zsk *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* as psdc_zoom_process / psdc_zoom_process_device */
+int psdc_zsk_process(psdc_zsk *h, uint32_t channel, const float *x, size_t len);
+int psdc_zsk_process_device(psdc_zsk *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_zsk_sync(psdc_zsk *h);
+int psdc_zsk_num_stages(psdc_zsk *h, uint32_t channel);
+/* raw f64 accumulators of one stage (as psdc_sk_stage_moments, per side): n/2 + 1 doubles each; any may be NULL */
+int psdc_zsk_stage_moments(psdc_zsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper,
+                           double *s1_lower, double *s2_upper, double *s2_lower);
+/* psdc_zoom_psd of rows 0 and 1 */
+int psdc_zsk_psd(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                 float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* the merged SK of both sides (as psdc_sk_sk): sk_upper, sk_lower `cap` doubles each, either may be NULL; the Breaks and the
+ * length are those of psdc_zsk_psd */
+int psdc_zsk_sk(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
+                double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* as psdc_zoom_stats_read */
+int psdc_zsk_stats_read(psdc_zsk *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_zsk_last_error(const psdc_zsk *h);
+
+typedef struct psdc_iqsk psdc_iqsk;
+int psdc_iqsk_supported(uint32_t n);
+/* mirrors psdc_iq_create / psdc_iq_create_window */
+psdc_iqsk *psdc_iqsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+psdc_iqsk *psdc_iqsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                   int device);
+void psdc_iqsk_destroy(psdc_iqsk *h);
+int psdc_iqsk_reset(psdc_iqsk *h);
+int psdc_iqsk_set_detrend(psdc_iqsk *h, int detrend_kind);
+int psdc_iqsk_set_avg(psdc_iqsk *h, uint32_t limit, uint32_t count);
+/* as psdc_iq_set_carrier: the retune, default 0, 0 */
+int psdc_iqsk_set_carrier(psdc_iqsk *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* the four f32 sample routes of psdc_iq_*: planar and interleaved, host and device */
+int psdc_iqsk_process(psdc_iqsk *h, uint32_t channel, const float *i, const float *q, size_t len);
+int psdc_iqsk_process_device(psdc_iqsk *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event);
+int psdc_iqsk_process_interleaved(psdc_iqsk *h, uint32_t channel, const float *iq, size_t len);
+int psdc_iqsk_process_interleaved_device(psdc_iqsk *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event);
+int psdc_iqsk_sync(psdc_iqsk *h);
+int psdc_iqsk_num_stages(psdc_iqsk *h, uint32_t channel);
+/* as psdc_zsk_stage_moments, psdc_zsk_psd (psdc_iq_psd of rows 0 and 1) and psdc_zsk_sk */
+int psdc_iqsk_stage_moments(psdc_iqsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper,
+                            double *s1_lower, double *s2_upper, double *s2_lower);
+int psdc_iqsk_psd(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                  float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+int psdc_iqsk_sk(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
+                 double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* as psdc_iq_stats_read: complex samples accepted */
+int psdc_iqsk_stats_read(psdc_iqsk *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_iqsk_last_error(const psdc_iqsk *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -457,6 +457,28 @@ def lib():
     f("psdc_sk_sk", i32, [H, u32, i32, u32, i32, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
     f("psdc_sk_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
     f("psdc_sk_last_error", C.c_char_p, [H])
+    for pre in ("psdc_zsk_", "psdc_iqsk_"):
+        f(pre + "supported", i32, [u32])
+        f(pre + "create", H, [u32, i32, u32, i32])
+        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+        f(pre + "destroy", None, [H])
+        f(pre + "reset", i32, [H])
+        f(pre + "set_detrend", i32, [H, i32])
+        f(pre + "set_avg", i32, [H, u32, u32])
+        f(pre + "set_carrier", i32, [H, u32, u64, u64])
+        f(pre + "sync", i32, [H])
+        f(pre + "num_stages", i32, [H, u32])
+        f(pre + "stage_moments", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp, dp, dp])
+        f(pre + "psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+        f(pre + "sk", i32, [H, u32, i32, u32, i32, dp, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+        f(pre + "last_error", C.c_char_p, [H])
+    f("psdc_zsk_process", i32, [H, u32, fp, sz])
+    f("psdc_zsk_process_device", i32, [H, u32, vp, sz, vp])
+    f("psdc_iqsk_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_iqsk_process_device", i32, [H, u32, vp, vp, sz, vp])
+    f("psdc_iqsk_process_interleaved", i32, [H, u32, fp, sz])
+    f("psdc_iqsk_process_interleaved_device", i32, [H, u32, vp, sz, vp])
     _lib = L
     return L
 
@@ -508,6 +530,14 @@ EXPORTS = [
     "psdc_sk_supported", "psdc_sk_create", "psdc_sk_create_window", "psdc_sk_destroy", "psdc_sk_reset", "psdc_sk_set_detrend",
     "psdc_sk_set_avg", "psdc_sk_process", "psdc_sk_process_device", "psdc_sk_sync", "psdc_sk_num_stages",
     "psdc_sk_stage_moments", "psdc_sk_psd", "psdc_sk_sk", "psdc_sk_stats_read", "psdc_sk_last_error",
+    "psdc_zsk_supported", "psdc_zsk_create", "psdc_zsk_create_window", "psdc_zsk_destroy", "psdc_zsk_reset",
+    "psdc_zsk_set_detrend", "psdc_zsk_set_avg", "psdc_zsk_set_carrier", "psdc_zsk_process", "psdc_zsk_process_device",
+    "psdc_zsk_sync", "psdc_zsk_num_stages", "psdc_zsk_stage_moments", "psdc_zsk_psd", "psdc_zsk_sk", "psdc_zsk_stats_read",
+    "psdc_zsk_last_error",
+    "psdc_iqsk_supported", "psdc_iqsk_create", "psdc_iqsk_create_window", "psdc_iqsk_destroy", "psdc_iqsk_reset",
+    "psdc_iqsk_set_detrend", "psdc_iqsk_set_avg", "psdc_iqsk_set_carrier", "psdc_iqsk_process", "psdc_iqsk_process_device",
+    "psdc_iqsk_process_interleaved", "psdc_iqsk_process_interleaved_device", "psdc_iqsk_sync", "psdc_iqsk_num_stages",
+    "psdc_iqsk_stage_moments", "psdc_iqsk_psd", "psdc_iqsk_sk", "psdc_iqsk_stats_read", "psdc_iqsk_last_error",
 ]
 
 
@@ -2006,6 +2036,233 @@ class IqCascade:
 
     def close(self):
         self._b.close()
+
+
+def zoom_sk_supported(n):
+    """Whether ZoomSkCascade[Bank] and IqSkCascade[Bank] take the size n: a power of two 64 ... 4096 (sk_supported)"""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_zsk_supported(n))
+
+
+class ZoomSkCascadeBank:
+    """`n_channels` independent zoom spectral kurtosis cascades (psdc_zsk_*): ZoomCascadeBank's carrier, mixer and two-sided
+    cascade, with S2 = sum |Z|^4 kept beside S1 = sum |Z|^2 on both sides.  psd() is ZoomCascadeBank's; sk() is sk_from_moments
+    of the same stages and bins, per side: 1 where the sideband holds stationary (circular) Gaussian noise, at every bin --
+    offset 0 and Nyquist included, every bin of a complex stream being complex; 0 on a line; about 2/d - 1 for power that is on
+    a fraction d of the time.  A real stream is not circular where its own DC and Nyquist fall (offset f0 in `lower`,
+    0.5 - f0 in `upper`): there SK rises towards 2.  two_sided() lays either read-out out over (-0.5, 0.5]."""
+
+    _P = "psdc_zsk_"
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
+        else:
+            self._h = self._f("create")(n, int(window), n_channels, device)
+        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
+        if not self._h:
+            msg = self._f("last_error")(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def _f(self, name):
+        return getattr(self._L, self._P + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._f("last_error")(self._h)
+            raise PsdError(rc, msg.decode() if msg else "")
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        self._ck(self._f("reset")(self._h))
+        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
+
+    def set_detrend(self, d):
+        self._ck(self._f("set_detrend")(self._h, int(d)))
+
+    def set_avg(self, avg):
+        self._ck(self._f("set_avg")(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
+        """The channel's carrier, as ZoomCascadeBank.set_carrier takes it.  Returns the f0 actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        self._ck(self._f("set_carrier")(self._h, channel, ftw, phase0))
+        self.carriers[channel] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._L.psdc_zsk_process(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zsk_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._f("sync")(self._h))
+
+    def num_stages(self, channel=0):
+        return self._ck(self._f("num_stages")(self._h, channel))
+
+    def stage_moments(self, channel, stage):
+        """(info, s1_upper, s1_lower, s2_upper, s2_lower) of one stage: its raw f64 accumulators sum w |Z|^2 and sum w |Z|^4"""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        rows = [np.empty(b, np.float64) for _ in range(4)]
+        dp = C.POINTER(C.c_double)
+        self._ck(self._f("stage_moments")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
+        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, *rows)
+
+    def _merged(self, fn, dtype, ctype, channel, opts):
+        ns = self.num_stages(channel)
+        cap = max(1, ns * (self.n // 2 + 1))
+        up, lo = np.empty(cap, dtype), np.empty(cap, dtype)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        cp = C.POINTER(ctype)
+        self._ck(fn(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band), up.ctypes.data_as(cp),
+                    lo.ctypes.data_as(cp), cap, C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def psd(self, channel=0, opts=MergeOpts()):
+        """(upper, lower, breaks): the zoom read-out of the S1 rows, as ZoomCascadeBank.psd() returns it"""
+        return self._merged(self._f("psd"), np.float32, C.c_float, channel, opts)
+
+    def sk(self, channel=0, opts=MergeOpts()):
+        """(sk_upper, sk_lower, breaks): float64 SK of every bin of psd(), from the stage and bin psd() took it from"""
+        return self._merged(self._f("sk"), np.float64, C.c_double, channel, opts)
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+    stats = stats_read
+
+
+class IqSkCascadeBank(ZoomSkCascadeBank):
+    """`n_channels` independent IQ spectral kurtosis cascades (psdc_iqsk_*): ZoomSkCascadeBank for streams that are complex
+    already, fed as IqCascadeBank is and turned by an optional carrier (default none).  Circular complex Gaussian noise reads 1
+    at every bin of both sides."""
+
+    _P = "psdc_iqsk_"
+
+    def process(self, channel, z):
+        """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
+        real arrays of one length (the planar route)."""
+        if isinstance(z, (tuple, list)):
+            if len(z) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
+            i = np.ascontiguousarray(z[0], dtype=np.float32)
+            q = np.ascontiguousarray(z[1], dtype=np.float32)
+            if i.ndim != 1 or i.shape != q.shape:
+                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
+            self._ck(self._L.psdc_iqsk_process(self._h, channel, _fptr(i), _fptr(q), i.size))
+            return
+        z = np.asarray(z)
+        if not np.iscomplexobj(z):
+            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
+        z = np.ascontiguousarray(z, dtype=np.complex64)
+        self._ck(self._L.psdc_iqsk_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); the rest as
+        ZoomSkCascadeBank.process_device"""
+        self._ck(self._L.psdc_iqsk_process_interleaved_device(self._h, channel, C.c_void_p(ptr), length,
+                                                              C.c_void_p(after) if after else None))
+
+    def process_device_planar(self, channel, pi, pq, length, after=None):
+        """pi, pq: device addresses of `length` f32 samples each, the I and the Q stream (process_device's rules)"""
+        self._ck(self._L.psdc_iqsk_process_device(self._h, channel, C.c_void_p(pi), C.c_void_p(pq), length,
+                                                  C.c_void_p(after) if after else None))
+
+
+class ZoomSkCascade:
+    """One real stream around one carrier: ZoomSkCascade(n, f0=0.2) or ZoomSkCascade(n, ftw=...): psd() beside sk(), both
+    two-sided.  `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    _BANK = ZoomSkCascadeBank
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = self._BANK(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0):
+        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
+        self.ftw, self.phase0 = self._b.carriers[0]
+        return self.f0
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x):
+        self._b.process(0, x)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def psd(self, opts=MergeOpts()):
+        return self._b.psd(0, opts)
+
+    def sk(self, opts=MergeOpts()):
+        return self._b.sk(0, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_moments(self, i):
+        return self._b.stage_moments(0, i)
+
+    def reset(self):
+        self._b.reset()
+        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    stats = stats_read
+
+    def close(self):
+        self._b.close()
+
+
+class IqSkCascade(ZoomSkCascade):
+    """One complex stream: IqSkCascade(n) analyses it as it is, IqSkCascade(n, f0=0.2) or IqSkCascade(n, ftw=...) retunes it
+    first.  process() takes a complex array or a pair (i, q), as IqCascade.process does."""
+
+    _BANK = IqSkCascadeBank
+
+    def process_device_planar(self, pi, pq, length, after=None):
+        self._b.process_device_planar(0, pi, pq, length, after)
 
 
 ZCSD_STEADY_LAUNCHES = 5  # PSDC_ZCSD_STEADY_LAUNCHES: two mixers; segments, decimators, fold + tails

@@ -10,7 +10,8 @@
 // object (psdc_iqcsd_*) is the zoom cross kind with that feed for both sides at once: its unit is two complex channels, turned by
 // one pair mixer (iq_pair_mix_kernel, iq_cross_frames_kernel) into the same four streams; a spectral kurtosis object (psdc_sk_*)
 // has one real channel a unit, m = 1 stream fed as a pair's are, on sk_kernel with the rows S1 = sum w P and S2 = sum w P^2 of
-// sk_fft.h.  Below, "pair" stands for any of these units.
+// sk_fft.h; a zoom / IQ spectral kurtosis object (psdc_zsk_*, psdc_iqsk_*) is the zoom / IQ kind on zoom_sk_kernel, with the four
+// rows of zoom_sk_fft.h.  Below, "pair" stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -30,6 +31,8 @@
 #include "sample_int.h"
 #include "sk.h"
 #include "sk_fft.h"
+#include "zoom_sk.h"
+#include "zoom_sk_fft.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -75,8 +78,9 @@ struct XObj {
     bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
     bool iq = false;     // psdc_iq (with zoom), psdc_iqcsd (with zoom and zcross): I and Q come from the caller, through the complex mixer
     bool sk = false;     // psdc_sk: one real stream a unit (m = 1), sk_kernel and its two rows S1, S2
+    bool zsk = false;    // psdc_zsk (with zoom), psdc_iqsk (with zoom and iq): zoom_sk_kernel and its four rows S1, S2 upper / lower
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return zcross ? 8 : zoom || sk ? 2 : matrix ? m * m : 4; }
+    uint32_t rows() const { return zcross ? 8 : zsk ? ZSK_ROWS : zoom || sk ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
     // (an IQ channel two: its I and its Q; an IQ cross pair four)
@@ -137,6 +141,8 @@ struct psdc_zcsd : XObj {};
 struct psdc_iq : XObj {};
 struct psdc_iqcsd : XObj {};
 struct psdc_sk : XObj {};
+struct psdc_zsk : XObj {};
+struct psdc_iqsk : XObj {};
 
 namespace {
 
@@ -408,8 +414,9 @@ int run_round(XObj *h, bool *did)
         } else {
             CrossBatch *cb = new CrossBatch();
             fill(cb, pair_job);
-            e = h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                : h->sk ? launch_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+            e = h->zsk    ? launch_zoom_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                : h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                : h->sk   ? launch_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
                         : launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
             delete cb;
         }
@@ -568,7 +575,7 @@ std::string zcsd_size_text(uint32_t n)
 
 // T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
 // psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed;
-// psdc_sk (m = 1: one real stream, sk_kernel)
+// psdc_sk (m = 1: one real stream, sk_kernel); psdc_zsk is psdc_zoom and psdc_iqsk is psdc_iq on zoom_sk_kernel
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
@@ -576,8 +583,10 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
     constexpr bool matrix = std::is_same<T, psdc_csm>::value;
     constexpr bool iqcsd = std::is_same<T, psdc_iqcsd>::value;
     constexpr bool zcross = std::is_same<T, psdc_zcsd>::value || iqcsd;
-    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd;
-    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq;
+    constexpr bool iqsk = std::is_same<T, psdc_iqsk>::value;
+    constexpr bool zsk = std::is_same<T, psdc_zsk>::value || iqsk;
+    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd || iqsk;
+    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq || zsk;
     constexpr bool sk = std::is_same<T, psdc_sk>::value;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
@@ -630,6 +639,10 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         if (iq) {
             h->iq = true;
             h->tag = iqcsd ? "psdc_iqcsd" : "psdc_iq";
+        }
+        if (zsk) {
+            h->zsk = true;
+            h->tag = iqsk ? "psdc_iqsk" : "psdc_zsk";
         }
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
@@ -2640,5 +2653,263 @@ int psdc_sk_stats_read(psdc_sk *h, uint64_t *launches, uint64_t *samples_in, int
 }
 
 const char *psdc_sk_last_error(const psdc_sk *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+} // extern "C"
+
+// ---- zoom / IQ spectral kurtosis: the zoom / IQ object on zoom_sk_kernel, rows S1 upper, S1 lower, S2 upper, S2 lower ----
+
+namespace {
+
+// the f64 rows of every stage of a channel (ns x ZSK_ROWS x bins) and what a stitch needs beside them; rows 0 and 1 in f32 as
+// two_rows_psd_impl hands a zoom object's to the stitch (ns x 2 x bins)
+struct ZskIn {
+    std::vector<uint64_t> c64, pend;
+    std::vector<uint32_t> avgs;
+    std::vector<double> acc;
+    std::vector<float> rows01;
+    uint32_t ns = 0;
+};
+
+int zsk_in(XObj *h, uint32_t channel, ZskIn *in)
+{
+    int rc;
+    if ((rc = drain(h)) || (rc = sync_all(h)))
+        return rc;
+    const auto &st = h->pairs[channel];
+    const uint32_t ns = (uint32_t)st.size();
+    const size_t b = bins(h);
+    in->ns = ns;
+    in->c64.resize(std::max<uint32_t>(ns, 1));
+    in->pend.resize(std::max<uint32_t>(ns, 1));
+    in->avgs.resize(std::max<uint32_t>(ns, 1));
+    in->acc.resize(std::max<size_t>(1, (size_t)ns * ZSK_ROWS * b));
+    in->rows01.resize(std::max<size_t>(1, (size_t)ns * 2 * b));
+    for (uint32_t i = 0; i < ns; ++i) {
+        in->c64[i] = st[i].count64;
+        in->pend[i] = pending_for(h->geo, st[i].total);
+        in->avgs[i] = cur_avg(h, i);
+        double *a = &in->acc[(size_t)i * ZSK_ROWS * b];
+        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * ZSK_ROWS * b, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < 2 * b; ++k)
+            in->rows01[(size_t)i * 2 * b + k] = (float)a[k];
+    }
+    return PSDC_OK;
+}
+
+// the zoom read-out of rows 0 and 1 (sk_upper == sk_lower == NULL: upper / lower written where given), or the SK of every bin
+// that read-out takes, both sides, selected by its Breaks (upper == lower == NULL)
+int zsk_readout_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                     float *lower, double *sk_upper, double *sk_lower, size_t cap, size_t *len, psdc_break *breaks,
+                     size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    ZskIn in;
+    if ((rc = zsk_in(h, channel, &in)))
+        return rc;
+    float *outs[2] = {upper, lower};
+    psdc_break own[X_MAX_STAGES];
+    size_t l = 0, nb = 0;
+    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                          in.rows01.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, &l, own, X_MAX_STAGES, &nb);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    if ((sk_upper || sk_lower) && l > cap)
+        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
+    if (len)
+        *len = l;
+    if (n_breaks)
+        *n_breaks = nb;
+    if (breaks) {
+        if (nb > breaks_cap)
+            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
+        std::copy(own, own + nb, breaks);
+    }
+    if (sk_upper || sk_lower) {
+        const size_t b = bins(h);
+        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
+            const psdc_break &br = own[i];
+            if (!br.include)
+                continue;
+            const double *a = &in.acc[(size_t)(in.ns - 1 - i) * ZSK_ROWS * b];
+            for (uint64_t k = br.bins_start; k < br.bins_end; ++k) {
+                const size_t o = br.start + (k - br.bins_start);
+                if (sk_upper)
+                    sk_upper[o] = sk_estimate(br.count, a[k], a[2 * b + k]);
+                if (sk_lower)
+                    sk_lower[o] = sk_estimate(br.count, a[b + k], a[3 * b + k]);
+            }
+        }
+    }
+    return PSDC_OK;
+}
+
+int zsk_stage_moments_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
+                           double *s2_upper, double *s2_lower, const char *who)
+{
+    std::vector<double> acc;
+    double *outs[ZSK_ROWS] = {s1_upper, s1_lower, s2_upper, s2_lower};
+    const bool any = s1_upper || s1_lower || s2_upper || s2_lower;
+    int rc = stage_impl(h, channel, stage, stat, any ? &acc : nullptr, who);
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    for (int r = 0; r < ZSK_ROWS; ++r)
+        if (outs[r])
+            std::copy(acc.begin() + r * b, acc.begin() + (r + 1) * b, outs[r]);
+    return PSDC_OK;
+}
+
+template <class T>
+void zsk_destroy(T *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
+}
+
+} // namespace
+
+extern "C" {
+
+int psdc_zsk_supported(uint32_t n) { return psdc_sk_supported(n); }
+
+psdc_zsk *psdc_zsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_zsk>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zsk_create_window");
+}
+
+psdc_zsk *psdc_zsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_zsk>(n, window_kind, 2, n_channels, device, "psdc_zsk_create");
+}
+
+void psdc_zsk_destroy(psdc_zsk *h) { zsk_destroy(h); }
+int psdc_zsk_reset(psdc_zsk *h) { return reset_impl(h, "psdc_zsk_reset"); }
+int psdc_zsk_set_detrend(psdc_zsk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zsk_set_detrend"); }
+int psdc_zsk_set_avg(psdc_zsk *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zsk_set_avg"); }
+
+int psdc_zsk_set_carrier(psdc_zsk *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_zsk_set_carrier");
+}
+
+int psdc_zsk_process(psdc_zsk *h, uint32_t channel, const float *x, size_t len)
+{
+    const void *xs[1] = {x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, false, nullptr, "psdc_zsk_process");
+}
+
+int psdc_zsk_process_device(psdc_zsk *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, true, producer_event, "psdc_zsk_process_device");
+}
+
+int psdc_zsk_sync(psdc_zsk *h) { return sync_impl(h, "psdc_zsk_sync"); }
+int psdc_zsk_num_stages(psdc_zsk *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_zsk_num_stages"); }
+
+int psdc_zsk_stage_moments(psdc_zsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
+                           double *s2_upper, double *s2_lower)
+{
+    return zsk_stage_moments_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_zsk_stage_moments");
+}
+
+int psdc_zsk_psd(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                 float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
+                            breaks_cap, n_breaks, "psdc_zsk_psd");
+}
+
+int psdc_zsk_sk(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
+                double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, nullptr, sk_upper, sk_lower, cap, len,
+                            breaks, breaks_cap, n_breaks, "psdc_zsk_sk");
+}
+
+int psdc_zsk_stats_read(psdc_zsk *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_zsk_stats_read");
+}
+
+const char *psdc_zsk_last_error(const psdc_zsk *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+int psdc_iqsk_supported(uint32_t n) { return psdc_sk_supported(n); }
+
+psdc_iqsk *psdc_iqsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_iqsk>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iqsk_create_window");
+}
+
+psdc_iqsk *psdc_iqsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_iqsk>(n, window_kind, 2, n_channels, device, "psdc_iqsk_create");
+}
+
+void psdc_iqsk_destroy(psdc_iqsk *h) { zsk_destroy(h); }
+int psdc_iqsk_reset(psdc_iqsk *h) { return reset_impl(h, "psdc_iqsk_reset"); }
+int psdc_iqsk_set_detrend(psdc_iqsk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqsk_set_detrend"); }
+int psdc_iqsk_set_avg(psdc_iqsk *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqsk_set_avg"); }
+
+int psdc_iqsk_set_carrier(psdc_iqsk *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_iqsk_set_carrier");
+}
+
+int psdc_iqsk_process(psdc_iqsk *h, uint32_t channel, const float *i, const float *q, size_t len)
+{
+    return iq_feed(h, channel, i, q, false, SampleFmt{}, len, false, nullptr, "psdc_iqsk_process");
+}
+
+int psdc_iqsk_process_device(psdc_iqsk *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_i, d_q, false, SampleFmt{}, len, true, producer_event, "psdc_iqsk_process_device");
+}
+
+int psdc_iqsk_process_interleaved(psdc_iqsk *h, uint32_t channel, const float *iq, size_t len)
+{
+    return iq_feed(h, channel, iq, nullptr, true, SampleFmt{}, len, false, nullptr, "psdc_iqsk_process_interleaved");
+}
+
+int psdc_iqsk_process_interleaved_device(psdc_iqsk *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_iq, nullptr, true, SampleFmt{}, len, true, producer_event, "psdc_iqsk_process_interleaved_device");
+}
+
+int psdc_iqsk_sync(psdc_iqsk *h) { return sync_impl(h, "psdc_iqsk_sync"); }
+int psdc_iqsk_num_stages(psdc_iqsk *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_iqsk_num_stages"); }
+
+int psdc_iqsk_stage_moments(psdc_iqsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
+                            double *s2_upper, double *s2_lower)
+{
+    return zsk_stage_moments_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_iqsk_stage_moments");
+}
+
+int psdc_iqsk_psd(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                  float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
+                            breaks_cap, n_breaks, "psdc_iqsk_psd");
+}
+
+int psdc_iqsk_sk(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
+                 double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, nullptr, sk_upper, sk_lower, cap, len,
+                            breaks, breaks_cap, n_breaks, "psdc_iqsk_sk");
+}
+
+int psdc_iqsk_stats_read(psdc_iqsk *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_iqsk_stats_read");
+}
+
+const char *psdc_iqsk_last_error(const psdc_iqsk *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

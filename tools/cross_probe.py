@@ -62,6 +62,12 @@ profiles/real_int_probe.json unless --out names another file.
 CsdCascadeBank(n, 1) fed (x, x), the nearest the other objects come (two transforms and decimations, S1 three times, no S2).  Leg B:
 SkCascadeBank(n, 1) fed x.  A, B, A in turn --reps times; the rates, B / A, the largest |A' - A| / A and B's launches a steady call
 are recorded as findings, none is a gate.  Writes profiles/sk_probe.json unless --out names another file.
+--zoom --sk / --iq --sk: SK around a carrier against the first-moment object it extends.  One device-resident stream (real f32 /
+complex64, carrier 0.2) of 2^24 samples a call at N = 512, 1024, 4096.  Leg A: ZoomCascadeBank(n, 1) / IqCascadeBank(n, 1).  Leg B:
+ZoomSkCascadeBank(n, 1) / IqSkCascadeBank(n, 1) fed the same stream: the same transform with the second accumulator set.  A, B, A in
+turn --reps times with the windows and the sync of --sk; B / A of every turn, the largest |A' - A| / A, B's launches a steady call
+and the live stages are recorded as findings, none is a gate.  Each writes its family's entry ("zoom" / "iq") of
+profiles/zoom_sk_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -336,6 +342,48 @@ def sk_legs(pkg, torch, seconds, reps, call):
                      "b_beats_a": bool(min(ratios) > 1 + spread), "b_launches_per_call": launches, "stages": sb.num_stages(0)})
         pa.close()
         sb.close()
+    return legs
+
+
+def zoom_sk_legs(pkg, torch, seconds, reps, call, iq):
+    """One device-resident stream, carrier 0.2: real f32 (iq False) or complex64 interleaved (iq True).  A: ZoomCascadeBank /
+    IqCascadeBank; B: ZoomSkCascadeBank / IqSkCascadeBank, the same mixer and transform with S2 kept beside S1.  A / B / A in turn."""
+    x = torch.randn(call, dtype=torch.complex64 if iq else torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    legs = []
+    for n in (512, 1024, 4096):
+        za = (pkg.IqCascadeBank if iq else pkg.ZoomCascadeBank)(n, 1)
+        zb = (pkg.IqSkCascadeBank if iq else pkg.ZoomSkCascadeBank)(n, 1)
+        za.set_carrier(0, f0=0.2)
+        zb.set_carrier(0, f0=0.2)
+
+        def a_step():
+            za.process_device(0, x.data_ptr(), call)
+            return call
+
+        def b_step():
+            zb.process_device(0, x.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+        zb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = zb.stats_read()["launches"] / 8
+        zb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "call": call, "a_first_moment_gs_s": r3(a1), "b_sk_gs_s": r3(b), "a_again_gs_s": r3(a2),
+                     "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3), "ratio_max": round(max(ratios), 3),
+                     "aa_spread_max": round(spread, 4), "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread),
+                     "b_launches_per_call": launches, "stages": zb.num_stages(0), "a_stages": za.num_stages(0)})
+        za.close()
+        zb.close()
     return legs
 
 
@@ -884,12 +932,35 @@ def main():
                                                       "and CsmCascadeBank(n, 4) fed the four planar streams")
     ap.add_argument("--int", dest="int_feed", action="store_true", help="with --iq [--pair]: the sc16 feed against the complex64 feed of "
                                                                         "the same stream, host-fed and device-resident")
-    ap.add_argument("--sk", action="store_true", help="SkCascadeBank fed x against CsdCascadeBank fed (x, x); writes profiles/sk_probe.json")
+    ap.add_argument("--sk", action="store_true", help="SkCascadeBank fed x against CsdCascadeBank fed (x, x); writes profiles/sk_probe.json; "
+                                                      "with --zoom / --iq: ZoomSkCascadeBank / IqSkCascadeBank against ZoomCascadeBank / "
+                                                      "IqCascadeBank; writes profiles/zoom_sk_probe.json")
     ap.add_argument("--real-int", action="store_true", help="the s16 feed of PsdCascadeBank and CsdCascadeBank against the f32 feed of "
                                                             "the converted stream, host-fed and device-resident")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.sk and (a.zoom or a.iq):
+        path = a.out or os.path.join(ROOT, "profiles", "zoom_sk_probe.json")
+        record = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                record = json.loads(f.read() or "{}")
+        record.update({"metric": "zoom_sk_gsamples_s", "unit": "1e9 samples a second of one stream (complex samples for iq)",
+                       "note": "findings, no gate: A is the first-moment object on the same device-resident stream, B the same "
+                               "transform with the second accumulator set; not measured here: host memory, banks, the EWMA regime"})
+        for fam, on in (("zoom", a.zoom), ("iq", a.iq)):
+            if on:
+                before = gpu_state()
+                legs = zoom_sk_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, fam == "iq")
+                record[fam] = {"a": "IqCascadeBank" if fam == "iq" else "ZoomCascadeBank",
+                               "b": "IqSkCascadeBank" if fam == "iq" else "ZoomSkCascadeBank",
+                               "gpu_before": before, "gpu_after": gpu_state(), "legs": legs}
+        line = json.dumps(record)
+        print(line)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.sk:
         before = gpu_state()
         legs = sk_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2)

@@ -25,6 +25,12 @@ offset,Saa,Sbb,Re Sab,Im Sab (at F0 + offset),Saa,Sbb,Re Sab,Im Sab (at F0 - off
 SkCascade(512) and prints, or with --csv writes to DIR/sk_<trace>.csv, the lines frequency,psd,sk: the spectral kurtosis of every
 bin beside its density (1: stationary Gaussian noise; 0: a line of constant amplitude; above 1: power that comes and goes; NaN
 below two averages).  The summary line counts the bins more than 8 sk_sigma(count) away from 1.
+--zoom-sk F0[:TRACE] (repeatable; as --zoom) feeds that trace to a ZoomSkCascade(512) around the carrier F0, and --iq-sk I:Q[:F0]
+(repeatable; as --iq: traces of the frames with --file, two raw f32 files without it) the complex stream I + i Q to an
+IqSkCascade(512).  Each prints, or with --csv writes to DIR/zoomsk_<trace>_<F0>.csv / DIR/iqsk_<i>__<q>_<F0>.csv, the lines
+offset,psd,sk over the offsets -0.5 fs ... 0.5 fs from the carrier in ascending order (two_sided): the spectral kurtosis of the
+sideband power beside its density.  Circular Gaussian noise reads 1 at every offset, 0 included; a real stream rises towards 2
+where its own DC and Nyquist fall (offsets -F0 and 0.5 - F0).  The summary line counts the bins more than 8 sk_sigma(count) from 1.
 --sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
 integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
 then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
@@ -70,6 +76,10 @@ def main(argv=None):
                     help="IA:QA:IB:QB[:F0] -- two-sided auto and cross spectra of two complex streams, retuned by F0 (repeatable)")
     ap.add_argument("--sk", action="append", nargs="?", const="", default=[],
                     help="[TRACE] -- spectral kurtosis of every bin beside the PSD of that trace (repeatable; default the first trace)")
+    ap.add_argument("--zoom-sk", action="append", default=[],
+                    help="F0[:TRACE] -- two-sided spectral kurtosis beside the spectrum around the carrier F0 (repeatable)")
+    ap.add_argument("--iq-sk", action="append", default=[],
+                    help="I:Q[:F0] -- two-sided spectral kurtosis beside the spectrum of the complex stream I + i Q (repeatable)")
     ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
                     help="s16 / s8: --raw, --pair, --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
     ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
@@ -87,10 +97,12 @@ def main(argv=None):
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
-    if (a.iq or a.iq_pair) and not a.file:  # the planar raw files: the only input these options need
+    if (a.iq or a.iq_pair or a.iq_sk) and not a.file:  # the planar raw files: the only input these options need
         merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
         if a.csv:
             os.makedirs(a.csv, exist_ok=True)
+        if a.iq_sk:
+            iq_sk_streams(pkg, source, a, merge, None)
         if a.iq:
             iq_streams(pkg, source, a, merge, None)
         if a.iq_pair:
@@ -141,6 +153,10 @@ def main(argv=None):
         zoom_pairs(pkg, source, a, merge, names)
     if a.sk:
         sk_traces(pkg, source, a, merge, names)
+    if a.zoom_sk:
+        zoom_sk_traces(pkg, source, a, merge, names)
+    if a.iq_sk and a.file:
+        iq_sk_streams(pkg, source, a, merge, names)
     if a.iq and a.file:
         iq_streams(pkg, source, a, merge, names)
     if a.iq_pair and a.file:
@@ -291,6 +307,62 @@ def sk_traces(pkg, source, a, merge, names):
     bank.close()
 
 
+def two_sided_sk_report(pkg, bank, c, label, stem, a, merge):
+    """the read-out of one channel of a ZoomSkCascadeBank / IqSkCascadeBank: the summary line, and offset,psd,sk in two_sided order"""
+    if bank.num_stages(c) == 0:
+        print(f"{label}: no samples")
+        return
+    up, lo, breaks = bank.psd(c, merge)
+    sup, slo, _ = bank.sk(c, merge)
+    off, psd = pkg.two_sided(up, lo, breaks)
+    _, sk = pkg.two_sided(sup, slo, breaks)
+    sig = np.concatenate([np.full(b.bins.stop - b.bins.start, pkg.sk_sigma(max(b.count, 1))) for b in breaks if b.include] or [np.zeros(0)])
+    _, sigma = pkg.two_sided(sig, sig, breaks)
+    with np.errstate(invalid="ignore"):
+        odd = int(np.sum(np.abs(sk - 1.0) > 8.0 * sigma))
+    print(f"{label}: stages {bank.num_stages(c)} bins {psd.size} breaks {len(breaks)} median sk {np.nanmedian(sk) if sk.size else float('nan'):.6g} "
+          f"bins beyond 8 sigma of 1: {odd}")
+    lines = [f"{o:.9g},{p:.9g},{k:.9g}\n" for o, p, k in zip(off * a.fs, psd, sk)]
+    if a.csv:
+        safe = "".join(ch if ch.isalnum() else "_" for ch in stem)
+        with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+            f.writelines(lines)
+    else:
+        sys.stdout.writelines(lines)
+
+
+def zoom_sk_traces(pkg, source, a, merge, names):
+    """--zoom-sk: the named trace of every read (host_traces) into one zoom spectral kurtosis cascade per carrier"""
+    want = []
+    for z in a.zoom_sk:
+        f0, _, tr = z.partition(":")
+        want.append((float(f0), trace_arg(tr, names, "--zoom-sk")))
+    bank = pkg.ZoomSkCascadeBank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _) in enumerate(want)]
+    host_traces(source, pkg, a, [(idx,) for _, idx in want], lambda i, xs: bank.process(i, xs[0]))
+    for i, (_, idx) in enumerate(want):
+        two_sided_sk_report(pkg, bank, i, f"zoom sk {names[idx]} @ {used[i]:.12g}", f"zoomsk_{names[idx]}_{used[i]:.9g}", a, merge)
+    bank.close()
+
+
+def iq_sk_streams(pkg, source, a, merge, names):
+    """--iq-sk: two traces of every read (host_traces), or two raw f32 files (names None), into one IQ spectral kurtosis cascade per
+    stream"""
+    want = []
+    for z in a.iq_sk:
+        parts = z.split(":")
+        if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
+            raise SystemExit("--iq-sk takes I:Q[:F0]")
+        want.append((parts[0], parts[1], float(parts[2]) if len(parts) == 3 else 0.0))
+    bank = pkg.IqSkCascadeBank(1 << 9, len(want))
+    used, labels = iq_feed(pkg, source, a, bank, want, names, "--iq-sk")
+    for c, (li, lq) in enumerate(labels):
+        two_sided_sk_report(pkg, bank, c, f"iq sk {li}:{lq} @ {used[c]:.12g}", f"iqsk_{li}__{lq}_{used[c]:.9g}", a, merge)
+    bank.close()
+
+
 def zoom_pairs(pkg, source, a, merge, names):
     """--zoom-pair: the two named traces of every read (host_traces) into one zoom cross cascade per pair, one carrier on both sides"""
     want = []
@@ -324,15 +396,9 @@ def zoom_pairs(pkg, source, a, merge, names):
     bank.close()
 
 
-def iq_streams(pkg, source, a, merge, names):
-    """--iq: two traces of every read (host_traces), or two raw f32 files (names None), into one IQ cascade per stream"""
-    want = []
-    for z in a.iq:
-        parts = z.split(":")
-        if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
-            raise SystemExit("--iq takes I:Q[:F0]")
-        want.append((parts[0], parts[1], float(parts[2]) if len(parts) == 3 else 0.0))
-    bank = pkg.IqCascadeBank(1 << 9, len(want))
+def iq_feed(pkg, source, a, bank, want, names, opt):
+    """settle an IQ bank (AcqOpts, carriers) and feed it `want` = [(I, Q, F0)]: two traces of every read (host_traces), or two raw f32
+    files (names None).  Returns the carriers in use and the (I, Q) labels."""
     bank.set_detrend(pkg.Detrend[a.detrend.upper()])
     bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
     used = [bank.set_carrier(i, f0=f0) for i, (_, _, f0) in enumerate(want)]
@@ -340,7 +406,7 @@ def iq_streams(pkg, source, a, merge, names):
         labels = [(os.path.basename(i), os.path.basename(q)) for i, q, _ in want]
         for c, (pi, pq, _) in enumerate(want):
             if os.path.getsize(pi) != os.path.getsize(pq):
-                raise SystemExit(f"--iq: {pi} and {pq} differ in length")
+                raise SystemExit(f"{opt}: {pi} and {pq} differ in length")
             with open(pi, "rb") as fi, open(pq, "rb") as fq:
                 fed = 0
                 while a.max_bytes is None or fed < a.max_bytes:
@@ -350,9 +416,22 @@ def iq_streams(pkg, source, a, merge, names):
                     bank.process(c, (xi, xq))
                     fed += xi.nbytes
     else:
-        idx = [(trace_arg(i, names, "--iq"), trace_arg(q, names, "--iq")) for i, q, _ in want]
+        idx = [(trace_arg(i, names, opt), trace_arg(q, names, opt)) for i, q, _ in want]
         labels = [(names[i], names[q]) for i, q in idx]
         host_traces(source, pkg, a, idx, lambda c, xs: bank.process(c, (xs[0], xs[1])))
+    return used, labels
+
+
+def iq_streams(pkg, source, a, merge, names):
+    """--iq: two traces of every read (host_traces), or two raw f32 files (names None), into one IQ cascade per stream"""
+    want = []
+    for z in a.iq:
+        parts = z.split(":")
+        if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
+            raise SystemExit("--iq takes I:Q[:F0]")
+        want.append((parts[0], parts[1], float(parts[2]) if len(parts) == 3 else 0.0))
+    bank = pkg.IqCascadeBank(1 << 9, len(want))
+    used, labels = iq_feed(pkg, source, a, bank, want, names, "--iq")
     for c, (li, lq) in enumerate(labels):
         label = f"iq {li}:{lq} @ {used[c]:.12g}"
         if bank.num_stages(c) == 0:
