@@ -1301,6 +1301,104 @@ int psdc_iqsk_sk(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_
 int psdc_iqsk_stats_read(psdc_iqsk *h, uint64_t *launches, uint64_t *samples_in, int reset);
 const char *psdc_iqsk_last_error(const psdc_iqsk *h);
 
+/* ---- AM/PM cascades: amplitude and phase noise spectra of a carrier ------------------------------------------------
+ * The two-sided objects keep |Z_k|^2 of each sideband of a carrier.  Their sum is S_am + S_pm and their difference
+ * Im S_am,pm: how much of the sideband power is amplitude noise and how much phase noise they cannot say.  These two objects
+ * keep one more complex accumulator a bin on the same transform, the complementary spectrum comp[k] = sum_j w_j Z_j[k]
+ * Z_j[(N - k) mod N] -- a product WITHOUT a conjugate.  For z = A (1 + a(t) + i phi(t)), a and phi real and small,
+ *     (upper + lower) / 2 = |A|^2 (S_a + S_phi)                          upper - lower = -4 |A|^2 Im S_a,phi
+ *     comp conj(u)        = |A|^2 (S_a - S_phi + 2 i Re S_a,phi),        u = A^2 / |A|^2
+ * with S_a,phi = conj(a_k) phi_k: one transform a segment gives S_am, S_pm and the AM-PM cross spectrum at every stage.  The
+ * relation is a frequency-domain one: no unwrap, no per-sample transcendental, no state beyond the zoom object's.  psdc_zampm_* is
+ * the zoom object (a real stream plus a carrier, fed as psdc_zoom_* is) and psdc_iqampm_* the IQ object (a complex stream plus
+ * an optional retune, fed as psdc_iq_* is).  Both share one segment kernel (csrc/zoom_ampm.hip).
+ * Unit, carrier and stages: those of the zoom / IQ object fed the same stream and carrier -- segmentation, Window<N>, Detrend,
+ * /8 decimation of I and Q with the drain of 35 outputs, lazy stages, the averaging schedule (set_avg) with its EWMA weights,
+ * counts, pendings and Breaks.
+ * Rows: each (channel, stage) holds four f64 rows of n/2 + 1 bins, in this order, Z the transform of the segment's I + i Q:
+ *     row 0:  upper[k]   = sum_j w_j |Z_j[k]|^2                 row 1:  lower[k]   = sum_j w_j |Z_j[(N - k) mod N]|^2
+ *     row 2:  comp_re[k] = sum_j w_j Re(Z_j[k] Z_j[(N - k) mod N])   row 3:  comp_im[k] = the imaginary part of the same
+ * At k = 0 and k = N/2 the product is Z[k]^2.  All four rows are bilinear in Z: the weight goes on the samples as sqrt(w_j), as in
+ * the zoom object, and all four are folded with the same factor.  Rows 0 and 1 are the zoom / IQ object's `upper` and `lower`
+ * (to rounding: 2e-6).
+ * Carrier: bin 0 of comp at stage 0 is sum Z[0]^2 = A^2 (sum win)^2 per segment, so the carrier's phasor u = comp[0] / |comp[0]|,
+ * its power and the lock figure |comp[0]| / sqrt(upper[0] lower[0]) (1 for a carrier at the tuning word, towards 0 for one
+ * that turns during the average) come from the same rows; the Python module reads them (carrier(), am_pm()).
+ * Limits: the separation is a linear, small-modulation one -- phi^2 reads as AM at second order; the carrier must sit at the
+ * tuning word to within the reciprocal of the averaging time; bins 0 and 1 of every stage hold the carrier itself under Hann; a
+ * real stream's image at -2 f0 is where the zoom object has it.
+ * Merged read-out: psdc_zampm_psd / psdc_iqampm_psd are psdc_zoom_psd of rows 0 and 1.  psdc_zampm_sidebands /
+ * psdc_iqampm_sidebands stitch all four rows with that read-out's Breaks and its per-stage factor, in f64: the AM/PM split is
+ * a difference of nearly equal numbers when one modulation dominates.  Offsets are read as the zoom object's are.
+ * Sizes and windows are those of the zoom object (64 ... 4096); Detrend::Linear is PSDC_ERR_UNIMPLEMENTED as everywhere.  There
+ * is no CPU fallback.  Sample routes, stream ordering, the caller-keeps-memory rule, errors, the device rule and the bank rule
+ * are those of psdc_zoom_* / psdc_iq_*: a steady-state call is 1 + 3 kernel launches (mixer; segments, decimators, fold +
+ * tails); host and device calls of the same samples, and the same calls twice, give the same bits.  Only the f32 sample routes
+ * feed these objects: stream frames, the loss record and the integer feeds are not offered yet. */
+typedef struct psdc_zampm psdc_zampm;
+/* 1 where n is a size the object takes, else 0 */
+int psdc_zampm_supported(uint32_t n);
+/* mirrors psdc_zoom_create / psdc_zoom_create_window */
+psdc_zampm *psdc_zampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+psdc_zampm *psdc_zampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                     int device);
+void psdc_zampm_destroy(psdc_zampm *h);
+/* as psdc_zoom_reset: stages, buffers, settings, carriers and statistics */
+int psdc_zampm_reset(psdc_zampm *h);
+int psdc_zampm_set_detrend(psdc_zampm *h, int detrend_kind);
+int psdc_zampm_set_avg(psdc_zampm *h, uint32_t limit, uint32_t count);
+/* as psdc_zoom_set_carrier; PSDC_ERR_ARG once the channel has taken a sample */
+int psdc_zampm_set_carrier(psdc_zampm *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* as psdc_zoom_process / psdc_zoom_process_device */
+int psdc_zampm_process(psdc_zampm *h, uint32_t channel, const float *x, size_t len);
+int psdc_zampm_process_device(psdc_zampm *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_zampm_sync(psdc_zampm *h);
+int psdc_zampm_num_stages(psdc_zampm *h, uint32_t channel);
+/* raw f64 accumulators of one stage: n/2 + 1 doubles each; any may be NULL */
+int psdc_zampm_stage_rows(psdc_zampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower,
+                          double *comp_re, double *comp_im);
+/* psdc_zoom_psd of rows 0 and 1 */
+int psdc_zampm_psd(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                   float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* all four rows merged in f64: `cap` doubles each, any may be NULL; the Breaks and the length are those of psdc_zampm_psd */
+int psdc_zampm_sidebands(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                         double *upper, double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len,
+                         psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* as psdc_zoom_stats_read */
+int psdc_zampm_stats_read(psdc_zampm *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_zampm_last_error(const psdc_zampm *h);
+
+typedef struct psdc_iqampm psdc_iqampm;
+int psdc_iqampm_supported(uint32_t n);
+/* mirrors psdc_iq_create / psdc_iq_create_window */
+psdc_iqampm *psdc_iqampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device);
+psdc_iqampm *psdc_iqampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                       int device);
+void psdc_iqampm_destroy(psdc_iqampm *h);
+int psdc_iqampm_reset(psdc_iqampm *h);
+int psdc_iqampm_set_detrend(psdc_iqampm *h, int detrend_kind);
+int psdc_iqampm_set_avg(psdc_iqampm *h, uint32_t limit, uint32_t count);
+/* as psdc_iq_set_carrier: the retune, default 0, 0 */
+int psdc_iqampm_set_carrier(psdc_iqampm *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* the four f32 sample routes of psdc_iq_*: planar and interleaved, host and device */
+int psdc_iqampm_process(psdc_iqampm *h, uint32_t channel, const float *i, const float *q, size_t len);
+int psdc_iqampm_process_device(psdc_iqampm *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event);
+int psdc_iqampm_process_interleaved(psdc_iqampm *h, uint32_t channel, const float *iq, size_t len);
+int psdc_iqampm_process_interleaved_device(psdc_iqampm *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event);
+int psdc_iqampm_sync(psdc_iqampm *h);
+int psdc_iqampm_num_stages(psdc_iqampm *h, uint32_t channel);
+/* as psdc_zampm_stage_rows, psdc_zampm_psd (psdc_iq_psd of rows 0 and 1) and psdc_zampm_sidebands */
+int psdc_iqampm_stage_rows(psdc_iqampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower,
+                           double *comp_re, double *comp_im);
+int psdc_iqampm_psd(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
+                    float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+int psdc_iqampm_sidebands(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                          double *upper, double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len,
+                          psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* as psdc_iq_stats_read: complex samples accepted */
+int psdc_iqampm_stats_read(psdc_iqampm *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_iqampm_last_error(const psdc_iqampm *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -479,6 +479,28 @@ def lib():
     f("psdc_iqsk_process_device", i32, [H, u32, vp, vp, sz, vp])
     f("psdc_iqsk_process_interleaved", i32, [H, u32, fp, sz])
     f("psdc_iqsk_process_interleaved_device", i32, [H, u32, vp, sz, vp])
+    for pre in ("psdc_zampm_", "psdc_iqampm_"):
+        f(pre + "supported", i32, [u32])
+        f(pre + "create", H, [u32, i32, u32, i32])
+        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+        f(pre + "destroy", None, [H])
+        f(pre + "reset", i32, [H])
+        f(pre + "set_detrend", i32, [H, i32])
+        f(pre + "set_avg", i32, [H, u32, u32])
+        f(pre + "set_carrier", i32, [H, u32, u64, u64])
+        f(pre + "sync", i32, [H])
+        f(pre + "num_stages", i32, [H, u32])
+        f(pre + "stage_rows", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp, dp, dp])
+        f(pre + "psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+        f(pre + "sidebands", i32, [H, u32, i32, u32, i32, dp, dp, dp, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+        f(pre + "last_error", C.c_char_p, [H])
+    f("psdc_zampm_process", i32, [H, u32, fp, sz])
+    f("psdc_zampm_process_device", i32, [H, u32, vp, sz, vp])
+    f("psdc_iqampm_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_iqampm_process_device", i32, [H, u32, vp, vp, sz, vp])
+    f("psdc_iqampm_process_interleaved", i32, [H, u32, fp, sz])
+    f("psdc_iqampm_process_interleaved_device", i32, [H, u32, vp, sz, vp])
     _lib = L
     return L
 
@@ -538,6 +560,15 @@ EXPORTS = [
     "psdc_iqsk_set_detrend", "psdc_iqsk_set_avg", "psdc_iqsk_set_carrier", "psdc_iqsk_process", "psdc_iqsk_process_device",
     "psdc_iqsk_process_interleaved", "psdc_iqsk_process_interleaved_device", "psdc_iqsk_sync", "psdc_iqsk_num_stages",
     "psdc_iqsk_stage_moments", "psdc_iqsk_psd", "psdc_iqsk_sk", "psdc_iqsk_stats_read", "psdc_iqsk_last_error",
+    "psdc_zampm_supported", "psdc_zampm_create", "psdc_zampm_create_window", "psdc_zampm_destroy", "psdc_zampm_reset",
+    "psdc_zampm_set_detrend", "psdc_zampm_set_avg", "psdc_zampm_set_carrier", "psdc_zampm_process", "psdc_zampm_process_device",
+    "psdc_zampm_sync", "psdc_zampm_num_stages", "psdc_zampm_stage_rows", "psdc_zampm_psd", "psdc_zampm_sidebands",
+    "psdc_zampm_stats_read", "psdc_zampm_last_error",
+    "psdc_iqampm_supported", "psdc_iqampm_create", "psdc_iqampm_create_window", "psdc_iqampm_destroy", "psdc_iqampm_reset",
+    "psdc_iqampm_set_detrend", "psdc_iqampm_set_avg", "psdc_iqampm_set_carrier", "psdc_iqampm_process",
+    "psdc_iqampm_process_device", "psdc_iqampm_process_interleaved", "psdc_iqampm_process_interleaved_device", "psdc_iqampm_sync",
+    "psdc_iqampm_num_stages", "psdc_iqampm_stage_rows", "psdc_iqampm_psd", "psdc_iqampm_sidebands", "psdc_iqampm_stats_read",
+    "psdc_iqampm_last_error",
 ]
 
 
@@ -2043,15 +2074,11 @@ def zoom_sk_supported(n):
     return 0 <= n < (1 << 32) and bool(lib().psdc_zsk_supported(n))
 
 
-class ZoomSkCascadeBank:
-    """`n_channels` independent zoom spectral kurtosis cascades (psdc_zsk_*): ZoomCascadeBank's carrier, mixer and two-sided
-    cascade, with S2 = sum |Z|^4 kept beside S1 = sum |Z|^2 on both sides.  psd() is ZoomCascadeBank's; sk() is sk_from_moments
-    of the same stages and bins, per side: 1 where the sideband holds stationary (circular) Gaussian noise, at every bin --
-    offset 0 and Nyquist included, every bin of a complex stream being complex; 0 on a line; about 2/d - 1 for power that is on
-    a fraction d of the time.  A real stream is not circular where its own DC and Nyquist fall (offset f0 in `lower`,
-    0.5 - f0 in `upper`): there SK rises towards 2.  two_sided() lays either read-out out over (-0.5, 0.5]."""
+class _CarrierRowsBank:
+    """What the banks of four-row objects around a carrier share (ZoomSkCascadeBank, ZoomAmPmCascadeBank and their IQ
+    siblings): creation, settings, the carrier, and the merged read-out of two rows.  `_P` is the C prefix."""
 
-    _P = "psdc_zsk_"
+    _P = None
 
     def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
         self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
@@ -2108,29 +2135,11 @@ class ZoomSkCascadeBank:
         self.carriers[channel] = (ftw, phase0)
         return ftw / float(1 << 64)
 
-    def process(self, channel, x):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        self._ck(self._L.psdc_zsk_process(self._h, channel, _fptr(x), x.size))
-
-    def process_device(self, channel, ptr, length, after=None):
-        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
-        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
-        self._ck(self._L.psdc_zsk_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
-
     def sync(self):
         self._ck(self._f("sync")(self._h))
 
     def num_stages(self, channel=0):
         return self._ck(self._f("num_stages")(self._h, channel))
-
-    def stage_moments(self, channel, stage):
-        """(info, s1_upper, s1_lower, s2_upper, s2_lower) of one stage: its raw f64 accumulators sum w |Z|^2 and sum w |Z|^4"""
-        b = self.n // 2 + 1
-        st = _CStageStat()
-        rows = [np.empty(b, np.float64) for _ in range(4)]
-        dp = C.POINTER(C.c_double)
-        self._ck(self._f("stage_moments")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
-        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, *rows)
 
     def _merged(self, fn, dtype, ctype, channel, opts):
         ns = self.num_stages(channel)
@@ -2144,6 +2153,42 @@ class ZoomSkCascadeBank:
         m = plen.value
         return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
 
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+    stats = stats_read
+
+
+class ZoomSkCascadeBank(_CarrierRowsBank):
+    """`n_channels` independent zoom spectral kurtosis cascades (psdc_zsk_*): ZoomCascadeBank's carrier, mixer and two-sided
+    cascade, with S2 = sum |Z|^4 kept beside S1 = sum |Z|^2 on both sides.  psd() is ZoomCascadeBank's; sk() is sk_from_moments
+    of the same stages and bins, per side: 1 where the sideband holds stationary (circular) Gaussian noise, at every bin --
+    offset 0 and Nyquist included, every bin of a complex stream being complex; 0 on a line; about 2/d - 1 for power that is on
+    a fraction d of the time.  A real stream is not circular where its own DC and Nyquist fall (offset f0 in `lower`,
+    0.5 - f0 in `upper`): there SK rises towards 2.  two_sided() lays either read-out out over (-0.5, 0.5]."""
+
+    _P = "psdc_zsk_"
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._L.psdc_zsk_process(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zsk_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
+
+    def stage_moments(self, channel, stage):
+        """(info, s1_upper, s1_lower, s2_upper, s2_lower) of one stage: its raw f64 accumulators sum w |Z|^2 and sum w |Z|^4"""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        rows = [np.empty(b, np.float64) for _ in range(4)]
+        dp = C.POINTER(C.c_double)
+        self._ck(self._f("stage_moments")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
+        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, *rows)
+
     def psd(self, channel=0, opts=MergeOpts()):
         """(upper, lower, breaks): the zoom read-out of the S1 rows, as ZoomCascadeBank.psd() returns it"""
         return self._merged(self._f("psd"), np.float32, C.c_float, channel, opts)
@@ -2151,13 +2196,6 @@ class ZoomSkCascadeBank:
     def sk(self, channel=0, opts=MergeOpts()):
         """(sk_upper, sk_lower, breaks): float64 SK of every bin of psd(), from the stage and bin psd() took it from"""
         return self._merged(self._f("sk"), np.float64, C.c_double, channel, opts)
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
-
-    stats = stats_read
 
 
 class IqSkCascadeBank(ZoomSkCascadeBank):
@@ -2197,11 +2235,10 @@ class IqSkCascadeBank(ZoomSkCascadeBank):
                                                   C.c_void_p(after) if after else None))
 
 
-class ZoomSkCascade:
-    """One real stream around one carrier: ZoomSkCascade(n, f0=0.2) or ZoomSkCascade(n, ftw=...): psd() beside sk(), both
-    two-sided.  `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
+class _CarrierRowsCascade:
+    """What the single-channel objects over a _CarrierRowsBank share; `_BANK` is the bank's class."""
 
-    _BANK = ZoomSkCascadeBank
+    _BANK = None
 
     def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
         self.n = n
@@ -2230,14 +2267,8 @@ class ZoomSkCascade:
     def psd(self, opts=MergeOpts()):
         return self._b.psd(0, opts)
 
-    def sk(self, opts=MergeOpts()):
-        return self._b.sk(0, opts)
-
     def num_stages(self):
         return self._b.num_stages(0)
-
-    def stage_moments(self, i):
-        return self._b.stage_moments(0, i)
 
     def reset(self):
         self._b.reset()
@@ -2255,11 +2286,210 @@ class ZoomSkCascade:
         self._b.close()
 
 
+class ZoomSkCascade(_CarrierRowsCascade):
+    """One real stream around one carrier: ZoomSkCascade(n, f0=0.2) or ZoomSkCascade(n, ftw=...): psd() beside sk(), both
+    two-sided.  `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    _BANK = ZoomSkCascadeBank
+
+    def sk(self, opts=MergeOpts()):
+        return self._b.sk(0, opts)
+
+    def stage_moments(self, i):
+        return self._b.stage_moments(0, i)
+
+
 class IqSkCascade(ZoomSkCascade):
     """One complex stream: IqSkCascade(n) analyses it as it is, IqSkCascade(n, f0=0.2) or IqSkCascade(n, ftw=...) retunes it
     first.  process() takes a complex array or a pair (i, q), as IqCascade.process does."""
 
     _BANK = IqSkCascadeBank
+
+    def process_device_planar(self, pi, pq, length, after=None):
+        self._b.process_device_planar(0, pi, pq, length, after)
+
+
+def zoom_ampm_supported(n):
+    """Whether ZoomAmPmCascade[Bank] and IqAmPmCascade[Bank] take the size n: a power of two 64 ... 4096 (the zoom object's)"""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_zampm_supported(n))
+
+
+def am_pm_from_sidebands(upper, lower, comp, carrier):
+    """(s_am, s_pm, s_ampm) in f64 from the two sideband rows, the complementary row comp = sum Z_k Z_(N-k) (all three in one
+    normalisation) and the carrier's complex amplitude A.  With P = |A|^2, u = A^2 / |A|^2 and D = comp conj(u):
+        s_am = ((U + L)/2 + Re D) / (2 P),   s_pm = ((U + L)/2 - Re D) / (2 P),   s_ampm = Im D / (2 P) + 1j (L - U) / (4 P)
+    s_ampm = conj(a_k) phi_k is the AM-PM cross spectrum.  Only A^2 enters: the sign of A does not matter.
+    The separation is a linear, small-modulation one for z = A (1 + a + i phi): phi^2 reads as AM at second order (-phi^2 / 2
+    is amplitude).  The rows must come from a carrier that sat at the tuning word to within the reciprocal of the averaging time
+    (carrier()'s lock says whether it did); bins 0 and 1 of a stage hold the carrier itself under a Hann window."""
+    U, L = np.asarray(upper, np.float64), np.asarray(lower, np.float64)
+    comp = np.asarray(comp, np.complex128)
+    A = complex(carrier)
+    P = abs(A) ** 2
+    if not P > 0.0:
+        raise PsdError(ERR_ARG, "am_pm_from_sidebands: the carrier's amplitude must not be 0")
+    D = comp * np.conj(A * A / P)
+    mean = 0.5 * (U + L)
+    return (mean + D.real) / (2.0 * P), (mean - D.real) / (2.0 * P), D.imag / (2.0 * P) + 1j * (L - U) / (4.0 * P)
+
+
+def carrier_from_rows(n, window_power, count, upper0, lower0, comp0):
+    """(power, u, lock) of a carrier from bin 0 of a stage's raw rows: comp[0] = sum Z_0^2 = A^2 (sum win)^2 per segment, so
+    u = comp0 / |comp0| = A^2 / |A|^2, power = |A|^2 = |comp0| / (count n^2 window_power) (window_power the window's coherent
+    power gain, mean(win)^2: Window.power) and lock = |comp0| / sqrt(upper0 lower0): 1 for a carrier at the tuning word,
+    towards 0 for one that turns during the average."""
+    c = complex(comp0)
+    mag = abs(c)
+    if count < 1 or not mag > 0.0:
+        raise PsdError(ERR_ARG, "carrier: no carrier in bin 0 (no average yet, or comp[0] == 0)")
+    return mag / (float(count) * float(n) ** 2 * float(window_power)), c / mag, mag / float(np.sqrt(float(upper0) * float(lower0)))
+
+
+class ZoomAmPmCascadeBank(_CarrierRowsBank):
+    """`n_channels` independent AM/PM cascades (psdc_zampm_*): ZoomCascadeBank's carrier, mixer and two-sided cascade, with the
+    complementary spectrum comp[k] = sum Z_k Z_(N-k) kept beside upper and lower.  psd() is ZoomCascadeBank's; sidebands() adds
+    comp, all in f64; am_pm() separates them into the amplitude noise, phase noise and AM-PM cross spectra of the carrier.
+    Limits: the separation is a linear, small-modulation one (phi^2 reads as AM at second order); the carrier must sit at the
+    tuning word to within the reciprocal of the averaging time -- carrier()'s lock says whether it does; bins 0 and 1 of every
+    stage hold the carrier itself under Hann; a real stream's image at -2 f0 is where ZoomCascade has it.  Only f32 samples feed
+    it: no stream frames, loss record or integer feeds yet."""
+
+    _P = "psdc_zampm_"
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        super().__init__(n, n_channels, window, device)
+        self.detrend = Detrend.NONE
+
+    def reset(self):
+        super().reset()
+        self.detrend = Detrend.NONE
+
+    def set_detrend(self, d):
+        super().set_detrend(d)
+        self.detrend = Detrend(int(d))
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._L.psdc_zampm_process(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zampm_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
+
+    def stage_rows(self, channel, stage):
+        """(info, upper, lower, comp) of one stage: its raw accumulators, upper and lower f64, comp complex128"""
+        b = self.n // 2 + 1
+        st = _CStageStat()
+        rows = [np.empty(b, np.float64) for _ in range(4)]
+        dp = C.POINTER(C.c_double)
+        self._ck(self._f("stage_rows")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
+        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows[0], rows[1],
+                rows[2] + 1j * rows[3])
+
+    def psd(self, channel=0, opts=MergeOpts()):
+        """(upper, lower, breaks): the zoom read-out of rows 0 and 1, as ZoomCascadeBank.psd() returns it"""
+        return self._merged(self._f("psd"), np.float32, C.c_float, channel, opts)
+
+    def sidebands(self, channel=0, opts=MergeOpts()):
+        """(upper, lower, comp, breaks): all four rows merged as psd() merges, in f64 (comp complex128)"""
+        ns = self.num_stages(channel)
+        cap = max(1, ns * (self.n // 2 + 1))
+        rows = [np.empty(cap, np.float64) for _ in range(4)]
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        dp = C.POINTER(C.c_double)
+        self._ck(self._f("sidebands")(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                      *(r.ctypes.data_as(dp) for r in rows), cap, C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        return rows[0][:m].copy(), rows[1][:m].copy(), rows[2][:m] + 1j * rows[3][:m], [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def _window_power(self):
+        return self.window.power if isinstance(self.window, WindowTable) else WindowTable._kind(self.n, self.window).power
+
+    def carrier(self, channel=0):
+        """(power, u, lock) of the channel's carrier, read from bin 0 of stage 0 (carrier_from_rows): power = |A|^2 of the
+        baseband carrier (a real stream C cos(2 pi f0 j + th) has A = C/2 e^(i th)), u = A^2 / |A|^2, lock 1 for a carrier at the
+        tuning word.  Raises unless detrend is none (a detrend removes the carrier from bin 0) and stage 0 has an average."""
+        if self.detrend != Detrend.NONE:
+            raise PsdError(ERR_ARG, "carrier: bin 0 holds the carrier under Detrend.NONE only; pass am_pm() the carrier")
+        if self.num_stages(channel) < 1:
+            raise PsdError(ERR_ARG, "carrier: stage 0 has no average yet")
+        info, up, lo, comp = self.stage_rows(channel, 0)
+        return carrier_from_rows(self.n, self._window_power(), info["count"], up[0], lo[0], comp[0])
+
+    def am_pm(self, channel=0, carrier=None, opts=MergeOpts()):
+        """(s_am, s_pm, s_ampm, breaks) in f64, in the one-sided normalisation of psd(): am_pm_from_sidebands of sidebands().
+        carrier: the complex amplitude A of the baseband carrier, or None to take it from carrier() (Detrend.NONE only)."""
+        if carrier is None:
+            power, u, _ = self.carrier(channel)
+            carrier = np.sqrt(power) * np.sqrt(complex(u))
+        up, lo, comp, br = self.sidebands(channel, opts)
+        return (*am_pm_from_sidebands(up, lo, comp, carrier), br)
+
+
+class IqAmPmCascadeBank(ZoomAmPmCascadeBank):
+    """`n_channels` independent IQ AM/PM cascades (psdc_iqampm_*): ZoomAmPmCascadeBank for streams that are complex already (a
+    lock-in's or SDR's I/Q, Fls BI / BQ handed over as arrays), fed as IqCascadeBank is and turned by an optional carrier
+    (default none)."""
+
+    _P = "psdc_iqampm_"
+
+    def process(self, channel, z):
+        """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
+        real arrays of one length (the planar route)."""
+        if isinstance(z, (tuple, list)):
+            if len(z) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
+            i = np.ascontiguousarray(z[0], dtype=np.float32)
+            q = np.ascontiguousarray(z[1], dtype=np.float32)
+            if i.ndim != 1 or i.shape != q.shape:
+                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
+            self._ck(self._L.psdc_iqampm_process(self._h, channel, _fptr(i), _fptr(q), i.size))
+            return
+        z = np.asarray(z)
+        if not np.iscomplexobj(z):
+            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
+        z = np.ascontiguousarray(z, dtype=np.complex64)
+        self._ck(self._L.psdc_iqampm_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); the rest as
+        ZoomAmPmCascadeBank.process_device"""
+        self._ck(self._L.psdc_iqampm_process_interleaved_device(self._h, channel, C.c_void_p(ptr), length,
+                                                                C.c_void_p(after) if after else None))
+
+    def process_device_planar(self, channel, pi, pq, length, after=None):
+        """pi, pq: device addresses of `length` f32 samples each, the I and the Q stream (process_device's rules)"""
+        self._ck(self._L.psdc_iqampm_process_device(self._h, channel, C.c_void_p(pi), C.c_void_p(pq), length,
+                                                    C.c_void_p(after) if after else None))
+
+
+class ZoomAmPmCascade(_CarrierRowsCascade):
+    """One real stream around one carrier: ZoomAmPmCascade(n, f0=0.2) or ZoomAmPmCascade(n, ftw=...): psd() and sidebands(),
+    carrier() and am_pm() (ZoomAmPmCascadeBank has the definitions and the limits).  `f0` is the frequency in use
+    (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    _BANK = ZoomAmPmCascadeBank
+
+    def sidebands(self, opts=MergeOpts()):
+        return self._b.sidebands(0, opts)
+
+    def stage_rows(self, i):
+        return self._b.stage_rows(0, i)
+
+    def carrier(self):
+        return self._b.carrier(0)
+
+    def am_pm(self, carrier=None, opts=MergeOpts()):
+        return self._b.am_pm(0, carrier, opts)
+
+
+class IqAmPmCascade(ZoomAmPmCascade):
+    """One complex stream: IqAmPmCascade(n) analyses it as it is, IqAmPmCascade(n, f0=0.2) or IqAmPmCascade(n, ftw=...) retunes
+    it first.  process() takes a complex array or a pair (i, q), as IqCascade.process does."""
+
+    _BANK = IqAmPmCascadeBank
 
     def process_device_planar(self, pi, pq, length, after=None):
         self._b.process_device_planar(0, pi, pq, length, after)

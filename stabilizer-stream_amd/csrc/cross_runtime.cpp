@@ -11,7 +11,8 @@
 // one pair mixer (iq_pair_mix_kernel, iq_cross_frames_kernel) into the same four streams; a spectral kurtosis object (psdc_sk_*)
 // has one real channel a unit, m = 1 stream fed as a pair's are, on sk_kernel with the rows S1 = sum w P and S2 = sum w P^2 of
 // sk_fft.h; a zoom / IQ spectral kurtosis object (psdc_zsk_*, psdc_iqsk_*) is the zoom / IQ kind on zoom_sk_kernel, with the four
-// rows of zoom_sk_fft.h.  Below, "pair" stands for any of these units.
+// rows of zoom_sk_fft.h; an AM/PM object (psdc_zampm_*, psdc_iqampm_*) is the zoom / IQ kind on zoom_ampm_kernel, with the four rows
+// of zoom_ampm_fft.h.  Below, "pair" stands for any of these units.
 //
 // `n_pairs` independent pairs of streams (x, y) on one MI355X.  Per pair the stages follow PsdCascade<N>
 // (src/psd.rs:399-544) fed x: same segmentation, window, detrend, /8 decimation of each channel and lazy stages.  Per stage
@@ -33,6 +34,8 @@
 #include "sk_fft.h"
 #include "zoom_sk.h"
 #include "zoom_sk_fft.h"
+#include "zoom_ampm.h"
+#include "zoom_ampm_fft.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -79,8 +82,9 @@ struct XObj {
     bool iq = false;     // psdc_iq (with zoom), psdc_iqcsd (with zoom and zcross): I and Q come from the caller, through the complex mixer
     bool sk = false;     // psdc_sk: one real stream a unit (m = 1), sk_kernel and its two rows S1, S2
     bool zsk = false;    // psdc_zsk (with zoom), psdc_iqsk (with zoom and iq): zoom_sk_kernel and its four rows S1, S2 upper / lower
+    bool ampm = false;   // psdc_zampm (with zoom), psdc_iqampm (with zoom and iq): zoom_ampm_kernel and its four rows upper, lower, comp
     const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return zcross ? 8 : zsk ? ZSK_ROWS : zoom || sk ? 2 : matrix ? m * m : 4; }
+    uint32_t rows() const { return zcross ? 8 : zsk ? ZSK_ROWS : ampm ? ZAMPM_ROWS : zoom || sk ? 2 : matrix ? m * m : 4; }
     uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
     // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
     // (an IQ channel two: its I and its Q; an IQ cross pair four)
@@ -143,6 +147,8 @@ struct psdc_iqcsd : XObj {};
 struct psdc_sk : XObj {};
 struct psdc_zsk : XObj {};
 struct psdc_iqsk : XObj {};
+struct psdc_zampm : XObj {};
+struct psdc_iqampm : XObj {};
 
 namespace {
 
@@ -415,6 +421,7 @@ int run_round(XObj *h, bool *did)
             CrossBatch *cb = new CrossBatch();
             fill(cb, pair_job);
             e = h->zsk    ? launch_zoom_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
+                : h->ampm ? launch_zoom_ampm((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
                 : h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
                 : h->sk   ? launch_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
                         : launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
@@ -575,7 +582,8 @@ std::string zcsd_size_text(uint32_t n)
 
 // T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
 // psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed;
-// psdc_sk (m = 1: one real stream, sk_kernel); psdc_zsk is psdc_zoom and psdc_iqsk is psdc_iq on zoom_sk_kernel
+// psdc_sk (m = 1: one real stream, sk_kernel); psdc_zsk is psdc_zoom and psdc_iqsk is psdc_iq on zoom_sk_kernel; psdc_zampm is
+// psdc_zoom and psdc_iqampm is psdc_iq on zoom_ampm_kernel
 template <class T>
 T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
                const char *who)
@@ -585,8 +593,10 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
     constexpr bool zcross = std::is_same<T, psdc_zcsd>::value || iqcsd;
     constexpr bool iqsk = std::is_same<T, psdc_iqsk>::value;
     constexpr bool zsk = std::is_same<T, psdc_zsk>::value || iqsk;
-    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd || iqsk;
-    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq || zsk;
+    constexpr bool iqampm = std::is_same<T, psdc_iqampm>::value;
+    constexpr bool ampm = std::is_same<T, psdc_zampm>::value || iqampm;
+    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd || iqsk || iqampm;
+    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq || zsk || ampm;
     constexpr bool sk = std::is_same<T, psdc_sk>::value;
     if (matrix && !csm_supported((int)n, (int)m)) {
         xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
@@ -643,6 +653,10 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         if (zsk) {
             h->zsk = true;
             h->tag = iqsk ? "psdc_iqsk" : "psdc_zsk";
+        }
+        if (ampm) {
+            h->ampm = true;
+            h->tag = iqampm ? "psdc_iqampm" : "psdc_zampm";
         }
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
@@ -2911,5 +2925,207 @@ int psdc_iqsk_stats_read(psdc_iqsk *h, uint64_t *launches, uint64_t *samples_in,
 }
 
 const char *psdc_iqsk_last_error(const psdc_iqsk *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+} // extern "C"
+
+// ---- AM/PM: the zoom / IQ object on zoom_ampm_kernel, rows upper, lower, comp_re, comp_im ----
+
+namespace {
+
+static_assert(ZAMPM_ROWS == ZSK_ROWS, "the AM/PM read-out takes its stages through zsk_in: four f64 rows a stage");
+
+// the four rows stitched in f64: the row stitch picks the stages and bins from rows 0 and 1 (one set of Breaks, the zoom
+// read-out's), and every selected bin of the f64 accumulators is scaled by the f32 factor that stitch applies to the stage
+int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
+                        double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks,
+                        size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    ZskIn in;
+    if ((rc = zsk_in(h, channel, &in)))
+        return rc;
+    float *none[2] = {nullptr, nullptr};
+    double *outs[ZAMPM_ROWS] = {upper, lower, comp_re, comp_im};
+    const bool any = upper || lower || comp_re || comp_im;
+    psdc_break own[X_MAX_STAGES];
+    size_t l = 0, nb = 0;
+    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                          in.rows01.data(), 2, keep_overlap, min_count, keep_transition_band, none, 0, &l, own, X_MAX_STAGES, &nb);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    if (any && l > cap)
+        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
+    if (len)
+        *len = l;
+    if (n_breaks)
+        *n_breaks = nb;
+    if (breaks) {
+        if (nb > breaks_cap)
+            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
+        std::copy(own, own + nb, breaks);
+    }
+    if (any) {
+        const size_t b = bins(h);
+        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
+            const psdc_break &br = own[i];
+            if (!br.include)
+                continue;
+            const size_t si = in.ns - 1 - i;
+            const double *a = &in.acc[si * ZAMPM_ROWS * b];
+            const double gsc = 1.0f / (psdrt::stage_gain(h->n, in.c64[si], h->nenbw, h->power) * (float)br.decimation);
+            for (int r = 0; r < ZAMPM_ROWS; ++r)
+                if (outs[r])
+                    for (uint64_t k = br.bins_start; k < br.bins_end; ++k)
+                        outs[r][br.start + (k - br.bins_start)] = a[r * b + k] * gsc;
+        }
+    }
+    return PSDC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int psdc_zampm_supported(uint32_t n) { return psdc_sk_supported(n); }
+
+psdc_zampm *psdc_zampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_zampm>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zampm_create_window");
+}
+
+psdc_zampm *psdc_zampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_zampm>(n, window_kind, 2, n_channels, device, "psdc_zampm_create");
+}
+
+void psdc_zampm_destroy(psdc_zampm *h) { zsk_destroy(h); }
+int psdc_zampm_reset(psdc_zampm *h) { return reset_impl(h, "psdc_zampm_reset"); }
+int psdc_zampm_set_detrend(psdc_zampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zampm_set_detrend"); }
+int psdc_zampm_set_avg(psdc_zampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zampm_set_avg"); }
+
+int psdc_zampm_set_carrier(psdc_zampm *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_zampm_set_carrier");
+}
+
+int psdc_zampm_process(psdc_zampm *h, uint32_t channel, const float *x, size_t len)
+{
+    const void *xs[1] = {x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, false, nullptr, "psdc_zampm_process");
+}
+
+int psdc_zampm_process_device(psdc_zampm *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, true, producer_event, "psdc_zampm_process_device");
+}
+
+int psdc_zampm_sync(psdc_zampm *h) { return sync_impl(h, "psdc_zampm_sync"); }
+int psdc_zampm_num_stages(psdc_zampm *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_zampm_num_stages"); }
+
+int psdc_zampm_stage_rows(psdc_zampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower, double *comp_re,
+                          double *comp_im)
+{
+    return zsk_stage_moments_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_zampm_stage_rows");
+}
+
+int psdc_zampm_psd(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper, float *lower,
+                   size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
+                            breaks_cap, n_breaks, "psdc_zampm_psd");
+}
+
+int psdc_zampm_sidebands(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
+                         double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
+                         size_t *n_breaks)
+{
+    return ampm_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, comp_re, comp_im, cap, len,
+                               breaks, breaks_cap, n_breaks, "psdc_zampm_sidebands");
+}
+
+int psdc_zampm_stats_read(psdc_zampm *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_zampm_stats_read");
+}
+
+const char *psdc_zampm_last_error(const psdc_zampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+int psdc_iqampm_supported(uint32_t n) { return psdc_sk_supported(n); }
+
+psdc_iqampm *psdc_iqampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
+{
+    return create_impl<psdc_iqampm>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iqampm_create_window");
+}
+
+psdc_iqampm *psdc_iqampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
+{
+    return create_kind<psdc_iqampm>(n, window_kind, 2, n_channels, device, "psdc_iqampm_create");
+}
+
+void psdc_iqampm_destroy(psdc_iqampm *h) { zsk_destroy(h); }
+int psdc_iqampm_reset(psdc_iqampm *h) { return reset_impl(h, "psdc_iqampm_reset"); }
+int psdc_iqampm_set_detrend(psdc_iqampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqampm_set_detrend"); }
+int psdc_iqampm_set_avg(psdc_iqampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqampm_set_avg"); }
+
+int psdc_iqampm_set_carrier(psdc_iqampm *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_iqampm_set_carrier");
+}
+
+int psdc_iqampm_process(psdc_iqampm *h, uint32_t channel, const float *i, const float *q, size_t len)
+{
+    return iq_feed(h, channel, i, q, false, SampleFmt{}, len, false, nullptr, "psdc_iqampm_process");
+}
+
+int psdc_iqampm_process_device(psdc_iqampm *h, uint32_t channel, const float *d_i, const float *d_q, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_i, d_q, false, SampleFmt{}, len, true, producer_event, "psdc_iqampm_process_device");
+}
+
+int psdc_iqampm_process_interleaved(psdc_iqampm *h, uint32_t channel, const float *iq, size_t len)
+{
+    return iq_feed(h, channel, iq, nullptr, true, SampleFmt{}, len, false, nullptr, "psdc_iqampm_process_interleaved");
+}
+
+int psdc_iqampm_process_interleaved_device(psdc_iqampm *h, uint32_t channel, const float *d_iq, size_t len, void *producer_event)
+{
+    return iq_feed(h, channel, d_iq, nullptr, true, SampleFmt{}, len, true, producer_event, "psdc_iqampm_process_interleaved_device");
+}
+
+int psdc_iqampm_sync(psdc_iqampm *h) { return sync_impl(h, "psdc_iqampm_sync"); }
+int psdc_iqampm_num_stages(psdc_iqampm *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_iqampm_num_stages"); }
+
+int psdc_iqampm_stage_rows(psdc_iqampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower, double *comp_re,
+                           double *comp_im)
+{
+    return zsk_stage_moments_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_iqampm_stage_rows");
+}
+
+int psdc_iqampm_psd(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper, float *lower,
+                    size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
+                            breaks_cap, n_breaks, "psdc_iqampm_psd");
+}
+
+int psdc_iqampm_sidebands(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
+                          double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
+                          size_t *n_breaks)
+{
+    return ampm_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, comp_re, comp_im, cap, len,
+                               breaks, breaks_cap, n_breaks, "psdc_iqampm_sidebands");
+}
+
+int psdc_iqampm_stats_read(psdc_iqampm *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_iqampm_stats_read");
+}
+
+const char *psdc_iqampm_last_error(const psdc_iqampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

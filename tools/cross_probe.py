@@ -68,6 +68,13 @@ ZoomSkCascadeBank(n, 1) / IqSkCascadeBank(n, 1) fed the same stream: the same tr
 turn --reps times with the windows and the sync of --sk; B / A of every turn, the largest |A' - A| / A, B's launches a steady call
 and the live stages are recorded as findings, none is a gate.  Each writes its family's entry ("zoom" / "iq") of
 profiles/zoom_sk_probe.json unless --out names another file.
+--zoom --ampm / --iq --ampm: the AM/PM objects.  One device-resident stream (real f32 / complex64, carrier 0.2) of 2^24 samples a
+call at N = 512, 1024, 4096, the windows and the sync of --sk.  --zoom, first leg: A is ZoomCsdCascadeBank(n, 1) fed (x, x) with the
+carriers +ftw and -ftw -- the only way to the complementary spectrum without the object: two mixers, two transforms, eight rows --
+and B is ZoomAmPmCascadeBank(n, 1) fed x.  Second leg (the only one of --iq): A is the two-row object, ZoomCascadeBank /
+IqCascadeBank, and B the AM/PM bank: the cost of the two extra rows and the natural-order pass.  A, B, A in turn --reps times; B / A
+of every turn, the largest |A' - A| / A, B's launches a steady call and the live stages are recorded as findings, none is a gate.
+Each writes its family's entry ("zoom" / "iq") of profiles/zoom_ampm_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -381,6 +388,59 @@ def zoom_sk_legs(pkg, torch, seconds, reps, call, iq):
         legs.append({"n": n, "call": call, "a_first_moment_gs_s": r3(a1), "b_sk_gs_s": r3(b), "a_again_gs_s": r3(a2),
                      "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3), "ratio_max": round(max(ratios), 3),
                      "aa_spread_max": round(spread, 4), "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread),
+                     "b_launches_per_call": launches, "stages": zb.num_stages(0), "a_stages": za.num_stages(0)})
+        za.close()
+        zb.close()
+    return legs
+
+
+def ampm_legs(pkg, torch, seconds, reps, call, iq, recipe):
+    """One device-resident stream, carrier 0.2: real f32 (iq False) or complex64 interleaved (iq True).  B: ZoomAmPmCascadeBank /
+    IqAmPmCascadeBank.  A: with `recipe` ZoomCsdCascadeBank fed (x, x) with carriers +ftw and -ftw (S_ab upper is conj(comp)), else
+    the two-row object ZoomCascadeBank / IqCascadeBank.  A / B / A in turn."""
+    x = torch.randn(call, dtype=torch.complex64 if iq else torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    ftw = pkg.zoom_ftw(0.2)[0]
+    legs = []
+    for n in (512, 1024, 4096):
+        zb = (pkg.IqAmPmCascadeBank if iq else pkg.ZoomAmPmCascadeBank)(n, 1)
+        zb.set_carrier(0, ftw=ftw)
+        if recipe:
+            za = pkg.ZoomCsdCascadeBank(n, 1)
+            za.set_carrier(0, ftw=ftw, side=0)
+            za.set_carrier(0, ftw=(-ftw) % (1 << 64), side=1)
+        else:
+            za = (pkg.IqCascadeBank if iq else pkg.ZoomCascadeBank)(n, 1)
+            za.set_carrier(0, ftw=ftw)
+
+        def a_step():
+            if recipe:
+                za.process_device(0, x.data_ptr(), x.data_ptr(), call)
+            else:
+                za.process_device(0, x.data_ptr(), call)
+            return call
+
+        def b_step():
+            zb.process_device(0, x.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+        zb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = zb.stats_read()["launches"] / 8
+        zb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "call": call, "a_gs_s": r3(a1), "b_ampm_gs_s": r3(b), "a_again_gs_s": r3(a2),
+                     "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3), "ratio_max": round(max(ratios), 3),
+                     "aa_spread_max": round(spread, 4), "b_beats_a_beyond_spread": bool(min(ratios) > 1 + spread),
+                     "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread),
                      "b_launches_per_call": launches, "stages": zb.num_stages(0), "a_stages": za.num_stages(0)})
         za.close()
         zb.close()
@@ -937,9 +997,40 @@ def main():
                                                       "IqCascadeBank; writes profiles/zoom_sk_probe.json")
     ap.add_argument("--real-int", action="store_true", help="the s16 feed of PsdCascadeBank and CsdCascadeBank against the f32 feed of "
                                                             "the converted stream, host-fed and device-resident")
+    ap.add_argument("--ampm", action="store_true", help="with --zoom: ZoomAmPmCascadeBank against ZoomCsdCascadeBank fed (x, x) with "
+                                                        "carriers +-ftw, and against ZoomCascadeBank; with --iq: IqAmPmCascadeBank "
+                                                        "against IqCascadeBank; writes profiles/zoom_ampm_probe.json")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.ampm:
+        if not (a.zoom or a.iq):
+            raise SystemExit("--ampm goes with --zoom or --iq")
+        path = a.out or os.path.join(ROOT, "profiles", "zoom_ampm_probe.json")
+        record = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                record = json.loads(f.read() or "{}")
+        record.update({"metric": "zoom_ampm_gsamples_s", "unit": "1e9 samples a second of one stream (complex samples for iq)",
+                       "note": "findings, no gate: B is the AM/PM bank on one device-resident stream; A is the (x, x) recipe on the "
+                               "zoom cross object (vs_recipe) or the two-row object (vs_two_rows); not measured here: host memory, "
+                               "banks, the EWMA regime, N = 2048"})
+        for fam, on in (("zoom", a.zoom), ("iq", a.iq)):
+            if on:
+                before = gpu_state()
+                rec = {"b": "IqAmPmCascadeBank" if fam == "iq" else "ZoomAmPmCascadeBank", "gpu_before": before}
+                if fam == "zoom":
+                    rec["vs_recipe"] = {"a": "ZoomCsdCascadeBank fed (x, x), carriers +ftw / -ftw",
+                                        "legs": ampm_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, False, True)}
+                rec["vs_two_rows"] = {"a": "IqCascadeBank" if fam == "iq" else "ZoomCascadeBank",
+                                      "legs": ampm_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, fam == "iq", False)}
+                rec["gpu_after"] = gpu_state()
+                record[fam] = rec
+        line = json.dumps(record)
+        print(line)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.sk and (a.zoom or a.iq):
         path = a.out or os.path.join(ROOT, "profiles", "zoom_sk_probe.json")
         record = {}

@@ -31,6 +31,13 @@ IqSkCascade(512).  Each prints, or with --csv writes to DIR/zoomsk_<trace>_<F0>.
 offset,psd,sk over the offsets -0.5 fs ... 0.5 fs from the carrier in ascending order (two_sided): the spectral kurtosis of the
 sideband power beside its density.  Circular Gaussian noise reads 1 at every offset, 0 included; a real stream rises towards 2
 where its own DC and Nyquist fall (offsets -F0 and 0.5 - F0).  The summary line counts the bins more than 8 sk_sigma(count) from 1.
+--zoom-ampm F0[:TRACE] (repeatable; as --zoom) feeds that trace to a ZoomAmPmCascade(512) around the carrier F0, and --iq-ampm
+I:Q[:F0] (repeatable; as --iq) the complex stream I + i Q to an IqAmPmCascade(512).  Both run without a detrend whatever --detrend
+says: the carrier's amplitude and phase are read from bin 0 (carrier()), which a detrend removes.  Each prints, or with --csv writes
+to DIR/zoomampm_<trace>_<F0>.csv / DIR/iqampm_<i>__<q>_<F0>.csv, the lines offset,S_am,S_pm,Re S_ampm,Im S_ampm: the amplitude
+noise, phase noise and AM-PM cross spectra of the carrier (am_pm(): relative to the carrier, a linear small-modulation split).  The
+summary line gives the carrier's power, angle and lock (1: the carrier sits at F0; towards 0: it turned during the average and the
+split means nothing).
 --sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
 integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
 then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
@@ -80,6 +87,10 @@ def main(argv=None):
                     help="F0[:TRACE] -- two-sided spectral kurtosis beside the spectrum around the carrier F0 (repeatable)")
     ap.add_argument("--iq-sk", action="append", default=[],
                     help="I:Q[:F0] -- two-sided spectral kurtosis beside the spectrum of the complex stream I + i Q (repeatable)")
+    ap.add_argument("--zoom-ampm", action="append", default=[],
+                    help="F0[:TRACE] -- amplitude and phase noise spectra of the carrier F0 of that trace (repeatable)")
+    ap.add_argument("--iq-ampm", action="append", default=[],
+                    help="I:Q[:F0] -- amplitude and phase noise spectra of the carrier of the complex stream I + i Q (repeatable)")
     ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
                     help="s16 / s8: --raw, --pair, --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
     ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
@@ -97,12 +108,14 @@ def main(argv=None):
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
-    if (a.iq or a.iq_pair or a.iq_sk) and not a.file:  # the planar raw files: the only input these options need
+    if (a.iq or a.iq_pair or a.iq_sk or a.iq_ampm) and not a.file:  # the planar raw files: the only input these options need
         merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
         if a.csv:
             os.makedirs(a.csv, exist_ok=True)
         if a.iq_sk:
             iq_sk_streams(pkg, source, a, merge, None)
+        if a.iq_ampm:
+            iq_ampm_streams(pkg, source, a, merge, None)
         if a.iq:
             iq_streams(pkg, source, a, merge, None)
         if a.iq_pair:
@@ -157,6 +170,10 @@ def main(argv=None):
         zoom_sk_traces(pkg, source, a, merge, names)
     if a.iq_sk and a.file:
         iq_sk_streams(pkg, source, a, merge, names)
+    if a.zoom_ampm:
+        zoom_ampm_traces(pkg, source, a, merge, names)
+    if a.iq_ampm and a.file:
+        iq_ampm_streams(pkg, source, a, merge, names)
     if a.iq and a.file:
         iq_streams(pkg, source, a, merge, names)
     if a.iq_pair and a.file:
@@ -363,6 +380,56 @@ def iq_sk_streams(pkg, source, a, merge, names):
     bank.close()
 
 
+def ampm_report(pkg, bank, c, label, stem, a, merge):
+    """the read-out of one channel of a ZoomAmPmCascadeBank / IqAmPmCascadeBank: the summary line with the carrier, and
+    offset,S_am,S_pm,Re S_ampm,Im S_ampm in the order of the Breaks"""
+    if bank.num_stages(c) == 0 or bank.stage_rows(c, 0)[0]["count"] == 0:
+        print(f"{label}: no samples")
+        return
+    power, u, lock = bank.carrier(c)
+    s_am, s_pm, s_x, breaks = bank.am_pm(c, opts=merge)
+    off = pkg.Break.frequencies(breaks) * a.fs
+    print(f"{label}: stages {bank.num_stages(c)} bins {s_am.size} breaks {len(breaks)} carrier power {power:.9g} "
+          f"angle {0.5 * np.angle(u):.9g} lock {lock:.9g}")
+    lines = [f"{o:.9g},{am:.9g},{pm:.9g},{x.real:.9g},{x.imag:.9g}\n" for o, am, pm, x in zip(off, s_am, s_pm, s_x)]
+    if a.csv:
+        safe = "".join(ch if ch.isalnum() else "_" for ch in stem)
+        with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+            f.writelines(lines)
+    else:
+        sys.stdout.writelines(lines)
+
+
+def zoom_ampm_traces(pkg, source, a, merge, names):
+    """--zoom-ampm: the named trace of every read (host_traces) into one AM/PM cascade per carrier; no detrend (carrier() reads bin 0)"""
+    want = []
+    for z in a.zoom_ampm:
+        f0, _, tr = z.partition(":")
+        want.append((float(f0), trace_arg(tr, names, "--zoom-ampm")))
+    bank = pkg.ZoomAmPmCascadeBank(1 << 9, len(want))
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _) in enumerate(want)]
+    host_traces(source, pkg, a, [(idx,) for _, idx in want], lambda i, xs: bank.process(i, xs[0]))
+    for i, (_, idx) in enumerate(want):
+        ampm_report(pkg, bank, i, f"zoom am/pm {names[idx]} @ {used[i]:.12g}", f"zoomampm_{names[idx]}_{used[i]:.9g}", a, merge)
+    bank.close()
+
+
+def iq_ampm_streams(pkg, source, a, merge, names):
+    """--iq-ampm: two traces of every read (host_traces), or two raw f32 files (names None), into one IQ AM/PM cascade per stream"""
+    want = []
+    for z in a.iq_ampm:
+        parts = z.split(":")
+        if len(parts) not in (2, 3) or not parts[0] or not parts[1]:
+            raise SystemExit("--iq-ampm takes I:Q[:F0]")
+        want.append((parts[0], parts[1], float(parts[2]) if len(parts) == 3 else 0.0))
+    bank = pkg.IqAmPmCascadeBank(1 << 9, len(want))
+    used, labels = iq_feed(pkg, source, a, bank, want, names, "--iq-ampm", detrend=pkg.Detrend.NONE)
+    for c, (li, lq) in enumerate(labels):
+        ampm_report(pkg, bank, c, f"iq am/pm {li}:{lq} @ {used[c]:.12g}", f"iqampm_{li}__{lq}_{used[c]:.9g}", a, merge)
+    bank.close()
+
+
 def zoom_pairs(pkg, source, a, merge, names):
     """--zoom-pair: the two named traces of every read (host_traces) into one zoom cross cascade per pair, one carrier on both sides"""
     want = []
@@ -396,10 +463,10 @@ def zoom_pairs(pkg, source, a, merge, names):
     bank.close()
 
 
-def iq_feed(pkg, source, a, bank, want, names, opt):
+def iq_feed(pkg, source, a, bank, want, names, opt, detrend=None):
     """settle an IQ bank (AcqOpts, carriers) and feed it `want` = [(I, Q, F0)]: two traces of every read (host_traces), or two raw f32
-    files (names None).  Returns the carriers in use and the (I, Q) labels."""
-    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    files (names None).  detrend: in place of --detrend.  Returns the carriers in use and the (I, Q) labels."""
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()] if detrend is None else detrend)
     bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
     used = [bank.set_carrier(i, f0=f0) for i, (_, _, f0) in enumerate(want)]
     if names is None:
