@@ -43,10 +43,21 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 using namespace psdk;
+
+#if !defined(__HIPCC__)
+// A host build of this file (tests/host/cross_feed_check: the HIP runtime modelled on the CPU, no device code) sees none of the
+// launchers of sample_int.h, which declares them for hipcc alone.  The integer mixers are the check program's models; there is
+// no converter, as in a host build of runtime.cpp: the integer feeds of the pair and matrix objects fail there with a device error.
+namespace psdk {
+hipError_t launch_zoom_mix_int(const SintMixJob &j, int kind, hipStream_t s);
+hipError_t launch_iq_mix_int(const SintMixJob &j, int kind, hipStream_t s);
+hipError_t launch_iq_pair_mix_int(const SintPairMixJob &j, int kind, hipStream_t s);
+inline hipError_t launch_cvt_int(const SintCvtJob &, int, hipStream_t) { return hipErrorInvalidValue; }
+} // namespace psdk
+#endif
 
 namespace {
 
@@ -73,27 +84,41 @@ struct XStage {
     double *acc = nullptr; // device [rows][n/2 + 1]: xx, yy, re xy, im xy of a pair; the m * m rows of csm_fft.h of a group
 };
 
+struct XObj;
+
+// What tells the eleven families apart, one row each in KINDS (below XObj): the names in error texts, the streams and rows of a
+// unit, the feed in front of stage 0 and the segment kernel.  Everything else in this file is one runtime over these.
+enum class Feed {
+    PLAIN, // the m streams are the caller's, copied (or converted) into stage 0
+    ZOOM,  // a real channel a two streams: the mixer makes I and Q of it
+    IQ,    // a complex channel a two streams: the caller's I and Q through the complex mixer
+};
+struct KindDesc {
+    const char *tag, *unit, *units;
+    uint32_t m;    // streams of a unit (0: the caller's, psdc_csm)
+    uint32_t rows; // accumulator rows of a stage (0: m * m)
+    Feed feed;
+    int (*segments_per_tile)(int n, int m);
+    // the segment kernel: on CrossBatch jobs (two streams at most) or, for the kinds with up to four, on CsmBatch jobs
+    hipError_t (*launch_pair)(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s);
+    hipError_t (*launch_group)(const XObj &h, const CsmBatch &b);
+    std::string (*refusal)(uint32_t n, uint32_t m); // why the kind has no kernel for these sizes ("": it has), NULL: for every n
+};
+
 struct XObj {
+    const KindDesc *kind = nullptr;
     uint32_t n = 0, n_pairs = 0;
-    uint32_t m = 2;      // channels of a pair / group
-    bool matrix = false; // psdc_csm: csm_kernel and its row layout
-    bool zoom = false;   // psdc_zoom / psdc_zcsd: the streams are I and Q of mixed channels, fed through the mixer
-    bool zcross = false; // psdc_zcsd (with zoom): two mixed channels a unit, zoom_cross_kernel and its eight rows
-    bool iq = false;     // psdc_iq (with zoom), psdc_iqcsd (with zoom and zcross): I and Q come from the caller, through the complex mixer
-    bool sk = false;     // psdc_sk: one real stream a unit (m = 1), sk_kernel and its two rows S1, S2
-    bool zsk = false;    // psdc_zsk (with zoom), psdc_iqsk (with zoom and iq): zoom_sk_kernel and its four rows S1, S2 upper / lower
-    bool ampm = false;   // psdc_zampm (with zoom), psdc_iqampm (with zoom and iq): zoom_ampm_kernel and its four rows upper, lower, comp
-    const char *tag = "psdc_cross", *unit = "pair", *units = "n_pairs";
-    uint32_t rows() const { return zcross ? 8 : zsk ? ZSK_ROWS : ampm ? ZAMPM_ROWS : zoom || sk ? 2 : matrix ? m * m : 4; }
-    uint32_t reals() const { return zoom ? m / 2 : m; } // real streams a call feeds a unit (a mixed channel is two of the m)
-    // entries a unit has in a frames call's map: a zoom channel takes one trace, a zoom cross pair one for each side
-    // (an IQ channel two: its I and its Q; an IQ cross pair four)
-    uint32_t map_w() const { return iq ? m : zoom ? reals() : m; }
-    // f32 streams of STAGING samples a pinned staging slot and the landing buffer hold: an IQ unit's I and Q streams, else reals()
-    uint32_t lanes() const { return iq ? m : reals(); }
+    uint32_t m = 2; // streams of a pair / group
+    bool mixed() const { return kind->feed != Feed::PLAIN; } // the streams are I and Q of mixed channels, two a channel
+    uint32_t rows() const { return kind->rows ? kind->rows : m * m; }
+    uint32_t reals() const { return mixed() ? m / 2 : m; } // channels a unit has (a mixed channel is two of the m streams)
+    // f32 streams of STAGING samples a pinned staging slot and the landing buffer hold, which is also the entries a unit has in a
+    // frames call's map: a zoom channel takes one, a zoom cross pair one for each side, an IQ unit its I and Q streams, else m
+    uint32_t lanes() const { return kind->feed == Feed::ZOOM ? m / 2 : m; }
+    uint32_t map_w() const { return lanes(); }
     // host-memory frame bytes a pinned staging slot takes at once, and the size of d_frames: a zoom object's slot holds one
     // channel's STAGING floats (16 MB), a zoom cross object's two (32 MB), an IQ cross object's four (64 MB), the others' at least two
-    size_t frames_chunk() const { return sizeof(float) * STAGING * (zoom ? lanes() : 2); }
+    size_t frames_chunk() const { return sizeof(float) * STAGING * (mixed() ? lanes() : 2); }
     int device = 0;
     Geometry geo;
     float power = 0.25f, nenbw = 1.5f;
@@ -224,7 +249,7 @@ int ensure_room(XObj *h, XStage &s, uint64_t new_end)
 int add_stage(XObj *h, std::vector<XStage> &st)
 {
     if (st.size() >= X_MAX_STAGES)
-        return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": more than 16 stages");
+        return xfail(h, PSDC_ERR_ARG, std::string(h->kind->tag) + ": more than 16 stages");
     XStage s;
     XCHK(h, hipMalloc(&s.acc, sizeof(double) * h->rows() * bins(h)));
     XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * h->rows() * bins(h), h->stream));
@@ -274,11 +299,7 @@ CrossJob pair_job(const CsmJob &j)
 int run_round(XObj *h, bool *did)
 {
     const Geometry &g = h->geo;
-    const int spt = h->matrix   ? csm_segments_per_tile((int)h->n, (int)h->m)
-                    : h->zcross ? zoom_cross_segments_per_tile((int)h->n)
-                    : h->zoom   ? zoom_segments_per_tile((int)h->n)
-                    : h->sk     ? sk_segments_per_tile((int)h->n)
-                                : cross_segments_per_tile((int)h->n);
+    const int spt = h->kind->segments_per_tile((int)h->n, (int)h->m);
     const int nch = (int)h->m;
     std::vector<PlannedCross> cross;
     std::vector<DecJob> decs;
@@ -294,7 +315,7 @@ int run_round(XObj *h, bool *did)
             XStage &s = st[k];
             const uint64_t nb = j_new - s.segs;
             if (nb > (uint64_t)std::numeric_limits<int>::max() / 2)
-                return xfail(h, PSDC_ERR_ARG, std::string(h->tag) + ": too many segments in one round");
+                return xfail(h, PSDC_ERR_ARG, std::string(h->kind->tag) + ": too many segments in one round");
             const uint32_t avg = cur_avg(h, k);
             const EwmaPlan ew = plan_ewma(count_report(s.count64), avg, nb);
             PlannedCross pc{};
@@ -411,20 +432,15 @@ int run_round(XObj *h, bool *did)
                 cb->jobs[cb->njobs++] = conv(cross[i].job);
         };
         hipError_t e;
-        if (h->matrix || h->zcross) {
+        if (h->kind->launch_group) {
             CsmBatch *cb = new CsmBatch();
             fill(cb, [](const CsmJob &j) { return j; });
-            e = h->zcross ? launch_zoom_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                          : launch_csm((int)h->n, (int)h->m, *cb, h->d_win, h->d_tw, h->stream);
+            e = h->kind->launch_group(*h, *cb);
             delete cb;
         } else {
             CrossBatch *cb = new CrossBatch();
             fill(cb, pair_job);
-            e = h->zsk    ? launch_zoom_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                : h->ampm ? launch_zoom_ampm((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                : h->zoom ? launch_zoom((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                : h->sk   ? launch_sk((int)h->n, *cb, h->d_win, h->d_tw, h->stream)
-                        : launch_cross((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
+            e = h->kind->launch_pair((int)h->n, *cb, h->d_win, h->d_tw, h->stream);
             delete cb;
         }
         XCHK(h, e);
@@ -501,8 +517,8 @@ int sync_all(XObj *h)
 int check_pair(XObj *h, uint32_t pair, const char *who = nullptr)
 {
     if (pair >= h->n_pairs)
-        return xfail(h, PSDC_ERR_ARG, std::string(who ? who : h->tag) + ": " + h->unit + " " + std::to_string(pair) + " out of range (" +
-                                          h->units + " " + std::to_string(h->n_pairs) + ")");
+        return xfail(h, PSDC_ERR_ARG, std::string(who ? who : h->kind->tag) + ": " + h->kind->unit + " " + std::to_string(pair) + " out of range (" +
+                                          h->kind->units + " " + std::to_string(h->n_pairs) + ")");
     return PSDC_OK;
 }
 
@@ -546,19 +562,57 @@ void free_all(XObj *h)
     h->idle = true;
 }
 
-// the sizes of a matrix object, as text for a refusal
-std::string csm_size_text(uint32_t n, uint32_t m)
+// why a matrix object cannot have these sizes ("": it can)
+std::string csm_refusal(uint32_t n, uint32_t m)
 {
+    if (csm_supported(n <= 4096 ? (int)n : 0, m <= CSM_MAX_M ? (int)m : 0))
+        return "";
     if (m < 2 || m > CSM_MAX_M)
         return "m = " + std::to_string(m) + " is not supported: a group has 2 to 4 channels";
     return "n = " + std::to_string(n) + " with m = " + std::to_string(m) +
            " is not supported: n must be a power of two in [64, 2048], or 4096 with m = 2 or 3";
 }
 
-const char *check_args(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, bool matrix,
-                       bool zoom, bool zcross = false)
+// why a zoom cross object cannot have this size ("": it can)
+std::string zcsd_refusal(uint32_t n, uint32_t)
 {
-    if (!matrix && (n < 64 || n > 4096 || (n & (n - 1)) != 0))
+    if (zoom_cross_supported(n <= 4096 ? (int)n : 0))
+        return "";
+    return "n = " + std::to_string(n) + " is not supported: n must be a power of two in [64, " +
+           (zoom_cross_supported(4096) ? "4096]" : "2048]");
+}
+
+// One row a family.  A pair object is m = 2 on cross_kernel; a matrix object 2 <= m <= 4 on csm_kernel; a zoom object m = 2 (I and
+// Q) on zoom_kernel; a zoom cross object m = 4 (I and Q of two channels) on zoom_cross_kernel; psdc_iq is psdc_zoom and psdc_iqcsd
+// is psdc_zcsd with the IQ feed; psdc_sk is m = 1 on sk_kernel; psdc_zsk / psdc_iqsk are psdc_zoom / psdc_iq on zoom_sk_kernel;
+// psdc_zampm / psdc_iqampm are psdc_zoom / psdc_iq on zoom_ampm_kernel.
+enum Kind { K_CROSS, K_CSM, K_ZOOM, K_ZCSD, K_IQ, K_IQCSD, K_SK, K_ZSK, K_IQSK, K_ZAMPM, K_IQAMPM };
+constexpr auto SPT_CROSS = [](int n, int) { return cross_segments_per_tile(n); };
+constexpr auto SPT_ZOOM = [](int n, int) { return zoom_segments_per_tile(n); };
+constexpr auto SPT_ZCSD = [](int n, int) { return zoom_cross_segments_per_tile(n); };
+constexpr auto SPT_SK = [](int n, int) { return sk_segments_per_tile(n); };
+constexpr auto GROUP_CSM = [](const XObj &h, const CsmBatch &b) { return launch_csm((int)h.n, (int)h.m, b, h.d_win, h.d_tw, h.stream); };
+constexpr auto GROUP_ZCSD = [](const XObj &h, const CsmBatch &b) { return launch_zoom_cross((int)h.n, b, h.d_win, h.d_tw, h.stream); };
+constexpr KindDesc KINDS[] = {
+    // tag, unit, units, m, rows, feed, segments a tile, segment kernel (pair | group), refusal
+    {"psdc_cross", "pair", "n_pairs", 2, 4, Feed::PLAIN, SPT_CROSS, launch_cross, nullptr, nullptr},
+    {"psdc_csm", "group", "n_groups", 0, 0, Feed::PLAIN, csm_segments_per_tile, nullptr, GROUP_CSM, csm_refusal},
+    {"psdc_zoom", "channel", "n_channels", 2, 2, Feed::ZOOM, SPT_ZOOM, launch_zoom, nullptr, nullptr},
+    {"psdc_zcsd", "pair", "n_pairs", 4, 8, Feed::ZOOM, SPT_ZCSD, nullptr, GROUP_ZCSD, zcsd_refusal},
+    {"psdc_iq", "channel", "n_channels", 2, 2, Feed::IQ, SPT_ZOOM, launch_zoom, nullptr, nullptr},
+    {"psdc_iqcsd", "pair", "n_pairs", 4, 8, Feed::IQ, SPT_ZCSD, nullptr, GROUP_ZCSD, zcsd_refusal},
+    {"psdc_sk", "channel", "n_channels", 1, 2, Feed::PLAIN, SPT_SK, launch_sk, nullptr, nullptr},
+    {"psdc_zsk", "channel", "n_channels", 2, ZSK_ROWS, Feed::ZOOM, SPT_ZOOM, launch_zoom_sk, nullptr, nullptr},
+    {"psdc_iqsk", "channel", "n_channels", 2, ZSK_ROWS, Feed::IQ, SPT_ZOOM, launch_zoom_sk, nullptr, nullptr},
+    {"psdc_zampm", "channel", "n_channels", 2, ZAMPM_ROWS, Feed::ZOOM, SPT_ZOOM, launch_zoom_ampm, nullptr, nullptr},
+    {"psdc_iqampm", "channel", "n_channels", 2, ZAMPM_ROWS, Feed::IQ, SPT_ZOOM, launch_zoom_ampm, nullptr, nullptr},
+};
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_IQAMPM + 1, "one row a kind");
+
+// "": the arguments are fine
+std::string check_args(const KindDesc &kind, uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs)
+{
+    if (kind.m && (n < 64 || n > 4096 || (n & (n - 1)) != 0)) // (the caller's m: the kind's refusal has looked at n with it)
         return "n must be a power of two in [64, 4096]";
     if (!win)
         return "null window table";
@@ -567,47 +621,23 @@ const char *check_args(uint32_t n, const float *win, float power, float nenbw, s
     if (!(power > 0.0f) || !(nenbw > 0.0f))
         return "window power and nenbw must be > 0";
     if (n_pairs < 1 || n_pairs > X_MAX_PAIRS)
-        return matrix ? "n_groups must be in [1, 65536]" : zoom && !zcross ? "n_channels must be in [1, 65536]" : "n_pairs must be in [1, 65536]";
-    return nullptr;
+        return std::string(kind.units) + " must be in [1, 65536]";
+    return "";
 }
 
 void destroy_impl(XObj *h);
 
-// the size of a zoom cross object, as text for a refusal
-std::string zcsd_size_text(uint32_t n)
+// m: the caller's, for the kind that has none of its own
+XObj *create_impl(const KindDesc &kind, uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                  int device, const char *who, uint32_t m = 0)
 {
-    return "n = " + std::to_string(n) + " is not supported: n must be a power of two in [64, " +
-           (zoom_cross_supported(4096) ? "4096]" : "2048]");
-}
-
-// T = psdc_cross (m = 2, cross_kernel), psdc_csm (2 <= m <= 4, csm_kernel), psdc_zoom (m = 2: I and Q, zoom_kernel) or
-// psdc_zcsd (m = 4: I and Q of two channels, zoom_cross_kernel); psdc_iq is psdc_zoom and psdc_iqcsd is psdc_zcsd with the iq feed;
-// psdc_sk (m = 1: one real stream, sk_kernel); psdc_zsk is psdc_zoom and psdc_iqsk is psdc_iq on zoom_sk_kernel; psdc_zampm is
-// psdc_zoom and psdc_iqampm is psdc_iq on zoom_ampm_kernel
-template <class T>
-T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m, uint32_t n_pairs, int device,
-               const char *who)
-{
-    constexpr bool matrix = std::is_same<T, psdc_csm>::value;
-    constexpr bool iqcsd = std::is_same<T, psdc_iqcsd>::value;
-    constexpr bool zcross = std::is_same<T, psdc_zcsd>::value || iqcsd;
-    constexpr bool iqsk = std::is_same<T, psdc_iqsk>::value;
-    constexpr bool zsk = std::is_same<T, psdc_zsk>::value || iqsk;
-    constexpr bool iqampm = std::is_same<T, psdc_iqampm>::value;
-    constexpr bool ampm = std::is_same<T, psdc_zampm>::value || iqampm;
-    constexpr bool iq = std::is_same<T, psdc_iq>::value || iqcsd || iqsk || iqampm;
-    constexpr bool zoom = std::is_same<T, psdc_zoom>::value || zcross || iq || zsk || ampm;
-    constexpr bool sk = std::is_same<T, psdc_sk>::value;
-    if (matrix && !csm_supported((int)n, (int)m)) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
-        return nullptr;
-    }
-    if (zcross && !zoom_cross_supported(n <= 4096 ? (int)n : 0)) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + zcsd_size_text(n));
-        return nullptr;
-    }
-    if (const char *msg = check_args(n, win, power, nenbw, overlap, n_pairs, matrix, zoom || sk, zcross)) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + msg);
+    if (kind.m)
+        m = kind.m;
+    std::string why = kind.refusal ? kind.refusal(n, m) : "";
+    if (why.empty())
+        why = check_args(kind, n, win, power, nenbw, overlap, n_pairs);
+    if (!why.empty()) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + why);
         return nullptr;
     }
     int ndev = 0;
@@ -626,46 +656,13 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         xfail(nullptr, PSDC_ERR_DEVICE, std::string(who) + ": hipSetDevice: " + hipGetErrorString(scope.err));
         return nullptr;
     }
-    T *h = new T();
+    XObj *h = new XObj();
+    h->kind = &kind;
     h->n = n;
     h->m = m;
-    h->matrix = matrix;
-    if (matrix) {
-        h->tag = "psdc_csm";
-        h->unit = "group";
-        h->units = "n_groups";
-    }
-    if (zoom) {
-        h->zoom = true;
-        h->tag = "psdc_zoom";
-        h->unit = "channel";
-        h->units = "n_channels";
-        if (zcross) {
-            h->zcross = true;
-            h->tag = "psdc_zcsd";
-            h->unit = "pair";
-            h->units = "n_pairs";
-        }
-        if (iq) {
-            h->iq = true;
-            h->tag = iqcsd ? "psdc_iqcsd" : "psdc_iq";
-        }
-        if (zsk) {
-            h->zsk = true;
-            h->tag = iqsk ? "psdc_iqsk" : "psdc_zsk";
-        }
-        if (ampm) {
-            h->ampm = true;
-            h->tag = iqampm ? "psdc_iqampm" : "psdc_zampm";
-        }
+    if (h->mixed()) {
         h->ftw.assign((size_t)n_pairs * h->reals(), 0);
         h->phase0.assign((size_t)n_pairs * h->reals(), 0);
-    }
-    if (sk) {
-        h->sk = true;
-        h->tag = "psdc_sk";
-        h->unit = "channel";
-        h->units = "n_channels";
     }
     h->n_pairs = n_pairs;
     h->device = device;
@@ -681,7 +678,7 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
         // twice what is resident at one wavefront a SIMD (the kernel's registers allow no more); once and twice read the same
         // end to end within the noise of tools/cross_probe.py (N = 1024, one pair: 43.9 against 45.4 G pairs/s)
         h->resident = std::max<int64_t>(1, 2 * (int64_t)cus * 4 * 64 /
-                                               (matrix ? csm_block_threads((int)n, (int)m) : cross_block_threads((int)n)));
+                                               (kind.m ? cross_block_threads((int)n) : csm_block_threads((int)n, (int)m)));
     std::vector<cf> tw(n);
     for (uint32_t j = 0; j < n; ++j) {
         const double a = -2.0 * M_PI * (double)j / (double)n;
@@ -709,6 +706,76 @@ T *create_impl(uint32_t n, const float *win, float power, float nenbw, size_t ov
 }
 
 
+// ---- the feed skeleton: how samples reach stage 0 ----
+//
+// Every feed ends in run_round on the compute stream (h->stream); what differs is the way into stage 0.
+//   * Host samples of the objects without a mixer (process_impl) go up on the compute stream itself, through a pinned staging slot:
+//     nothing to order.
+//   * Everything else is written into stage 0 on the copy stream, beside the kernels of the round before: device samples (copied, or
+//     converted by one launch), mixer launches (whose host samples go up through a staging slot into the landing buffer d_land
+//     first, in pieces of STAGING samples) and frames decodes.  The event rules are those at XObj::copy_stream, and they are
+//     written out once, in feed_open and feed_close: the copy stream waits for the producer's event, for a grown buffer's move
+//     (ev_grow) and for round R - 2 (ev_round[R & 1]); round R waits for the copy stream (ev_copy).  Pieces of one call need
+//     no events between them: the uploads into the landing buffer and the mixers that read it are all on the copy stream.
+//   * A pinned staging slot is written by the host again only once the upload that read it last is done (stage_upload).
+// Host and device sources make the same launches on the same data -- a host piece is the device piece with the landing buffer as
+// its source -- and an integer call makes the launches of the f32 call of the same length (the raw integers take the front of each
+// staging and landing lane; the mixers convert them in registers, sample_int.h), so the same calls give the same bits on every route.
+
+// one stream of a staged upload: `bytes` from host memory at src, through the slot at float offset `off`, to device memory at dst
+struct Lane {
+    const void *src;
+    size_t bytes, off;
+    void *dst;
+};
+
+// Take the next pinned staging slot (waiting for the upload that read it last), fill its lanes and send them up on `stream`.
+// threaded: copy with psdrt::pinned_copy, which splits a large copy over a few threads (the frames path).
+int stage_upload(XObj *h, hipStream_t stream, const Lane *lanes, uint32_t n, bool threaded = false)
+{
+    const int slot = h->stage_cur;
+    if (h->ev_pending[slot])
+        XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
+    for (uint32_t i = 0; i < n; ++i) {
+        float *stg = h->h_stage[slot] + lanes[i].off;
+        if (threaded)
+            psdrt::pinned_copy(stg, lanes[i].src, lanes[i].bytes);
+        else
+            memcpy(stg, lanes[i].src, lanes[i].bytes);
+        XCHK(h, hipMemcpyAsync(lanes[i].dst, stg, lanes[i].bytes, hipMemcpyHostToDevice, stream));
+    }
+    XCHK(h, hipEventRecord(h->stage_ev[slot], stream));
+    h->ev_pending[slot] = true;
+    h->stage_cur ^= 1;
+    return PSDC_OK;
+}
+
+// Open the copy stream for what round R = h->rounds will read.  The caller has cleared h->grew and made room in stage 0
+// (stage0_room) for every unit it feeds.
+int feed_open(XObj *h, void *producer_event)
+{
+    if (producer_event)
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
+    if (h->grew) { // the held samples move to the new buffers on the compute stream: the copy stream goes behind them
+        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
+    }
+    const int slot = (int)(h->rounds & 1); // round R - 2
+    if (h->round_recorded[slot])
+        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
+    return PSDC_OK;
+}
+
+// The copy stream's work is enqueued and the caller has counted the samples in: round R goes behind it.
+int feed_close(XObj *h)
+{
+    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
+    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
+    h->idle = false;
+    bool did = false;
+    return run_round(h, &did);
+}
+
 // ---- frames (psdc_csd_process_frames[_device]) ----
 
 struct FedPair {
@@ -721,7 +788,7 @@ struct FedPair {
 int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair> *fed)
 {
     if (!map)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null " + h->unit + " map");
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null " + h->kind->unit + " map");
     fed->clear();
     const uint32_t w = h->map_w();
     for (uint32_t p = 0; p < h->n_pairs; ++p) {
@@ -738,16 +805,16 @@ int read_map(XObj *h, const uint32_t *map, const char *who, std::vector<FedPair>
         if (none == w)
             continue;
         if (none)
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) +
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->kind->unit + " " + std::to_string(p) +
                                               (w == 2 ? " names one trace and PSDC_TRACE_NONE"
                                                          : " names PSDC_TRACE_NONE for some of its traces only"));
         if (top >= 4)
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(p) + " names trace " +
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->kind->unit + " " + std::to_string(p) + " names trace " +
                                               std::to_string(top) + " (frames carry at most 4)");
         fed->push_back(fp);
     }
-    if (h->zoom && fed->empty()) // (a pair object takes such a call for its Loss)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the map feeds no " + h->unit);
+    if (h->mixed() && fed->empty()) // (a pair object takes such a call for its Loss)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the map feeds no " + h->kind->unit);
     return PSDC_OK;
 }
 
@@ -772,15 +839,10 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
                     // both are on the copy stream)
         if (!h->d_frames)
             XCHK(h, hipMalloc(&h->d_frames, h->frames_chunk()));
-        const int slot = h->stage_cur;
-        if (h->ev_pending[slot])
-            XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-        uint8_t *stg = reinterpret_cast<uint8_t *>(h->h_stage[slot]);
-        psdrt::pinned_copy(stg, src.host + f * frame_size, cnt * frame_size);
-        XCHK(h, hipMemcpyAsync(h->d_frames, stg, cnt * frame_size, hipMemcpyHostToDevice, h->copy_stream));
-        XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
-        h->ev_pending[slot] = true;
-        h->stage_cur ^= 1;
+        const Lane up{src.host + f * frame_size, cnt * frame_size, 0, h->d_frames};
+        int rc = stage_upload(h, h->copy_stream, &up, 1, true);
+        if (rc)
+            return rc;
         frames = h->d_frames;
     }
     // what both kinds of launch say about the frames
@@ -791,7 +853,9 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
         b->batches = batches;
         b->fmt = wf->id;
     };
-    if (h->zcross && h->iq) {
+    const Feed feed = h->kind->feed;
+    const bool two_sided = h->mixed() && h->m == 4; // two channels a unit
+    if (two_sided && feed == Feed::IQ) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += IQ_CROSS_FRAMES_MAX_PAIRS) {
             IqCrossFramesBatch b{};
             describe(&b);
@@ -810,7 +874,7 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
             XCHK(h, launch_iq_cross_frames(b, h->copy_stream));
             ++h->launches;
         }
-    } else if (h->zcross) {
+    } else if (two_sided) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_CROSS_FRAMES_MAX_PAIRS) {
             ZoomCrossFramesBatch b{};
             describe(&b);
@@ -828,7 +892,7 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
             XCHK(h, launch_zoom_cross_frames(b, h->copy_stream));
             ++h->launches;
         }
-    } else if (h->iq) {
+    } else if (feed == Feed::IQ) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_FRAMES_MAX_CH) {
             IqFramesBatch b{};
             describe(&b);
@@ -845,7 +909,7 @@ int decode_frames(XObj *h, const FrameSrc &src, size_t frame_size, const WireFmt
             XCHK(h, launch_iq_frames(b, h->copy_stream));
             ++h->launches;
         }
-    } else if (h->zoom) {
+    } else if (feed == Feed::ZOOM) {
         for (size_t i0 = 0; i0 < fed.size(); i0 += ZOOM_FRAMES_MAX_CH) {
             ZoomFramesBatch b{};
             describe(&b);
@@ -898,7 +962,7 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
         for (const FedPair &fp : fed) {
             const uint32_t top = *std::max_element(fp.tr, fp.tr + h->map_w());
             if ((int)top >= wf->ntraces)
-                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->unit + " " + std::to_string(fp.pair) + " names trace " +
+                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": " + h->kind->unit + " " + std::to_string(fp.pair) + " names trace " +
                                                   std::to_string(top) + " but " + wf->name + " frames carry " +
                                                   std::to_string(wf->ntraces) + " (frame " + std::to_string(f0) + ")");
         }
@@ -924,33 +988,23 @@ int ingest_frames(XObj *h, const std::vector<FedPair> &fed, const FrameSrc &src,
                     for (uint32_t c = 0; c < h->m; ++c)
                         dst[h->m * i + c] = s->buf.p[c][s->buf.cur] + (s->total - s->buf.base);
                 }
-                // the same order as psdc_cross_process_device's copies: behind a buffer's growth and round R - 2, before round R
-                if (h->grew) {
-                    XCHK(h, hipEventRecord(h->ev_grow, h->stream));
-                    XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
-                }
-                const int slot = (int)(h->rounds & 1);
-                if (h->round_recorded[slot])
-                    XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
+                int rc = feed_open(h, nullptr); // (a device call's producer has been waited for: frames_device_impl)
+                if (rc)
+                    return rc;
                 const size_t chunk = src.dev ? cnt : std::max<size_t>(1, h->frames_chunk() / frame_size);
                 for (size_t c0 = 0; c0 < cnt; c0 += chunk) {
-                    int rc = decode_frames(h, src, frame_size, wf, batches, f0 + c0, std::min(chunk, cnt - c0), fed, dst,
+                    rc = decode_frames(h, src, frame_size, wf, batches, f0 + c0, std::min(chunk, cnt - c0), fed, dst,
                                            c0 * per_frame);
                     if (rc)
                         return rc;
                 }
-                XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
-                XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
                 for (const FedPair &fp : fed) {
                     h->pairs[fp.pair][0].total += per_ch;
                     h->pairs_in += per_ch;
                 }
-                h->idle = false;
                 h->loss = trial; // the piece is in the streams: its frames count from here on
                 good += cnt;
-                bool did = false;
-                int rc = run_round(h, &did);
-                if (rc)
+                if ((rc = feed_close(h)))
                     return rc;
             } else { // header-only frames, or no pair fed: Loss only
                 h->loss = trial;
@@ -1016,26 +1070,29 @@ void destroy_impl(XObj *h)
         (void)hipStreamDestroy(h->stream);
 }
 
-template <class T>
-T *create_kind(uint32_t n, int window_kind, uint32_t m, uint32_t n_pairs, int device, const char *who)
+XObj *create_kind(const KindDesc &kind, uint32_t n, int window_kind, uint32_t n_pairs, int device, const char *who, uint32_t m = 0)
 {
-    constexpr bool matrix = std::is_same<T, psdc_csm>::value;
     psdrt::WindowConsts wc{};
-    if (window_kind == PSDC_WINDOW_CUSTOM || !psdrt::window_consts(n, window_kind, &wc)) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": window_kind must be PSDC_WINDOW_HANN or PSDC_WINDOW_RECTANGULAR");
-        return nullptr;
-    }
-    if (matrix && !csm_supported((int)n, (int)m)) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + csm_size_text(n, m));
-        return nullptr;
-    }
-    if (n < 64 || n > 4096 || (n & (n - 1)) != 0) {
-        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": n must be a power of two in [64, 4096]");
+    std::string why = kind.refusal ? kind.refusal(n, m) : ""; // (before the window: a refused size names itself)
+    if (why.empty() && (window_kind == PSDC_WINDOW_CUSTOM || !psdrt::window_consts(n, window_kind, &wc)))
+        why = "window_kind must be PSDC_WINDOW_HANN or PSDC_WINDOW_RECTANGULAR";
+    if (why.empty() && (n < 64 || n > 4096 || (n & (n - 1)) != 0))
+        why = "n must be a power of two in [64, 4096]";
+    if (!why.empty()) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + why);
         return nullptr;
     }
     std::vector<float> win(n);
     psdrt::window_weights(n, window_kind, win.data());
-    return create_impl<T>(n, win.data(), wc.power, wc.nenbw, wc.overlap, m, n_pairs, device, who);
+    return create_impl(kind, n, win.data(), wc.power, wc.nenbw, wc.overlap, n_pairs, device, who, m);
+}
+
+void destroy_obj(XObj *h)
+{
+    if (!h)
+        return;
+    destroy_impl(h);
+    delete h;
 }
 
 int reset_impl(XObj *h, const char *who)
@@ -1139,11 +1196,10 @@ int convert_piece(XObj *h, XStage *s, const void *const *src, const SampleFmt &f
     return PSDC_OK;
 }
 
-// x: h->m pointers (host memory).  fmt: f32 (psdc_cross_process, psdc_csm_process), or integers (psdc_sint_*): the raw integers
-// go up through the front of each staging lane into the front of each landing lane, in the f32 call's pieces, and one converter a
-// piece writes the bytes the f32 call's copies write -- so run_round sees the same streams and gives the same bits.
-int process_impl(XObj *h, uint32_t pair, const void *const *x, SampleFmt fmt, size_t len, const char *who)
+// the checks the two feeds of the objects without a mixer begin with; *go: there are samples to take
+int plain_args(XObj *h, uint32_t pair, const void *const *x, const SampleFmt &fmt, size_t len, const char *who, bool *go)
 {
+    *go = false;
     X_HANDLE(h, who);
     const bool ints = fmt.kind != SAMPLE_F32;
     int rc = check_pair(h, pair, ints ? who : nullptr);
@@ -1161,36 +1217,42 @@ int process_impl(XObj *h, uint32_t pair, const void *const *x, SampleFmt fmt, si
             if (!x || !x[c])
                 return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
     }
+    *go = true;
+    return PSDC_OK;
+}
+
+// x: h->m pointers (host memory).  fmt: f32 (psdc_cross_process, psdc_csm_process), or integers (psdc_sint_*): the raw integers
+// go up into the landing lanes and one converter a piece writes the bytes the f32 call's uploads write.
+int process_impl(XObj *h, uint32_t pair, const void *const *x, SampleFmt fmt, size_t len, const char *who)
+{
+    bool go = false;
+    int rc = plain_args(h, pair, x, fmt, len, who, &go);
+    if (rc || !go)
+        return rc;
+    const bool ints = fmt.kind != SAMPLE_F32;
     X_ON_DEVICE(h);
     if (ints && !h->d_land)
-        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * h->m * STAGING));
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * h->lanes() * STAGING));
     XStage *s = nullptr;
     if ((rc = stage0_room(h, pair, len, &s)))
         return rc;
     const size_t unit = fmt.bytes();
     for (size_t done = 0; done < len;) {
-        const size_t m = std::min(STAGING, len - done);
-        const int slot = h->stage_cur;
-        if (h->ev_pending[slot])
-            XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-        float *stg = h->h_stage[slot];
-        for (uint32_t c = 0; c < h->m; ++c)
-            memcpy(stg + c * STAGING, static_cast<const uint8_t *>(x[c]) + unit * done, unit * m);
+        const size_t cnt = std::min(STAGING, len - done);
         const size_t at = (size_t)(s->total + done - s->buf.base);
-        for (uint32_t c = 0; c < h->m; ++c)
-            XCHK(h, hipMemcpyAsync(ints ? h->d_land + c * STAGING : s->buf.p[c][s->buf.cur] + at, stg + c * STAGING, unit * m,
-                                   hipMemcpyHostToDevice, h->stream));
-        XCHK(h, hipEventRecord(h->stage_ev[slot], h->stream));
-        h->ev_pending[slot] = true;
-        h->stage_cur ^= 1;
-        if (ints) { // (the next piece's copies into the landing lanes run behind it: one stream)
-            const void *from[CSM_MAX_M] = {};
-            for (uint32_t c = 0; c < h->m; ++c)
-                from[c] = h->d_land + c * STAGING;
-            if ((rc = convert_piece(h, s, from, fmt, at, m, h->stream)))
-                return rc;
+        Lane up[CSM_MAX_M];
+        const void *from[CSM_MAX_M] = {};
+        for (uint32_t c = 0; c < h->m; ++c) {
+            float *land = ints ? h->d_land + c * STAGING : nullptr;
+            from[c] = land;
+            up[c] = {static_cast<const uint8_t *>(x[c]) + unit * done, unit * cnt, c * STAGING, ints ? land : s->buf.p[c][s->buf.cur] + at};
         }
-        done += m;
+        if ((rc = stage_upload(h, h->stream, up, h->m)))
+            return rc;
+        // (the next piece's uploads into the landing lanes run behind the converter: one stream)
+        if (ints && (rc = convert_piece(h, s, from, fmt, at, cnt, h->stream)))
+            return rc;
+        done += cnt;
     }
     s->total += len;
     h->pairs_in += len;
@@ -1200,338 +1262,204 @@ int process_impl(XObj *h, uint32_t pair, const void *const *x, SampleFmt fmt, si
 }
 
 // d_x: h->m device pointers (the array itself is host memory).  fmt as in process_impl: an integer call has ONE converter launch
-// on the copy stream where the f32 call has its m copies, under the same event rules.
+// where the f32 call has its m copies.
 int process_device_impl(XObj *h, uint32_t pair, const void *const *d_x, SampleFmt fmt, size_t len, void *producer_event, const char *who)
 {
-    X_HANDLE(h, who);
-    const bool ints = fmt.kind != SAMPLE_F32;
-    int rc = check_pair(h, pair, ints ? who : nullptr);
-    if (rc)
+    bool go = false;
+    int rc = plain_args(h, pair, d_x, fmt, len, who, &go);
+    if (rc || !go)
         return rc;
-    if (ints && (rc = check_fmt(h, fmt, who)))
-        return rc;
-    if (len == 0)
-        return PSDC_OK;
-    if (ints) {
-        if ((rc = check_int_ptrs(h, d_x, fmt, who)))
-            return rc;
-    } else {
-        for (uint32_t c = 0; c < h->m; ++c)
-            if (!d_x || !d_x[c])
-                return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-    }
     X_ON_DEVICE(h);
-    if (producer_event)
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
     XStage *s = nullptr;
     h->grew = false;
-    if ((rc = stage0_room(h, pair, len, &s)))
+    if ((rc = stage0_room(h, pair, len, &s)) || (rc = feed_open(h, producer_event)))
         return rc;
-    if (h->grew) { // the held samples move to the new buffers on the compute stream: the copy goes behind them
-        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
-    }
-    const int slot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
-    if (h->round_recorded[slot])
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[slot], 0));
     const size_t at = (size_t)(s->total - s->buf.base);
-    if (ints) {
+    if (fmt.kind != SAMPLE_F32) {
         if ((rc = convert_piece(h, s, d_x, fmt, at, len, h->copy_stream)))
             return rc;
     } else {
         for (uint32_t c = 0; c < h->m; ++c)
             XCHK(h, hipMemcpyAsync(s->buf.p[c][s->buf.cur] + at, d_x[c], sizeof(float) * len, hipMemcpyDeviceToDevice, h->copy_stream));
     }
-    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
-    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
     s->total += len;
     h->pairs_in += len;
-    h->idle = false;
-    bool did = false;
-    return run_round(h, &did);
+    return feed_close(h);
 }
 
-// A zoom unit takes len real samples of each of its reals() channels (xs: that many pointers), from host memory (dev == false: up through the pinned staging into the landing buffer,
-// as host frames go) or from device memory.  The mixer stands where psdc_cross_process_device has its copies and under the same
-// event rules: on the copy stream, behind a buffer's growth and round R - 2, and round R waits for it.  Both sources make the
-// same launches on the same data, so the same calls give the same bits from either.
-// fmt: f32 samples, or integers (psdc_int_*: sample_int.h) -- the raw integers take the f32 samples' way (the front of each
-// staging lane and landing lane, pieces of STAGING samples) and the integer mixer converts them in registers, so an integer
-// call makes the launches of the f32 call of the same length.
-int zoom_feed(XObj *h, uint32_t ch, const void *const *xs, SampleFmt fmt, size_t len, bool dev, void *producer_event, const char *who)
+// The sources of a mixer feed: src[c] (NULL: none) starts in staging / landing lane c, and `unit` bytes of it are one stream sample.
+//   zoom (reals() real channels): src[0 .. reals() - 1], unit = one number
+//   IQ planar: src[0] = I, src[1] = Q, unit = 4;  IQ interleaved: src[0] = the (re, im) pairs, unit = two numbers
+//   IQ pair planar: src[0 .. 3] = I_a, Q_a, I_b, Q_b;  interleaved: src[0], src[2] = the pairs of side a, b (over lanes 0-1, 2-3)
+struct MixSrc {
+    const void *src[CSM_MAX_M];
+    size_t unit;
+};
+
+// A mixer-fronted unit takes len samples of each source, from host memory (up through the pinned staging into the landing buffer,
+// pieces of STAGING samples) or from device memory (one piece).  mix(from, dst, j0, cnt) launches the family's mixer(s) for one
+// piece on the copy stream: cnt samples of source c at from[c], to the unit's stream c at dst[c]; the first is stream sample j0
+// (the samples the unit has taken since create or reset).
+template <class Mix>
+int mixer_feed(XObj *h, uint32_t unit, size_t len, bool dev, void *producer_event, const MixSrc &in, Mix mix)
 {
+    X_ON_DEVICE(h);
+    if (!dev && !h->d_land)
+        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * h->lanes() * STAGING));
+    XStage *s = nullptr;
+    h->grew = false;
+    int rc = stage0_room(h, unit, len, &s);
+    if (rc || (rc = feed_open(h, producer_event)))
+        return rc;
+    const size_t piece = dev ? len : STAGING;
+    for (size_t done = 0; done < len;) {
+        const size_t cnt = std::min(piece, len - done);
+        const void *from[CSM_MAX_M] = {};
+        Lane up[CSM_MAX_M];
+        uint32_t n_up = 0;
+        for (uint32_t c = 0; c < CSM_MAX_M; ++c) {
+            if (!in.src[c])
+                continue;
+            from[c] = static_cast<const uint8_t *>(in.src[c]) + in.unit * done;
+            if (!dev) { // through lane c of the slot into lane c of the landing buffer, which the mixer then reads
+                up[n_up++] = {from[c], in.unit * cnt, c * STAGING, h->d_land + c * STAGING};
+                from[c] = h->d_land + c * STAGING;
+            }
+        }
+        if (!dev && (rc = stage_upload(h, h->copy_stream, up, n_up)))
+            return rc;
+        float *dst[CSM_MAX_M] = {};
+        for (uint32_t c = 0; c < h->m; ++c)
+            dst[c] = s->buf.p[c][s->buf.cur] + (size_t)(s->total + done - s->buf.base);
+        if ((rc = mix(from, dst, s->total + done, cnt)))
+            return rc;
+        done += cnt;
+    }
+    s->total += len;
+    h->pairs_in += len;
+    return feed_close(h);
+}
+
+// the checks every mixer feed begins with; *go: there are samples to take
+int mixer_args(XObj *h, uint32_t unit, const SampleFmt &fmt, size_t len, const char *who, bool *go)
+{
+    *go = false;
     X_HANDLE(h, who);
-    int rc = check_pair(h, ch, fmt.kind == SAMPLE_F32 ? nullptr : who);
+    int rc = check_pair(h, unit, fmt.kind == SAMPLE_F32 ? nullptr : who);
     if (rc)
         return rc;
     if ((rc = check_fmt(h, fmt, who)))
         return rc;
-    if (len == 0)
-        return PSDC_OK;
+    *go = len != 0;
+    return PSDC_OK;
+}
+
+// A zoom unit: len real samples of each of its reals() channels (xs: that many pointers), f32 or integers; one mixer a channel.
+int zoom_feed(XObj *h, uint32_t ch, const void *const *xs, SampleFmt fmt, size_t len, bool dev, void *producer_event, const char *who)
+{
+    bool go = false;
+    int rc = mixer_args(h, ch, fmt, len, who, &go);
+    if (rc || !go)
+        return rc;
     const uint32_t nx = h->reals();
-    const size_t unit = fmt.bytes(); // of one sample
+    MixSrc in{{}, fmt.bytes()};
     for (uint32_t c = 0; c < nx; ++c) {
         if (!xs[c])
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-        if ((uintptr_t)xs[c] % unit)
-            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to " + std::to_string(unit) + " bytes");
+        if ((uintptr_t)xs[c] % in.unit)
+            return xfail(h, PSDC_ERR_ARG, std::string(who) + ": the samples are not aligned to " + std::to_string(in.unit) + " bytes");
+        in.src[c] = xs[c];
     }
-    X_ON_DEVICE(h);
-    if (producer_event)
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
-    if (!dev && !h->d_land)
-        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * nx * STAGING));
-    XStage *s = nullptr;
-    h->grew = false;
-    if ((rc = stage0_room(h, ch, len, &s)))
-        return rc;
-    if (h->grew) {
-        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
-    }
-    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
-    if (h->round_recorded[rslot])
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
-    const size_t piece = dev ? len : STAGING;
-    for (size_t done = 0; done < len;) {
-        const size_t cnt = std::min(piece, len - done);
-        if (!dev) { // (the mixers of the piece before have read the landing buffer: all are on the copy stream)
-            const int slot = h->stage_cur;
-            if (h->ev_pending[slot])
-                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-            for (uint32_t c = 0; c < nx; ++c) {
-                memcpy(h->h_stage[slot] + c * STAGING, static_cast<const uint8_t *>(xs[c]) + unit * done, unit * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, h->h_stage[slot] + c * STAGING, unit * cnt,
-                                       hipMemcpyHostToDevice, h->copy_stream));
-            }
-            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
-            h->ev_pending[slot] = true;
-            h->stage_cur ^= 1;
-        }
-        const size_t at = (size_t)(s->total + done - s->buf.base);
-        for (uint32_t c = 0; c < nx; ++c) { // one mixer a channel
-            const void *src = dev ? static_cast<const void *>(static_cast<const uint8_t *>(xs[c]) + unit * done) : h->d_land + c * STAGING;
-            float *dst_i = s->buf.p[2 * c][s->buf.cur] + at, *dst_q = s->buf.p[2 * c + 1][s->buf.cur] + at;
-            const uint64_t j0 = s->total + done; // the stream index: samples the channel has taken since create or reset
+    return mixer_feed(h, ch, len, dev, producer_event, in, [&](const void *const *from, float *const *dst, uint64_t j0, size_t cnt) -> int {
+        for (uint32_t c = 0; c < nx; ++c) {
             const uint64_t ftw = h->ftw[(size_t)nx * ch + c], phase0 = h->phase0[(size_t)nx * ch + c];
             if (fmt.kind == SAMPLE_F32) {
-                const ZoomMixJob mj{static_cast<const float *>(src), dst_i, dst_q, cnt, j0, ftw, phase0};
+                const ZoomMixJob mj{static_cast<const float *>(from[c]), dst[2 * c], dst[2 * c + 1], cnt, j0, ftw, phase0};
                 XCHK(h, launch_zoom_mix(mj, h->copy_stream));
             } else {
-                const SintMixJob mj{src, dst_i, dst_q, cnt, j0, ftw, phase0, fmt.scale};
+                const SintMixJob mj{from[c], dst[2 * c], dst[2 * c + 1], cnt, j0, ftw, phase0, fmt.scale};
                 XCHK(h, launch_zoom_mix_int(mj, fmt.kind, h->copy_stream));
             }
             ++h->launches;
         }
-        done += cnt;
-    }
-    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
-    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-    s->total += len;
-    h->pairs_in += len;
-    h->idle = false;
-    bool did = false;
-    return run_round(h, &did);
+        return PSDC_OK;
+    });
 }
 
-// An IQ channel takes len complex samples: planar (src_q != NULL: two f32 streams, each 4-byte aligned) or interleaved (src_q ==
-// NULL: src_i points to (re, im) pairs, 8-byte aligned), from host memory (up through the pinned staging into the landing buffer)
-// or from device memory.  zoom_feed with the complex mixer in place of the real one: the same stream, the same events, and the
-// same launches on the same data from either memory, so all four routes give the same bits for the same calls.
-// fmt: f32, or integers (psdc_int_*: always interleaved, src_i points to the (re, im) integer pairs) as in zoom_feed.
-int iq_feed(XObj *h, uint32_t ch, const void *src_i_, const float *src_q, bool interleaved, SampleFmt fmt, size_t len, bool dev,
-            void *producer_event, const char *who)
+// the pointers of a complex feed: planar (every one of the n f32 streams 4-byte aligned) or interleaved ((re, im) pairs at the
+// even ones, aligned to a pair; integers are always interleaved)
+int check_iq_ptrs(XObj *h, const void *const *src, uint32_t n, bool interleaved, size_t unit, const char *who)
 {
-    X_HANDLE(h, who);
-    int rc = check_pair(h, ch, fmt.kind == SAMPLE_F32 ? nullptr : who);
-    if (rc)
-        return rc;
-    if ((rc = check_fmt(h, fmt, who)))
-        return rc;
-    if (len == 0)
-        return PSDC_OK;
-    const float *src_i = static_cast<const float *>(src_i_); // (f32 only)
-    const size_t unit = 2 * fmt.bytes();                     // of one interleaved complex sample
-    if (!src_i_ || (!interleaved && !src_q))
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
-    if (interleaved ? (uintptr_t)src_i_ % unit != 0 : (uintptr_t)src_i % sizeof(float) != 0 || (uintptr_t)src_q % sizeof(float) != 0)
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to " + std::to_string(unit) + " bytes"
-                                                                      : std::string(": the samples are not aligned to 4 bytes")));
-    X_ON_DEVICE(h);
-    if (producer_event)
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
-    if (!dev && !h->d_land)
-        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * 2 * STAGING));
-    XStage *s = nullptr;
-    h->grew = false;
-    if ((rc = stage0_room(h, ch, len, &s)))
-        return rc;
-    if (h->grew) {
-        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
-    }
-    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
-    if (h->round_recorded[rslot])
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
-    const size_t piece = dev ? len : STAGING;
-    for (size_t done = 0; done < len;) {
-        const size_t cnt = std::min(piece, len - done);
-        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
-            const int slot = h->stage_cur;
-            if (h->ev_pending[slot])
-                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-            float *stg = h->h_stage[slot];
-            if (interleaved) { // the pairs as they are: cnt units at the front of the slot and of the landing buffer
-                memcpy(stg, static_cast<const uint8_t *>(src_i_) + unit * done, unit * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land, stg, unit * cnt, hipMemcpyHostToDevice, h->copy_stream));
-            } else {
-                memcpy(stg, src_i + done, sizeof(float) * cnt);
-                memcpy(stg + STAGING, src_q + done, sizeof(float) * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land, stg, sizeof(float) * cnt, hipMemcpyHostToDevice, h->copy_stream));
-                XCHK(h, hipMemcpyAsync(h->d_land + STAGING, stg + STAGING, sizeof(float) * cnt, hipMemcpyHostToDevice,
-                                       h->copy_stream));
-            }
-            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
-            h->ev_pending[slot] = true;
-            h->stage_cur ^= 1;
-        }
-        const size_t at = (size_t)(s->total + done - s->buf.base);
-        if (fmt.kind != SAMPLE_F32) {
-            const void *src = dev ? static_cast<const void *>(static_cast<const uint8_t *>(src_i_) + unit * done) : h->d_land;
-            const SintMixJob ij{src, s->buf.p[0][s->buf.cur] + at, s->buf.p[1][s->buf.cur] + at, cnt, s->total + done, h->ftw[ch],
-                                h->phase0[ch], fmt.scale};
-            XCHK(h, launch_iq_mix_int(ij, fmt.kind, h->copy_stream));
-            ++h->launches;
-            done += cnt;
-            continue;
-        }
-        IqMixJob mj{};
-        if (interleaved) {
-            mj.src_i = dev ? src_i + 2 * done : h->d_land;
-        } else {
-            mj.src_i = dev ? src_i + done : h->d_land;
-            mj.src_q = dev ? src_q + done : h->d_land + STAGING;
-        }
-        mj.dst_i = s->buf.p[0][s->buf.cur] + at;
-        mj.dst_q = s->buf.p[1][s->buf.cur] + at;
-        mj.len = cnt;
-        mj.j0 = s->total + done; // the stream index: complex samples the channel has taken since create or reset
-        mj.ftw = h->ftw[ch];
-        mj.phase0 = h->phase0[ch];
-        XCHK(h, launch_iq_mix(mj, interleaved, h->copy_stream));
-        ++h->launches;
-        done += cnt;
-    }
-    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
-    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-    s->total += len;
-    h->pairs_in += len;
-    h->idle = false;
-    bool did = false;
-    return run_round(h, &did);
-}
-
-// An IQ cross pair takes len complex samples of each side: planar (src: I_a, Q_a, I_b, Q_b, four f32 streams, each 4-byte
-// aligned) or interleaved (src[0], src[2]: the (re, im) pairs of side a and side b, 8-byte aligned; src[1], src[3] unused), from
-// host memory (up through the pinned staging into the landing buffer) or from device memory.  iq_feed with the pair mixer in place
-// of the complex one: the same stream, the same events, ONE mixer launch a piece for both sides, and the same launches on the same
-// data from either memory, so all four routes give the same bits for the same calls.
-// fmt: f32, or integers (psdc_int_*: always interleaved, src[0] and src[2] point to the sides' (re, im) integer pairs) as in
-// zoom_feed.
-int iq_pair_feed(XObj *h, uint32_t pair, const void *const (&src)[4], bool interleaved, SampleFmt fmt, size_t len, bool dev,
-                 void *producer_event, const char *who)
-{
-    X_HANDLE(h, who);
-    int rc = check_pair(h, pair, fmt.kind == SAMPLE_F32 ? nullptr : who);
-    if (rc)
-        return rc;
-    if ((rc = check_fmt(h, fmt, who)))
-        return rc;
-    if (len == 0)
-        return PSDC_OK;
-    const size_t unit = (interleaved ? 2 : 1) * fmt.bytes(); // of one sample of a stream: a pair, or one f32
-    for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
+    for (uint32_t c = 0; c < n; c += interleaved ? 2 : 1) {
         if (!src[c])
             return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
         if ((uintptr_t)src[c] % unit != 0)
             return xfail(h, PSDC_ERR_ARG, std::string(who) + (interleaved ? ": the (re, im) pairs are not aligned to " + std::to_string(unit) + " bytes"
                                                                           : std::string(": the samples are not aligned to 4 bytes")));
     }
-    X_ON_DEVICE(h);
-    if (producer_event)
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, (hipEvent_t)producer_event, 0));
-    if (!dev && !h->d_land)
-        XCHK(h, hipMalloc(&h->d_land, sizeof(float) * 4 * STAGING));
-    XStage *s = nullptr;
-    h->grew = false;
-    if ((rc = stage0_room(h, pair, len, &s)))
+    return PSDC_OK;
+}
+
+// An IQ channel: len complex samples, planar (src_q != NULL) or interleaved (src_q == NULL: src_i points to the pairs); one mixer.
+int iq_feed(XObj *h, uint32_t ch, const void *src_i, const float *src_q, bool interleaved, SampleFmt fmt, size_t len, bool dev,
+            void *producer_event, const char *who)
+{
+    bool go = false;
+    int rc = mixer_args(h, ch, fmt, len, who, &go);
+    if (rc || !go)
         return rc;
-    if (h->grew) {
-        XCHK(h, hipEventRecord(h->ev_grow, h->stream));
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_grow, 0));
-    }
-    const int rslot = (int)(h->rounds & 1); // round R - 2 (the round about to run is R = h->rounds)
-    if (h->round_recorded[rslot])
-        XCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_round[rslot], 0));
-    const size_t piece = dev ? len : STAGING;
-    for (size_t done = 0; done < len;) {
-        const size_t cnt = std::min(piece, len - done);
-        if (!dev) { // (the mixer of the piece before has read the landing buffer: both are on the copy stream)
-            const int slot = h->stage_cur;
-            if (h->ev_pending[slot])
-                XCHK(h, hipEventSynchronize(h->stage_ev[slot]));
-            float *stg = h->h_stage[slot];
-            // planar: stream c in lane c; interleaved: side a's pairs in lanes 0 and 1, side b's in lanes 2 and 3, as they are
-            for (int c = 0; c < 4; c += interleaved ? 2 : 1) {
-                memcpy(stg + c * STAGING, static_cast<const uint8_t *>(src[c]) + unit * done, unit * cnt);
-                XCHK(h, hipMemcpyAsync(h->d_land + c * STAGING, stg + c * STAGING, unit * cnt, hipMemcpyHostToDevice, h->copy_stream));
-            }
-            XCHK(h, hipEventRecord(h->stage_ev[slot], h->copy_stream));
-            h->ev_pending[slot] = true;
-            h->stage_cur ^= 1;
-        }
-        const size_t at = (size_t)(s->total + done - s->buf.base);
-        const void *from[4] = {};
-        for (int c = 0; c < 4; c += interleaved ? 2 : 1)
-            from[c] = dev ? static_cast<const void *>(static_cast<const uint8_t *>(src[c]) + unit * done) : h->d_land + c * STAGING;
-        const uint64_t j0 = s->total + done; // the stream index: complex samples each side has taken since create or reset
+    const MixSrc in{{src_i, interleaved ? nullptr : src_q}, (interleaved ? 2 : 1) * fmt.bytes()};
+    if (!src_i || (!interleaved && !src_q))
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null sample pointer");
+    if ((rc = check_iq_ptrs(h, in.src, 2, interleaved, in.unit, who)))
+        return rc;
+    return mixer_feed(h, ch, len, dev, producer_event, in, [&](const void *const *from, float *const *dst, uint64_t j0, size_t cnt) -> int {
         if (fmt.kind == SAMPLE_F32) {
-            IqPairMixJob mj{};
-            for (int c = 0; c < 4; ++c) {
-                mj.src[c] = static_cast<const float *>(from[c]);
-                mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
-            }
-            mj.len = cnt;
-            mj.j0 = j0;
-            for (int side = 0; side < 2; ++side) {
-                mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
-                mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
-            }
-            XCHK(h, launch_iq_pair_mix(mj, interleaved, h->copy_stream));
+            const IqMixJob mj{static_cast<const float *>(from[0]), static_cast<const float *>(from[1]), dst[0], dst[1], cnt, j0, h->ftw[ch],
+                              h->phase0[ch]};
+            XCHK(h, launch_iq_mix(mj, interleaved, h->copy_stream));
         } else {
-            SintPairMixJob mj{};
-            for (int c = 0; c < 4; ++c)
-                mj.dst[c] = s->buf.p[c][s->buf.cur] + at;
-            mj.len = cnt;
-            mj.j0 = j0;
-            mj.scale = fmt.scale;
-            for (int side = 0; side < 2; ++side) {
-                mj.src[side] = from[2 * side];
-                mj.ftw[side] = h->ftw[2 * (size_t)pair + side];
-                mj.phase0[side] = h->phase0[2 * (size_t)pair + side];
-            }
-            XCHK(h, launch_iq_pair_mix_int(mj, fmt.kind, h->copy_stream));
+            const SintMixJob mj{from[0], dst[0], dst[1], cnt, j0, h->ftw[ch], h->phase0[ch], fmt.scale};
+            XCHK(h, launch_iq_mix_int(mj, fmt.kind, h->copy_stream));
         }
         ++h->launches;
-        done += cnt;
-    }
-    XCHK(h, hipEventRecord(h->ev_copy, h->copy_stream));
-    XCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-    s->total += len;
-    h->pairs_in += len;
-    h->idle = false;
-    bool did = false;
-    return run_round(h, &did);
+        return PSDC_OK;
+    });
+}
+
+// An IQ cross pair: len complex samples of each side, planar (src: I_a, Q_a, I_b, Q_b) or interleaved (src[0], src[2]: the pairs
+// of side a and side b; src[1], src[3] unused); ONE mixer launch a piece for both sides.
+int iq_pair_feed(XObj *h, uint32_t pair, const void *const (&src)[4], bool interleaved, SampleFmt fmt, size_t len, bool dev,
+                 void *producer_event, const char *who)
+{
+    bool go = false;
+    int rc = mixer_args(h, pair, fmt, len, who, &go);
+    if (rc || !go)
+        return rc;
+    MixSrc in{{}, (interleaved ? 2 : 1) * fmt.bytes()};
+    if ((rc = check_iq_ptrs(h, src, 4, interleaved, in.unit, who)))
+        return rc;
+    for (int c = 0; c < 4; c += interleaved ? 2 : 1)
+        in.src[c] = src[c];
+    return mixer_feed(h, pair, len, dev, producer_event, in, [&](const void *const *from, float *const *dst, uint64_t j0, size_t cnt) -> int {
+        IqPairMixJob mj{};
+        SintPairMixJob ij{};
+        for (int c = 0; c < 4; ++c) {
+            mj.src[c] = static_cast<const float *>(from[c]);
+            mj.dst[c] = ij.dst[c] = dst[c];
+        }
+        mj.len = ij.len = cnt;
+        mj.j0 = ij.j0 = j0;
+        ij.scale = fmt.scale;
+        for (int side = 0; side < 2; ++side) {
+            ij.src[side] = from[2 * side];
+            mj.ftw[side] = ij.ftw[side] = h->ftw[2 * (size_t)pair + side];
+            mj.phase0[side] = ij.phase0[side] = h->phase0[2 * (size_t)pair + side];
+        }
+        XCHK(h, fmt.kind == SAMPLE_F32 ? launch_iq_pair_mix(mj, interleaved, h->copy_stream) : launch_iq_pair_mix_int(ij, fmt.kind, h->copy_stream));
+        ++h->launches;
+        return PSDC_OK;
+    });
 }
 
 int sync_impl(XObj *h, const char *who)
@@ -1861,21 +1789,15 @@ extern "C" {
 psdc_cross *psdc_cross_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
                                      int device)
 {
-    return create_impl<psdc_cross>(n, win, power, nenbw, overlap, 2, n_pairs, device, "psdc_cross_create_window");
+    return static_cast<psdc_cross *>(create_impl(KINDS[K_CROSS], n, win, power, nenbw, overlap, n_pairs, device, "psdc_cross_create_window"));
 }
 
 psdc_cross *psdc_cross_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
 {
-    return create_kind<psdc_cross>(n, window_kind, 2, n_pairs, device, "psdc_cross_create");
+    return static_cast<psdc_cross *>(create_kind(KINDS[K_CROSS], n, window_kind, n_pairs, device, "psdc_cross_create"));
 }
 
-void psdc_cross_destroy(psdc_cross *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_cross_destroy(psdc_cross *h) { destroy_obj(h); }
 
 int psdc_cross_reset(psdc_cross *h) { return reset_impl(h, "psdc_cross_reset"); }
 int psdc_cross_set_detrend(psdc_cross *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_cross_set_detrend"); }
@@ -1988,25 +1910,15 @@ int psdc_csm_supported(uint32_t n, uint32_t m) { return n <= 4096 && m <= CSM_MA
 psdc_csm *psdc_csm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t m,
                                  uint32_t n_groups, int device)
 {
-    return create_impl<psdc_csm>(n, win, power, nenbw, overlap, m, n_groups, device, "psdc_csm_create_window");
+    return static_cast<psdc_csm *>(create_impl(KINDS[K_CSM], n, win, power, nenbw, overlap, n_groups, device, "psdc_csm_create_window", m));
 }
 
 psdc_csm *psdc_csm_create(uint32_t n, int window_kind, uint32_t m, uint32_t n_groups, int device)
 {
-    if (!csm_supported(n <= 4096 ? (int)n : 0, m <= CSM_MAX_M ? (int)m : 0)) { // (before the window: a refused size names itself)
-        xfail(nullptr, PSDC_ERR_ARG, "psdc_csm_create: " + csm_size_text(n, m));
-        return nullptr;
-    }
-    return create_kind<psdc_csm>(n, window_kind, m, n_groups, device, "psdc_csm_create");
+    return static_cast<psdc_csm *>(create_kind(KINDS[K_CSM], n, window_kind, n_groups, device, "psdc_csm_create", m));
 }
 
-void psdc_csm_destroy(psdc_csm *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_csm_destroy(psdc_csm *h) { destroy_obj(h); }
 
 int psdc_csm_reset(psdc_csm *h) { return reset_impl(h, "psdc_csm_reset"); }
 int psdc_csm_set_detrend(psdc_csm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_csm_set_detrend"); }
@@ -2094,21 +2006,15 @@ const char *psdc_csm_last_error(const psdc_csm *h) { return h ? h->err.c_str() :
 psdc_zoom *psdc_zoom_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
                                    int device)
 {
-    return create_impl<psdc_zoom>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zoom_create_window");
+    return static_cast<psdc_zoom *>(create_impl(KINDS[K_ZOOM], n, win, power, nenbw, overlap, n_channels, device, "psdc_zoom_create_window"));
 }
 
 psdc_zoom *psdc_zoom_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_zoom>(n, window_kind, 2, n_channels, device, "psdc_zoom_create");
+    return static_cast<psdc_zoom *>(create_kind(KINDS[K_ZOOM], n, window_kind, n_channels, device, "psdc_zoom_create"));
 }
 
-void psdc_zoom_destroy(psdc_zoom *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_zoom_destroy(psdc_zoom *h) { destroy_obj(h); }
 
 int psdc_zoom_reset(psdc_zoom *h) { return reset_impl(h, "psdc_zoom_reset"); }
 int psdc_zoom_set_detrend(psdc_zoom *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zoom_set_detrend"); }
@@ -2172,21 +2078,15 @@ const char *psdc_zoom_last_error(const psdc_zoom *h) { return h ? h->err.c_str()
 
 psdc_iq *psdc_iq_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_iq>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iq_create_window");
+    return static_cast<psdc_iq *>(create_impl(KINDS[K_IQ], n, win, power, nenbw, overlap, n_channels, device, "psdc_iq_create_window"));
 }
 
 psdc_iq *psdc_iq_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_iq>(n, window_kind, 2, n_channels, device, "psdc_iq_create");
+    return static_cast<psdc_iq *>(create_kind(KINDS[K_IQ], n, window_kind, n_channels, device, "psdc_iq_create"));
 }
 
-void psdc_iq_destroy(psdc_iq *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_iq_destroy(psdc_iq *h) { destroy_obj(h); }
 
 int psdc_iq_reset(psdc_iq *h) { return reset_impl(h, "psdc_iq_reset"); }
 int psdc_iq_set_detrend(psdc_iq *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iq_set_detrend"); }
@@ -2261,25 +2161,15 @@ int psdc_zcsd_supported(uint32_t n) { return n <= 4096 && zoom_cross_supported((
 psdc_zcsd *psdc_zcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
                                    int device)
 {
-    return create_impl<psdc_zcsd>(n, win, power, nenbw, overlap, 4, n_pairs, device, "psdc_zcsd_create_window");
+    return static_cast<psdc_zcsd *>(create_impl(KINDS[K_ZCSD], n, win, power, nenbw, overlap, n_pairs, device, "psdc_zcsd_create_window"));
 }
 
 psdc_zcsd *psdc_zcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
 {
-    if (!psdc_zcsd_supported(n)) { // (before the window: a refused size names itself)
-        xfail(nullptr, PSDC_ERR_ARG, "psdc_zcsd_create: " + zcsd_size_text(n));
-        return nullptr;
-    }
-    return create_kind<psdc_zcsd>(n, window_kind, 4, n_pairs, device, "psdc_zcsd_create");
+    return static_cast<psdc_zcsd *>(create_kind(KINDS[K_ZCSD], n, window_kind, n_pairs, device, "psdc_zcsd_create"));
 }
 
-void psdc_zcsd_destroy(psdc_zcsd *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_zcsd_destroy(psdc_zcsd *h) { destroy_obj(h); }
 
 int psdc_zcsd_reset(psdc_zcsd *h) { return reset_impl(h, "psdc_zcsd_reset"); }
 int psdc_zcsd_set_detrend(psdc_zcsd *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zcsd_set_detrend"); }
@@ -2352,25 +2242,15 @@ int psdc_iqcsd_supported(uint32_t n) { return psdc_zcsd_supported(n); }
 psdc_iqcsd *psdc_iqcsd_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
                                      int device)
 {
-    return create_impl<psdc_iqcsd>(n, win, power, nenbw, overlap, 4, n_pairs, device, "psdc_iqcsd_create_window");
+    return static_cast<psdc_iqcsd *>(create_impl(KINDS[K_IQCSD], n, win, power, nenbw, overlap, n_pairs, device, "psdc_iqcsd_create_window"));
 }
 
 psdc_iqcsd *psdc_iqcsd_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
 {
-    if (!psdc_iqcsd_supported(n)) { // (before the window: a refused size names itself)
-        xfail(nullptr, PSDC_ERR_ARG, "psdc_iqcsd_create: " + zcsd_size_text(n));
-        return nullptr;
-    }
-    return create_kind<psdc_iqcsd>(n, window_kind, 4, n_pairs, device, "psdc_iqcsd_create");
+    return static_cast<psdc_iqcsd *>(create_kind(KINDS[K_IQCSD], n, window_kind, n_pairs, device, "psdc_iqcsd_create"));
 }
 
-void psdc_iqcsd_destroy(psdc_iqcsd *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_iqcsd_destroy(psdc_iqcsd *h) { destroy_obj(h); }
 
 int psdc_iqcsd_reset(psdc_iqcsd *h) { return reset_impl(h, "psdc_iqcsd_reset"); }
 int psdc_iqcsd_set_detrend(psdc_iqcsd *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqcsd_set_detrend"); }
@@ -2598,21 +2478,15 @@ int psdc_sk_supported(uint32_t n) { return n <= 4096 && cross_supported((int)n) 
 
 psdc_sk *psdc_sk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_sk>(n, win, power, nenbw, overlap, 1, n_channels, device, "psdc_sk_create_window");
+    return static_cast<psdc_sk *>(create_impl(KINDS[K_SK], n, win, power, nenbw, overlap, n_channels, device, "psdc_sk_create_window"));
 }
 
 psdc_sk *psdc_sk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_sk>(n, window_kind, 1, n_channels, device, "psdc_sk_create");
+    return static_cast<psdc_sk *>(create_kind(KINDS[K_SK], n, window_kind, n_channels, device, "psdc_sk_create"));
 }
 
-void psdc_sk_destroy(psdc_sk *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
+void psdc_sk_destroy(psdc_sk *h) { destroy_obj(h); }
 
 int psdc_sk_reset(psdc_sk *h) { return reset_impl(h, "psdc_sk_reset"); }
 int psdc_sk_set_detrend(psdc_sk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_sk_set_detrend"); }
@@ -2777,15 +2651,6 @@ int zsk_stage_moments_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage
     return PSDC_OK;
 }
 
-template <class T>
-void zsk_destroy(T *h)
-{
-    if (!h)
-        return;
-    destroy_impl(h);
-    delete h;
-}
-
 } // namespace
 
 extern "C" {
@@ -2794,15 +2659,15 @@ int psdc_zsk_supported(uint32_t n) { return psdc_sk_supported(n); }
 
 psdc_zsk *psdc_zsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_zsk>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zsk_create_window");
+    return static_cast<psdc_zsk *>(create_impl(KINDS[K_ZSK], n, win, power, nenbw, overlap, n_channels, device, "psdc_zsk_create_window"));
 }
 
 psdc_zsk *psdc_zsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_zsk>(n, window_kind, 2, n_channels, device, "psdc_zsk_create");
+    return static_cast<psdc_zsk *>(create_kind(KINDS[K_ZSK], n, window_kind, n_channels, device, "psdc_zsk_create"));
 }
 
-void psdc_zsk_destroy(psdc_zsk *h) { zsk_destroy(h); }
+void psdc_zsk_destroy(psdc_zsk *h) { destroy_obj(h); }
 int psdc_zsk_reset(psdc_zsk *h) { return reset_impl(h, "psdc_zsk_reset"); }
 int psdc_zsk_set_detrend(psdc_zsk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zsk_set_detrend"); }
 int psdc_zsk_set_avg(psdc_zsk *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zsk_set_avg"); }
@@ -2858,15 +2723,15 @@ int psdc_iqsk_supported(uint32_t n) { return psdc_sk_supported(n); }
 
 psdc_iqsk *psdc_iqsk_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_iqsk>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iqsk_create_window");
+    return static_cast<psdc_iqsk *>(create_impl(KINDS[K_IQSK], n, win, power, nenbw, overlap, n_channels, device, "psdc_iqsk_create_window"));
 }
 
 psdc_iqsk *psdc_iqsk_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_iqsk>(n, window_kind, 2, n_channels, device, "psdc_iqsk_create");
+    return static_cast<psdc_iqsk *>(create_kind(KINDS[K_IQSK], n, window_kind, n_channels, device, "psdc_iqsk_create"));
 }
 
-void psdc_iqsk_destroy(psdc_iqsk *h) { zsk_destroy(h); }
+void psdc_iqsk_destroy(psdc_iqsk *h) { destroy_obj(h); }
 int psdc_iqsk_reset(psdc_iqsk *h) { return reset_impl(h, "psdc_iqsk_reset"); }
 int psdc_iqsk_set_detrend(psdc_iqsk *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqsk_set_detrend"); }
 int psdc_iqsk_set_avg(psdc_iqsk *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqsk_set_avg"); }
@@ -2994,15 +2859,15 @@ int psdc_zampm_supported(uint32_t n) { return psdc_sk_supported(n); }
 
 psdc_zampm *psdc_zampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_zampm>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_zampm_create_window");
+    return static_cast<psdc_zampm *>(create_impl(KINDS[K_ZAMPM], n, win, power, nenbw, overlap, n_channels, device, "psdc_zampm_create_window"));
 }
 
 psdc_zampm *psdc_zampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_zampm>(n, window_kind, 2, n_channels, device, "psdc_zampm_create");
+    return static_cast<psdc_zampm *>(create_kind(KINDS[K_ZAMPM], n, window_kind, n_channels, device, "psdc_zampm_create"));
 }
 
-void psdc_zampm_destroy(psdc_zampm *h) { zsk_destroy(h); }
+void psdc_zampm_destroy(psdc_zampm *h) { destroy_obj(h); }
 int psdc_zampm_reset(psdc_zampm *h) { return reset_impl(h, "psdc_zampm_reset"); }
 int psdc_zampm_set_detrend(psdc_zampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zampm_set_detrend"); }
 int psdc_zampm_set_avg(psdc_zampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zampm_set_avg"); }
@@ -3059,15 +2924,15 @@ int psdc_iqampm_supported(uint32_t n) { return psdc_sk_supported(n); }
 
 psdc_iqampm *psdc_iqampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, int device)
 {
-    return create_impl<psdc_iqampm>(n, win, power, nenbw, overlap, 2, n_channels, device, "psdc_iqampm_create_window");
+    return static_cast<psdc_iqampm *>(create_impl(KINDS[K_IQAMPM], n, win, power, nenbw, overlap, n_channels, device, "psdc_iqampm_create_window"));
 }
 
 psdc_iqampm *psdc_iqampm_create(uint32_t n, int window_kind, uint32_t n_channels, int device)
 {
-    return create_kind<psdc_iqampm>(n, window_kind, 2, n_channels, device, "psdc_iqampm_create");
+    return static_cast<psdc_iqampm *>(create_kind(KINDS[K_IQAMPM], n, window_kind, n_channels, device, "psdc_iqampm_create"));
 }
 
-void psdc_iqampm_destroy(psdc_iqampm *h) { zsk_destroy(h); }
+void psdc_iqampm_destroy(psdc_iqampm *h) { destroy_obj(h); }
 int psdc_iqampm_reset(psdc_iqampm *h) { return reset_impl(h, "psdc_iqampm_reset"); }
 int psdc_iqampm_set_detrend(psdc_iqampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqampm_set_detrend"); }
 int psdc_iqampm_set_avg(psdc_iqampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqampm_set_avg"); }

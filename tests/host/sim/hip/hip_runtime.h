@@ -12,24 +12,38 @@
 // as on the real runtime).  A host that recycles a staging buffer, frees a stream buffer or lets a span go before the device
 // has consumed it therefore fails here as it would (sometimes) fail there.  hipStreamQuery reports "not ready" while that
 // stream has operations queued: the coalescing of in-place spans on a busy device is exercised as on hardware.
+//
+// Trace (tests/host/cross_feed_check.cpp): with sim::rt().trace set, every asynchronous copy, event record, event wait and host
+// wait for an event appends a line to it, and so does whatever a modelled launcher passes to sim::trace().  A line names its
+// stream and events by their order of creation and prints a pointer as allocation serial + offset (sim::pname), so two runs
+// that make the same calls print the same text whatever the addresses.
 #pragma once
+#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
+#include <string>
+#include <vector>
 
 typedef int hipError_t;
 enum : int { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorNotReady = 600 };
 enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3, hipMemcpyDefault = 4 };
 constexpr unsigned hipStreamNonBlocking = 1, hipEventDisableTiming = 2, hipHostMallocDefault = 0;
+enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 63 };
 
 struct sim_stream {
     long pending = 0; // operations of this stream still in the queue
+    long id = 0;      // order of creation (0: the null stream)
 };
 struct sim_event {
     long seq = -1; // position of its latest record in the queue's numbering (-1: never recorded)
+    long id = 0;   // order of creation
+    long gen = 0;  // records so far
 };
 typedef sim_stream *hipStream_t;
 typedef sim_event *hipEvent_t;
@@ -47,6 +61,10 @@ struct Runtime {
     sim_stream null_stream;
     size_t live_bytes = 0, live_blocks = 0, total_ops = 0;
     bool fail_next_malloc = false; // fault injection
+    // trace: the lines of each stream (index: its id; the last entry holds the host's waits) and what names a pointer
+    std::vector<std::vector<std::string>> *trace = nullptr;
+    std::map<uintptr_t, std::pair<size_t, long>> blocks; // base -> (bytes, serial) of every live allocation
+    long next_block = 0, next_stream = 0, next_event = 0;
 };
 inline Runtime &rt()
 {
@@ -75,6 +93,43 @@ inline void run_until(long seq) // run every queued operation numbered <= seq
 }
 inline void drain() { run_until(rt().next_seq); }
 
+// memory a trace may name: every hipMalloc / hipHostMalloc, and what the check program registers of its own
+inline void note_block(const void *p, size_t bytes) { rt().blocks[(uintptr_t)p] = {bytes, rt().next_block++}; }
+inline void drop_block(const void *p) { rt().blocks.erase((uintptr_t)p); }
+inline std::string pname(const void *p)
+{
+    Runtime &r = rt();
+    auto it = r.blocks.upper_bound((uintptr_t)p);
+    if (!p || it == r.blocks.begin())
+        return p ? "?" : "null";
+    --it;
+    if ((uintptr_t)p - it->first > it->second.first) // (one past the end still belongs to the block)
+        return "?";
+    return "a" + std::to_string(it->second.second) + "+" + std::to_string((uintptr_t)p - it->first);
+}
+constexpr long TRACE_HOST = -1; // the group of the host's own waits
+inline void trace_line(long stream_id, std::string line)
+{
+    Runtime &r = rt();
+    if (!r.trace)
+        return;
+    const size_t g = stream_id == TRACE_HOST ? 0 : (size_t)stream_id + 1;
+    if (r.trace->size() <= g)
+        r.trace->resize(g + 1);
+    (*r.trace)[g].push_back(std::move(line));
+}
+inline void trace(long stream_id, const char *fmt, ...)
+{
+    if (!rt().trace)
+        return;
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    trace_line(stream_id, buf);
+}
+
 } // namespace sim
 
 inline const char *hipGetErrorString(hipError_t e)
@@ -98,6 +153,11 @@ inline hipError_t hipDeviceSynchronize()
     sim::drain();
     return hipSuccess;
 }
+inline hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int)
+{
+    *v = 256; // compute units of the device the library is written for
+    return hipSuccess;
+}
 inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi)
 {
     *lo = 0;
@@ -119,6 +179,7 @@ inline hipError_t hipMalloc(T **p, size_t bytes)
         return hipErrorOutOfMemory;
     memset((void *)*p, 0xA5, bytes); // device memory is not zeroed: a read of something never written shows
     sim::rt().live_blocks += 1;
+    sim::note_block(*p, bytes);
     return hipSuccess;
 }
 inline hipError_t hipFree(void *p)
@@ -126,14 +187,18 @@ inline hipError_t hipFree(void *p)
     sim::drain(); // hipFree waits for outstanding work, like the real one
     if (p)
         sim::rt().live_blocks -= 1;
+    sim::drop_block(p);
     free(p);
     return hipSuccess;
 }
-inline hipError_t hipHostMalloc(void **p, size_t bytes, unsigned)
+template <class T>
+inline hipError_t hipHostMalloc(T **p, size_t bytes, unsigned = hipHostMallocDefault)
 {
-    *p = malloc(bytes ? bytes : 1);
-    if (*p)
+    *p = static_cast<T *>(malloc(bytes ? bytes : 1));
+    if (*p) {
         sim::rt().live_blocks += 1;
+        sim::note_block(*p, bytes);
+    }
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 inline hipError_t hipHostFree(void *p)
@@ -141,12 +206,14 @@ inline hipError_t hipHostFree(void *p)
     sim::drain();
     if (p)
         sim::rt().live_blocks -= 1;
+    sim::drop_block(p);
     free(p);
     return hipSuccess;
 }
 
-inline hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t s)
+inline hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s)
 {
+    sim::trace(sim::S(s)->id, "copy kind %d %s <- %s bytes %zu", (int)kind, sim::pname(dst).c_str(), sim::pname(src).c_str(), bytes);
     sim::enqueue(s, [=] { memmove(dst, src, bytes); });
     return hipSuccess;
 }
@@ -178,6 +245,7 @@ inline hipError_t hipMemset(void *dst, int v, size_t bytes)
 inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)
 {
     *s = new sim_stream();
+    (*s)->id = ++sim::rt().next_stream;
     return hipSuccess;
 }
 inline hipError_t hipStreamCreate(hipStream_t *s) { return hipStreamCreateWithFlags(s, 0); }
@@ -204,6 +272,7 @@ inline hipError_t hipStreamQuery(hipStream_t s) { return sim::S(s)->pending ? hi
 inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned)
 {
     *e = new sim_event();
+    (*e)->id = ++sim::rt().next_event;
     return hipSuccess;
 }
 inline hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
@@ -215,11 +284,14 @@ inline hipError_t hipEventDestroy(hipEvent_t e)
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
     e->seq = sim::rt().next_seq; // the marker operation below gets this number
+    e->gen += 1;
+    sim::trace(sim::S(s)->id, "record e%ld#%ld", e->id, e->gen);
     sim::enqueue(s, [] {});
     return hipSuccess;
 }
 inline hipError_t hipEventSynchronize(hipEvent_t e)
 {
+    sim::trace(sim::TRACE_HOST, "host waits e%ld#%ld", e->id, e->gen);
     if (e->seq >= 0)
         sim::run_until(e->seq);
     return hipSuccess;
@@ -227,7 +299,7 @@ inline hipError_t hipEventSynchronize(hipEvent_t e)
 inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
 {
     // FIFO execution: the record (already queued, or already run) precedes everything queued from here on
-    (void)e;
+    sim::trace(sim::S(s)->id, "wait e%ld#%ld", e->id, e->gen);
     sim::enqueue(s, [] {});
     return hipSuccess;
 }

@@ -413,6 +413,7 @@ hipError_t launch_dec(const DecBatch &b, hipStream_t s)
 {
     if (b.ntiles <= 0)
         return hipSuccess;
+    sim::trace(sim::S(s)->id, "dec jobs %d tiles %d drain %d", b.njobs, b.ntiles, b.drain);
     sim::enqueue(s, [b] {
         int tiles = 0;
         for (int ji = 0; ji < b.njobs; ++ji) {

@@ -93,6 +93,24 @@ def test_round_planner_on_the_cpu_under_sanitizers():
     assert "every segment and every decimator output exactly once" in r.stdout
 
 
+@pytest.mark.timeout(600)
+def test_cross_feeds_on_the_cpu_under_sanitizers():
+    """tests/host/cross_feed_check: the host runtime of the cross-spectral objects (csrc/cross_runtime.cpp, unchanged) linked with
+    the host model of the HIP runtime (tests/host/sim/) and with models of its launchers, built with -fsanitize=address,undefined.
+    One object each of psdc_cross, psdc_csm (m = 3), psdc_zoom, psdc_zcsd, psdc_iq, psdc_iqcsd and psdc_sk at n = 64 takes every
+    sample route it has (host / device, planar / interleaved, f32 / s16) at the call lengths 1, 63, 8 * 64 + 1 and, from host
+    memory, STAGING + 5 (two pieces), with buffers that grow, rounds R - 2 to wait for and a producer event; psdc_zoom and
+    psdc_cross take host and device frames.  The samples carry their identity: every segment of every stream must hold the
+    samples of its index (so no staging slot was written early and no piece landed at a wrong offset) and come exactly once,
+    every address the feeds hand to a launcher is touched, and nothing stays allocated."""
+    host = os.path.join(ROOT, "tests", "host")
+    subprocess.run(["make", "-C", host, "cross_feed_check"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
+    r = subprocess.run([os.path.join(host, "cross_feed_check")], capture_output=True, text=True, timeout=550, env=env)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "every segment exactly once from the samples of its index, nothing left allocated" in r.stdout
+
+
 def test_cpp_source_mirror(pkg, ora, tmp_path):
     """cpp/source.hpp, the C++ mirror of the reference's file-backed Source (src/source.rs:135-157): get() at the
     reference's granularity (512 raw samples / one frame per call, --repeat wrap), AdcDac decode on the host
