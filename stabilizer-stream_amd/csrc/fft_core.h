@@ -40,6 +40,19 @@ PSDK_HD cf lds_ld(const cf *p)
 #endif
 }
 
+// Its sibling for stores: one 8-byte LDS store that stays single.  Paired, two of them leave as a ds_write2_b64: ~13
+// store-path cycles where two ds_write_b64 take ~6 + 6, and an 8-bit offset field (in units of 8 bytes) where the single
+// form has 16 bits of bytes, so that constants beyond it cost an address add each.
+PSDK_HD void lds_st(cf *p, cf x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    *(volatile __attribute__((address_space(3))) f2v *)p = f2v{x.re, x.im};
+#else
+    *p = x;
+#endif
+}
+
 // The inter-pass twiddles of a radix-R pass held in an LDS table tw[(q - 1) * 16 + s] (q = 1 .. R - 1): applied to the NB
 // butterflies of a lane, v[R i + q] *= tw_q, reading the table as SINGLE 8-byte reads in batches of B that are in flight
 // together.  Left to the compiler the reads pair up as ds_read2_b64 (8 LDS cycles for 16 bytes a lane where two ds_read_b64

@@ -33,6 +33,11 @@
 #ifndef PSDK_ADDTID
 #define PSDK_ADDTID 1
 #endif
+// 1: the first exchange's stores of the N = 1024 team kernel as sixteen single
+// ds_write_b64 (store0<true>); 0: left to the backend, which pairs them (A/B)
+#ifndef PSDK_ST0_SINGLE
+#define PSDK_ST0_SINGLE 1
+#endif
 
 namespace psdk {
 
@@ -71,14 +76,21 @@ struct TeamFft {
         }
     }
 
+    // ONE: sixteen single 8-byte stores (lds_st), every constant in the 16-bit offset field; otherwise the backend pairs
+    // them into eight ds_write2_b64 and rebuilds the addresses its 8-bit offsets do not reach
+    template <bool ONE = false>
     static PSDK_HD void store0(int tl, const cf *v, cf *frame)
     {
         cf *base = frame + (4 * tl + (tl >> 2)); // swz(q L1 + 4 tl + c) = base + q (L1 + L1/16) + c
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                base[(L1 + L1 / 16) * q + c] = v[4 * q + c];
+            for (int c = 0; c < 4; ++c) {
+                if constexpr (ONE)
+                    lds_st(base + (L1 + L1 / 16) * q + c, v[4 * q + c]);
+                else
+                    base[(L1 + L1 / 16) * q + c] = v[4 * q + c];
+            }
     }
 
     // pass 1: butterfly i of the lane works in block b = NB1 (tl / 16) + i with s = tl % 16:

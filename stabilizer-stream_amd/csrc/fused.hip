@@ -32,6 +32,14 @@
 #ifndef PSDK_HOIST_LOOKAHEAD
 #define PSDK_HOIST_LOOKAHEAD 1
 #endif
+// The N = 1024 f32 kernels (the team is the wavefront, so its job, run and stream positions are the same in every lane; the
+// compiler cannot see that and carries them per lane).  Each 1: on, 0: the per-lane form of every other size (A/B).
+#ifndef PSDK_UADDR
+#define PSDK_UADDR 1 // the stream positions of a run as scalar bases + one loop-invariant per-lane byte offset
+#endif
+#ifndef PSDK_ULOOP
+#define PSDK_ULOOP 1 // the run's first pair and length as scalars: the pair loop's counter and its `more` flags compare in SALU
+#endif
 
 namespace psdk {
 
@@ -79,6 +87,17 @@ __device__ __forceinline__ float team_bcast(float v, int team_lane0, int tl)
         return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), tl));
     else
         return __shfl(v, team_lane0 + tl, 64);
+}
+
+// a pointer that is the same in every lane of the wavefront, as a scalar: both halves through readfirstlane, so what is
+// derived from it -- the advance per pair, the choice between two of them -- is SALU work and a load takes it as its base
+template <class P>
+__device__ __forceinline__ P *wave_uniform(P *p)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return reinterpret_cast<P *>((uintptr_t)hi << 32 | lo);
 }
 
 // two floats to dwords dwa + lane and dwb + lane of the wavefront's LDS frame (m0: TeamFft::lds_base; dwa, dwb constants once the
@@ -391,10 +410,33 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
 #endif
 
     // this team's run: pairs [p0, p0 + nrun) of the job (the job's last teams get fewer or none)
-    const int p0 = (wb * TEAMS + team) * run;
+    // UNI: the team is the wavefront and the stream plain f32.  Then p0 is the same in every lane (ULOOP: said so once, which
+    // makes nrun, the loop counter and the `more` flags scalars), and so are the run's stream positions (UADDR): cp, safe and
+    // the output pointer are scalar bases WITHOUT the lane's share, which every access adds as one loop-invariant 32-bit byte
+    // offset (voff; the bases are 64-bit, a span may lie anywhere) -- the loads take base, offset and constant in one instruction.
+    // The input base points N/4 float4 into its chunk: the pieces a pair loads (2048 ... 5120 bytes in) are then all within the
+    // signed 13-bit constant of a global load.
+    constexpr bool UNI = TEAM == 64 && !FRAMES;
+    constexpr bool UADDR = UNI && PSDK_UADDR != 0, ULOOP = UNI && PSDK_ULOOP != 0;
+    const int p0 = ULOOP ? __builtin_amdgcn_readfirstlane((wb * TEAMS + team) * run) : (wb * TEAMS + team) * run;
     const int nrun = min(run, npairs - p0);
     const bool act0 = nrun > 0;
-    const float4 *cp = reinterpret_cast<const float4 *>(job.src) + (size_t)p0 * (N / 4) + tl;
+    unsigned voff = UADDR ? 16u * (unsigned)tl : 0u, voff_o = UADDR ? 8u * (unsigned)tl : 0u; // (loads, stage-C store)
+    const float4 *cp = UADDR ? wave_uniform(reinterpret_cast<const float4 *>(job.src) + (size_t)p0 * (N / 4) + N / 4)
+                             : reinterpret_cast<const float4 *>(job.src) + (size_t)p0 * (N / 4) + tl;
+    // (Inside the loop the offset goes through lane_off first: an empty statement that keeps its zero-extension in the block
+    // of the access.  Hoisted out of the loop, as an invariant is, the backend sees a 64-bit per-lane value come in from
+    // another block and adds it to the base in VALU.)
+    auto lane_off = [](unsigned &v) { // (in place: the statement ties input and output, a copy of a kept value would be a move)
+        asm volatile("" : "+v"(v));
+        return v;
+    };
+    auto ld4 = [](const float4 *c, int k, unsigned vo) -> float4 { // UADDR: piece k of the chunk whose base is c
+        // (global address space by hand: the trip through readfirstlane hides where the pointer came from)
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v r = *(const __attribute__((address_space(1))) f4v *)(reinterpret_cast<const char *>(c + (k - N / 4)) + vo);
+        return make_float4(r.x, r.y, r.z, r.w);
+    };
     // ... or, in a FRAMES launch, trace job.fch of a frame span (sp: the sample index of the same piece within the span)
     const bool fr = FRAMES && job.fspan >= 0;
     const FrameSpan &fsp = batch.fspans[fr ? job.fspan : 0];
@@ -417,7 +459,10 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                 return g;
             }
         }
-        g.set(c[k]);
+        if constexpr (UADDR)
+            g.set(ld4(c, k, voff));
+        else
+            g.set(c[k]);
         return g;
     };
     auto volts = [&](G4 &g) { // raw wire words -> volts, in place (a no-op for f32 jobs)
@@ -428,7 +473,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
     };
     // where the look-ahead loads go once there is nothing left to look ahead to: pieces that were
     // read before (every job holds at least one pair = 3N/2 samples)
-    const float4 *safe = act0 ? cp : reinterpret_cast<const float4 *>(job.src) + tl;
+    const float4 *safe = act0 ? cp : reinterpret_cast<const float4 *>(job.src) + (UADDR ? N / 4 : tl);
+    if constexpr (UADDR && !ULOOP) // (the A/B arm without scalar loop control: the choice itself was made per lane)
+        safe = wave_uniform(safe);
     unsigned safe_s = act0 ? sp : job.s_off + 4u * tl;
     G4 ga[2], gb[2], gc[2];
     {
@@ -641,6 +688,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                 if constexpr (PSDK_ABL & 512) { // (512: a nontemporal store)
                     __builtin_nontemporal_store(y0, o + 2 * tl);
                     __builtin_nontemporal_store(y1, o + 2 * tl + 1);
+                } else if constexpr (UADDR) { // (o: the scalar base of the pair's outputs)
+                    typedef float f2v __attribute__((ext_vector_type(2)));
+                    *(__attribute__((address_space(1))) f2v *)(reinterpret_cast<char *>(o) + lane_off(voff_o)) = f2v{y0, y1};
                 } else {
                     *reinterpret_cast<f2 *>(o + 2 * tl) = {y0, y1};
                 }
@@ -710,7 +760,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
         { // chunk p + 1 upper -> up, chunk p + 2 lower -> lo, in flight during the FFT.  Issued
           // unconditionally (after the last pair: re-reads, unused) -- a load under a branch is
           // waited for at the branch's end, which would expose the HBM latency once per pair.
-            const float4 *src = more ? cnext : safe;
+            const float4 *src = more ? cnext : safe; // (UADDR: a scalar choice between two scalar bases)
+            if constexpr (UADDR && !ULOOP)
+                src = wave_uniform(src);
             const unsigned ssrc = more ? snext : safe_s;
             safe = src;
             safe_s = ssrc;
@@ -736,6 +788,12 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                     glo[0].set(src[N / 4]);
                     glo[1].set(src[N / 4 + TEAM]);
                 }
+            } else if constexpr (UADDR) {
+                const unsigned vo = lane_off(voff);
+                gup[0].set(ld4(src, 2 * TEAM, vo));
+                gup[1].set(ld4(src, 3 * TEAM, vo));
+                glo[0].set(ld4(src, N / 4, vo));
+                glo[1].set(ld4(src, N / 4 + TEAM, vo));
             } else {
                 gup[0].set(src[2 * TEAM]);
                 gup[1].set(src[3 * TEAM]);
@@ -782,7 +840,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                 v[s] = {keep[s], v[s].re};
         }
         T::pass0(tl, v, s_tw0);
-        T::store0(tl, v, frame);
+        T::template store0<UNI && PSDK_ST0_SINGLE != 0>(tl, v, frame);
         wave_sync();
         PSDK_STAMP(6);
         if constexpr (!(PSDK_ABL & 8)) {
@@ -819,6 +877,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
 
     {
         float *o = job.dst + (size_t)p0 * (N / 8);
+        if constexpr (UADDR)
+            o = wave_uniform(o);
         if constexpr (PSDK_ABL & 2048) // (2048: the output stream rounded down to a 128-byte boundary -- what its alignment costs)
             o = reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(o) & ~(uintptr_t)127);
         for (int i = 0; i < nrun; i += 2) {
