@@ -41,7 +41,69 @@
 #define PSDK_ULOOP 1 // the run's first pair and length as scalars: the pair loop's counter and its `more` flags compare in SALU
 #endif
 
+// Fair issue among the wavefronts of a SIMD (the same kernels): the FFT phase of a pair runs at a priority that depends on the
+// wavefront's rank in its SIMD and, rotating, on the pair -- below the decimator's in every case.  Priorities only: no arithmetic,
+// address or run boundary depends on it.  0: every FFT phase at priority 0 (A/B); 1: the rotation (level of pair p for rank r:
+// entry (p + r) mod 4 of 0 1 2 1); 3: the same table indexed by the rank alone, no rotation (A/B).
+#ifndef PSDK_FAIR
+#define PSDK_FAIR 1
+#endif
+// the same in the f32 kernels of N = 512, whose wavefronts hold two teams: the key is the first active lane's (A/B).  (N = 256:
+// no gain on the bench -- -0.3 % over eight alternations against an A/A spread of 0.7 % --, so those kernels stay as they were.)
+#ifndef PSDK_FAIR_SMALL
+#define PSDK_FAIR_SMALL 1
+#endif
+// the rank: 0 the hardware wave slot within the SIMD (HW_ID.WAVE_ID, 0 ... 3 in the census), 1 (A/B): 2 (wave index >= 4) + workgroup
+// parity (wavefronts w and w + 4 of a workgroup share a SIMD)
+#ifndef PSDK_FAIR_RANK
+#define PSDK_FAIR_RANK 0
+#endif
+static_assert(PSDK_FAIR == 0 || PSDK_DEC_PRIO == 3, "the FFT levels 0 ... 2 must stay below the decimator's priority");
+
 namespace psdk {
+
+// -DPSDK_CENSUS (tools/stamps/build_census.sh): every wavefront of a launch leaves one record of when and where it ran -- 100 MHz
+// s_memrealtime at kernel entry, before its first pair and after its last, its HW_ID and XCC_ID registers, workgroup, wave index,
+// job and run -- in g_census, which nothing in the kernel reads; one lane, plain vector stores.  Only launches with a job whose runs
+// are g_census_min_run pairs or longer are recorded (psdc_debug_census_min_run): the shorter launches behind a round, which drain
+// the deep stages, would overwrite the round's own records.  Never defined in the shipped build.
+#ifdef PSDK_CENSUS
+constexpr int CENSUS_MAX_WAVES = 8192, CENSUS_WORDS = 8;
+__device__ int g_census_min_run = 32;
+__device__ unsigned long long g_census[CENSUS_MAX_WAVES * CENSUS_WORDS];
+// kind 1: a compute wavefront, 2: a wavefront of an aux workgroup
+__device__ __forceinline__ void census_put(const FusedBatch &batch, int kind, unsigned long long t_entry, unsigned long long t_first,
+                                           int ji, int run, int nrun, int npairs)
+{
+    bool big = false;
+    const int min_run = g_census_min_run;
+    for (int j = 0; j < batch.njobs; ++j)
+        big |= batch.jobs[j].run >= min_run;
+    const unsigned long long t_exit = __builtin_amdgcn_s_memrealtime();
+    const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11)); // HW_ID, XCC_ID
+    const unsigned w = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (threadIdx.x % 64 == 0 && w < (unsigned)CENSUS_MAX_WAVES && big) {
+        unsigned long long *r = g_census + (size_t)w * CENSUS_WORDS;
+        r[0] = t_entry;
+        r[1] = t_first;
+        r[2] = t_exit;
+        r[3] = (unsigned long long)xcc << 32 | hw;
+        r[4] = (unsigned long long)(threadIdx.x / 64) << 32 | blockIdx.x;
+        r[5] = (unsigned long long)kind << 32 | (unsigned)ji;
+        r[6] = (unsigned long long)(unsigned)nrun << 32 | (unsigned)run;
+        r[7] = (unsigned long long)gridDim.x << 32 | (unsigned)npairs;
+    }
+}
+#define PSDK_CENSUS_ENTRY() const unsigned long long census_t0 = __builtin_amdgcn_s_memrealtime()
+#define PSDK_CENSUS_AUX() census_put(batch, 2, census_t0, census_t0, -1, 0, 0, 0)
+#else
+#define PSDK_CENSUS_ENTRY() \
+    do {                    \
+    } while (0)
+#define PSDK_CENSUS_AUX() \
+    do {                  \
+    } while (0)
+#endif
 
 // -DPSDK_STAMPS (tools/stamps): the first wavefront of workgroup 0 sums the s_memtime ticks it
 // spends in each phase of pair_step into g_stamps; never defined in the shipped build.
@@ -292,12 +354,16 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
 #if PSDK_FOLD
 #if PSDK_AUX_BACK
     if ((int)blockIdx.x >= batch.nblocks) { // (uniform: the whole workgroup takes the aux role and leaves)
+        PSDK_CENSUS_ENTRY();
         fused_aux_role<FUSED_WAVES * 64>(aux, (int)blockIdx.x - batch.nblocks, reinterpret_cast<double *>(s_frames));
+        PSDK_CENSUS_AUX();
         return;
     }
 #else
     if ((int)blockIdx.x < aux.nblocks) { // (uniform: the whole workgroup takes the aux role and leaves)
+        PSDK_CENSUS_ENTRY();
         fused_aux_role<FUSED_WAVES * 64>(aux, (int)blockIdx.x, reinterpret_cast<double *>(s_frames));
+        PSDK_CENSUS_AUX();
         return;
     }
 #endif
@@ -305,6 +371,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
 #ifdef PSDK_STAMPS
     const unsigned long long t_entry = __builtin_amdgcn_s_memtime();
 #endif
+    PSDK_CENSUS_ENTRY();
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
     const int tm = lane / TEAM, tl = lane % TEAM; // team within the wavefront, lane within the team
@@ -418,6 +485,12 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
     // signed 13-bit constant of a global load.
     constexpr bool UNI = TEAM == 64 && !FRAMES;
     constexpr bool UADDR = UNI && PSDK_UADDR != 0, ULOOP = UNI && PSDK_ULOOP != 0;
+    // FAIR: this wavefront's rank among those of its SIMD, a scalar (PSDK_FAIR above)
+    constexpr bool FAIR = PSDK_FAIR != 0 && !FRAMES && (TEAM == 64 || (N == 512 && PSDK_FAIR_SMALL != 0));
+    int fair_rank = 0;
+    if constexpr (FAIR)
+        fair_rank = PSDK_FAIR_RANK == 0 ? (int)(__builtin_amdgcn_s_getreg(4 | (3 << 11)) & 3u) // HW_ID.WAVE_ID[3:0]
+                                        : __builtin_amdgcn_readfirstlane(2 * (wv >> 2) + (bid & 1));
     const int p0 = ULOOP ? __builtin_amdgcn_readfirstlane((wb * TEAMS + team) * run) : (wb * TEAMS + team) * run;
     const int nrun = min(run, npairs - p0);
     const bool act0 = nrun > 0;
@@ -705,7 +778,28 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
         } // PSDK_ABL & 4
         wave_sync(); // the frame is reused by the FFT
         PSDK_STAMP(4);
-        __builtin_amdgcn_s_setprio(0);
+        if constexpr (FAIR) {
+            // The instruction takes an immediate and ignores EXEC: one constant s_setprio an arm, each behind a scalar branch on
+            // a bit of the key; level 1, every other pair, falls through to the end.  The loop's second half tests the key of
+            // its first half (its own is that + 1: odd when c is even, else bit 1 flipped), which saves its scalar add.
+            const int c = __builtin_amdgcn_readfirstlane(PSDK_FAIR == 1 ? p - (ODD ? 1 : 0) + fair_rank : fair_rank);
+            if constexpr (ODD && PSDK_FAIR == 1)
+                asm volatile("s_bitcmp0_b32 %0, 0\n\ts_cbranch_scc1 .Lfair1_%=\n\t"
+                             "s_bitcmp0_b32 %0, 1\n\ts_cbranch_scc1 .Lfair2_%=\n\t"
+                             "s_setprio 0\n\ts_branch .Lfair3_%=\n"
+                             ".Lfair2_%=:\n\ts_setprio 2\n\ts_branch .Lfair3_%=\n"
+                             ".Lfair1_%=:\n\ts_setprio 1\n"
+                             ".Lfair3_%=:" ::"s"(c) : "scc", "memory");
+            else
+                asm volatile("s_bitcmp1_b32 %0, 0\n\ts_cbranch_scc1 .Lfair1_%=\n\t"
+                             "s_bitcmp1_b32 %0, 1\n\ts_cbranch_scc1 .Lfair2_%=\n\t"
+                             "s_setprio 0\n\ts_branch .Lfair3_%=\n"
+                             ".Lfair2_%=:\n\ts_setprio 2\n\ts_branch .Lfair3_%=\n"
+                             ".Lfair1_%=:\n\ts_setprio 1\n"
+                             ".Lfair3_%=:" ::"s"(c) : "scc", "memory");
+        } else {
+            __builtin_amdgcn_s_setprio(0);
+        }
 
         // ---- FFT of the pair: re = segment 2p, im = segment 2p + 1 -------------------------
         cf v[16];
@@ -881,6 +975,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
             o = wave_uniform(o);
         if constexpr (PSDK_ABL & 2048) // (2048: the output stream rounded down to a 128-byte boundary -- what its alignment costs)
             o = reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(o) & ~(uintptr_t)127);
+#ifdef PSDK_CENSUS
+        const unsigned long long census_t1 = __builtin_amdgcn_s_memrealtime();
+#endif
         for (int i = 0; i < nrun; i += 2) {
             pair_step(ga, gb, gc, cp + N / 4, sp + N, i + 1 < nrun, o, p0 + i, std::false_type{});
             cp += N / 4;
@@ -895,6 +992,11 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
                     o += N / 8;
             }
         }
+        if constexpr (FAIR)
+            __builtin_amdgcn_s_setprio(0);
+#ifdef PSDK_CENSUS
+        census_put(batch, 1, census_t0, census_t1, ji, run, nrun, npairs);
+#endif
     }
 
     PSDK_STAMP(0);
@@ -1135,6 +1237,30 @@ hipError_t launch_fused(int n, const FusedBatch &b, const float *win, const cf *
 
 } // namespace psdk
 
+#ifdef PSDK_CENSUS
+// copies the records of the launches since the last call (a later launch overwrites an earlier one's) and clears them;
+// out: max_waves x 8 words, a record whose kind (word 5, high half) is 0 is empty
+extern "C" int psdc_debug_census(unsigned long long *out, int max_waves)
+{
+    const size_t all = (size_t)psdk::CENSUS_MAX_WAVES * psdk::CENSUS_WORDS * sizeof(unsigned long long);
+    const size_t bytes = std::min(all, (size_t)std::max(max_waves, 0) * psdk::CENSUS_WORDS * sizeof(unsigned long long));
+    void *dev = nullptr;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipGetSymbolAddress(&dev, HIP_SYMBOL(psdk::g_census));
+    if (e == hipSuccess)
+        e = hipMemcpy(out, dev, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemset(dev, 0, all);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    return (int)e;
+}
+extern "C" int psdc_debug_census_min_run(int pairs)
+{
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(psdk::g_census_min_run), &pairs, sizeof(pairs));
+}
+#endif
 #ifdef PSDK_STAMPS
 extern "C" int psdc_debug_stamps(unsigned long long *out16)
 {
