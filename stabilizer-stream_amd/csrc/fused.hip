@@ -59,8 +59,33 @@
 #define PSDK_FAIR_RANK 0
 #endif
 static_assert(PSDK_FAIR == 0 || PSDK_DEC_PRIO == 3, "the FFT levels 0 ... 2 must stay below the decimator's priority");
+// The same levels from feedback (N = 1024 f32 kernels, where PSDK_FAIR is 1): every PSDK_FAIR_FB_K pairs a wavefront publishes the
+// pairs left in its run in its SIMD's row of g_fair_progress and reads the row; with the most left of the four it runs its FFT
+// phases at level 2, with the fewest at 0, else at 1, until the next read.  A hint only: nothing waits on the table, and whatever
+// it holds gives a level 0 ... 2.  0: off (the rotation alone: the listing of every kernel is the one without this switch);
+// 1 (A/B): entries closer than K pairs to this wavefront's fall back to the rotation; 2: feedback alone, a tie counts as "not
+// ahead of me" (the census and the bench prefer it: exit spread inside a SIMD 0.005 against 0.014 of the launch).
+#ifndef PSDK_FAIR_FB
+#define PSDK_FAIR_FB 2
+#endif
+// pairs between two publish / read / decide steps: a power of two, at least 2 (the step sits in the loop's first half).  A/B at
+// FB 2: K = 2 -0.7 %, K = 8 the same as 4 within the A/A spread.
+#ifndef PSDK_FAIR_FB_K
+#define PSDK_FAIR_FB_K 4
+#endif
+static_assert(PSDK_FAIR_FB_K >= 2 && (PSDK_FAIR_FB_K & (PSDK_FAIR_FB_K - 1)) == 0, "the publish period is a power of two >= 2");
 
 namespace psdk {
+
+// Progress table of the feedback above: one row of four dwords per SIMD -- a dword per hardware wave slot (HW_ID.WAVE_ID & 3) --,
+// the row index XCC_ID[3:0] : HW_ID.SE_ID[2:0] : SH_ID : CU_ID[3:0] : SIMD_ID[1:0], every bit pattern of the fields (256 KiB; a
+// launch touches the rows of the SIMDs that exist, 16 KiB).  Zero when the module is loaded, and every wavefront leaves a zero
+// behind, so between launches the table is zero: "no pair left".  One per device: the wavefronts of other handles on a SIMD
+// show their own progress, which is as good a hint.
+#if PSDK_FAIR_FB
+constexpr int FAIR_ROW_BITS = 14;
+__device__ __attribute__((aligned(16))) unsigned g_fair_progress[4u << FAIR_ROW_BITS]; // (a row is one 16-byte scalar load)
+#endif
 
 // -DPSDK_CENSUS (tools/stamps/build_census.sh): every wavefront of a launch leaves one record of when and where it ran -- 100 MHz
 // s_memrealtime at kernel entry, before its first pair and after its last, its HW_ID and XCC_ID registers, workgroup, wave index,
@@ -494,6 +519,29 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
     const int p0 = ULOOP ? __builtin_amdgcn_readfirstlane((wb * TEAMS + team) * run) : (wb * TEAMS + team) * run;
     const int nrun = min(run, npairs - p0);
     const bool act0 = nrun > 0;
+#if PSDK_FAIR_FB
+    // FB: the levels from the progress table (PSDK_FAIR_FB above).  Everything here is a scalar: the row (fb_row; this wavefront's
+    // dword in it is entry fair_rank), the level in force (fb_lvl: 0 ... 2, or 3 = the rotation) and the loop's position.
+    constexpr bool FB = FAIR && ULOOP && PSDK_FAIR == 1 && PSDK_FAIR_RANK == 0;
+    typedef unsigned fb_u4 __attribute__((ext_vector_type(4)));
+    const unsigned *fb_row = nullptr;
+    int fb_lvl = 3;
+#ifdef PSDK_CENSUS
+    int census_lvl0 = 0; // the level decided at the run's first pair, + 1 (0: none; 4: the rotation)
+#endif
+    auto fb_publish = [&](int left) { // one plain vector store of the same dword from every lane: scalar base, no EXEC handling
+        *(__attribute__((address_space(1))) unsigned *)(fb_row + fair_rank) = (unsigned)left;
+    };
+    if constexpr (FB) {
+        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)); // HW_ID, XCC_ID[3:0]
+        const unsigned row = (xcc & 15u) << 10 | ((hw >> 8) & 0xFFu) << 2 | ((hw >> 4) & 3u); // (SE, SH, CU: HW_ID[15:8]; SIMD: [5:4])
+        static_assert(FAIR_ROW_BITS == 14, "the row index above is 4 + 8 + 2 bits");
+        fb_row = wave_uniform(g_fair_progress + 4u * row);
+        fb_publish(max(nrun, 0)); // run start
+    }
+#else
+    constexpr bool FB = false;
+#endif
     unsigned voff = UADDR ? 16u * (unsigned)tl : 0u, voff_o = UADDR ? 8u * (unsigned)tl : 0u; // (loads, stage-C store)
     const float4 *cp = UADDR ? wave_uniform(reinterpret_cast<const float4 *>(job.src) + (size_t)p0 * (N / 4) + N / 4)
                              : reinterpret_cast<const float4 *>(job.src) + (size_t)p0 * (N / 4) + tl;
@@ -782,7 +830,54 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
             // The instruction takes an immediate and ignores EXEC: one constant s_setprio an arm, each behind a scalar branch on
             // a bit of the key; level 1, every other pair, falls through to the end.  The loop's second half tests the key of
             // its first half (its own is that + 1: odd when c is even, else bit 1 flipped), which saves its scalar add.
-            const int c = __builtin_amdgcn_readfirstlane(PSDK_FAIR == 1 ? p - (ODD ? 1 : 0) + fair_rank : fair_rank);
+            int c = __builtin_amdgcn_readfirstlane(PSDK_FAIR == 1 ? p - (ODD ? 1 : 0) + fair_rank : fair_rank);
+#if PSDK_FAIR_FB
+            if constexpr (FB) {
+                // Every K pairs, between the decimator and the FFT phase of the loop's first half: publish, read, decide.  The read
+                // is one scalar load of the row, glc: from L2, which the four wavefronts of a SIMD share, not from a scalar-cache
+                // line of an earlier read; its wait is in the same statement, so no register is written behind the compiler's
+                // back.  The three other entries are compared with what this wavefront has left (its own dword is not used: the
+                // store below need not have arrived).  FB 2: "more" = entries with strictly more pairs left, "less" = the rest.  FB 1:
+                // more = at least K more, less = at least K fewer; an entry that is neither sends the wavefront back to the rotation.
+                constexpr int K = PSDK_FAIR_FB_K;
+                if constexpr (!ODD) {
+                    const int done = __builtin_amdgcn_readfirstlane(p - p0);
+                    if ((done & (K - 1)) == 0) {
+                        const unsigned left = (unsigned)(nrun - done);
+                        fb_publish((int)left);
+                        fb_u4 r;
+                        asm volatile("s_load_dwordx4 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(fb_row) : "memory");
+                        // (Sign bits of differences, not comparisons: a comparison's boolean goes through VCC and VALU selects,
+                        // these stay in SALU.  Entries are clamped first, so a foreign value cannot wrap a difference; `left` is
+                        // at most the run, far below the clamp.)
+                        const unsigned e[4] = {r.x, r.y, r.z, r.w};
+                        const unsigned hi = PSDK_FAIR_FB == 2 ? left + 1u : left + (unsigned)K;             // more: v >= hi
+                        const unsigned lo1 = left > (unsigned)K ? left - (unsigned)K + 1u : 1u;              // less: v < lo1
+                        unsigned not_more = 0, less = 0;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const unsigned v = j == fair_rank ? left : min(e[j], 1u << 24); // (itself: neither more nor less)
+                            not_more += (v - hi) >> 31;
+                            less += (v - lo1) >> 31;
+                        }
+                        const unsigned more = 4u - not_more;
+                        if constexpr (PSDK_FAIR_FB == 2)
+                            less = 3u - more; // (a tie counts as behind: every other entry is one or the other)
+                        // more = 0: the most left of the four, level 2; 3: the fewest, level 0; else 1 -- two bits each of 0x16
+                        const unsigned by_rank = (0x16u >> (2u * more)) & 3u;
+                        fb_lvl = (int)(more + less == 3u ? by_rank : 3u);
+#ifdef PSDK_CENSUS
+                        if (done == 0)
+                            census_lvl0 = fb_lvl + 1;
+#endif
+                    }
+                }
+                // the key of the branches below for a fixed level L: L in the first half; in the second half, whose arms test
+                // the first half's key, (L + 3) mod 4 (3 -> level 0, 0 -> 1, 1 -> 2)
+                if (fb_lvl != 3)
+                    c = ODD ? (fb_lvl + 3) & 3 : fb_lvl;
+            }
+#endif
             if constexpr (ODD && PSDK_FAIR == 1)
                 asm volatile("s_bitcmp0_b32 %0, 0\n\ts_cbranch_scc1 .Lfair1_%=\n\t"
                              "s_bitcmp0_b32 %0, 1\n\ts_cbranch_scc1 .Lfair2_%=\n\t"
@@ -994,8 +1089,17 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, EWMA ? PSDK_EWMA_WPS : FUSED_WAVE
         }
         if constexpr (FAIR)
             __builtin_amdgcn_s_setprio(0);
+#if PSDK_FAIR_FB
+        if constexpr (FB)
+            fb_publish(0); // leaving: the slot reads as finished until its next wavefront publishes
+#endif
 #ifdef PSDK_CENSUS
+#if PSDK_FAIR_FB
+        // (with the feedback: the levels of the first and the last decision ride above the kind, 4 bits each, + 1)
+        census_put(batch, 1 | (FB && act0 ? census_lvl0 << 8 | (fb_lvl + 1) << 12 : 0), census_t0, census_t1, ji, run, nrun, npairs);
+#else
         census_put(batch, 1, census_t0, census_t1, ji, run, nrun, npairs);
+#endif
 #endif
     }
 

@@ -2,7 +2,7 @@
 # Wave-census build of the team kernels (-DPSDK_CENSUS, csrc/fused.hip) into tools/stamps/libpsdcascade_census.so: every
 # wavefront of a fused launch records when and where it ran (tools/stamps/census.py reads the records).  The shipped library is
 # never built this way.
-#   CENSUS_EXTRA="-DPSDK_FAIR=0"   more flags for fused.hip (the A/B switches of the kernel)
+#   CENSUS_EXTRA="-DPSDK_FAIR_FB=0"   more flags for fused.hip (the A/B switches of the kernel)
 #   CENSUS_OUT=path.so             another output file (one per variant)
 set -e
 here=$(cd "$(dirname "$0")" && pwd)

@@ -16,6 +16,9 @@ import numpy as np
 TICK_US = 0.01  # s_memrealtime: 100 MHz
 WORDS = 8
 MAX_WAVES = 8192
+# share of the vector issue rate of four resident wavefronts that a SIMD reaches with fewer (three waves/SIMD
+# measured -21 %, two at most 0.76 of the rate -- 0.6 taken --, one 0.35 taken)
+ISSUE_RATE = {4: 1.0, 3: 0.79, 2: 0.6, 1: 0.35}
 
 
 def decode(rec):
@@ -27,12 +30,15 @@ def decode(rec):
     kind = hi(rec[:, 5])
     keep = kind != 0
     rec, kind = rec[keep], kind[keep]
+    lvl_first, lvl_last = (kind >> 8) & 15, (kind >> 12) & 15  # PSDK_FAIR_FB: level + 1 of the first / last decision (0: none, 4: rotation)
+    kind = kind & 0xFF
     hw = lo(rec[:, 3])
     return {
         "entry": rec[:, 0].astype(np.int64), "first": rec[:, 1].astype(np.int64), "exit": rec[:, 2].astype(np.int64),
         "slot": hw & 15, "simd": (hw >> 4) & 3, "cu": (hw >> 8) & 15, "sh": (hw >> 12) & 1, "se": (hw >> 13) & 7,
         "xcd": hi(rec[:, 3]) & 15, "wg": lo(rec[:, 4]), "wave": hi(rec[:, 4]), "job": s32(lo(rec[:, 5])), "kind": kind,
         "run": s32(lo(rec[:, 6])), "nrun": np.maximum(s32(hi(rec[:, 6])), 0), "npairs": s32(lo(rec[:, 7])), "grid": hi(rec[:, 7]),
+        "lvl_first": lvl_first, "lvl_last": lvl_last,
     }
 
 
@@ -108,7 +114,7 @@ def reduce_census(rec):
     nmax = int(c["nrun"].max())
     full = c["nrun"] == nmax
     simd_last = np.zeros(w, dtype=np.int64)
-    spreads, rank_exit = [], {}
+    spreads, rank_exit, ideal, late = [], {}, [], []
     for u in np.unique(simd_id):
         m = simd_id == u
         simd_last[m] = c["exit"][m].max()
@@ -118,8 +124,22 @@ def reduce_census(rec):
             spreads.append((e[-1] - e[0]) / span)
             for i, x in enumerate(e):
                 rank_exit.setdefault(i, []).append((x - t0) / span)
+        if mf.sum() == 4:  # the bound of equal progress: the same work at the issue rate of four, all four leaving together
+            s0 = float(c["entry"][mf].min())
+            edges = np.concatenate(([s0], e.astype(np.float64)))
+            work = float(sum(ISSUE_RATE[4 - k] * (edges[k + 1] - edges[k]) for k in range(4)))
+            ideal.append((s0 + work / ISSUE_RATE[4] - t0) / span)
+            late.append((e[-1] - s0 - work / ISSUE_RATE[4]) / span)
     out["simd_exit_spread"] = _dist(spreads)
     out["simd_exit_by_order"] = {str(i): _dist(v) for i, v in sorted(rank_exit.items())}
+    # (SIMDs with exactly four full-run wavefronts; the last exit of such a SIMD against the exit all four would share)
+    out["equal_progress_bound"] = {"issue_rate": {str(k): v for k, v in ISSUE_RATE.items()}, "ideal_common_exit": _dist(ideal),
+                                   "last_exit_minus_ideal": _dist(late)}
+    if c["lvl_last"].any():  # PSDK_FAIR_FB: the levels of the first and the last decision of a run, by wave slot
+        name = {1: "0", 2: "1", 3: "2", 4: "rotation"}
+        tab = lambda col: {str(s): {name[int(k)]: int(n_) for k, n_ in zip(*np.unique(col[(c["slot"] == s) & (col != 0)], return_counts=True))}
+                           for s in np.unique(c["slot"])}
+        out["feedback_levels"] = {"first": tab(c["lvl_first"]), "last": tab(c["lvl_last"])}
     out["waves_per_simd"] = _dist(np.unique(simd_id, return_counts=True)[1])
     mean_full = float(life[full].mean())
     tail = (t_end - c["exit"]).astype(np.float64)
@@ -150,6 +170,12 @@ def report(r, file=sys.stdout):
     if sp:
         p(f"exit spread inside a SIMD (full runs, last - first, fraction of span): mean {sp['mean']:.4f} p50 {sp['p50']:.4f} p90 {sp['p90']:.4f} max {sp['max']:.4f}")
         p("  exit by order within the SIMD: " + "  ".join(f"{k}: {v['mean']:.4f}" for k, v in r["simd_exit_by_order"].items()))
+    b = r.get("equal_progress_bound")
+    if b and b["ideal_common_exit"]:
+        p(f"equal progress (SIMDs of four full runs, n={b['ideal_common_exit']['n']}): ideal common exit p50 {b['ideal_common_exit']['p50']:.4f}, "
+          f"last exit - ideal mean {b['last_exit_minus_ideal']['mean']:.4f} p50 {b['last_exit_minus_ideal']['p50']:.4f} of the span")
+    for when, t in r.get("feedback_levels", {}).items():
+        p(f"  feedback level at the {when} decision, by slot: {t}")
     lo = r["loss"]
     p(f"empty slot-time {lo['total']:.4f} = quantisation {lo['quantisation']:.4f} (by construction {r['quantisation_by_construction']:.4f}) "
       f"+ within SIMD {lo['within_simd']:.4f} + empty SIMD {lo['empty_simd']:.4f} + ramp {lo['ramp']:.4f}")
