@@ -1399,6 +1399,94 @@ int psdc_iqampm_sidebands(psdc_iqampm *h, uint32_t channel, int keep_overlap, ui
 int psdc_iqampm_stats_read(psdc_iqampm *h, uint64_t *launches, uint64_t *samples_in, int reset);
 const char *psdc_iqampm_last_error(const psdc_iqampm *h);
 
+/* ---- AM/PM cross cascades: cross-correlated amplitude and phase noise of two channels --------------------------------
+ * Two channels a and b on one carrier (two ADCs on one oscillator, two lock-ins, the two arms of a cross-correlation phase-noise
+ * set-up): what the channels share survives the average of the cross spectra of their modulations, each channel's own noise
+ * goes down as 1 / sqrt(count).  psdc_zxampm_* is the zoom cross object (two real streams, a carrier a side, fed as psdc_zcsd_*
+ * is) and psdc_iqxampm_* the IQ cross object (two complex streams, an optional retune a side, fed as psdc_iqcsd_* is), both
+ * on one segment kernel (csrc/zoom_ampm_cross.hip) that transforms each channel once a segment.
+ * Unit, carriers and stages: those of the zoom cross / IQ cross object fed the same streams and carriers -- segmentation,
+ * Window<N>, Detrend, /8 decimation of I and Q, lazy stages, the averaging schedule with its EWMA weights, counts, pendings and
+ * Breaks.
+ * Rows: each (pair, stage) holds twelve f64 rows of n/2 + 1 bins; kn = (N - k) mod N.
+ *     rows 0 ... 7:  the zoom cross object's eight rows, in its order and with its signs (S_aa, S_bb, Re S_ab, Im S_ab, each upper
+ *                    then lower; S_ab = conj(Z_a) Z_b; lower is the value at bin kn, not conjugated)
+ *     rows 8, 9:     Re, Im of cab[k] = sum_j w_j Z_a,j[k] Z_b,j[kn]      a product WITHOUT a conjugate
+ *     rows 10, 11:   Re, Im of cba[k] = sum_j w_j Z_a,j[kn] Z_b,j[k]
+ * At k = 0 and k = N/2, cab == cba.  All twelve are bilinear in Z: the weight goes on the samples as sqrt(w_j).
+ * Model: z_x = A_x (1 + a_x + i phi_x), v_x = A_x / |A_x|.  The carriers enter through w = conj(v_a) v_b, q = v_a v_b and
+ * P = |A_a| |A_b| only, read from bin 0 of stage 0 under Detrend::None: sab_up[0] = P w count n^2 window_power and
+ * cab[0] = P q count n^2 window_power; the locks are |sab_up[0]| / sqrt(saa_up[0] sbb_up[0]) and
+ * |cab[0]| / sqrt(saa_up[0] sbb_lo[0]).  With U = sab_up, L = sab_lo, T1 = U conj(w), T2 = conj(cab) q, T3 = cba conj(q),
+ * T4 = conj(L) w:
+ *     s_am    = conj(a_a) a_b     = ( T1 + T2 + T3 + T4) / (4 P)        s_pm    = conj(phi_a) phi_b = (T1 - T2 - T3 + T4) / (4 P)
+ *     s_am_pm = conj(a_a) phi_b   = ( T1 - T2 + T3 - T4) / (4 i P)      s_pm_am = conj(phi_a) a_b   = i (T1 + T2 - T3 - T4) / (4 P)
+ * The Python module reads them (carriers(), am_pm_cross()).
+ * Limits: those of the AM/PM cascades -- a linear, small-modulation split (phi^2 reads as AM at second order); both carriers at
+ * their tuning words to within the reciprocal of the averaging time (the locks say whether they are); bins 0 and 1 of every
+ * stage hold the carriers themselves under Hann.
+ * Merged read-out: psdc_zxampm_sidebands / psdc_iqxampm_sidebands stitch all twelve rows in f64 with ONE set of Breaks, taken from
+ * rows 0 and 1 as psdc_zampm_sidebands takes them, and the per-stage factor of that read-out.
+ * Sizes and windows are those of the zoom cross object; the twelve-row kernel uses no scratch memory at any of them.  There is no
+ * CPU fallback.  Sample routes, stream ordering, the caller-keeps-memory rule, errors, the device rule and the bank rule are those
+ * of psdc_zcsd_* / psdc_iqcsd_*, and so are the kernel launches of a steady-state call (PSDC_ZCSD_STEADY_LAUNCHES,
+ * PSDC_IQCSD_STEADY_LAUNCHES); host and device calls of the same samples, and the same calls twice, give the same bits.  Only the
+ * f32 sample routes feed these objects: stream frames, the loss record and the integer feeds are not offered. */
+typedef struct psdc_zxampm psdc_zxampm;
+/* 1 where n is a size the object takes, else 0 */
+int psdc_zxampm_supported(uint32_t n);
+/* mirrors psdc_zcsd_create / psdc_zcsd_create_window */
+psdc_zxampm *psdc_zxampm_create(uint32_t n, int window_kind, uint32_t n_pairs, int device);
+psdc_zxampm *psdc_zxampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                       int device);
+void psdc_zxampm_destroy(psdc_zxampm *h);
+int psdc_zxampm_reset(psdc_zxampm *h);
+int psdc_zxampm_set_detrend(psdc_zxampm *h, int detrend_kind);
+int psdc_zxampm_set_avg(psdc_zxampm *h, uint32_t limit, uint32_t count);
+/* as psdc_zcsd_set_carrier: side 0 is channel a, 1 channel b */
+int psdc_zxampm_set_carrier(psdc_zxampm *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0);
+/* as psdc_zcsd_process / psdc_zcsd_process_device */
+int psdc_zxampm_process(psdc_zxampm *h, uint32_t pair, const float *x, const float *y, size_t len);
+int psdc_zxampm_process_device(psdc_zxampm *h, uint32_t pair, const float *d_x, const float *d_y, size_t len, void *producer_event);
+int psdc_zxampm_sync(psdc_zxampm *h);
+int psdc_zxampm_num_stages(psdc_zxampm *h, uint32_t pair);
+/* raw f64 accumulators of one stage: rows[12][n/2 + 1], or NULL for the statistics alone */
+int psdc_zxampm_stage_rows(psdc_zxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows);
+/* all twelve rows merged in f64: rows[12][cap] (row r starts at rows + r * cap), or NULL for the length and the Breaks alone */
+int psdc_zxampm_sidebands(psdc_zxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
+                          size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+/* as psdc_zcsd_stats_read */
+int psdc_zxampm_stats_read(psdc_zxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset);
+const char *psdc_zxampm_last_error(const psdc_zxampm *h);
+
+typedef struct psdc_iqxampm psdc_iqxampm;
+int psdc_iqxampm_supported(uint32_t n);
+/* mirrors psdc_iqcsd_create / psdc_iqcsd_create_window */
+psdc_iqxampm *psdc_iqxampm_create(uint32_t n, int window_kind, uint32_t n_pairs, int device);
+psdc_iqxampm *psdc_iqxampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs,
+                                         int device);
+void psdc_iqxampm_destroy(psdc_iqxampm *h);
+int psdc_iqxampm_reset(psdc_iqxampm *h);
+int psdc_iqxampm_set_detrend(psdc_iqxampm *h, int detrend_kind);
+int psdc_iqxampm_set_avg(psdc_iqxampm *h, uint32_t limit, uint32_t count);
+/* as psdc_iqcsd_set_carrier: the retune of one side, default 0, 0 */
+int psdc_iqxampm_set_carrier(psdc_iqxampm *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0);
+/* the four f32 sample routes of psdc_iqcsd_*: planar and interleaved, host and device */
+int psdc_iqxampm_process(psdc_iqxampm *h, uint32_t pair, const float *ia, const float *qa, const float *ib, const float *qb, size_t len);
+int psdc_iqxampm_process_device(psdc_iqxampm *h, uint32_t pair, const float *d_ia, const float *d_qa, const float *d_ib,
+                                const float *d_qb, size_t len, void *producer_event);
+int psdc_iqxampm_process_interleaved(psdc_iqxampm *h, uint32_t pair, const float *za, const float *zb, size_t len);
+int psdc_iqxampm_process_interleaved_device(psdc_iqxampm *h, uint32_t pair, const float *d_za, const float *d_zb, size_t len,
+                                            void *producer_event);
+int psdc_iqxampm_sync(psdc_iqxampm *h);
+int psdc_iqxampm_num_stages(psdc_iqxampm *h, uint32_t pair);
+/* as psdc_zxampm_stage_rows and psdc_zxampm_sidebands */
+int psdc_iqxampm_stage_rows(psdc_iqxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows);
+int psdc_iqxampm_sidebands(psdc_iqxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
+                           size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks);
+int psdc_iqxampm_stats_read(psdc_iqxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset);
+const char *psdc_iqxampm_last_error(const psdc_iqxampm *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

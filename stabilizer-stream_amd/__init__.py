@@ -501,6 +501,27 @@ def lib():
     f("psdc_iqampm_process_device", i32, [H, u32, vp, vp, sz, vp])
     f("psdc_iqampm_process_interleaved", i32, [H, u32, fp, sz])
     f("psdc_iqampm_process_interleaved_device", i32, [H, u32, vp, sz, vp])
+    for pre in ("psdc_zxampm_", "psdc_iqxampm_"):
+        f(pre + "supported", i32, [u32])
+        f(pre + "create", H, [u32, i32, u32, i32])
+        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
+        f(pre + "destroy", None, [H])
+        f(pre + "reset", i32, [H])
+        f(pre + "set_detrend", i32, [H, i32])
+        f(pre + "set_avg", i32, [H, u32, u32])
+        f(pre + "set_carrier", i32, [H, u32, u32, u64, u64])
+        f(pre + "sync", i32, [H])
+        f(pre + "num_stages", i32, [H, u32])
+        f(pre + "stage_rows", i32, [H, u32, u32, C.POINTER(_CStageStat), dp])
+        f(pre + "sidebands", i32, [H, u32, i32, u32, i32, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
+        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+        f(pre + "last_error", C.c_char_p, [H])
+    f("psdc_zxampm_process", i32, [H, u32, fp, fp, sz])
+    f("psdc_zxampm_process_device", i32, [H, u32, vp, vp, sz, vp])
+    f("psdc_iqxampm_process", i32, [H, u32, fp, fp, fp, fp, sz])
+    f("psdc_iqxampm_process_device", i32, [H, u32, vp, vp, vp, vp, sz, vp])
+    f("psdc_iqxampm_process_interleaved", i32, [H, u32, fp, fp, sz])
+    f("psdc_iqxampm_process_interleaved_device", i32, [H, u32, vp, vp, sz, vp])
     _lib = L
     return L
 
@@ -569,6 +590,15 @@ EXPORTS = [
     "psdc_iqampm_process_device", "psdc_iqampm_process_interleaved", "psdc_iqampm_process_interleaved_device", "psdc_iqampm_sync",
     "psdc_iqampm_num_stages", "psdc_iqampm_stage_rows", "psdc_iqampm_psd", "psdc_iqampm_sidebands", "psdc_iqampm_stats_read",
     "psdc_iqampm_last_error",
+    "psdc_zxampm_supported", "psdc_zxampm_create", "psdc_zxampm_create_window", "psdc_zxampm_destroy", "psdc_zxampm_reset",
+    "psdc_zxampm_set_detrend", "psdc_zxampm_set_avg", "psdc_zxampm_set_carrier", "psdc_zxampm_process",
+    "psdc_zxampm_process_device", "psdc_zxampm_sync", "psdc_zxampm_num_stages", "psdc_zxampm_stage_rows", "psdc_zxampm_sidebands",
+    "psdc_zxampm_stats_read", "psdc_zxampm_last_error",
+    "psdc_iqxampm_supported", "psdc_iqxampm_create", "psdc_iqxampm_create_window", "psdc_iqxampm_destroy", "psdc_iqxampm_reset",
+    "psdc_iqxampm_set_detrend", "psdc_iqxampm_set_avg", "psdc_iqxampm_set_carrier", "psdc_iqxampm_process",
+    "psdc_iqxampm_process_device", "psdc_iqxampm_process_interleaved", "psdc_iqxampm_process_interleaved_device",
+    "psdc_iqxampm_sync", "psdc_iqxampm_num_stages", "psdc_iqxampm_stage_rows", "psdc_iqxampm_sidebands", "psdc_iqxampm_stats_read",
+    "psdc_iqxampm_last_error",
 ]
 
 
@@ -3039,6 +3069,321 @@ class IqCsdCascade:
 
     def close(self):
         self._b.close()
+
+
+def zoom_ampm_cross_supported(n):
+    """Whether ZoomAmPmCsdCascade[Bank] and IqAmPmCsdCascade[Bank] take the size n: the zoom cross object's sizes (the twelve-row
+    kernel needs no scratch memory at any of them).  Needs no GPU."""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_zxampm_supported(n))
+
+
+def carriers_from_rows(n, window_power, count, saa_up0, sbb_up0, sbb_lo0, sab_up0, cab0):
+    """(p_ab, w, q, lock_w, lock_q) of a pair's carriers from bin 0 of a stage's raw rows.  With v_x = A_x / |A_x|:
+    sab_up[0] = P w count n^2 window_power and cab[0] = P q count n^2 window_power, where P = |A_a| |A_b|, w = conj(v_a) v_b and
+    q = v_a v_b; so p_ab = |sab_up0| / (count n^2 window_power), w = sab_up0 / |sab_up0|, q = cab0 / |cab0|,
+    lock_w = |sab_up0| / sqrt(saa_up0 sbb_up0) and lock_q = |cab0| / sqrt(saa_up0 sbb_lo0): 1 for carriers at their tuning
+    words, towards 0 when one turns against the other (lock_w) or against its tuning word (lock_q) during the average."""
+    u, c = complex(sab_up0), complex(cab0)
+    if count < 1 or not abs(u) > 0.0 or not abs(c) > 0.0:
+        raise PsdError(ERR_ARG, "carriers: no carriers in bin 0 (no average yet, or sab_up[0] == 0 or cab[0] == 0)")
+    saa, sbu, sbl = float(saa_up0), float(sbb_up0), float(sbb_lo0)
+    return (abs(u) / (float(count) * float(n) ** 2 * float(window_power)), u / abs(u), c / abs(c),
+            abs(u) / float(np.sqrt(saa * sbu)), abs(c) / float(np.sqrt(saa * sbl)))
+
+
+def am_pm_cross_from_sidebands(sab_up, sab_lo, cab, cba, p_ab, w, q):
+    """(s_am, s_pm, s_am_pm, s_pm_am), complex128, from the cross rows of a pair (all four in one normalisation) and the carriers'
+    p_ab = |A_a| |A_b|, w = conj(v_a) v_b, q = v_a v_b (v_x = A_x / |A_x|).  With U = sab_up, L = sab_lo, T1 = U conj(w),
+    T2 = conj(cab) q, T3 = cba conj(q), T4 = conj(L) w:
+        s_am    = conj(a_a) a_b     = ( T1 + T2 + T3 + T4) / (4 P)      s_pm    = conj(phi_a) phi_b = (T1 - T2 - T3 + T4) / (4 P)
+        s_am_pm = conj(a_a) phi_b   = ( T1 - T2 + T3 - T4) / (4i P)     s_pm_am = conj(phi_a) a_b   = i (T1 + T2 - T3 - T4) / (4 P)
+    The separation is a linear, small-modulation one for z_x = A_x (1 + a_x + i phi_x): phi^2 reads as AM at second order.  The
+    rows must come from carriers that sat at their tuning words to within the reciprocal of the averaging time (carriers()'s
+    locks say whether they did); bins 0 and 1 of a stage hold the carriers themselves under a Hann window."""
+    U, L = np.asarray(sab_up, np.complex128), np.asarray(sab_lo, np.complex128)
+    cab, cba = np.asarray(cab, np.complex128), np.asarray(cba, np.complex128)
+    P, w, q = float(p_ab), complex(w), complex(q)
+    if not P > 0.0 or not abs(w) > 0.0 or not abs(q) > 0.0:
+        raise PsdError(ERR_ARG, "am_pm_cross_from_sidebands: p_ab, w and q must not be 0")
+    w, q = w / abs(w), q / abs(q)
+    t1, t2, t3, t4 = U * np.conj(w), np.conj(cab) * q, cba * np.conj(q), np.conj(L) * w
+    return ((t1 + t2 + t3 + t4) / (4.0 * P), (t1 - t2 - t3 + t4) / (4.0 * P), (t1 - t2 + t3 - t4) / (4.0j * P),
+            1j * (t1 + t2 - t3 - t4) / (4.0 * P))
+
+
+class ZoomAmPmCsdCascadeBank:
+    """`n_pairs` independent AM/PM cross cascades (psdc_zxampm_*): ZoomCsdCascadeBank's pair -- two real streams a and b, each
+    mixed down from a carrier of its own -- on one transform a channel and segment, with the two complementary cross spectra
+    cab[k] = sum Z_a[k] Z_b[N-k] and cba[k] = sum Z_a[N-k] Z_b[k] (products WITHOUT a conjugate) kept beside the zoom cross
+    object's eight rows.  csd() is ZoomCsdCascadeBank's; sidebands() adds cab and cba, all in f64; am_pm_cross() separates them into
+    the cross spectra of the two channels' amplitude and phase modulation: what both channels share stays, each channel's own
+    noise averages down as 1 / sqrt(count).
+    Limits (those of ZoomAmPmCascadeBank): the separation is a linear, small-modulation one (phi^2 reads as AM at second order);
+    both carriers must sit at their tuning words to within the reciprocal of the averaging time -- carriers()'s locks say whether
+    they do; bins 0 and 1 of every stage hold the carriers themselves under Hann.  Only f32 samples feed it: no stream frames,
+    loss record or integer feeds."""
+
+    _P = "psdc_zxampm_"
+
+    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
+        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
+        else:
+            self._h = self._f("create")(n, int(window), n_pairs, device)
+        # (ftw, phase0) of both sides of every pair, as set
+        self.carriers_set = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
+        self.detrend = Detrend.NONE
+        if not self._h:
+            msg = self._f("last_error")(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def _f(self, name):
+        return getattr(self._L, self._P + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._f("last_error")(self._h)
+            raise PsdError(rc, msg.decode() if msg else "")
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: the carriers (ftw = 0, phase0 = 0) and the detrend too."""
+        self._ck(self._f("reset")(self._h))
+        self.carriers_set = {k: (0, 0) for k in self.carriers_set}
+        self.detrend = Detrend.NONE
+
+    def set_detrend(self, d):
+        self._ck(self._f("set_detrend")(self._h, int(d)))
+        self.detrend = Detrend(int(d))
+
+    def set_avg(self, avg):
+        self._ck(self._f("set_avg")(self._h, avg.limit, avg.count))
+
+    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
+        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as ZoomCsdCascadeBank.set_carrier.
+        Returns the f0 actually used."""
+        if (f0 is None) == (ftw is None):
+            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+        if ftw is None:
+            ftw = zoom_ftw(f0)[0]
+        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+        if side is not None and side not in (0, 1):
+            raise PsdError(ERR_ARG, f"side {side} out of range (0: channel a, 1: channel b)")
+        for s in ((0, 1) if side is None else (side,)):
+            self._ck(self._f("set_carrier")(self._h, pair, s, ftw, phase0))
+            self.carriers_set[(pair, s)] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+    def process(self, pair, x, y):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        if x.size != y.size:
+            raise PsdError(ERR_ARG, "x and y must have equal lengths")
+        self._ck(self._L.psdc_zxampm_process(self._h, pair, _fptr(x), _fptr(y), x.size))
+
+    def process_device(self, pair, px, py, length, after=None):
+        """px, py: device addresses of `length` f32 samples each; after: a hipEvent_t handle recorded behind their producer, or
+        None when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._L.psdc_zxampm_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
+                                                    C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._f("sync")(self._h))
+
+    def num_stages(self, pair=0):
+        return self._ck(self._f("num_stages")(self._h, pair))
+
+    def stage_rows(self, pair, stage):
+        """(info, rows) of one stage's raw f64 accumulators: rows (12, n/2 + 1) in the layout of include/psdcascade.h -- the zoom
+        cross object's eight, then Re cab, Im cab, Re cba, Im cba"""
+        st = _CStageStat()
+        rows = np.empty((12, self.n // 2 + 1), np.float64)
+        self._ck(self._f("stage_rows")(self._h, pair, stage, C.byref(st), rows.ctypes.data_as(C.POINTER(C.c_double))))
+        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
+
+    def _merged(self, pair, opts):
+        ns = self.num_stages(pair)
+        cap = max(1, ns * (self.n // 2 + 1))
+        rows = np.zeros((12, cap), np.float64)
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(self._f("sidebands")(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
+                                      rows.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(plen), br, ns, C.byref(nb)))
+        return rows[:, :plen.value], [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def sidebands(self, pair=0, opts=MergeOpts()):
+        """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, cab, cba, breaks): all twelve rows merged with one set of Breaks, in
+        f64 (the last four complex128)"""
+        r, br = self._merged(pair, opts)
+        return (r[0].copy(), r[1].copy(), r[2].copy(), r[3].copy(), r[4] + 1j * r[6], r[5] + 1j * r[7], r[8] + 1j * r[9],
+                r[10] + 1j * r[11], br)
+
+    def csd(self, pair=0, opts=MergeOpts()):
+        """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): ZoomCsdCascadeBank.csd()'s tuple (f32, sab complex64), taken
+        from rows 0 ... 7"""
+        r, br = self._merged(pair, opts)
+        return (*(r[i].astype(np.float32) for i in range(4)), (r[4] + 1j * r[6]).astype(np.complex64),
+                (r[5] + 1j * r[7]).astype(np.complex64), br)
+
+    def _window_power(self):
+        return self.window.power if isinstance(self.window, WindowTable) else WindowTable._kind(self.n, self.window).power
+
+    def carriers(self, pair=0):
+        """(p_ab, w, q, lock_w, lock_q) of the pair's carriers, read from bin 0 of stage 0 (carriers_from_rows).  Raises unless
+        detrend is none (a detrend removes the carriers from bin 0) and stage 0 has an average."""
+        if self.detrend != Detrend.NONE:
+            raise PsdError(ERR_ARG, "carriers: bin 0 holds the carriers under Detrend.NONE only; pass am_pm_cross() the carriers")
+        if self.num_stages(pair) < 1:
+            raise PsdError(ERR_ARG, "carriers: stage 0 has no average yet")
+        info, r = self.stage_rows(pair, 0)
+        return carriers_from_rows(self.n, self._window_power(), info["count"], r[0, 0], r[2, 0], r[3, 0], r[4, 0] + 1j * r[6, 0],
+                                  r[8, 0] + 1j * r[9, 0])
+
+    def am_pm_cross(self, pair=0, carriers=None, opts=MergeOpts()):
+        """(s_am, s_pm, s_am_pm, s_pm_am, breaks), complex128, in the one-sided normalisation of psd(): am_pm_cross_from_sidebands
+        of sidebands().  carriers: (p_ab, w, q), or None to take them from carriers() (Detrend.NONE only)."""
+        if carriers is None:
+            carriers = self.carriers(pair)
+        p_ab, w, q = carriers[:3]
+        sb = self.sidebands(pair, opts)
+        return (*am_pm_cross_from_sidebands(sb[4], sb[5], sb[6], sb[7], p_ab, w, q), sb[8])
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "pairs_in": si.value}
+
+
+class IqAmPmCsdCascadeBank(ZoomAmPmCsdCascadeBank):
+    """`n_pairs` independent IQ AM/PM cross cascades (psdc_iqxampm_*): ZoomAmPmCsdCascadeBank for two streams that are complex
+    already (two lock-ins' or SDRs' I/Q), fed as IqCsdCascadeBank is and turned by an optional carrier a side (default none)."""
+
+    _P = "psdc_iqxampm_"
+
+    def process(self, pair, za, zb):
+        """za, zb: two complex arrays of one length (converted to complex64 and fed as (re, im) pairs: the interleaved route), or
+        two pairs (ia, qa), (ib, qb) of real arrays of one length (the planar route)."""
+        planar = [isinstance(z, (tuple, list)) for z in (za, zb)]
+        if all(planar):
+            if len(za) != 2 or len(zb) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (ia, qa), (ib, qb)")
+            x = [np.ascontiguousarray(v, dtype=np.float32) for v in (*za, *zb)]
+            if any(v.ndim != 1 or v.shape != x[0].shape for v in x):
+                raise PsdError(ERR_ARG, "the four streams differ in length (" + ", ".join(str(v.size) for v in x) + ")")
+            self._ck(self._L.psdc_iqxampm_process(self._h, pair, *[_fptr(v) for v in x], x[0].size))
+            return
+        if any(planar):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q), not one of each")
+        za, zb = np.asarray(za), np.asarray(zb)
+        if not (np.iscomplexobj(za) and np.iscomplexobj(zb)):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q)")
+        za = np.ascontiguousarray(za, dtype=np.complex64)
+        zb = np.ascontiguousarray(zb, dtype=np.complex64)
+        if za.ndim != 1 or za.shape != zb.shape:
+            raise PsdError(ERR_ARG, f"za and zb differ in length ({za.size} and {zb.size})")
+        self._ck(self._L.psdc_iqxampm_process_interleaved(self._h, pair, za.ctypes.data_as(C.POINTER(C.c_float)),
+                                                          zb.ctypes.data_as(C.POINTER(C.c_float)), za.size))
+
+    def process_device(self, pair, pa, pb, length, after=None):
+        """pa, pb: device addresses of `length` (re, im) pairs of f32 each (two complex64 tensors' memory; 8-byte aligned); the
+        rest as ZoomAmPmCsdCascadeBank.process_device"""
+        self._ck(self._L.psdc_iqxampm_process_interleaved_device(self._h, pair, C.c_void_p(pa), C.c_void_p(pb), length,
+                                                                 C.c_void_p(after) if after else None))
+
+    def process_device_planar(self, pair, pia, pqa, pib, pqb, length, after=None):
+        """pia, pqa, pib, pqb: device addresses of `length` f32 samples each, the I and Q streams of side a and of side b"""
+        self._ck(self._L.psdc_iqxampm_process_device(self._h, pair, C.c_void_p(pia), C.c_void_p(pqa), C.c_void_p(pib),
+                                                     C.c_void_p(pqb), length, C.c_void_p(after) if after else None))
+
+
+class ZoomAmPmCsdCascade:
+    """One pair around a carrier: ZoomAmPmCsdCascade(n, f0=0.2) or ZoomAmPmCsdCascade(n, ftw=...) sets both sides;
+    set_carrier(side=...) sets one.  csd(), sidebands(), carriers() and am_pm_cross() (ZoomAmPmCsdCascadeBank has the definitions
+    and the limits).  reset() keeps the object's carriers."""
+
+    _BANK = ZoomAmPmCsdCascadeBank
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        self.n = n
+        self._b = self._BANK(n, 1, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
+        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
+        self.carriers_set = [self._b.carriers_set[(0, 0)], self._b.carriers_set[(0, 1)]]
+        return f
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x, y):
+        self._b.process(0, x, y)
+
+    def process_device(self, px, py, length, after=None):
+        self._b.process_device(0, px, py, length, after)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def sidebands(self, opts=MergeOpts()):
+        return self._b.sidebands(0, opts)
+
+    def carriers(self):
+        return self._b.carriers(0)
+
+    def am_pm_cross(self, carriers=None, opts=MergeOpts()):
+        return self._b.am_pm_cross(0, carriers, opts)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_rows(self, i):
+        return self._b.stage_rows(0, i)
+
+    def reset(self):
+        car = list(self.carriers_set)
+        self._b.reset()
+        for s, (ftw, ph) in enumerate(car):
+            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    def close(self):
+        self._b.close()
+
+
+class IqAmPmCsdCascade(ZoomAmPmCsdCascade):
+    """One pair of complex streams: IqAmPmCsdCascade(n) analyses them as they are, IqAmPmCsdCascade(n, f0=0.2) or
+    IqAmPmCsdCascade(n, ftw=...) retunes both sides first.  process() takes two complex arrays or two pairs (i, q), as
+    IqCsdCascade.process does."""
+
+    _BANK = IqAmPmCsdCascadeBank
+
+    def process_device_planar(self, pia, pqa, pib, pqb, length, after=None):
+        self._b.process_device_planar(0, pia, pqa, pib, pqb, length, after)
 
 
 def coherence(sxx, syy, sxy):

@@ -36,6 +36,7 @@
 #include "zoom_sk_fft.h"
 #include "zoom_ampm.h"
 #include "zoom_ampm_fft.h"
+#include "zoom_ampm_cross_fft.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -86,7 +87,7 @@ struct XStage {
 
 struct XObj;
 
-// What tells the eleven families apart, one row each in KINDS (below XObj): the names in error texts, the streams and rows of a
+// What tells the thirteen families apart, one row each in KINDS (below XObj): the names in error texts, the streams and rows of a
 // unit, the feed in front of stage 0 and the segment kernel.  Everything else in this file is one runtime over these.
 enum class Feed {
     PLAIN, // the m streams are the caller's, copied (or converted) into stage 0
@@ -101,7 +102,7 @@ struct KindDesc {
     int (*segments_per_tile)(int n, int m);
     // the segment kernel: on CrossBatch jobs (two streams at most) or, for the kinds with up to four, on CsmBatch jobs
     hipError_t (*launch_pair)(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s);
-    hipError_t (*launch_group)(const XObj &h, const CsmBatch &b);
+    hipError_t (*launch_group)(const XObj &h, CsmBatch &b); // (the kind may mark the batch for its launcher: CsmBatch::variant)
     std::string (*refusal)(uint32_t n, uint32_t m); // why the kind has no kernel for these sizes ("": it has), NULL: for every n
 };
 
@@ -174,6 +175,8 @@ struct psdc_zsk : XObj {};
 struct psdc_iqsk : XObj {};
 struct psdc_zampm : XObj {};
 struct psdc_iqampm : XObj {};
+struct psdc_zxampm : XObj {};
+struct psdc_iqxampm : XObj {};
 
 namespace {
 
@@ -585,14 +588,19 @@ std::string zcsd_refusal(uint32_t n, uint32_t)
 // One row a family.  A pair object is m = 2 on cross_kernel; a matrix object 2 <= m <= 4 on csm_kernel; a zoom object m = 2 (I and
 // Q) on zoom_kernel; a zoom cross object m = 4 (I and Q of two channels) on zoom_cross_kernel; psdc_iq is psdc_zoom and psdc_iqcsd
 // is psdc_zcsd with the IQ feed; psdc_sk is m = 1 on sk_kernel; psdc_zsk / psdc_iqsk are psdc_zoom / psdc_iq on zoom_sk_kernel;
-// psdc_zampm / psdc_iqampm are psdc_zoom / psdc_iq on zoom_ampm_kernel.
-enum Kind { K_CROSS, K_CSM, K_ZOOM, K_ZCSD, K_IQ, K_IQCSD, K_SK, K_ZSK, K_IQSK, K_ZAMPM, K_IQAMPM };
+// psdc_zampm / psdc_iqampm are psdc_zoom / psdc_iq on zoom_ampm_kernel; psdc_zxampm / psdc_iqxampm are psdc_zcsd / psdc_iqcsd on
+// zoom_ampm_cross_kernel, which launch_zoom_cross runs for a batch marked ZCROSS_VARIANT_AMPM.
+enum Kind { K_CROSS, K_CSM, K_ZOOM, K_ZCSD, K_IQ, K_IQCSD, K_SK, K_ZSK, K_IQSK, K_ZAMPM, K_IQAMPM, K_ZXAMPM, K_IQXAMPM };
 constexpr auto SPT_CROSS = [](int n, int) { return cross_segments_per_tile(n); };
 constexpr auto SPT_ZOOM = [](int n, int) { return zoom_segments_per_tile(n); };
 constexpr auto SPT_ZCSD = [](int n, int) { return zoom_cross_segments_per_tile(n); };
 constexpr auto SPT_SK = [](int n, int) { return sk_segments_per_tile(n); };
-constexpr auto GROUP_CSM = [](const XObj &h, const CsmBatch &b) { return launch_csm((int)h.n, (int)h.m, b, h.d_win, h.d_tw, h.stream); };
-constexpr auto GROUP_ZCSD = [](const XObj &h, const CsmBatch &b) { return launch_zoom_cross((int)h.n, b, h.d_win, h.d_tw, h.stream); };
+constexpr auto GROUP_CSM = [](const XObj &h, CsmBatch &b) { return launch_csm((int)h.n, (int)h.m, b, h.d_win, h.d_tw, h.stream); };
+constexpr auto GROUP_ZCSD = [](const XObj &h, CsmBatch &b) { return launch_zoom_cross((int)h.n, b, h.d_win, h.d_tw, h.stream); };
+constexpr auto GROUP_ZXAMPM = [](const XObj &h, CsmBatch &b) {
+    b.variant = ZCROSS_VARIANT_AMPM;
+    return launch_zoom_cross((int)h.n, b, h.d_win, h.d_tw, h.stream);
+};
 constexpr KindDesc KINDS[] = {
     // tag, unit, units, m, rows, feed, segments a tile, segment kernel (pair | group), refusal
     {"psdc_cross", "pair", "n_pairs", 2, 4, Feed::PLAIN, SPT_CROSS, launch_cross, nullptr, nullptr},
@@ -606,8 +614,10 @@ constexpr KindDesc KINDS[] = {
     {"psdc_iqsk", "channel", "n_channels", 2, ZSK_ROWS, Feed::IQ, SPT_ZOOM, launch_zoom_sk, nullptr, nullptr},
     {"psdc_zampm", "channel", "n_channels", 2, ZAMPM_ROWS, Feed::ZOOM, SPT_ZOOM, launch_zoom_ampm, nullptr, nullptr},
     {"psdc_iqampm", "channel", "n_channels", 2, ZAMPM_ROWS, Feed::IQ, SPT_ZOOM, launch_zoom_ampm, nullptr, nullptr},
+    {"psdc_zxampm", "pair", "n_pairs", 4, ZXAMPM_ROWS, Feed::ZOOM, SPT_ZCSD, nullptr, GROUP_ZXAMPM, zcsd_refusal},
+    {"psdc_iqxampm", "pair", "n_pairs", 4, ZXAMPM_ROWS, Feed::IQ, SPT_ZCSD, nullptr, GROUP_ZXAMPM, zcsd_refusal},
 };
-static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_IQAMPM + 1, "one row a kind");
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_IQXAMPM + 1, "one row a kind");
 
 // "": the arguments are fine
 std::string check_args(const KindDesc &kind, uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs)
@@ -2548,7 +2558,8 @@ const char *psdc_sk_last_error(const psdc_sk *h) { return h ? h->err.c_str() : x
 
 namespace {
 
-// the f64 rows of every stage of a channel (ns x ZSK_ROWS x bins) and what a stitch needs beside them; rows 0 and 1 in f32 as
+// the f64 rows of every stage of a unit (ns x rows() x bins: ZSK_ROWS of them for the SK and AM/PM kinds, ZXAMPM_ROWS for the AM/PM
+// cross kinds) and what a stitch needs beside them; rows 0 and 1 in f32 as
 // two_rows_psd_impl hands a zoom object's to the stitch (ns x 2 x bins)
 struct ZskIn {
     std::vector<uint64_t> c64, pend;
@@ -2565,19 +2576,19 @@ int zsk_in(XObj *h, uint32_t channel, ZskIn *in)
         return rc;
     const auto &st = h->pairs[channel];
     const uint32_t ns = (uint32_t)st.size();
-    const size_t b = bins(h);
+    const size_t b = bins(h), nr = h->rows();
     in->ns = ns;
     in->c64.resize(std::max<uint32_t>(ns, 1));
     in->pend.resize(std::max<uint32_t>(ns, 1));
     in->avgs.resize(std::max<uint32_t>(ns, 1));
-    in->acc.resize(std::max<size_t>(1, (size_t)ns * ZSK_ROWS * b));
+    in->acc.resize(std::max<size_t>(1, (size_t)ns * nr * b));
     in->rows01.resize(std::max<size_t>(1, (size_t)ns * 2 * b));
     for (uint32_t i = 0; i < ns; ++i) {
         in->c64[i] = st[i].count64;
         in->pend[i] = pending_for(h->geo, st[i].total);
         in->avgs[i] = cur_avg(h, i);
-        double *a = &in->acc[(size_t)i * ZSK_ROWS * b];
-        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * ZSK_ROWS * b, hipMemcpyDeviceToHost));
+        double *a = &in->acc[(size_t)i * nr * b];
+        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * nr * b, hipMemcpyDeviceToHost));
         for (size_t k = 0; k < 2 * b; ++k)
             in->rows01[(size_t)i * 2 * b + k] = (float)a[k];
     }
@@ -2799,11 +2810,11 @@ namespace {
 
 static_assert(ZAMPM_ROWS == ZSK_ROWS, "the AM/PM read-out takes its stages through zsk_in: four f64 rows a stage");
 
-// the four rows stitched in f64: the row stitch picks the stages and bins from rows 0 and 1 (one set of Breaks, the zoom
-// read-out's), and every selected bin of the f64 accumulators is scaled by the f32 factor that stitch applies to the stage
-int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
-                        double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks,
-                        size_t breaks_cap, size_t *n_breaks, const char *who)
+// the rows() rows of a unit stitched in f64 into outs[r] (NULL: that row is not wanted): the row stitch picks the stages and bins
+// from rows 0 and 1 (one set of Breaks, the zoom read-out's), and every selected bin of the f64 accumulators is scaled by the f32
+// factor that stitch applies to the stage
+int rows_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *const *outs,
+                        size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
 {
     X_HANDLE(h, who);
     int rc = check_pair(h, channel);
@@ -2814,8 +2825,8 @@ int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t mi
     if ((rc = zsk_in(h, channel, &in)))
         return rc;
     float *none[2] = {nullptr, nullptr};
-    double *outs[ZAMPM_ROWS] = {upper, lower, comp_re, comp_im};
-    const bool any = upper || lower || comp_re || comp_im;
+    const size_t nr = h->rows();
+    const bool any = std::any_of(outs, outs + nr, [](double *o) { return o != nullptr; });
     psdc_break own[X_MAX_STAGES];
     size_t l = 0, nb = 0;
     rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
@@ -2840,15 +2851,24 @@ int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t mi
             if (!br.include)
                 continue;
             const size_t si = in.ns - 1 - i;
-            const double *a = &in.acc[si * ZAMPM_ROWS * b];
+            const double *a = &in.acc[si * nr * b];
             const double gsc = 1.0f / (psdrt::stage_gain(h->n, in.c64[si], h->nenbw, h->power) * (float)br.decimation);
-            for (int r = 0; r < ZAMPM_ROWS; ++r)
+            for (size_t r = 0; r < nr; ++r)
                 if (outs[r])
                     for (uint64_t k = br.bins_start; k < br.bins_end; ++k)
                         outs[r][br.start + (k - br.bins_start)] = a[r * b + k] * gsc;
         }
     }
     return PSDC_OK;
+}
+
+int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
+                        double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks,
+                        size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    double *outs[ZAMPM_ROWS] = {upper, lower, comp_re, comp_im};
+    return rows_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks,
+                               who);
 }
 
 } // namespace
@@ -2992,5 +3012,164 @@ int psdc_iqampm_stats_read(psdc_iqampm *h, uint64_t *launches, uint64_t *samples
 }
 
 const char *psdc_iqampm_last_error(const psdc_iqampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+} // extern "C"
+
+// ---- AM/PM cross: the zoom cross / IQ cross object on zoom_ampm_cross_kernel, the twelve rows of zoom_ampm_cross_fft.h ----
+
+namespace {
+
+// the twelve f64 rows of one stage as they lie on the device: rows[12][n/2 + 1]
+int xampm_stage_rows_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows, const char *who)
+{
+    std::vector<double> acc;
+    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, who);
+    if (rc)
+        return rc;
+    std::copy(acc.begin(), acc.end(), rows);
+    return PSDC_OK;
+}
+
+// the twelve rows stitched in f64 into rows[12][cap] (rows_sidebands_impl: one set of Breaks, from rows 0 and 1 -- the zoom
+// read-out's of channel a)
+int xampm_sidebands_impl(XObj *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows, size_t cap,
+                         size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+{
+    double *outs[ZXAMPM_ROWS];
+    for (int r = 0; r < ZXAMPM_ROWS; ++r)
+        outs[r] = rows ? rows + (size_t)r * cap : nullptr;
+    return rows_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks, who);
+}
+
+} // namespace
+
+extern "C" {
+
+// (the twelve-row kernel uses no scratch at any size of the zoom cross object: none is refused beyond that object's)
+int psdc_zxampm_supported(uint32_t n) { return psdc_zcsd_supported(n); }
+
+psdc_zxampm *psdc_zxampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, int device)
+{
+    return static_cast<psdc_zxampm *>(create_impl(KINDS[K_ZXAMPM], n, win, power, nenbw, overlap, n_pairs, device, "psdc_zxampm_create_window"));
+}
+
+psdc_zxampm *psdc_zxampm_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    return static_cast<psdc_zxampm *>(create_kind(KINDS[K_ZXAMPM], n, window_kind, n_pairs, device, "psdc_zxampm_create"));
+}
+
+void psdc_zxampm_destroy(psdc_zxampm *h) { destroy_obj(h); }
+int psdc_zxampm_reset(psdc_zxampm *h) { return reset_impl(h, "psdc_zxampm_reset"); }
+int psdc_zxampm_set_detrend(psdc_zxampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zxampm_set_detrend"); }
+int psdc_zxampm_set_avg(psdc_zxampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_zxampm_set_avg"); }
+
+int psdc_zxampm_set_carrier(psdc_zxampm *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0)
+{
+    return pair_carrier_impl(h, pair, side, ftw, phase0, "psdc_zxampm_set_carrier");
+}
+
+int psdc_zxampm_process(psdc_zxampm *h, uint32_t pair, const float *x, const float *y, size_t len)
+{
+    const void *xs[2] = {x, y};
+    return zoom_feed(h, pair, xs, SampleFmt{}, len, false, nullptr, "psdc_zxampm_process");
+}
+
+int psdc_zxampm_process_device(psdc_zxampm *h, uint32_t pair, const float *d_x, const float *d_y, size_t len, void *producer_event)
+{
+    const void *xs[2] = {d_x, d_y};
+    return zoom_feed(h, pair, xs, SampleFmt{}, len, true, producer_event, "psdc_zxampm_process_device");
+}
+
+int psdc_zxampm_sync(psdc_zxampm *h) { return sync_impl(h, "psdc_zxampm_sync"); }
+int psdc_zxampm_num_stages(psdc_zxampm *h, uint32_t pair) { return num_stages_impl(h, pair, "psdc_zxampm_num_stages"); }
+
+int psdc_zxampm_stage_rows(psdc_zxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows)
+{
+    return xampm_stage_rows_impl(h, pair, stage, stat, rows, "psdc_zxampm_stage_rows");
+}
+
+int psdc_zxampm_sidebands(psdc_zxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
+                          size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return xampm_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap, n_breaks,
+                                "psdc_zxampm_sidebands");
+}
+
+int psdc_zxampm_stats_read(psdc_zxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    return stats_impl(h, launches, pairs_in, reset, "psdc_zxampm_stats_read");
+}
+
+const char *psdc_zxampm_last_error(const psdc_zxampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+int psdc_iqxampm_supported(uint32_t n) { return psdc_zxampm_supported(n); }
+
+psdc_iqxampm *psdc_iqxampm_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs, int device)
+{
+    return static_cast<psdc_iqxampm *>(create_impl(KINDS[K_IQXAMPM], n, win, power, nenbw, overlap, n_pairs, device, "psdc_iqxampm_create_window"));
+}
+
+psdc_iqxampm *psdc_iqxampm_create(uint32_t n, int window_kind, uint32_t n_pairs, int device)
+{
+    return static_cast<psdc_iqxampm *>(create_kind(KINDS[K_IQXAMPM], n, window_kind, n_pairs, device, "psdc_iqxampm_create"));
+}
+
+void psdc_iqxampm_destroy(psdc_iqxampm *h) { destroy_obj(h); }
+int psdc_iqxampm_reset(psdc_iqxampm *h) { return reset_impl(h, "psdc_iqxampm_reset"); }
+int psdc_iqxampm_set_detrend(psdc_iqxampm *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_iqxampm_set_detrend"); }
+int psdc_iqxampm_set_avg(psdc_iqxampm *h, uint32_t limit, uint32_t count) { return set_avg_impl(h, limit, count, "psdc_iqxampm_set_avg"); }
+
+int psdc_iqxampm_set_carrier(psdc_iqxampm *h, uint32_t pair, uint32_t side, uint64_t ftw, uint64_t phase0)
+{
+    return pair_carrier_impl(h, pair, side, ftw, phase0, "psdc_iqxampm_set_carrier");
+}
+
+int psdc_iqxampm_process(psdc_iqxampm *h, uint32_t pair, const float *ia, const float *qa, const float *ib, const float *qb, size_t len)
+{
+    const void *const src[4] = {ia, qa, ib, qb};
+    return iq_pair_feed(h, pair, src, false, SampleFmt{}, len, false, nullptr, "psdc_iqxampm_process");
+}
+
+int psdc_iqxampm_process_device(psdc_iqxampm *h, uint32_t pair, const float *d_ia, const float *d_qa, const float *d_ib, const float *d_qb,
+                                size_t len, void *producer_event)
+{
+    const void *const src[4] = {d_ia, d_qa, d_ib, d_qb};
+    return iq_pair_feed(h, pair, src, false, SampleFmt{}, len, true, producer_event, "psdc_iqxampm_process_device");
+}
+
+int psdc_iqxampm_process_interleaved(psdc_iqxampm *h, uint32_t pair, const float *za, const float *zb, size_t len)
+{
+    const void *const src[4] = {za, nullptr, zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, SampleFmt{}, len, false, nullptr, "psdc_iqxampm_process_interleaved");
+}
+
+int psdc_iqxampm_process_interleaved_device(psdc_iqxampm *h, uint32_t pair, const float *d_za, const float *d_zb, size_t len,
+                                            void *producer_event)
+{
+    const void *const src[4] = {d_za, nullptr, d_zb, nullptr};
+    return iq_pair_feed(h, pair, src, true, SampleFmt{}, len, true, producer_event, "psdc_iqxampm_process_interleaved_device");
+}
+
+int psdc_iqxampm_sync(psdc_iqxampm *h) { return sync_impl(h, "psdc_iqxampm_sync"); }
+int psdc_iqxampm_num_stages(psdc_iqxampm *h, uint32_t pair) { return num_stages_impl(h, pair, "psdc_iqxampm_num_stages"); }
+
+int psdc_iqxampm_stage_rows(psdc_iqxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows)
+{
+    return xampm_stage_rows_impl(h, pair, stage, stat, rows, "psdc_iqxampm_stage_rows");
+}
+
+int psdc_iqxampm_sidebands(psdc_iqxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
+                           size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
+{
+    return xampm_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap, n_breaks,
+                                "psdc_iqxampm_sidebands");
+}
+
+int psdc_iqxampm_stats_read(psdc_iqxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset)
+{
+    return stats_impl(h, launches, pairs_in, reset, "psdc_iqxampm_stats_read");
+}
+
+const char *psdc_iqxampm_last_error(const psdc_iqxampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

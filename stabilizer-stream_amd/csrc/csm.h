@@ -32,6 +32,7 @@ struct CsmBatch {
     int nblocks;
     int hop;
     int detrend;
+    int variant; // 0 unless set: which segment kernel launch_zoom_cross runs (zoom_ampm_cross_fft.h); the other launchers do not read it
     CsmJob jobs[CSM_MAX_JOBS];
 };
 

@@ -12,6 +12,8 @@
 // decimator hbf_dec8_kernel (kernels.hip), four jobs a (pair, stage).
 #include "zoom_cross.h"
 #include "cross_channel.h"
+#include "zoom_ampm_cross.h"
+#include "zoom_ampm_cross_fft.h"
 #include "zoom_cross_fft.h"
 
 namespace psdk {
@@ -120,6 +122,11 @@ hipError_t launch_zoom_cross(int n, const CsmBatch &b, const float *win, const c
 {
     if (b.nblocks <= 0)
         return hipSuccess;
+    // a batch of the AM/PM cross kinds (cross_runtime.cpp marks it): the same jobs on the twelve-row kernel
+    if (b.variant == ZCROSS_VARIANT_AMPM)
+        return launch_zoom_ampm_cross(n, b, win, tw, s);
+    if (b.variant != ZCROSS_VARIANT_CSD)
+        return hipErrorInvalidValue;
 #define X(NN)                                                                                                      \
     if (n == NN) {                                                                                                 \
         hipLaunchKernelGGL(zoom_cross_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw); \

@@ -75,6 +75,13 @@ and B is ZoomAmPmCascadeBank(n, 1) fed x.  Second leg (the only one of --iq): A 
 IqCascadeBank, and B the AM/PM bank: the cost of the two extra rows and the natural-order pass.  A, B, A in turn --reps times; B / A
 of every turn, the largest |A' - A| / A, B's launches a steady call and the live stages are recorded as findings, none is a gate.
 Each writes its family's entry ("zoom" / "iq") of profiles/zoom_ampm_probe.json unless --out names another file.
+--zoom --pair --ampm / --iq --pair --ampm: the AM/PM cross objects.  Two device-resident streams (real f32 / complex64, carrier 0.2
+on both sides) of 2^24 samples a call at N = 512, 1024, 4096, the windows and the sync of --sk.  A is the only way to the twelve
+rows without the object: a ZoomCsdCascadeBank(n, 2) whose pairs are (a:+ftw, b:+ftw) and (a:+ftw, b:-ftw) -- four mixers, four
+transforms, eight decimator jobs -- or, for --iq, an IqCsdCascadeBank(n, 2) fed (a, b) and (a, conj b).  B is
+ZoomAmPmCsdCascadeBank(n, 1) / IqAmPmCsdCascadeBank(n, 1) fed (a, b): two transforms.  A, B, A in turn --reps times; B / A of every
+turn, the largest |A' - A| / A, B's launches a steady call and the live stages are recorded as findings, none is a gate.  Each writes
+its family's entry ("zoom" / "iq") of profiles/zoom_ampm_cross_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -438,6 +445,56 @@ def ampm_legs(pkg, torch, seconds, reps, call, iq, recipe):
         spread = max(abs(y - u) / u for u, y in zip(a1, a2))
         r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
         legs.append({"n": n, "call": call, "a_gs_s": r3(a1), "b_ampm_gs_s": r3(b), "a_again_gs_s": r3(a2),
+                     "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3), "ratio_max": round(max(ratios), 3),
+                     "aa_spread_max": round(spread, 4), "b_beats_a_beyond_spread": bool(min(ratios) > 1 + spread),
+                     "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread),
+                     "b_launches_per_call": launches, "stages": zb.num_stages(0), "a_stages": za.num_stages(0)})
+        za.close()
+        zb.close()
+    return legs
+
+
+def ampm_pair_legs(pkg, torch, seconds, reps, call, iq):
+    """Two device-resident streams, carrier 0.2 on both sides: real f32 (iq False) or complex64 interleaved (iq True).
+    B: ZoomAmPmCsdCascadeBank / IqAmPmCsdCascadeBank, one pair.  A: the two-pair recipe on ZoomCsdCascadeBank (pair 1 with -ftw on
+    side b) / IqCsdCascadeBank (pair 1 fed conj b).  A / B / A in turn; a sample pair is one sample of each side."""
+    dt = torch.complex64 if iq else torch.float32
+    xa, xb = torch.randn(call, dtype=dt, device="cuda"), torch.randn(call, dtype=dt, device="cuda")
+    xc = torch.conj(xb).resolve_conj().contiguous() if iq else xb
+    torch.cuda.synchronize()
+    ftw = pkg.zoom_ftw(0.2)[0]
+    legs = []
+    for n in (512, 1024, 4096):
+        zb = (pkg.IqAmPmCsdCascadeBank if iq else pkg.ZoomAmPmCsdCascadeBank)(n, 1)
+        zb.set_carrier(0, ftw=ftw)
+        za = (pkg.IqCsdCascadeBank if iq else pkg.ZoomCsdCascadeBank)(n, 2)
+        za.set_carrier(0, ftw=ftw)
+        za.set_carrier(1, ftw=ftw, side=0)
+        za.set_carrier(1, ftw=ftw if iq else (-ftw) % (1 << 64), side=1)
+
+        def a_step():
+            za.process_device(0, xa.data_ptr(), xb.data_ptr(), call)
+            za.process_device(1, xa.data_ptr(), xc.data_ptr(), call)
+            return call
+
+        def b_step():
+            zb.process_device(0, xa.data_ptr(), xb.data_ptr(), call)
+            return call
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+            b.append(timed(b_step, zb.sync, seconds)[0] / 1e9)
+            a2.append(timed(a_step, za.sync, seconds)[0] / 1e9)
+        zb.stats_read(reset=True)
+        for _ in range(8):
+            b_step()
+        launches = zb.stats_read()["launches"] / 8
+        zb.sync()
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+        legs.append({"n": n, "call": call, "a_gpairs_s": r3(a1), "b_gpairs_s": r3(b), "a_again_gpairs_s": r3(a2),
                      "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3), "ratio_max": round(max(ratios), 3),
                      "aa_spread_max": round(spread, 4), "b_beats_a_beyond_spread": bool(min(ratios) > 1 + spread),
                      "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread),
@@ -999,10 +1056,37 @@ def main():
                                                             "the converted stream, host-fed and device-resident")
     ap.add_argument("--ampm", action="store_true", help="with --zoom: ZoomAmPmCascadeBank against ZoomCsdCascadeBank fed (x, x) with "
                                                         "carriers +-ftw, and against ZoomCascadeBank; with --iq: IqAmPmCascadeBank "
-                                                        "against IqCascadeBank; writes profiles/zoom_ampm_probe.json")
+                                                        "against IqCascadeBank; writes profiles/zoom_ampm_probe.json; with --pair: "
+                                                        "ZoomAmPmCsdCascadeBank / IqAmPmCsdCascadeBank against the two-pair recipe on "
+                                                        "the eight-row object; writes profiles/zoom_ampm_cross_probe.json")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.ampm and a.pair:
+        if not (a.zoom or a.iq):
+            raise SystemExit("--pair --ampm goes with --zoom or --iq")
+        path = a.out or os.path.join(ROOT, "profiles", "zoom_ampm_cross_probe.json")
+        record = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                record = json.loads(f.read() or "{}")
+        record.update({"metric": "zoom_ampm_cross_gpairs_s", "unit": "1e9 sample pairs a second (one sample of each side; complex for iq)",
+                       "note": "findings, no gate: B is the AM/PM cross bank on one device-resident pair (two transforms a segment); A "
+                               "is the two-pair recipe on the eight-row object (four); not measured here: host memory, banks, the EWMA "
+                               "regime, N = 2048, two different carriers"})
+        for fam, on in (("zoom", a.zoom), ("iq", a.iq)):
+            if on:
+                before = gpu_state()
+                record[fam] = {"a": ("IqCsdCascadeBank(n, 2) fed (a, b) and (a, conj b)" if fam == "iq" else
+                                     "ZoomCsdCascadeBank(n, 2): pairs (a:+ftw, b:+ftw) and (a:+ftw, b:-ftw)"),
+                               "b": "IqAmPmCsdCascadeBank" if fam == "iq" else "ZoomAmPmCsdCascadeBank", "gpu_before": before,
+                               "legs": ampm_pair_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, fam == "iq"),
+                               "gpu_after": gpu_state()}
+        line = json.dumps(record)
+        print(line)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.ampm:
         if not (a.zoom or a.iq):
             raise SystemExit("--ampm goes with --zoom or --iq")

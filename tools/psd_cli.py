@@ -38,6 +38,12 @@ to DIR/zoomampm_<trace>_<F0>.csv / DIR/iqampm_<i>__<q>_<F0>.csv, the lines offse
 noise, phase noise and AM-PM cross spectra of the carrier (am_pm(): relative to the carrier, a linear small-modulation split).  The
 summary line gives the carrier's power, angle and lock (1: the carrier sits at F0; towards 0: it turned during the average and the
 split means nothing).
+--zoom-ampm-pair F0:X:Y (repeatable; as --zoom-pair) feeds the traces X and Y to a ZoomAmPmCsdCascade(512) with the carrier F0 on both
+sides, and --iq-ampm-pair IA:QA:IB:QB[:F0] (repeatable; as --iq-pair) two complex streams to an IqAmPmCsdCascade(512); no detrend,
+as for --zoom-ampm.  Each prints, or with --csv writes to DIR/zoomampmpair_<x>__<y>_<F0>.csv /
+DIR/iqampmpair_<ia>__<qa>__<ib>__<qb>_<F0>.csv, the lines offset, then Re and Im of s_am, s_pm, s_am_pm, s_pm_am: the cross spectra
+of the two channels' amplitude and phase modulation (am_pm_cross(): what both channels share stays, each channel's own noise
+averages down).  The summary line gives p_ab = |A_a| |A_b|, the angles of w = conj(v_a) v_b and q = v_a v_b, and the two locks.
 --sample-format s16|s8 (default f32: everything above, unchanged) reads raw INTEGER files and feeds them as they are through the
 integer feeds (process_int; the device converts, sample = integer * --scale, default 2^-15 for s16 and 2^-7 for s8).  The options
 then name files, and no --file / --raw is read: --zoom F0:FILE and --zoom-pair F0:FILEA:FILEB take files of real integers, --iq
@@ -91,6 +97,10 @@ def main(argv=None):
                     help="F0[:TRACE] -- amplitude and phase noise spectra of the carrier F0 of that trace (repeatable)")
     ap.add_argument("--iq-ampm", action="append", default=[],
                     help="I:Q[:F0] -- amplitude and phase noise spectra of the carrier of the complex stream I + i Q (repeatable)")
+    ap.add_argument("--zoom-ampm-pair", action="append", default=[],
+                    help="F0:X:Y -- cross spectra of the amplitude and phase modulation of traces X and Y on the carrier F0 (repeatable)")
+    ap.add_argument("--iq-ampm-pair", action="append", default=[],
+                    help="IA:QA:IB:QB[:F0] -- cross spectra of the amplitude and phase modulation of two complex streams (repeatable)")
     ap.add_argument("--sample-format", default="f32", choices=["f32", "s16", "s8"],
                     help="s16 / s8: --raw, --pair, --zoom, --zoom-pair, --iq and --iq-pair name raw integer files (real integers / interleaved pairs)")
     ap.add_argument("--scale", type=float, default=None, help="with --sample-format s16 / s8: sample = integer * SCALE (default 2^-15 / 2^-7)")
@@ -108,7 +118,7 @@ def main(argv=None):
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
-    if (a.iq or a.iq_pair or a.iq_sk or a.iq_ampm) and not a.file:  # the planar raw files: the only input these options need
+    if (a.iq or a.iq_pair or a.iq_sk or a.iq_ampm or a.iq_ampm_pair) and not a.file:  # the planar raw files: the only input these options need
         merge = pkg.MergeOpts(keep_overlap=a.keep_overlap, min_count=a.avg_min, keep_transition_band=a.keep_transition_band)
         if a.csv:
             os.makedirs(a.csv, exist_ok=True)
@@ -120,6 +130,8 @@ def main(argv=None):
             iq_streams(pkg, source, a, merge, None)
         if a.iq_pair:
             iq_pairs(pkg, source, a, merge, None)
+        if a.iq_ampm_pair:
+            iq_ampm_pairs(pkg, source, a, merge, None)
         if not a.raw:
             return 0
     integral_start, integral_end = a.integral_start * a.fs, a.integral_end * a.fs  # src/bin/psd.rs:161-162
@@ -178,6 +190,10 @@ def main(argv=None):
         iq_streams(pkg, source, a, merge, names)
     if a.iq_pair and a.file:
         iq_pairs(pkg, source, a, merge, names)
+    if a.zoom_ampm_pair:
+        zoom_ampm_pairs(pkg, source, a, merge, names)
+    if a.iq_ampm_pair and a.file:
+        iq_ampm_pairs(pkg, source, a, merge, names)
     loss = bank.loss()
     if not a.raw:
         tot = loss["received"] + loss["dropped"]
@@ -517,24 +533,25 @@ def iq_streams(pkg, source, a, merge, names):
     bank.close()
 
 
-def iq_pairs(pkg, source, a, merge, names):
-    """--iq-pair: four traces of every read (host_traces), or four raw f32 files (names None), into one IQ cross cascade per pair,
-    one carrier on both sides"""
+def iq_pair_feed(pkg, source, a, make_bank, args, names, opt, detrend=None):
+    """parse the IA:QA:IB:QB[:F0] arguments of `opt`, settle a bank of make_bank(n, n_pairs) (AcqOpts, one carrier on both sides of a
+    pair) and feed it: four traces of every read (host_traces), or four raw f32 files (names None).  detrend: in place of
+    --detrend.  Returns the bank, the carriers in use and the four labels of every pair."""
     want = []
-    for z in a.iq_pair:
+    for z in args:
         parts = z.split(":")
         if len(parts) not in (4, 5) or not all(parts[:4]):
-            raise SystemExit("--iq-pair takes IA:QA:IB:QB[:F0]")
+            raise SystemExit(opt + " takes IA:QA:IB:QB[:F0]")
         want.append((tuple(parts[:4]), float(parts[4]) if len(parts) == 5 else 0.0))
-    bank = pkg.IqCsdCascadeBank(1 << 9, len(want))
-    bank.set_detrend(pkg.Detrend[a.detrend.upper()])
+    bank = make_bank(1 << 9, len(want))
+    bank.set_detrend(pkg.Detrend[a.detrend.upper()] if detrend is None else detrend)
     bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
     used = [bank.set_carrier(i, f0=f0) for i, (_, f0) in enumerate(want)]
     if names is None:
         labels = [tuple(os.path.basename(f) for f in files) for files, _ in want]
         for p, (files, _) in enumerate(want):
             if len({os.path.getsize(f) for f in files}) != 1:
-                raise SystemExit("--iq-pair: " + ", ".join(files) + " differ in length")
+                raise SystemExit(opt + ": " + ", ".join(files) + " differ in length")
             fh = [open(f, "rb") for f in files]
             fed = 0
             while a.max_bytes is None or fed < a.max_bytes:
@@ -546,9 +563,15 @@ def iq_pairs(pkg, source, a, merge, names):
             for f in fh:
                 f.close()
     else:
-        idx = [tuple(trace_arg(t, names, "--iq-pair") for t in tr) for tr, _ in want]
+        idx = [tuple(trace_arg(t, names, opt) for t in tr) for tr, _ in want]
         labels = [tuple(names[i] for i in four) for four in idx]
         host_traces(source, pkg, a, idx, lambda p, xs: bank.process(p, (xs[0], xs[1]), (xs[2], xs[3])))
+    return bank, used, labels
+
+
+def iq_pairs(pkg, source, a, merge, names):
+    """--iq-pair: four traces of every read, or four raw f32 files (names None), into one IQ cross cascade per pair (iq_pair_feed)"""
+    bank, used, labels = iq_pair_feed(pkg, source, a, pkg.IqCsdCascadeBank, a.iq_pair, names, "--iq-pair")
     for p, lab in enumerate(labels):
         label = f"iq pair {lab[0]}:{lab[1]}:{lab[2]}:{lab[3]} @ {used[p]:.12g}"
         if bank.num_stages(p) == 0:
@@ -566,6 +589,55 @@ def iq_pairs(pkg, source, a, merge, names):
                 f.writelines(lines)
         else:
             sys.stdout.writelines(lines)
+    bank.close()
+
+
+def ampm_pair_report(pkg, bank, p, label, stem, a, merge):
+    """the read-out of one pair of a ZoomAmPmCsdCascadeBank / IqAmPmCsdCascadeBank: the summary line with the carriers, and offset,
+    then Re and Im of s_am, s_pm, s_am_pm, s_pm_am in the order of the Breaks"""
+    if bank.num_stages(p) == 0 or bank.stage_rows(p, 0)[0]["count"] == 0:
+        print(f"{label}: no samples")
+        return
+    p_ab, w, q, lock_w, lock_q = bank.carriers(p)
+    *spectra, breaks = bank.am_pm_cross(p, opts=merge)
+    off = pkg.Break.frequencies(breaks) * a.fs
+    print(f"{label}: stages {bank.num_stages(p)} bins {spectra[0].size} breaks {len(breaks)} p_ab {p_ab:.9g} "
+          f"angle w {np.angle(w):.9g} angle q {np.angle(q):.9g} lock_w {lock_w:.9g} lock_q {lock_q:.9g}")
+    lines = [f"{o:.9g}," + ",".join(f"{v.real:.9g},{v.imag:.9g}" for v in row) + "\n" for o, *row in zip(off, *spectra)]
+    if a.csv:
+        safe = "".join(ch if ch.isalnum() else "_" for ch in stem)
+        with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+            f.writelines(lines)
+    else:
+        sys.stdout.writelines(lines)
+
+
+def zoom_ampm_pairs(pkg, source, a, merge, names):
+    """--zoom-ampm-pair: the two named traces of every read (host_traces) into one AM/PM cross cascade per pair, one carrier on both
+    sides; no detrend (carriers() reads bin 0)"""
+    want = []
+    for z in a.zoom_ampm_pair:
+        parts = z.split(":")
+        if len(parts) != 3:
+            raise SystemExit("--zoom-ampm-pair takes F0:X:Y")
+        want.append((float(parts[0]), trace_arg(parts[1], names, "--zoom-ampm-pair"), trace_arg(parts[2], names, "--zoom-ampm-pair")))
+    bank = pkg.ZoomAmPmCsdCascadeBank(1 << 9, len(want))
+    bank.set_avg(pkg.AvgOpts(limit=max(0, a.avg_max - 1), count=max(0, a.avg - 1)))
+    used = [bank.set_carrier(i, f0=f0) for i, (f0, _, _) in enumerate(want)]
+    host_traces(source, pkg, a, [(x, y) for _, x, y in want], lambda i, xs: bank.process(i, xs[0], xs[1]))
+    for i, (_, x, y) in enumerate(want):
+        ampm_pair_report(pkg, bank, i, f"zoom am/pm pair {names[x]}:{names[y]} @ {used[i]:.12g}",
+                         f"zoomampmpair_{names[x]}__{names[y]}_{used[i]:.9g}", a, merge)
+    bank.close()
+
+
+def iq_ampm_pairs(pkg, source, a, merge, names):
+    """--iq-ampm-pair: four traces of every read, or four raw f32 files (names None), into one IQ AM/PM cross cascade per pair"""
+    bank, used, labels = iq_pair_feed(pkg, source, a, pkg.IqAmPmCsdCascadeBank, a.iq_ampm_pair, names, "--iq-ampm-pair",
+                                      detrend=pkg.Detrend.NONE)
+    for p, lab in enumerate(labels):
+        ampm_pair_report(pkg, bank, p, f"iq am/pm pair {lab[0]}:{lab[1]}:{lab[2]}:{lab[3]} @ {used[p]:.12g}",
+                         f"iqampmpair_{lab[0]}__{lab[1]}__{lab[2]}__{lab[3]}_{used[p]:.9g}", a, merge)
     bank.close()
 
 
