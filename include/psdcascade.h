@@ -1487,6 +1487,113 @@ int psdc_iqxampm_sidebands(psdc_iqxampm *h, uint32_t pair, int keep_overlap, uin
 int psdc_iqxampm_stats_read(psdc_iqxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset);
 const char *psdc_iqxampm_last_error(const psdc_iqxampm *h);
 
+/* ---- waterfall cascades: time-resolved PSD and SK per stage ---------------------------------------------------------
+ * Every other object averages over the whole stream: one set of accumulator rows a stage, read as the average since the last
+ * reset.  These two keep, per stage, a ring of the most recent BLOCKS of segments, so that a spectrum that moves in time (a
+ * drifting carrier, a mode hop, a spur that comes and goes, a servo ringing after a step) can be seen moving.  psdc_wf_* is the
+ * spectral kurtosis object (real streams, fed as psdc_sk_* is) and psdc_zwf_* the zoom spectral kurtosis object (a real stream
+ * mixed down from a carrier, fed as psdc_zsk_* is); the segment kernels, mixers, decimators and feeds are theirs, unchanged.
+ * Construction: creation takes the sibling's arguments and
+ *     block  B: segments a ring row, 2 ... 2^24 (SK needs M >= 2),
+ *     depth  K: ring rows a stage, K >= 1.
+ * A (channel, stage) ring is K * rows * (n/2 + 1) * 8 bytes (rows: 2 for psdc_wf, 4 for psdc_zwf); creation fails with
+ * PSDC_ERR_ARG and a text naming the numbers when that exceeds 2^27 bytes.  Rings are allocated with their stages, lazily.
+ * Sizes and windows are those of psdc_sk_supported / psdc_zsk_supported.  set_detrend and (psdc_zwf) set_carrier are the
+ * siblings'.  There is no set_avg: every segment has weight 1.
+ * Blocks and ring slots: block b of stage k is the segments [b B, (b + 1) B) of that stage, counted from the stream's start or
+ * the last reset.  Block b lives in ring slot b mod K; the ring holds the newest min(K, blocks started) blocks.  The newest
+ * block may be partial: its count is the number of its segments folded so far; every other block's count is B.  A slot holds
+ * the sibling's rows of its block: S1 = sum P and S2 = sum P^2 (psdc_wf), or s1_upper, s1_lower, s2_upper, s2_lower (psdc_zwf).
+ * A block that takes a slot over OVERWRITES it: what the slot held, a NaN included, does not decay into the new block.
+ * Stage k's blocks are 8^k times longer in input time than stage 0's: the cascade's constant relative resolution, in time too.
+ * Nominal time: block b of stage k nominally covers the input samples
+ *     [b B hop 8^k,  ((b + 1) B - 1) hop 8^k + n 8^k),      hop = n - overlap.
+ * The decimators' delay (their filter length and the 35 drained outputs a stage) is NOT included: a deeper stage's blocks lie
+ * later in input time than this by that delay.
+ * Feeding and draining: process, process_device, sync, reset, num_stages and stats_read behave as on the siblings; read-outs
+ * drain.  A steady round whose pieces fit one job table costs the sibling's launches (3, and 1 + 3 for psdc_zwf); a round that
+ * crosses many blocks is cut into one segment-kernel job a block and may take further launches, and a round longer than a ring
+ * folds into a slot once a launch, in block order.  Host and device calls of the same samples, and the same calls twice, give
+ * the same bits.
+ * Read-outs: psdc_*_stage_blocks reports a stage's ring; psdc_*_stage_rows returns the raw f64 moment rows of the newest
+ * `max_rows` blocks, oldest first, with each row's absolute block index and count; psdc_*_image turns them into f32 images on the
+ * device (csrc/waterfall.hip), oldest block first:
+ *     psd[r][k] = float32(S1[r][k] * (double)gsc_r),   gsc_r = 1.0f / (gain(n, count_r) * (float)8^stage),
+ * the f32 factor the merged read-out applies to an included stage of that count and decimation (src/psd.rs:515-517), and
+ *     sk[r][k]  = float32((M + 1) / (M - 1) * (M S2 / S1^2 - 1)),   M = count_r, evaluated in f64,
+ * NaN where count_r < 2 or S1 == 0, as the spectral kurtosis object defines it.  psdc_wf images are [rows][n/2 + 1];
+ * psdc_zwf images are [rows][2][n/2 + 1], side 0 upper and side 1 lower.
+ * Out of scope: IQ feeds, stream frames, `loss` and integer feeds; averaging schedules and EWMA; cross, matrix and AM/PM
+ * waterfalls; skipping pieces of blocks that the same round overwrites; compensating the decimators' delay in the nominal
+ * time; more than one GPU an object.  There is no CPU fallback. */
+typedef struct psdc_wf psdc_wf;
+typedef struct psdc_zwf psdc_zwf;
+/* what a stage's ring holds */
+typedef struct psdc_wf_blocks {
+    uint32_t block;        /* B: segments a block */
+    uint32_t depth;        /* K: ring rows */
+    uint64_t started;      /* blocks started since the stream's start or the last reset */
+    uint32_t rows_valid;   /* min(K, started) */
+    uint32_t newest_count; /* segments folded into the newest block, 1 ... B (0 before the first segment) */
+    uint64_t pending;      /* as psdc_stage_stat.pending */
+} psdc_wf_blocks;
+/* 1 where n is a size the object takes, else 0 (psdc_sk_supported) */
+int psdc_wf_supported(uint32_t n);
+psdc_wf *psdc_wf_create(uint32_t n, int window_kind, uint32_t n_channels, uint32_t block, uint32_t depth, int device);
+psdc_wf *psdc_wf_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                               uint32_t block, uint32_t depth, int device);
+void psdc_wf_destroy(psdc_wf *h);
+/* stages, rings, buffers, the detrend setting and statistics; block and depth stay */
+int psdc_wf_reset(psdc_wf *h);
+int psdc_wf_set_detrend(psdc_wf *h, int detrend_kind);
+/* as psdc_sk_process / psdc_sk_process_device */
+int psdc_wf_process(psdc_wf *h, uint32_t channel, const float *x, size_t len);
+int psdc_wf_process_device(psdc_wf *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_wf_sync(psdc_wf *h);
+int psdc_wf_num_stages(psdc_wf *h, uint32_t channel);
+int psdc_wf_stage_blocks(psdc_wf *h, uint32_t channel, uint32_t stage, psdc_wf_blocks *out);
+/* the newest min(max_rows, rows_valid) blocks, oldest first: *n_rows of them; block_index, counts: max_rows entries, always
+ * written; s1, s2: [max_rows][n/2 + 1] doubles, either may be NULL */
+int psdc_wf_stage_rows(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, uint64_t *block_index, uint32_t *counts,
+                       double *s1, double *s2, uint32_t *n_rows);
+/* the same rows as images: psd, sk [max_rows][n/2 + 1] floats in host memory, either (not both) may be NULL */
+int psdc_wf_image(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *psd, float *sk, uint64_t *block_index,
+                  uint32_t *counts, uint32_t *n_rows);
+/* the same with d_psd, d_sk in device memory (min(max_rows, depth) rows each at most; the caller's own work on that memory must
+ * have completed); returns when the kernel has completed; block_index and counts are host arrays */
+int psdc_wf_image_device(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *d_psd, float *d_sk,
+                         uint64_t *block_index, uint32_t *counts, uint32_t *n_rows);
+int psdc_wf_stats_read(psdc_wf *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_wf_last_error(const psdc_wf *h);
+
+/* 1 where n is a size the object takes, else 0 (psdc_zsk_supported) */
+int psdc_zwf_supported(uint32_t n);
+psdc_zwf *psdc_zwf_create(uint32_t n, int window_kind, uint32_t n_channels, uint32_t block, uint32_t depth, int device);
+psdc_zwf *psdc_zwf_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels,
+                                 uint32_t block, uint32_t depth, int device);
+void psdc_zwf_destroy(psdc_zwf *h);
+/* as psdc_wf_reset, and the carriers */
+int psdc_zwf_reset(psdc_zwf *h);
+int psdc_zwf_set_detrend(psdc_zwf *h, int detrend_kind);
+/* as psdc_zsk_set_carrier */
+int psdc_zwf_set_carrier(psdc_zwf *h, uint32_t channel, uint64_t ftw, uint64_t phase0);
+/* as psdc_zsk_process / psdc_zsk_process_device */
+int psdc_zwf_process(psdc_zwf *h, uint32_t channel, const float *x, size_t len);
+int psdc_zwf_process_device(psdc_zwf *h, uint32_t channel, const float *d_x, size_t len, void *producer_event);
+int psdc_zwf_sync(psdc_zwf *h);
+int psdc_zwf_num_stages(psdc_zwf *h, uint32_t channel);
+int psdc_zwf_stage_blocks(psdc_zwf *h, uint32_t channel, uint32_t stage, psdc_wf_blocks *out);
+/* as psdc_wf_stage_rows, the four rows of a slot: [max_rows][n/2 + 1] doubles each, any may be NULL */
+int psdc_zwf_stage_rows(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, uint64_t *block_index, uint32_t *counts,
+                        double *s1_upper, double *s1_lower, double *s2_upper, double *s2_lower, uint32_t *n_rows);
+/* as psdc_wf_image / psdc_wf_image_device; psd, sk: [max_rows][2][n/2 + 1] floats, side 0 upper, side 1 lower */
+int psdc_zwf_image(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *psd, float *sk, uint64_t *block_index,
+                   uint32_t *counts, uint32_t *n_rows);
+int psdc_zwf_image_device(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *d_psd, float *d_sk,
+                          uint64_t *block_index, uint32_t *counts, uint32_t *n_rows);
+int psdc_zwf_stats_read(psdc_zwf *h, uint64_t *launches, uint64_t *samples_in, int reset);
+const char *psdc_zwf_last_error(const psdc_zwf *h);
+
 /* Last error text of a handle; with h == NULL, of the calling thread's last
  * failed psdc_create / handle-less call. */
 const char *psdc_last_error(const psdc_handle *h);

@@ -144,6 +144,11 @@ class _CStageStat(C.Structure):
                 ("pending", C.c_uint64), ("processed", C.c_uint64)]
 
 
+class _CWfBlocks(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("depth", C.c_uint32), ("started", C.c_uint64),
+                ("rows_valid", C.c_uint32), ("newest_count", C.c_uint32), ("pending", C.c_uint64)]
+
+
 class _CLoss(C.Structure):
     _fields_ = [("received", C.c_uint64), ("dropped", C.c_uint64),
                 ("next_seq", C.c_uint32), ("have_seq", C.c_uint32)]
@@ -522,6 +527,25 @@ def lib():
     f("psdc_iqxampm_process_device", i32, [H, u32, vp, vp, vp, vp, sz, vp])
     f("psdc_iqxampm_process_interleaved", i32, [H, u32, fp, fp, sz])
     f("psdc_iqxampm_process_interleaved_device", i32, [H, u32, vp, vp, sz, vp])
+    up = C.POINTER(u32)
+    for pre, nrows in (("psdc_wf_", 2), ("psdc_zwf_", 4)):
+        f(pre + "supported", i32, [u32])
+        f(pre + "create", H, [u32, i32, u32, u32, u32, i32])
+        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, u32, u32, i32])
+        f(pre + "destroy", None, [H])
+        f(pre + "reset", i32, [H])
+        f(pre + "set_detrend", i32, [H, i32])
+        f(pre + "process", i32, [H, u32, fp, sz])
+        f(pre + "process_device", i32, [H, u32, vp, sz, vp])
+        f(pre + "sync", i32, [H])
+        f(pre + "num_stages", i32, [H, u32])
+        f(pre + "stage_blocks", i32, [H, u32, u32, C.POINTER(_CWfBlocks)])
+        f(pre + "stage_rows", i32, [H, u32, u32, u32, C.POINTER(u64), up] + [dp] * nrows + [up])
+        f(pre + "image", i32, [H, u32, u32, u32, fp, fp, C.POINTER(u64), up, up])
+        f(pre + "image_device", i32, [H, u32, u32, u32, vp, vp, C.POINTER(u64), up, up])
+        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
+        f(pre + "last_error", C.c_char_p, [H])
+    f("psdc_zwf_set_carrier", i32, [H, u32, u64, u64])
     _lib = L
     return L
 
@@ -599,6 +623,13 @@ EXPORTS = [
     "psdc_iqxampm_process_device", "psdc_iqxampm_process_interleaved", "psdc_iqxampm_process_interleaved_device",
     "psdc_iqxampm_sync", "psdc_iqxampm_num_stages", "psdc_iqxampm_stage_rows", "psdc_iqxampm_sidebands", "psdc_iqxampm_stats_read",
     "psdc_iqxampm_last_error",
+    "psdc_wf_supported", "psdc_wf_create", "psdc_wf_create_window", "psdc_wf_destroy", "psdc_wf_reset", "psdc_wf_set_detrend",
+    "psdc_wf_process", "psdc_wf_process_device", "psdc_wf_sync", "psdc_wf_num_stages", "psdc_wf_stage_blocks",
+    "psdc_wf_stage_rows", "psdc_wf_image", "psdc_wf_image_device", "psdc_wf_stats_read", "psdc_wf_last_error",
+    "psdc_zwf_supported", "psdc_zwf_create", "psdc_zwf_create_window", "psdc_zwf_destroy", "psdc_zwf_reset",
+    "psdc_zwf_set_detrend", "psdc_zwf_set_carrier", "psdc_zwf_process", "psdc_zwf_process_device", "psdc_zwf_sync",
+    "psdc_zwf_num_stages", "psdc_zwf_stage_blocks", "psdc_zwf_stage_rows", "psdc_zwf_image", "psdc_zwf_image_device",
+    "psdc_zwf_stats_read", "psdc_zwf_last_error",
 ]
 
 
@@ -2337,6 +2368,291 @@ class IqSkCascade(ZoomSkCascade):
 
     def process_device_planar(self, pi, pq, length, after=None):
         self._b.process_device_planar(0, pi, pq, length, after)
+
+
+def waterfall_supported(n):
+    """Whether WaterfallCascade[Bank] takes the size n (sk_supported)"""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_wf_supported(n))
+
+
+def zoom_waterfall_supported(n):
+    """Whether ZoomWaterfallCascade[Bank] takes the size n (zoom_sk_supported)"""
+    return 0 <= n < (1 << 32) and bool(lib().psdc_zwf_supported(n))
+
+
+def waterfall_block_span(n, overlap, block, stage, b):
+    """range of the input samples that block b of `stage` of a waterfall cascade nominally covers:
+    [b B hop 8^stage, ((b + 1) B - 1) hop 8^stage + n 8^stage) with hop = n - overlap.  The decimators' delay is not included: a
+    deeper stage's blocks lie later in input time by it."""
+    hop, d = n - overlap, 8 ** stage
+    return range(b * block * hop * d, ((b + 1) * block - 1) * hop * d + n * d)
+
+
+class WaterfallCascadeBank:
+    """`n_channels` independent waterfall cascades (psdc_wf_*): SkCascadeBank's stages, but every stage keeps a ring of its
+    `depth` most recent blocks of `block` segments, each with its own S1 = sum P and S2 = sum P^2, where SkCascadeBank keeps one
+    average.  image() gives a stage's PSD and spectral kurtosis against time, oldest block first; stage k's blocks are 8^k times
+    longer than stage 0's.  Every segment has weight 1: there is no set_avg."""
+
+    _P = "psdc_wf_"
+    _ROWS = 2
+
+    def __init__(self, n, n_channels=1, block=64, depth=64, window=Window.HANN, device=0):
+        self.n, self.n_channels, self.block, self.depth, self.window, self.device = n, n_channels, block, depth, window, device
+        self._L = lib()
+        bad = [k for k, v in (("n", n), ("n_channels", n_channels), ("block", block), ("depth", depth)) if not 0 <= v <= U32_MAX]
+        if bad:
+            raise PsdError(ERR_ARG, f"{self._P}create: {bad[0]} must be in [0, 2^32)")
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._wt = window
+            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, block, depth, device)
+        else:
+            self._wt = None
+            self._h = self._f("create")(n, int(window), n_channels, block, depth, device)
+        if not self._h:
+            msg = self._f("last_error")(None)
+            msg = msg.decode() if msg else ""
+            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
+            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
+
+    def _f(self, name):
+        return getattr(self._L, self._P + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._f("last_error")(self._h)
+            raise PsdError(rc, msg.decode() if msg else "")
+        return rc
+
+    def _table(self):
+        if self._wt is None:
+            self._wt = WindowTable._kind(self.n, self.window)
+        return self._wt
+
+    def reset(self):
+        self._ck(self._f("reset")(self._h))
+
+    def set_detrend(self, d):
+        self._ck(self._f("set_detrend")(self._h, int(d)))
+
+    def process(self, channel, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        self._ck(self._f("process")(self._h, channel, _fptr(x), x.size))
+
+    def process_device(self, channel, ptr, length, after=None):
+        """ptr: device address of `length` f32 samples; after: a hipEvent_t handle recorded behind their producer, or None
+        when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
+        self._ck(self._f("process_device")(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
+
+    def sync(self):
+        self._ck(self._f("sync")(self._h))
+
+    def num_stages(self, channel=0):
+        return self._ck(self._f("num_stages")(self._h, channel))
+
+    def stage_blocks(self, channel, stage):
+        """dict(block, depth, started, rows_valid, newest_count, pending) of one stage's ring"""
+        b = _CWfBlocks()
+        self._ck(self._f("stage_blocks")(self._h, channel, stage, C.byref(b)))
+        return {k: int(getattr(b, k)) for k, _ in _CWfBlocks._fields_}
+
+    def _cap(self, max_rows):
+        cap = self.depth if max_rows is None else int(max_rows)
+        if not 0 <= cap <= U32_MAX:
+            raise PsdError(ERR_ARG, "max_rows must be in [0, 2^32)")
+        return min(cap, self.depth)
+
+    def stage_rows(self, channel, stage, max_rows=None):
+        """(block_index, counts, s1, s2): the raw f64 moment rows [rows][n/2 + 1] of the newest `max_rows` blocks (default: all
+        the ring holds), oldest first, with each row's absolute block index and its number of segments"""
+        cap = self._cap(max_rows)
+        b = self.n // 2 + 1
+        idx, cnt, nr = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32), C.c_uint32()
+        rows = [np.empty((max(cap, 1), b), np.float64) for _ in range(self._ROWS)]
+        dp = C.POINTER(C.c_double)
+        self._ck(self._f("stage_rows")(self._h, channel, stage, cap, idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       cnt.ctypes.data_as(C.POINTER(C.c_uint32)), *(r.ctypes.data_as(dp) for r in rows), C.byref(nr)))
+        m = nr.value
+        return (idx[:m].copy(), cnt[:m].copy(), *(r[:m].copy() for r in rows))
+
+    def _image_shape(self, rows):
+        return (rows, self.n // 2 + 1)
+
+    def image(self, channel, stage, max_rows=None):
+        """(psd, sk, block_index, counts): float32 images [rows][n/2 + 1] of the newest `max_rows` blocks, oldest first, made on
+        the device: psd is S1 scaled as the merged read-out scales an included stage of the row's count, sk the spectral
+        kurtosis of the row's own segments (NaN below two segments and without power)"""
+        cap = self._cap(max_rows)
+        idx, cnt, nr = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32), C.c_uint32()
+        psd, sk = np.empty(self._image_shape(max(cap, 1)), np.float32), np.empty(self._image_shape(max(cap, 1)), np.float32)
+        self._ck(self._f("image")(self._h, channel, stage, cap, _fptr(psd), _fptr(sk), idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                  cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nr)))
+        m = nr.value
+        return psd[:m].copy(), sk[:m].copy(), idx[:m].copy(), cnt[:m].copy()
+
+    def image_device(self, channel, stage, psd_ptr, sk_ptr, max_rows=None):
+        """image() written into device memory: psd_ptr, sk_ptr are device addresses (a torch tensor's data_ptr()) of
+        min(max_rows, depth) x the row shape of image() float32 each, either may be None.  Returns (block_index, counts) when the
+        kernel has completed; their length is the number of rows written."""
+        cap = self._cap(max_rows)
+        idx, cnt, nr = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32), C.c_uint32()
+        self._ck(self._f("image_device")(self._h, channel, stage, cap, C.c_void_p(psd_ptr) if psd_ptr else None,
+                                         C.c_void_p(sk_ptr) if sk_ptr else None, idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nr)))
+        m = nr.value
+        return idx[:m].copy(), cnt[:m].copy()
+
+    def block_span(self, stage, b):
+        """range of the input samples block b of `stage` nominally covers:
+        [b B hop 8^stage, ((b + 1) B - 1) hop 8^stage + n 8^stage).  The decimators' delay is not included."""
+        return waterfall_block_span(self.n, self._table().overlap, self.block, stage, b)
+
+    def _recent(self, channel, blocks, opts, nsides):
+        ns = self.num_stages(channel)
+        counts, avgs, pend = [], [], []
+        rows = np.zeros((nsides, max(ns, 1), self.n // 2 + 1), np.float32)
+        for k in range(ns):
+            got = self.stage_rows(channel, k, blocks)
+            counts.append(int(got[1].sum()))
+            avgs.append(U32_MAX >> (3 * k) if 3 * k < 32 else 0)
+            pend.append(self.stage_blocks(channel, k)["pending"])
+            for s in range(nsides):
+                rows[s, k] = got[2 + s].sum(axis=0)
+        out = [stitch(self.n, counts, avgs, pend, rows[s, :ns], opts, window=self._table()) for s in range(nsides)]
+        return [o[0] for o in out], out[0][1]
+
+    def recent_psd(self, channel=0, blocks=1, opts=MergeOpts()):
+        """(psd, breaks): the stitched log-resolution spectrum of the recent past: per stage the sum of its newest `blocks` ring
+        rows (None: all it holds), merged by stitch() with the summed counts"""
+        p, br = self._recent(channel, blocks, opts, 1)
+        return p[0], br
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, "samples_in": si.value}
+
+    stats = stats_read
+
+
+class ZoomWaterfallCascadeBank(WaterfallCascadeBank):
+    """`n_channels` independent zoom waterfall cascades (psdc_zwf_*): ZoomSkCascadeBank's carrier, mixer and two-sided stages with
+    a ring of blocks a stage.  Fed as ZoomCascadeBank is.  Rows come per side, images as [rows][2][n/2 + 1] with side 0 the
+    upper and side 1 the lower sideband."""
+
+    _P = "psdc_zwf_"
+    _ROWS = 4
+
+    def __init__(self, n, n_channels=1, f0=None, ftw=None, block=64, depth=64, window=Window.HANN, device=0):
+        super().__init__(n, n_channels, block, depth, window, device)
+        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}
+        if f0 is not None or ftw is not None:
+            for c in range(n_channels):
+                self.set_carrier(c, f0=f0, ftw=ftw)
+
+    def reset(self):
+        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
+        super().reset()
+        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
+
+    set_carrier = _CarrierRowsBank.set_carrier
+
+    def stage_rows(self, channel, stage, max_rows=None):
+        """(block_index, counts, s1_upper, s1_lower, s2_upper, s2_lower), as WaterfallCascadeBank.stage_rows per side"""
+        return super().stage_rows(channel, stage, max_rows)
+
+    def _image_shape(self, rows):
+        return (rows, 2, self.n // 2 + 1)
+
+    def recent_psd(self, channel=0, blocks=1, opts=MergeOpts()):
+        """(upper, lower, breaks): WaterfallCascadeBank.recent_psd of each side, as ZoomCascadeBank.psd() lays them out"""
+        p, br = self._recent(channel, blocks, opts, 2)
+        return p[0], p[1], br
+
+
+class WaterfallCascade:
+    """One real stream: WaterfallCascade(n, block=64, depth=64).  image(stage) is that stage's PSD and SK against time."""
+
+    _BANK = WaterfallCascadeBank
+
+    def __init__(self, n, block=64, depth=64, window=Window.HANN, device=0):
+        self.n, self.block, self.depth = n, block, depth
+        self._b = self._BANK(n, 1, block=block, depth=depth, window=window, device=device)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def process(self, x):
+        self._b.process(0, x)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def stage_blocks(self, stage):
+        return self._b.stage_blocks(0, stage)
+
+    def stage_rows(self, stage, max_rows=None):
+        return self._b.stage_rows(0, stage, max_rows)
+
+    def image(self, stage, max_rows=None):
+        return self._b.image(0, stage, max_rows)
+
+    def image_device(self, stage, psd_ptr, sk_ptr, max_rows=None):
+        return self._b.image_device(0, stage, psd_ptr, sk_ptr, max_rows)
+
+    def block_span(self, stage, b):
+        return self._b.block_span(stage, b)
+
+    def recent_psd(self, blocks=1, opts=MergeOpts()):
+        return self._b.recent_psd(0, blocks, opts)
+
+    def reset(self):
+        self._b.reset()
+
+    def sync(self):
+        self._b.sync()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+    stats = stats_read
+
+    def close(self):
+        self._b.close()
+
+
+class ZoomWaterfallCascade(WaterfallCascade):
+    """One real stream around one carrier: ZoomWaterfallCascade(n, f0=0.2, block=64, depth=64) or (n, ftw=...).  `f0` is the
+    frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, block=64, depth=64, window=Window.HANN, device=0):
+        self.n, self.block, self.depth = n, block, depth
+        self._b = ZoomWaterfallCascadeBank(n, 1, block=block, depth=depth, window=window, device=device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0):
+        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
+        self.ftw, self.phase0 = self._b.carriers[0]
+        return self.f0
+
+    def reset(self):
+        self._b.reset()
+        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
 
 
 def zoom_ampm_supported(n):

@@ -39,12 +39,14 @@ struct CrossBatch {
 };
 
 // acc[r][k] = g_total acc[r][k] + sum_b partial[b][r][k], in f64, b in order; r < CrossPostBatch::nrows
+// fresh != 0: acc[r][k] = sum_b partial[b][r][k], and acc is not read (a waterfall ring slot taken over by a new block: what it
+// held may be anything, a NaN included, which g_total = 0 would keep)
 struct CrossFoldJob {
     const float *partial;
     double *acc; // [nrows][n/2 + 1]
     double g_total;
     int nparts;
-    int pad;
+    int fresh;
 };
 
 // carry a stream tail to the front of the other buffer: workgroups [block_begin, block_begin + nblocks) of the tail part of the

@@ -115,7 +115,10 @@ __global__ __launch_bounds__(POST_THREADS) void cross_post_kernel(const CrossPos
 #pragma unroll
             for (int i = 0; i < FOLD_SLICES; ++i)
                 s += part[i][lane];
-            job.acc[e] = job.g_total * job.acc[e] + s;
+            if (job.fresh)
+                job.acc[e] = s;
+            else
+                job.acc[e] = job.g_total * job.acc[e] + s;
         }
         return;
     }

@@ -37,6 +37,9 @@
 #include "zoom_ampm.h"
 #include "zoom_ampm_fft.h"
 #include "zoom_ampm_cross_fft.h"
+#include "waterfall.h"
+#include "waterfall_plan.h"
+#include "waterfall_read.h"
 #include "host_runtime.h"
 
 #include <algorithm>
@@ -57,6 +60,8 @@ hipError_t launch_zoom_mix_int(const SintMixJob &j, int kind, hipStream_t s);
 hipError_t launch_iq_mix_int(const SintMixJob &j, int kind, hipStream_t s);
 hipError_t launch_iq_pair_mix_int(const SintPairMixJob &j, int kind, hipStream_t s);
 inline hipError_t launch_cvt_int(const SintCvtJob &, int, hipStream_t) { return hipErrorInvalidValue; }
+// (nor a waterfall read-out kernel: psdc_wf_image[_device] fail there with a device error)
+inline hipError_t launch_wf_image(const WfImageJob &, hipStream_t) { return hipErrorInvalidValue; }
 } // namespace psdk
 #endif
 
@@ -83,11 +88,12 @@ struct XStage {
     uint64_t count64 = 0;
     XBuf buf;
     double *acc = nullptr; // device [rows][n/2 + 1]: xx, yy, re xy, im xy of a pair; the m * m rows of csm_fft.h of a group
+                           // (a waterfall kind: the stage's ring, [wf_depth] such row sets)
 };
 
 struct XObj;
 
-// What tells the thirteen families apart, one row each in KINDS (below XObj): the names in error texts, the streams and rows of a
+// What tells the fifteen families apart, one row each in KINDS (below XObj): the names in error texts, the streams and rows of a
 // unit, the feed in front of stage 0 and the segment kernel.  Everything else in this file is one runtime over these.
 enum class Feed {
     PLAIN, // the m streams are the caller's, copied (or converted) into stage 0
@@ -125,6 +131,9 @@ struct XObj {
     float power = 0.25f, nenbw = 1.5f;
     int detrend = PSDC_DETREND_NONE;
     uint32_t avg_limit = 0xFFFFFFFFu, avg_count = 0xFFFFFFFFu;
+    // waterfall kinds (include/psdcascade.h, "waterfall cascades"): segments a block and ring slots a stage; 0: not a waterfall
+    uint32_t wf_block = 0, wf_depth = 0;
+    size_t acc_sets() const { return wf_block ? wf_depth : 1; } // row sets a stage's `acc` holds
     hipStream_t stream = nullptr;
     // Device-fed samples are copied into stage 0 on a stream of their own, beside the kernels of the round before: the copy of
     // the samples of round R writes stage-0 buffer regions that only rounds <= R - 2 read (the round before has carried its
@@ -254,8 +263,8 @@ int add_stage(XObj *h, std::vector<XStage> &st)
     if (st.size() >= X_MAX_STAGES)
         return xfail(h, PSDC_ERR_ARG, std::string(h->kind->tag) + ": more than 16 stages");
     XStage s;
-    XCHK(h, hipMalloc(&s.acc, sizeof(double) * h->rows() * bins(h)));
-    XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * h->rows() * bins(h), h->stream));
+    XCHK(h, hipMalloc(&s.acc, sizeof(double) * h->acc_sets() * h->rows() * bins(h)));
+    XCHK(h, hipMemsetAsync(s.acc, 0, sizeof(double) * h->acc_sets() * h->rows() * bins(h), h->stream));
     st.push_back(s);
     return PSDC_OK;
 }
@@ -320,23 +329,38 @@ int run_round(XObj *h, bool *did)
             if (nb > (uint64_t)std::numeric_limits<int>::max() / 2)
                 return xfail(h, PSDC_ERR_ARG, std::string(h->kind->tag) + ": too many segments in one round");
             const uint32_t avg = cur_avg(h, k);
-            const EwmaPlan ew = plan_ewma(count_report(s.count64), avg, nb);
             PlannedCross pc{};
             CsmJob &cj = pc.job;
             for (int c = 0; c < nch; ++c)
                 cj.src[c] = s.buf.p[c][s.buf.cur];
             cj.src_base = (long long)s.buf.base;
-            cj.seg0 = (long long)s.segs;
-            cj.log2_gamma = ew.gamma > 0.0f ? std::log2((double)ew.gamma) : -std::numeric_limits<double>::infinity();
-            cj.nseg = (int)nb;
-            cj.ntiles = (int)((nb + spt - 1) / spt);
             cj.step0 = 1;
-            cj.nb = (int)ew.nb;
-            cj.is_m1 = (int)std::min<int64_t>(ew.i_s - 1, std::numeric_limits<int>::max());
-            cj.ewma = ew.ewma ? 1 : 0;
-            pc.fold.acc = s.acc;
-            pc.fold.g_total = ew.g_total;
-            cross.push_back(pc);
+            auto span = [&](uint64_t seg0, uint64_t nseg) {
+                cj.seg0 = (long long)seg0;
+                cj.nseg = (int)nseg;
+                cj.ntiles = (int)((nseg + spt - 1) / spt);
+            };
+            if (h->wf_block) {
+                // a waterfall stage: one job a piece of a block, every segment with weight 1, folded into the block's ring slot
+                pc.fold.g_total = 1.0;
+                wf_cut(s.segs, j_new, h->wf_block, h->wf_depth, [&](const WfPiece &p) {
+                    span(p.seg0, p.nseg);
+                    cj.nb = (int)p.nseg;
+                    pc.fold.acc = s.acc + (size_t)p.slot * h->rows() * bins(h);
+                    pc.fold.fresh = p.fresh ? 1 : 0;
+                    cross.push_back(pc);
+                });
+            } else {
+                const EwmaPlan ew = plan_ewma(count_report(s.count64), avg, nb);
+                span(s.segs, nb);
+                cj.log2_gamma = ew.gamma > 0.0f ? std::log2((double)ew.gamma) : -std::numeric_limits<double>::infinity();
+                cj.nb = (int)ew.nb;
+                cj.is_m1 = (int)std::min<int64_t>(ew.i_s - 1, std::numeric_limits<int>::max());
+                cj.ewma = ew.ewma ? 1 : 0;
+                pc.fold.acc = s.acc;
+                pc.fold.g_total = ew.g_total;
+                cross.push_back(pc);
+            }
             // decimator: samples [dec, p_new) of each channel, outputs m >= drain land in stage k + 1
             const uint64_t p_new = decimated_prefix(g, j_new);
             const uint64_t e_old = emitted_for(g, s.dec), e_new = emitted_for(g, p_new);
@@ -471,8 +495,13 @@ int run_round(XObj *h, bool *did)
         pb->nbins = (int)bins(h);
         pb->nrows = (int)h->rows();
         pb->fold_xb = cross_fold_blocks((int)h->rows(), (int)bins(h));
-        for (; fi < cross.size() && pb->nfold < CROSS_MAX_FOLD; ++fi)
+        for (; fi < cross.size() && pb->nfold < CROSS_MAX_FOLD; ++fi) {
+            // a round longer than a waterfall ring folds into a slot more than once: a launch's folds run in no order, so a slot's
+            // next fold waits for the next launch (the pieces are in segment order: the newest block is the one that stays)
+            if (h->wf_block && std::any_of(pb->fold, pb->fold + pb->nfold, [&](const CrossFoldJob &f) { return f.acc == cross[fi].fold.acc; }))
+                break;
             pb->fold[pb->nfold++] = cross[fi].fold;
+        }
         for (; ti < tails.size() && pb->ntail < CROSS_MAX_TAIL; ++ti) {
             CrossTailJob tj = tails[ti];
             tj.block_begin = pb->tail_blocks;
@@ -590,7 +619,8 @@ std::string zcsd_refusal(uint32_t n, uint32_t)
 // is psdc_zcsd with the IQ feed; psdc_sk is m = 1 on sk_kernel; psdc_zsk / psdc_iqsk are psdc_zoom / psdc_iq on zoom_sk_kernel;
 // psdc_zampm / psdc_iqampm are psdc_zoom / psdc_iq on zoom_ampm_kernel; psdc_zxampm / psdc_iqxampm are psdc_zcsd / psdc_iqcsd on
 // zoom_ampm_cross_kernel, which launch_zoom_cross runs for a batch marked ZCROSS_VARIANT_AMPM.
-enum Kind { K_CROSS, K_CSM, K_ZOOM, K_ZCSD, K_IQ, K_IQCSD, K_SK, K_ZSK, K_IQSK, K_ZAMPM, K_IQAMPM, K_ZXAMPM, K_IQXAMPM };
+// psdc_wf / psdc_zwf are psdc_sk / psdc_zsk with a ring of row sets a stage (XObj::wf_block, run_round).
+enum Kind { K_CROSS, K_CSM, K_ZOOM, K_ZCSD, K_IQ, K_IQCSD, K_SK, K_ZSK, K_IQSK, K_ZAMPM, K_IQAMPM, K_ZXAMPM, K_IQXAMPM, K_WF, K_ZWF };
 constexpr auto SPT_CROSS = [](int n, int) { return cross_segments_per_tile(n); };
 constexpr auto SPT_ZOOM = [](int n, int) { return zoom_segments_per_tile(n); };
 constexpr auto SPT_ZCSD = [](int n, int) { return zoom_cross_segments_per_tile(n); };
@@ -616,8 +646,10 @@ constexpr KindDesc KINDS[] = {
     {"psdc_iqampm", "channel", "n_channels", 2, ZAMPM_ROWS, Feed::IQ, SPT_ZOOM, launch_zoom_ampm, nullptr, nullptr},
     {"psdc_zxampm", "pair", "n_pairs", 4, ZXAMPM_ROWS, Feed::ZOOM, SPT_ZCSD, nullptr, GROUP_ZXAMPM, zcsd_refusal},
     {"psdc_iqxampm", "pair", "n_pairs", 4, ZXAMPM_ROWS, Feed::IQ, SPT_ZCSD, nullptr, GROUP_ZXAMPM, zcsd_refusal},
+    {"psdc_wf", "channel", "n_channels", 1, SK_ROWS, Feed::PLAIN, SPT_SK, launch_sk, nullptr, nullptr},
+    {"psdc_zwf", "channel", "n_channels", 2, ZSK_ROWS, Feed::ZOOM, SPT_ZOOM, launch_zoom_sk, nullptr, nullptr},
 };
-static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_IQXAMPM + 1, "one row a kind");
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == K_ZWF + 1, "one row a kind");
 
 // "": the arguments are fine
 std::string check_args(const KindDesc &kind, uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_pairs)
@@ -3171,5 +3203,331 @@ int psdc_iqxampm_stats_read(psdc_iqxampm *h, uint64_t *launches, uint64_t *pairs
 }
 
 const char *psdc_iqxampm_last_error(const psdc_iqxampm *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+} // extern "C"
+
+// ---- waterfall: the SK / zoom SK object with a ring of row sets a stage, one block of wf_block segments a slot (run_round cuts the
+// pieces); read out as raw moment rows or, through wf_image_kernel, as PSD and SK images ----
+
+namespace {
+
+constexpr uint64_t WF_MAX_BLOCK = (uint64_t)1 << 24;
+constexpr uint64_t WF_MAX_RING_BYTES = (uint64_t)1 << 27;
+
+// "": block, depth and the ring they make at size n are fine
+std::string wf_refusal(const KindDesc &kind, uint32_t n, uint32_t block, uint32_t depth)
+{
+    if (block < 2 || block > WF_MAX_BLOCK)
+        return "block = " + std::to_string(block) + ": block must be in [2, 2^24] segments (SK needs two)";
+    if (depth < 1)
+        return "depth = 0: depth must be at least 1 ring row a stage";
+    if (n > 4096)
+        return ""; // (the size is refused by name below)
+    const uint64_t bytes = (uint64_t)depth * kind.rows * (n / 2 + 1) * sizeof(double);
+    if (bytes > WF_MAX_RING_BYTES)
+        return "a stage's ring of depth " + std::to_string(depth) + " x " + std::to_string(kind.rows) + " rows x " +
+               std::to_string(n / 2 + 1) + " bins x 8 bytes = " + std::to_string(bytes) + " bytes: it must be at most 2^27 = " +
+               std::to_string(WF_MAX_RING_BYTES) + " bytes";
+    return "";
+}
+
+XObj *wf_create(Kind k, uint32_t n, int window_kind, const float *win, float power, float nenbw, size_t overlap, bool table,
+                uint32_t n_channels, uint32_t block, uint32_t depth, int device, const char *who)
+{
+    const std::string why = wf_refusal(KINDS[k], n, block, depth);
+    if (!why.empty()) {
+        xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": " + why);
+        return nullptr;
+    }
+    XObj *h = table ? create_impl(KINDS[k], n, win, power, nenbw, overlap, n_channels, device, who)
+                    : create_kind(KINDS[k], n, window_kind, n_channels, device, who);
+    if (h) {
+        h->wf_block = block;
+        h->wf_depth = depth;
+    }
+    return h;
+}
+
+// a drained stage of a waterfall object and what its ring holds
+struct WfStage {
+    const XStage *s = nullptr;
+    uint64_t started = 0;
+    uint32_t valid = 0, newest = 0;
+};
+
+int wf_stage(XObj *h, uint32_t channel, uint32_t stage, WfStage *out, const char *who)
+{
+    int rc = check_pair(h, channel);
+    if (rc)
+        return rc;
+    if ((rc = drain(h)))
+        return rc;
+    const auto &st = h->pairs[channel];
+    if (stage >= st.size())
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": stage " + std::to_string(stage) + " out of range (" +
+                                          std::to_string(st.size()) + " stages)");
+    out->s = &st[stage];
+    out->started = wf_blocks_started(st[stage].segs, h->wf_block);
+    out->valid = wf_valid_rows(out->started, h->wf_depth);
+    out->newest = wf_newest_count(st[stage].segs, h->wf_block);
+    return PSDC_OK;
+}
+
+int wf_stage_blocks_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_wf_blocks *out, const char *who)
+{
+    X_HANDLE(h, who);
+    if (!out)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output");
+    X_ON_DEVICE(h);
+    WfStage w;
+    int rc = wf_stage(h, channel, stage, &w, who);
+    if (rc)
+        return rc;
+    out->block = h->wf_block;
+    out->depth = h->wf_depth;
+    out->started = w.started;
+    out->rows_valid = w.valid;
+    out->newest_count = w.newest;
+    out->pending = pending_for(h->geo, w.s->total);
+    return PSDC_OK;
+}
+
+// the rows a read-out of at most max_rows rows returns: their number, absolute block indices and counts (oldest first)
+uint32_t wf_rows_meta(const XObj *h, const WfStage &w, uint32_t max_rows, uint64_t *block_index, uint32_t *counts)
+{
+    const uint32_t nr = std::min(max_rows, w.valid);
+    for (uint32_t r = 0; r < nr; ++r) {
+        block_index[r] = wf_row_block(w.started, nr, r);
+        counts[r] = r + 1 == nr ? w.newest : h->wf_block;
+    }
+    return nr;
+}
+
+// outs[i]: row i of every returned block, [max_rows][n/2 + 1] f64, NULL: not wanted
+int wf_stage_rows_impl(XObj *h, uint32_t channel, uint32_t stage, uint32_t max_rows, uint64_t *block_index, uint32_t *counts,
+                       double *const *outs, uint32_t *n_rows, const char *who)
+{
+    X_HANDLE(h, who);
+    if (!block_index || !counts || !n_rows)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output (block_index, counts and n_rows are always written)");
+    X_ON_DEVICE(h);
+    WfStage w;
+    int rc = wf_stage(h, channel, stage, &w, who);
+    if (rc)
+        return rc;
+    const uint32_t nr = wf_rows_meta(h, w, max_rows, block_index, counts);
+    *n_rows = nr;
+    bool any = false;
+    for (uint32_t i = 0; i < h->rows(); ++i)
+        any = any || outs[i];
+    if (!nr || !any)
+        return PSDC_OK;
+    if ((rc = sync_all(h)))
+        return rc;
+    // the nr slots are consecutive in the ring, in at most two runs (one before the ring's end, one from its start)
+    const size_t b = bins(h), set = h->rows() * b;
+    std::vector<double> host((size_t)nr * set);
+    const uint32_t first = wf_row_slot(w.started, h->wf_depth, nr, 0);
+    const uint32_t run0 = std::min(nr, h->wf_depth - first);
+    XCHK(h, hipMemcpy(host.data(), w.s->acc + (size_t)first * set, sizeof(double) * run0 * set, hipMemcpyDeviceToHost));
+    if (nr > run0)
+        XCHK(h, hipMemcpy(host.data() + (size_t)run0 * set, w.s->acc, sizeof(double) * (nr - run0) * set, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < nr; ++r)
+        for (uint32_t i = 0; i < h->rows(); ++i)
+            if (outs[i])
+                std::copy(&host[(size_t)r * set + i * b], &host[(size_t)r * set + (i + 1) * b], outs[i] + (size_t)r * b);
+    return PSDC_OK;
+}
+
+// psd / sk: [rows][sides][n/2 + 1] f32 images of the newest min(max_rows, valid) blocks through wf_image_kernel; device: the two
+// are device memory, else host arrays filled through a device buffer of the call's own
+int wf_image_impl(XObj *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *psd, float *sk, bool device, uint64_t *block_index,
+                  uint32_t *counts, uint32_t *n_rows, const char *who)
+{
+    X_HANDLE(h, who);
+    if (!psd && !sk)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output (give psd, sk or both)");
+    if (!block_index || !counts || !n_rows)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output (block_index, counts and n_rows are always written)");
+    X_ON_DEVICE(h);
+    WfStage w;
+    int rc = wf_stage(h, channel, stage, &w, who);
+    if (rc)
+        return rc;
+    const uint32_t nr = wf_rows_meta(h, w, max_rows, block_index, counts);
+    *n_rows = nr;
+    if (!nr)
+        return PSDC_OK;
+    const uint32_t sides = h->rows() / 2;
+    const size_t image = (size_t)nr * sides * bins(h);
+    float *tmp = nullptr;
+    if (!device)
+        XCHK(h, hipMalloc(&tmp, sizeof(float) * image * 2));
+    const float dec = (float)((uint64_t)1 << (3 * stage)); // (the stitch's `decimation` of this stage)
+    WfImageJob j{};
+    j.ring = w.s->acc;
+    j.psd = device ? psd : (psd ? tmp : nullptr);
+    j.sk = device ? sk : (sk ? tmp + image : nullptr);
+    j.started = w.started;
+    j.depth = h->wf_depth;
+    j.nr = nr;
+    j.nbins = (unsigned)bins(h);
+    j.sides = sides;
+    j.block = h->wf_block;
+    j.newest = w.newest;
+    j.gsc_block = 1.0f / (psdrt::stage_gain(h->n, h->wf_block, h->nenbw, h->power) * dec);
+    j.gsc_newest = 1.0f / (psdrt::stage_gain(h->n, w.newest, h->nenbw, h->power) * dec);
+    hipError_t e = launch_wf_image(j, h->stream);
+    if (e == hipSuccess) {
+        ++h->launches;
+        e = hipStreamSynchronize(h->stream);
+    }
+    if (e == hipSuccess && !device && psd)
+        e = hipMemcpy(psd, tmp, sizeof(float) * image, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !device && sk)
+        e = hipMemcpy(sk, tmp + image, sizeof(float) * image, hipMemcpyDeviceToHost);
+    if (tmp)
+        (void)hipFree(tmp);
+    XCHK(h, e);
+    return PSDC_OK;
+}
+
+} // namespace
+
+struct psdc_wf : XObj {};
+struct psdc_zwf : XObj {};
+
+extern "C" {
+
+int psdc_wf_supported(uint32_t n) { return psdc_sk_supported(n); }
+
+psdc_wf *psdc_wf_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, uint32_t block,
+                               uint32_t depth, int device)
+{
+    return static_cast<psdc_wf *>(wf_create(K_WF, n, 0, win, power, nenbw, overlap, true, n_channels, block, depth, device, "psdc_wf_create_window"));
+}
+
+psdc_wf *psdc_wf_create(uint32_t n, int window_kind, uint32_t n_channels, uint32_t block, uint32_t depth, int device)
+{
+    return static_cast<psdc_wf *>(wf_create(K_WF, n, window_kind, nullptr, 0, 0, 0, false, n_channels, block, depth, device, "psdc_wf_create"));
+}
+
+void psdc_wf_destroy(psdc_wf *h) { destroy_obj(h); }
+int psdc_wf_reset(psdc_wf *h) { return reset_impl(h, "psdc_wf_reset"); }
+int psdc_wf_set_detrend(psdc_wf *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_wf_set_detrend"); }
+
+int psdc_wf_process(psdc_wf *h, uint32_t channel, const float *x, size_t len)
+{
+    const void *xs[1] = {x};
+    return process_impl(h, channel, xs, SampleFmt{}, len, "psdc_wf_process");
+}
+
+int psdc_wf_process_device(psdc_wf *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return process_device_impl(h, channel, xs, SampleFmt{}, len, producer_event, "psdc_wf_process_device");
+}
+
+int psdc_wf_sync(psdc_wf *h) { return sync_impl(h, "psdc_wf_sync"); }
+int psdc_wf_num_stages(psdc_wf *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_wf_num_stages"); }
+
+int psdc_wf_stage_blocks(psdc_wf *h, uint32_t channel, uint32_t stage, psdc_wf_blocks *out)
+{
+    return wf_stage_blocks_impl(h, channel, stage, out, "psdc_wf_stage_blocks");
+}
+
+int psdc_wf_stage_rows(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, uint64_t *block_index, uint32_t *counts, double *s1,
+                       double *s2, uint32_t *n_rows)
+{
+    double *const outs[SK_ROWS] = {s1, s2};
+    return wf_stage_rows_impl(h, channel, stage, max_rows, block_index, counts, outs, n_rows, "psdc_wf_stage_rows");
+}
+
+int psdc_wf_image(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *psd, float *sk, uint64_t *block_index,
+                  uint32_t *counts, uint32_t *n_rows)
+{
+    return wf_image_impl(h, channel, stage, max_rows, psd, sk, false, block_index, counts, n_rows, "psdc_wf_image");
+}
+
+int psdc_wf_image_device(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *d_psd, float *d_sk, uint64_t *block_index,
+                         uint32_t *counts, uint32_t *n_rows)
+{
+    return wf_image_impl(h, channel, stage, max_rows, d_psd, d_sk, true, block_index, counts, n_rows, "psdc_wf_image_device");
+}
+
+int psdc_wf_stats_read(psdc_wf *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_wf_stats_read");
+}
+
+const char *psdc_wf_last_error(const psdc_wf *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+int psdc_zwf_supported(uint32_t n) { return psdc_zsk_supported(n); }
+
+psdc_zwf *psdc_zwf_create_window(uint32_t n, const float *win, float power, float nenbw, size_t overlap, uint32_t n_channels, uint32_t block,
+                                 uint32_t depth, int device)
+{
+    return static_cast<psdc_zwf *>(wf_create(K_ZWF, n, 0, win, power, nenbw, overlap, true, n_channels, block, depth, device, "psdc_zwf_create_window"));
+}
+
+psdc_zwf *psdc_zwf_create(uint32_t n, int window_kind, uint32_t n_channels, uint32_t block, uint32_t depth, int device)
+{
+    return static_cast<psdc_zwf *>(wf_create(K_ZWF, n, window_kind, nullptr, 0, 0, 0, false, n_channels, block, depth, device, "psdc_zwf_create"));
+}
+
+void psdc_zwf_destroy(psdc_zwf *h) { destroy_obj(h); }
+int psdc_zwf_reset(psdc_zwf *h) { return reset_impl(h, "psdc_zwf_reset"); }
+int psdc_zwf_set_detrend(psdc_zwf *h, int detrend_kind) { return set_detrend_impl(h, detrend_kind, "psdc_zwf_set_detrend"); }
+
+int psdc_zwf_set_carrier(psdc_zwf *h, uint32_t channel, uint64_t ftw, uint64_t phase0)
+{
+    return set_carrier_impl(h, channel, ftw, phase0, "psdc_zwf_set_carrier");
+}
+
+int psdc_zwf_process(psdc_zwf *h, uint32_t channel, const float *x, size_t len)
+{
+    const void *xs[1] = {x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, false, nullptr, "psdc_zwf_process");
+}
+
+int psdc_zwf_process_device(psdc_zwf *h, uint32_t channel, const float *d_x, size_t len, void *producer_event)
+{
+    const void *xs[1] = {d_x};
+    return zoom_feed(h, channel, xs, SampleFmt{}, len, true, producer_event, "psdc_zwf_process_device");
+}
+
+int psdc_zwf_sync(psdc_zwf *h) { return sync_impl(h, "psdc_zwf_sync"); }
+int psdc_zwf_num_stages(psdc_zwf *h, uint32_t channel) { return num_stages_impl(h, channel, "psdc_zwf_num_stages"); }
+
+int psdc_zwf_stage_blocks(psdc_zwf *h, uint32_t channel, uint32_t stage, psdc_wf_blocks *out)
+{
+    return wf_stage_blocks_impl(h, channel, stage, out, "psdc_zwf_stage_blocks");
+}
+
+int psdc_zwf_stage_rows(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, uint64_t *block_index, uint32_t *counts,
+                        double *s1_upper, double *s1_lower, double *s2_upper, double *s2_lower, uint32_t *n_rows)
+{
+    double *const outs[ZSK_ROWS] = {s1_upper, s1_lower, s2_upper, s2_lower};
+    return wf_stage_rows_impl(h, channel, stage, max_rows, block_index, counts, outs, n_rows, "psdc_zwf_stage_rows");
+}
+
+int psdc_zwf_image(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *psd, float *sk, uint64_t *block_index,
+                   uint32_t *counts, uint32_t *n_rows)
+{
+    return wf_image_impl(h, channel, stage, max_rows, psd, sk, false, block_index, counts, n_rows, "psdc_zwf_image");
+}
+
+int psdc_zwf_image_device(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, float *d_psd, float *d_sk,
+                          uint64_t *block_index, uint32_t *counts, uint32_t *n_rows)
+{
+    return wf_image_impl(h, channel, stage, max_rows, d_psd, d_sk, true, block_index, counts, n_rows, "psdc_zwf_image_device");
+}
+
+int psdc_zwf_stats_read(psdc_zwf *h, uint64_t *launches, uint64_t *samples_in, int reset)
+{
+    return stats_impl(h, launches, samples_in, reset, "psdc_zwf_stats_read");
+}
+
+const char *psdc_zwf_last_error(const psdc_zwf *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
 
 } // extern "C"

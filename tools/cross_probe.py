@@ -82,6 +82,12 @@ transforms, eight decimator jobs -- or, for --iq, an IqCsdCascadeBank(n, 2) fed 
 ZoomAmPmCsdCascadeBank(n, 1) / IqAmPmCsdCascadeBank(n, 1) fed (a, b): two transforms.  A, B, A in turn --reps times; B / A of every
 turn, the largest |A' - A| / A, B's launches a steady call and the live stages are recorded as findings, none is a gate.  Each writes
 its family's entry ("zoom" / "iq") of profiles/zoom_ampm_cross_probe.json unless --out names another file.
+--waterfall / --zoom --waterfall: what cutting a round into blocks costs.  One device-resident real f32 stream (carrier 0.2 for
+--zoom) of 2^24 samples a call at N = 512, 1024, 4096, the windows and the sync of --sk.  Leg A: SkCascadeBank(n, 1) /
+ZoomSkCascadeBank(n, 1).  Leg B: WaterfallCascadeBank(n, 1) / ZoomWaterfallCascadeBank(n, 1) with depth 64, at block 64 and at block
+4096.  A, B, A in turn --reps times; B / A of every turn, the largest |A' - A| / A, the launches a steady call of both, and the time
+of one image_device call of every stage are recorded as findings, none is a gate.  Each writes its entry ("real" / "zoom") of
+profiles/waterfall_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -398,6 +404,65 @@ def zoom_sk_legs(pkg, torch, seconds, reps, call, iq):
                      "b_launches_per_call": launches, "stages": zb.num_stages(0), "a_stages": za.num_stages(0)})
         za.close()
         zb.close()
+    return legs
+
+
+def waterfall_legs(pkg, torch, seconds, reps, call, zoom):
+    """One device-resident real f32 stream (zoom: carrier 0.2).  A: SkCascadeBank / ZoomSkCascadeBank; B: WaterfallCascadeBank /
+    ZoomWaterfallCascadeBank with depth 64 at block 64 (a call crosses many blocks: a job a block) and block 4096 (about as many
+    segments as a call of 2^24 samples has at N = 4096: a piece or two a stage).  A / B / A in turn; then B's launches a steady call and
+    one image_device of every stage into a tensor."""
+    x = torch.randn(call, device="cuda")
+    torch.cuda.synchronize()
+    legs = []
+    r3 = lambda vs: [round(v, 3) for v in vs]  # noqa: E731
+    for n in (512, 1024, 4096):
+        for block in (64, 4096):
+            sa = (pkg.ZoomSkCascadeBank if zoom else pkg.SkCascadeBank)(n, 1)
+            wb = (pkg.ZoomWaterfallCascadeBank if zoom else pkg.WaterfallCascadeBank)(n, 1, block=block, depth=64)
+            if zoom:
+                sa.set_carrier(0, f0=0.2)
+                wb.set_carrier(0, f0=0.2)
+
+            def a_step():
+                sa.process_device(0, x.data_ptr(), call)
+                return call
+
+            def b_step():
+                wb.process_device(0, x.data_ptr(), call)
+                return call
+
+            a1, b, a2 = [], [], []
+            for _ in range(reps):
+                a1.append(timed(a_step, sa.sync, seconds)[0] / 1e9)
+                b.append(timed(b_step, wb.sync, seconds)[0] / 1e9)
+                a2.append(timed(a_step, sa.sync, seconds)[0] / 1e9)
+            launches = []
+            for obj, step in ((sa, a_step), (wb, b_step)):
+                obj.stats_read(reset=True)
+                for _ in range(8):
+                    step()
+                launches.append(obj.stats_read()["launches"] / 8)
+                obj.sync()
+            sides = 2 if zoom else 1
+            img = torch.empty((64, sides, n // 2 + 1), device="cuda")
+            sk = torch.empty_like(img)
+            torch.cuda.synchronize()
+            image_us = []
+            for k in range(wb.num_stages(0)):
+                wb.image_device(0, k, img.data_ptr(), sk.data_ptr())  # (the first call of a stage pays nothing extra; timed below)
+                t0 = time.perf_counter()
+                idx, _ = wb.image_device(0, k, img.data_ptr(), sk.data_ptr())
+                image_us.append({"stage": k, "rows": int(idx.size), "us": round((time.perf_counter() - t0) * 1e6, 1)})
+            ratios = [y / u for u, y in zip(a1, b)]
+            spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+            legs.append({"n": n, "call": call, "block": block, "depth": 64, "a_sk_gs_s": r3(a1), "b_waterfall_gs_s": r3(b),
+                         "a_again_gs_s": r3(a2), "ratio_b_over_a": r3(ratios), "ratio_min": round(min(ratios), 3),
+                         "ratio_max": round(max(ratios), 3), "aa_spread_max": round(spread, 4),
+                         "b_below_a_beyond_spread": bool(max(ratios) < 1 - spread), "a_launches_per_call": launches[0],
+                         "b_launches_per_call": launches[1], "stages": wb.num_stages(0), "image_device": image_us})
+            sa.close()
+            wb.close()
     return legs
 
 
@@ -1059,9 +1124,32 @@ def main():
                                                         "against IqCascadeBank; writes profiles/zoom_ampm_probe.json; with --pair: "
                                                         "ZoomAmPmCsdCascadeBank / IqAmPmCsdCascadeBank against the two-pair recipe on "
                                                         "the eight-row object; writes profiles/zoom_ampm_cross_probe.json")
+    ap.add_argument("--waterfall", action="store_true", help="WaterfallCascadeBank against SkCascadeBank (with --zoom: the zoom objects) "
+                                                             "at block 64 and 4096, depth 64; writes profiles/waterfall_probe.json")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.waterfall:
+        fam = "zoom" if a.zoom else "real"
+        path = a.out or os.path.join(ROOT, "profiles", "waterfall_probe.json")
+        record = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                record = json.loads(f.read() or "{}")
+        record.update({"metric": "waterfall_gsamples_s", "unit": "1e9 samples a second of one real stream",
+                       "note": "findings, no gate: A is the spectral kurtosis object on the same device-resident stream, B the same segment "
+                               "kernel with a round cut into one job a block and folded into ring slots; image_device: one call a stage, "
+                               "host time to its return; not measured here: host memory, banks, other depths, block sizes between"})
+        before = gpu_state()
+        legs = waterfall_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, a.zoom)
+        record[fam] = {"a": "ZoomSkCascadeBank" if a.zoom else "SkCascadeBank",
+                       "b": "ZoomWaterfallCascadeBank" if a.zoom else "WaterfallCascadeBank",
+                       "gpu_before": before, "gpu_after": gpu_state(), "legs": legs}
+        line = json.dumps(record)
+        print(line)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.ampm and a.pair:
         if not (a.zoom or a.iq):
             raise SystemExit("--pair --ampm goes with --zoom or --iq")

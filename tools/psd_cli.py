@@ -31,6 +31,12 @@ IqSkCascade(512).  Each prints, or with --csv writes to DIR/zoomsk_<trace>_<F0>.
 offset,psd,sk over the offsets -0.5 fs ... 0.5 fs from the carrier in ascending order (two_sided): the spectral kurtosis of the
 sideband power beside its density.  Circular Gaussian noise reads 1 at every offset, 0 included; a real stream rises towards 2
 where its own DC and Nyquist fall (offsets -F0 and 0.5 - F0).  The summary line counts the bins more than 8 sk_sigma(count) from 1.
+--waterfall BLOCK:DEPTH[:TRACE] (repeatable; TRACE as for --sk) feeds that trace to a WaterfallCascade(512, block=BLOCK, depth=DEPTH),
+and --zoom-waterfall F0:BLOCK:DEPTH[:TRACE] to a ZoomWaterfallCascade(512) around the carrier F0: per stage the newest DEPTH blocks
+of BLOCK segments, each with its own PSD and spectral kurtosis (every segment has weight 1: --avg and --avg-max do not apply).
+Each prints, or with --csv writes to DIR/waterfall_<trace>_stage<k>.csv / DIR/zoom_waterfall_<trace>_<F0>_stage<k>.csv, one file a
+stage: a header line with the block indices and counts, then one line a block, oldest first, with the PSD of every bin followed by
+the SK of every bin (the zoom option: upper then lower sideband of each).
 --zoom-ampm F0[:TRACE] (repeatable; as --zoom) feeds that trace to a ZoomAmPmCascade(512) around the carrier F0, and --iq-ampm
 I:Q[:F0] (repeatable; as --iq) the complex stream I + i Q to an IqAmPmCascade(512).  Both run without a detrend whatever --detrend
 says: the carrier's amplitude and phase are read from bin 0 (carrier()), which a detrend removes.  Each prints, or with --csv writes
@@ -93,6 +99,11 @@ def main(argv=None):
                     help="F0[:TRACE] -- two-sided spectral kurtosis beside the spectrum around the carrier F0 (repeatable)")
     ap.add_argument("--iq-sk", action="append", default=[],
                     help="I:Q[:F0] -- two-sided spectral kurtosis beside the spectrum of the complex stream I + i Q (repeatable)")
+    ap.add_argument("--waterfall", action="append", default=[],
+                    help="BLOCK:DEPTH[:TRACE] -- PSD and spectral kurtosis of that trace against time: per stage the newest DEPTH blocks of "
+                         "BLOCK segments (repeatable)")
+    ap.add_argument("--zoom-waterfall", action="append", default=[],
+                    help="F0:BLOCK:DEPTH[:TRACE] -- the same, two-sided around the carrier F0 (repeatable)")
     ap.add_argument("--zoom-ampm", action="append", default=[],
                     help="F0[:TRACE] -- amplitude and phase noise spectra of the carrier F0 of that trace (repeatable)")
     ap.add_argument("--iq-ampm", action="append", default=[],
@@ -182,6 +193,10 @@ def main(argv=None):
         zoom_sk_traces(pkg, source, a, merge, names)
     if a.iq_sk and a.file:
         iq_sk_streams(pkg, source, a, merge, names)
+    if a.waterfall:
+        waterfall_traces(pkg, source, a, names)
+    if a.zoom_waterfall:
+        zoom_waterfall_traces(pkg, source, a, names)
     if a.zoom_ampm:
         zoom_ampm_traces(pkg, source, a, merge, names)
     if a.iq_ampm and a.file:
@@ -338,6 +353,63 @@ def sk_traces(pkg, source, a, merge, names):
         else:
             sys.stdout.writelines(lines)
     bank.close()
+
+
+def waterfall_report(pkg, g, label, stem, a):
+    """the read-out of a WaterfallCascade / ZoomWaterfallCascade: the summary line, and per stage the images of image(): one line a
+    block, oldest first, the PSD of every bin followed by the SK of every bin (a zoom object: upper then lower of each), behind a
+    header line with the block indices and counts"""
+    ns = g.num_stages()
+    if ns == 0:
+        print(f"{label}: no samples")
+        return
+    print(f"{label}: {ns} stages, block {g.block} depth {g.depth}, rows " + " ".join(str(g.stage_blocks(k)["rows_valid"]) for k in range(ns)))
+    for k in range(ns):
+        psd, sk, idx, cnt = g.image(k)
+        span = g.block_span(k, int(idx[-1])) if idx.size else range(0)
+        head = (f"# stage {k}: blocks {' '.join(map(str, idx.tolist()))}; counts {' '.join(map(str, cnt.tolist()))}; columns: psd then sk, "
+                f"{psd[0].size if idx.size else 0} each; the newest block nominally ends at input sample {span.stop}\n")
+        lines = [",".join(f"{v:.9g}" for v in np.concatenate([p.ravel(), s.ravel()])) + "\n" for p, s in zip(psd, sk)]
+        if a.csv:
+            safe = "".join(ch if ch.isalnum() else "_" for ch in f"{stem}_stage{k}")
+            with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+                f.write(head)
+                f.writelines(lines)
+        else:
+            sys.stdout.write(head)
+            sys.stdout.writelines(lines)
+
+
+def waterfall_spec(z, opt, lead):
+    """BLOCK:DEPTH[:TRACE] behind `lead` leading fields"""
+    parts = z.split(":", lead + 2)
+    if len(parts) < lead + 2 or not (parts[lead].isdigit() and parts[lead + 1].isdigit()):
+        raise SystemExit(f"{opt} takes {'F0:' if lead else ''}BLOCK:DEPTH[:TRACE]")
+    return parts[:lead], int(parts[lead]), int(parts[lead + 1]), parts[lead + 2] if len(parts) > lead + 2 else ""
+
+
+def waterfall_traces(pkg, source, a, names):
+    """--waterfall BLOCK:DEPTH[:TRACE]: the named trace of every read (host_traces) into one waterfall cascade each"""
+    for z in a.waterfall:
+        _, block, depth, tr = waterfall_spec(z, "--waterfall", 0)
+        idx = trace_arg(tr, names, "--waterfall")
+        g = pkg.WaterfallCascade(1 << 9, block=block, depth=depth)
+        g.set_detrend(pkg.Detrend[a.detrend.upper()])
+        host_traces(source, pkg, a, [(idx,)], lambda i, xs: g.process(xs[0]))
+        waterfall_report(pkg, g, f"waterfall {names[idx]}", f"waterfall_{names[idx]}", a)
+        g.close()
+
+
+def zoom_waterfall_traces(pkg, source, a, names):
+    """--zoom-waterfall F0:BLOCK:DEPTH[:TRACE]: the named trace into one zoom waterfall cascade around the carrier F0 each"""
+    for z in a.zoom_waterfall:
+        (f0,), block, depth, tr = waterfall_spec(z, "--zoom-waterfall", 1)
+        idx = trace_arg(tr, names, "--zoom-waterfall")
+        g = pkg.ZoomWaterfallCascade(1 << 9, f0=float(f0), block=block, depth=depth)
+        g.set_detrend(pkg.Detrend[a.detrend.upper()])
+        host_traces(source, pkg, a, [(idx,)], lambda i, xs: g.process(xs[0]))
+        waterfall_report(pkg, g, f"zoom_waterfall {names[idx]} @ {g.f0:.12g}", f"zoom_waterfall_{names[idx]}_{g.f0:.9g}", a)
+        g.close()
 
 
 def two_sided_sk_report(pkg, bank, c, label, stem, a, merge):
