@@ -239,398 +239,194 @@ def lib():
                           "(there is no Python/CPU fallback for the PSD kernels)")
     _one_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    H, u32, u64, i32, sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_size_t
-    fp = C.POINTER(C.c_float)
-
-    def f(name, res, args):
+    for name, (res, args) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
-
-    f("psdc_abi_version", i32, [])
-    f("psdc_last_error", C.c_char_p, [H])
-    f("psdc_create", H, [u32, i32, u32, i32])
-    f("psdc_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_window_get", i32, [H, C.POINTER(i32), fp, fp, C.POINTER(sz), fp])
-    f("psdc_window_table", i32, [u32, i32, fp, fp, fp, C.POINTER(sz)])
-    f("psdc_stage_create_window", H, [u32, fp, C.c_float, C.c_float, sz, i32])
-    f("psdc_stitch_window", i32, [u32, C.c_float, C.c_float, sz, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp,
-                                  i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_readout_bytes", sz, [u32, u32])
-    f("psdc_pack_readout", i32, [H, C.c_void_p, sz, C.POINTER(sz)])
-    f("psdc_pack_init", i32, [C.c_void_p, sz, u32, C.c_float, C.c_float, sz, u32])
-    f("psdc_pack_channel", i32, [C.c_void_p, sz, u32, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp])
-    f("psdc_pack_pad", i32, [C.c_void_p, sz, C.c_void_p, sz, u32])
-    f("psdc_unpack_info", i32, [C.c_void_p, sz, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)])
-    f("psdc_unpack_stitch", i32, [C.c_void_p, sz, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz,
-                                  C.POINTER(sz)])
-    f("psdc_destroy", None, [H])
-    f("psdc_clone", H, [H])
-    f("psdc_reset", i32, [H])
-    f("psdc_configure", i32, [H, i32, C.c_int64])
-    f("psdc_set_detrend", i32, [H, i32])
-    f("psdc_set_avg", i32, [H, u32, u32])
-    f("psdc_process", i32, [H, u32, fp, sz])
-    f("psdc_process_device", i32, [H, u32, C.c_void_p, sz])
-    f("psdc_process_device_after", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
-    f("psdc_record_consumed", i32, [H, C.c_void_p])
-    f("psdc_process_adcdac_frames", i32, [H, C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_process_frames", i32, [H, C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_process_frames_device", i32, [H, C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_process_adcdac_frames_device", i32, [H, C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_flush", i32, [H])
-    f("psdc_sync", i32, [H])
-    f("psdc_num_stages", i32, [H, u32])
-    f("psdc_stage_info", i32, [H, u32, u32, C.POINTER(_CStageStat)])
-    f("psdc_stage_spectrum", i32, [H, u32, u32, fp])
-    f("psdc_stage_gain", i32, [H, u32, u32, fp])
-    f("psdc_stage_buf", i32, [H, u32, u32, fp, sz, C.POINTER(sz)])
-    f("psdc_read_channel", i32, [H, u32, u32, C.POINTER(u32), C.POINTER(_CStageStat), fp])
-    f("psdc_psd", i32, [H, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz,
-                        C.POINTER(sz)])
-    f("psdc_rbw", C.c_float, [H])
-    f("psdc_frequencies", sz, [C.POINTER(_CBreak), sz, fp, sz])
-    f("psdc_hbf_response_length", i32, [i32])
-    f("psdc_stitch", i32, [u32, i32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), fp, i32,
-                           u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_plan_counts", i32, [u32, i32, u64, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
-    f("psdc_var_eval", C.c_float, [i32, i32, C.c_float, sz, fp, fp, sz, C.c_float])
-    f("psdc_hbf_dec8", i32, [i32, fp, sz, fp])
-    f("psdc_fill_noise_device", i32, [i32, C.c_void_p, sz, u64, u64])
-    f("psdc_profile_read", i32, [H, C.POINTER(_CProfile), i32])
-    f("psdc_trace_plot", i32, [fp, fp, sz, C.c_float, i32, C.c_float, C.c_float, fp, C.POINTER(C.c_double), sz,
-                               C.POINTER(sz)])
-    f("psdc_stage_create", H, [u32, i32, i32])
-    f("psdc_stage_destroy", None, [H])
-    f("psdc_stage_clone", H, [H])
-    f("psdc_stage_set_avg", i32, [H, u32])
-    f("psdc_stage_set_detrend", i32, [H, i32])
-    f("psdc_stage_process", i32, [H, fp, sz, fp, sz, C.POINTER(sz)])
-    f("psdc_stage_process_device", i32, [H, C.c_void_p, sz, C.c_void_p, sz, C.POINTER(sz)])
-    f("psdc_stage_get_spectrum", i32, [H, fp])
-    f("psdc_stage_get_count", i32, [H, C.POINTER(u32)])
-    f("psdc_stage_get_gain", i32, [H, fp])
-    f("psdc_stage_get_buf", i32, [H, fp, sz, C.POINTER(sz)])
-    f("psdc_stage_last_error", C.c_char_p, [H])
-    f("psdc_cross_create", H, [u32, i32, u32, i32])
-    f("psdc_cross_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_cross_destroy", None, [H])
-    f("psdc_cross_reset", i32, [H])
-    f("psdc_cross_set_detrend", i32, [H, i32])
-    f("psdc_cross_set_avg", i32, [H, u32, u32])
-    f("psdc_cross_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_cross_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
-    f("psdc_cross_sync", i32, [H])
-    f("psdc_cross_num_stages", i32, [H, u32])
-    f("psdc_cross_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp, fp])
-    f("psdc_cross_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_cross_stitch", i32, [u32, C.c_float, C.c_float, sz, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp,
-                                 i32, u32, i32, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_cross_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_cross_last_error", C.c_char_p, [H])
-    f("psdc_csd_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_csd_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_csd_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    pp = C.POINTER(C.c_void_p)
-    f("psdc_csm_supported", i32, [u32, u32])
-    f("psdc_csm_create", H, [u32, i32, u32, u32, i32])
-    f("psdc_csm_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, u32, i32])
-    f("psdc_csm_destroy", None, [H])
-    f("psdc_csm_reset", i32, [H])
-    f("psdc_csm_set_detrend", i32, [H, i32])
-    f("psdc_csm_set_avg", i32, [H, u32, u32])
-    f("psdc_csm_process", i32, [H, u32, pp, sz])
-    f("psdc_csm_process_device", i32, [H, u32, pp, sz, C.c_void_p])
-    f("psdc_csm_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_csm_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_csm_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_csm_sync", i32, [H])
-    f("psdc_csm_num_stages", i32, [H, u32])
-    f("psdc_csm_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
-    f("psdc_csm_csd", i32, [H, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_csm_stitch", i32, [u32, u32, C.c_float, C.c_float, sz, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), fp,
-                               i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_csm_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_csm_last_error", C.c_char_p, [H])
-    f("psdc_zoom_create", H, [u32, i32, u32, i32])
-    f("psdc_zoom_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_zoom_destroy", None, [H])
-    f("psdc_zoom_reset", i32, [H])
-    f("psdc_zoom_set_detrend", i32, [H, i32])
-    f("psdc_zoom_set_avg", i32, [H, u32, u32])
-    f("psdc_zoom_set_carrier", i32, [H, u32, u64, u64])
-    f("psdc_zoom_process", i32, [H, u32, fp, sz])
-    f("psdc_zoom_process_device", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
-    f("psdc_zoomcascade_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_zoomcascade_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_zoomcascade_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_zoom_sync", i32, [H])
-    f("psdc_zoom_num_stages", i32, [H, u32])
-    f("psdc_zoom_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp])
-    f("psdc_zoom_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_zoom_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_zoom_last_error", C.c_char_p, [H])
-    f("psdc_zcsd_supported", i32, [u32])
-    f("psdc_zcsd_create", H, [u32, i32, u32, i32])
-    f("psdc_zcsd_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_zcsd_destroy", None, [H])
-    f("psdc_zcsd_reset", i32, [H])
-    f("psdc_zcsd_set_detrend", i32, [H, i32])
-    f("psdc_zcsd_set_avg", i32, [H, u32, u32])
-    f("psdc_zcsd_set_carrier", i32, [H, u32, u32, u64, u64])
-    f("psdc_zcsd_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_zcsd_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
-    f("psdc_zoomcsdcascade_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_zoomcsdcascade_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_zoomcsdcascade_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_zcsd_sync", i32, [H])
-    f("psdc_zcsd_num_stages", i32, [H, u32])
-    f("psdc_zcsd_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
-    f("psdc_zcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_zcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_zcsd_last_error", C.c_char_p, [H])
-    f("psdc_iq_create", H, [u32, i32, u32, i32])
-    f("psdc_iq_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_iq_destroy", None, [H])
-    f("psdc_iq_reset", i32, [H])
-    f("psdc_iq_set_detrend", i32, [H, i32])
-    f("psdc_iq_set_avg", i32, [H, u32, u32])
-    f("psdc_iq_set_carrier", i32, [H, u32, u64, u64])
-    f("psdc_iq_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_iq_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
-    f("psdc_iq_process_interleaved", i32, [H, u32, fp, sz])
-    f("psdc_iq_process_interleaved_device", i32, [H, u32, C.c_void_p, sz, C.c_void_p])
-    f("psdc_iq_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_iq_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_iq_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_iq_sync", i32, [H])
-    f("psdc_iq_num_stages", i32, [H, u32])
-    f("psdc_iq_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp, fp])
-    f("psdc_iq_psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_iq_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_iq_last_error", C.c_char_p, [H])
-    f("psdc_iqcsd_supported", i32, [u32])
-    f("psdc_iqcsd_create", H, [u32, i32, u32, i32])
-    f("psdc_iqcsd_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_iqcsd_destroy", None, [H])
-    f("psdc_iqcsd_reset", i32, [H])
-    f("psdc_iqcsd_set_detrend", i32, [H, i32])
-    f("psdc_iqcsd_set_avg", i32, [H, u32, u32])
-    f("psdc_iqcsd_set_carrier", i32, [H, u32, u32, u64, u64])
-    f("psdc_iqcsd_process", i32, [H, u32, fp, fp, fp, fp, sz])
-    f("psdc_iqcsd_process_device", i32, [H, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
-    f("psdc_iqcsd_process_interleaved", i32, [H, u32, fp, fp, sz])
-    f("psdc_iqcsd_process_interleaved_device", i32, [H, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
-    f("psdc_iqcsd_process_frames", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz)])
-    f("psdc_iqcsd_process_frames_device", i32, [H, C.POINTER(u32), C.c_void_p, sz, sz, C.POINTER(sz), C.c_void_p])
-    f("psdc_iqcsd_loss_read", i32, [H, C.POINTER(_CLoss), i32])
-    f("psdc_iqcsd_sync", i32, [H])
-    f("psdc_iqcsd_num_stages", i32, [H, u32])
-    f("psdc_iqcsd_stage_spectra", i32, [H, u32, u32, C.POINTER(_CStageStat), fp])
-    f("psdc_iqcsd_csd", i32, [H, u32, i32, u32, i32, fp, fp, fp, fp, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_iqcsd_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_iqcsd_last_error", C.c_char_p, [H])
-    vp, fl = C.c_void_p, C.c_float
-    f("psdc_int_zoom_process", i32, [H, u32, vp, i32, fl, sz])
-    f("psdc_int_zoom_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
-    f("psdc_int_zcsd_process", i32, [H, u32, vp, vp, i32, fl, sz])
-    f("psdc_int_zcsd_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
-    f("psdc_int_iq_process", i32, [H, u32, vp, i32, fl, sz])
-    f("psdc_int_iq_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
-    f("psdc_int_iqcsd_process", i32, [H, u32, vp, vp, i32, fl, sz])
-    f("psdc_int_iqcsd_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
-    f("psdc_sint_process", i32, [H, u32, vp, i32, fl, sz])
-    f("psdc_sint_process_device", i32, [H, u32, vp, i32, fl, sz, vp])
-    f("psdc_sint_cross_process", i32, [H, u32, vp, vp, i32, fl, sz])
-    f("psdc_sint_cross_process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
-    f("psdc_sint_csm_process", i32, [H, u32, pp, i32, fl, sz])
-    f("psdc_sint_csm_process_device", i32, [H, u32, pp, i32, fl, sz, vp])
-    dp = C.POINTER(C.c_double)
-    f("psdc_sk_supported", i32, [u32])
-    f("psdc_sk_create", H, [u32, i32, u32, i32])
-    f("psdc_sk_create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-    f("psdc_sk_destroy", None, [H])
-    f("psdc_sk_reset", i32, [H])
-    f("psdc_sk_set_detrend", i32, [H, i32])
-    f("psdc_sk_set_avg", i32, [H, u32, u32])
-    f("psdc_sk_process", i32, [H, u32, fp, sz])
-    f("psdc_sk_process_device", i32, [H, u32, vp, sz, vp])
-    f("psdc_sk_sync", i32, [H])
-    f("psdc_sk_num_stages", i32, [H, u32])
-    f("psdc_sk_stage_moments", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp])
-    f("psdc_sk_psd", i32, [H, u32, i32, u32, i32, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_sk_sk", i32, [H, u32, i32, u32, i32, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-    f("psdc_sk_stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-    f("psdc_sk_last_error", C.c_char_p, [H])
-    for pre in ("psdc_zsk_", "psdc_iqsk_"):
-        f(pre + "supported", i32, [u32])
-        f(pre + "create", H, [u32, i32, u32, i32])
-        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-        f(pre + "destroy", None, [H])
-        f(pre + "reset", i32, [H])
-        f(pre + "set_detrend", i32, [H, i32])
-        f(pre + "set_avg", i32, [H, u32, u32])
-        f(pre + "set_carrier", i32, [H, u32, u64, u64])
-        f(pre + "sync", i32, [H])
-        f(pre + "num_stages", i32, [H, u32])
-        f(pre + "stage_moments", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp, dp, dp])
-        f(pre + "psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-        f(pre + "sk", i32, [H, u32, i32, u32, i32, dp, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-        f(pre + "last_error", C.c_char_p, [H])
-    f("psdc_zsk_process", i32, [H, u32, fp, sz])
-    f("psdc_zsk_process_device", i32, [H, u32, vp, sz, vp])
-    f("psdc_iqsk_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_iqsk_process_device", i32, [H, u32, vp, vp, sz, vp])
-    f("psdc_iqsk_process_interleaved", i32, [H, u32, fp, sz])
-    f("psdc_iqsk_process_interleaved_device", i32, [H, u32, vp, sz, vp])
-    for pre in ("psdc_zampm_", "psdc_iqampm_"):
-        f(pre + "supported", i32, [u32])
-        f(pre + "create", H, [u32, i32, u32, i32])
-        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-        f(pre + "destroy", None, [H])
-        f(pre + "reset", i32, [H])
-        f(pre + "set_detrend", i32, [H, i32])
-        f(pre + "set_avg", i32, [H, u32, u32])
-        f(pre + "set_carrier", i32, [H, u32, u64, u64])
-        f(pre + "sync", i32, [H])
-        f(pre + "num_stages", i32, [H, u32])
-        f(pre + "stage_rows", i32, [H, u32, u32, C.POINTER(_CStageStat), dp, dp, dp, dp])
-        f(pre + "psd", i32, [H, u32, i32, u32, i32, fp, fp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-        f(pre + "sidebands", i32, [H, u32, i32, u32, i32, dp, dp, dp, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-        f(pre + "last_error", C.c_char_p, [H])
-    f("psdc_zampm_process", i32, [H, u32, fp, sz])
-    f("psdc_zampm_process_device", i32, [H, u32, vp, sz, vp])
-    f("psdc_iqampm_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_iqampm_process_device", i32, [H, u32, vp, vp, sz, vp])
-    f("psdc_iqampm_process_interleaved", i32, [H, u32, fp, sz])
-    f("psdc_iqampm_process_interleaved_device", i32, [H, u32, vp, sz, vp])
-    for pre in ("psdc_zxampm_", "psdc_iqxampm_"):
-        f(pre + "supported", i32, [u32])
-        f(pre + "create", H, [u32, i32, u32, i32])
-        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, i32])
-        f(pre + "destroy", None, [H])
-        f(pre + "reset", i32, [H])
-        f(pre + "set_detrend", i32, [H, i32])
-        f(pre + "set_avg", i32, [H, u32, u32])
-        f(pre + "set_carrier", i32, [H, u32, u32, u64, u64])
-        f(pre + "sync", i32, [H])
-        f(pre + "num_stages", i32, [H, u32])
-        f(pre + "stage_rows", i32, [H, u32, u32, C.POINTER(_CStageStat), dp])
-        f(pre + "sidebands", i32, [H, u32, i32, u32, i32, dp, sz, C.POINTER(sz), C.POINTER(_CBreak), sz, C.POINTER(sz)])
-        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-        f(pre + "last_error", C.c_char_p, [H])
-    f("psdc_zxampm_process", i32, [H, u32, fp, fp, sz])
-    f("psdc_zxampm_process_device", i32, [H, u32, vp, vp, sz, vp])
-    f("psdc_iqxampm_process", i32, [H, u32, fp, fp, fp, fp, sz])
-    f("psdc_iqxampm_process_device", i32, [H, u32, vp, vp, vp, vp, sz, vp])
-    f("psdc_iqxampm_process_interleaved", i32, [H, u32, fp, fp, sz])
-    f("psdc_iqxampm_process_interleaved_device", i32, [H, u32, vp, vp, sz, vp])
-    up = C.POINTER(u32)
-    for pre, nrows in (("psdc_wf_", 2), ("psdc_zwf_", 4)):
-        f(pre + "supported", i32, [u32])
-        f(pre + "create", H, [u32, i32, u32, u32, u32, i32])
-        f(pre + "create_window", H, [u32, fp, C.c_float, C.c_float, sz, u32, u32, u32, i32])
-        f(pre + "destroy", None, [H])
-        f(pre + "reset", i32, [H])
-        f(pre + "set_detrend", i32, [H, i32])
-        f(pre + "process", i32, [H, u32, fp, sz])
-        f(pre + "process_device", i32, [H, u32, vp, sz, vp])
-        f(pre + "sync", i32, [H])
-        f(pre + "num_stages", i32, [H, u32])
-        f(pre + "stage_blocks", i32, [H, u32, u32, C.POINTER(_CWfBlocks)])
-        f(pre + "stage_rows", i32, [H, u32, u32, u32, C.POINTER(u64), up] + [dp] * nrows + [up])
-        f(pre + "image", i32, [H, u32, u32, u32, fp, fp, C.POINTER(u64), up, up])
-        f(pre + "image_device", i32, [H, u32, u32, u32, vp, vp, C.POINTER(u64), up, up])
-        f(pre + "stats_read", i32, [H, C.POINTER(u64), C.POINTER(u64), i32])
-        f(pre + "last_error", C.c_char_p, [H])
-    f("psdc_zwf_set_carrier", i32, [H, u32, u64, u64])
     _lib = L
     return L
 
 
-EXPORTS = [
-    "psdc_abi_version", "psdc_last_error", "psdc_create", "psdc_destroy", "psdc_clone", "psdc_reset",
-    "psdc_configure", "psdc_set_detrend", "psdc_set_avg", "psdc_process", "psdc_process_device",
-    "psdc_process_adcdac_frames", "psdc_process_frames", "psdc_process_frames_device", "psdc_loss_read", "psdc_flush", "psdc_sync", "psdc_num_stages", "psdc_stage_info",
-    "psdc_stage_spectrum", "psdc_stage_gain", "psdc_stage_buf", "psdc_read_channel", "psdc_psd", "psdc_rbw",
-    "psdc_frequencies", "psdc_hbf_response_length", "psdc_stitch", "psdc_plan_counts",
-    "psdc_var_eval", "psdc_hbf_dec8", "psdc_fill_noise_device", "psdc_profile_read",
-    "psdc_process_device_after", "psdc_record_consumed", "psdc_trace_plot", "psdc_process_adcdac_frames_device",
-    "psdc_stage_create", "psdc_stage_destroy", "psdc_stage_clone", "psdc_stage_set_avg", "psdc_stage_set_detrend",
-    "psdc_stage_process", "psdc_stage_process_device", "psdc_stage_get_spectrum", "psdc_stage_get_count",
-    "psdc_stage_get_gain", "psdc_stage_get_buf", "psdc_stage_last_error",
-    "psdc_create_window", "psdc_window_get", "psdc_window_table", "psdc_stage_create_window", "psdc_stitch_window",
-    "psdc_readout_bytes", "psdc_pack_readout", "psdc_unpack_info", "psdc_unpack_stitch",
-    "psdc_pack_init", "psdc_pack_channel", "psdc_pack_pad",
-    "psdc_cross_create", "psdc_cross_create_window", "psdc_cross_destroy", "psdc_cross_reset", "psdc_cross_set_detrend",
-    "psdc_cross_set_avg", "psdc_cross_process", "psdc_cross_process_device", "psdc_cross_sync", "psdc_cross_num_stages",
-    "psdc_cross_stage_spectra", "psdc_cross_csd", "psdc_cross_stitch", "psdc_cross_stats_read", "psdc_cross_last_error",
-    "psdc_csd_process_frames", "psdc_csd_process_frames_device", "psdc_csd_loss_read",
-    "psdc_csm_supported", "psdc_csm_create", "psdc_csm_create_window", "psdc_csm_destroy", "psdc_csm_reset",
-    "psdc_csm_set_detrend", "psdc_csm_set_avg", "psdc_csm_process", "psdc_csm_process_device", "psdc_csm_process_frames",
-    "psdc_csm_process_frames_device", "psdc_csm_loss_read", "psdc_csm_sync", "psdc_csm_num_stages", "psdc_csm_stage_spectra",
-    "psdc_csm_csd", "psdc_csm_stitch", "psdc_csm_stats_read", "psdc_csm_last_error",
-    "psdc_zoom_create", "psdc_zoom_create_window", "psdc_zoom_destroy", "psdc_zoom_reset", "psdc_zoom_set_detrend",
-    "psdc_zoom_set_avg", "psdc_zoom_set_carrier", "psdc_zoom_process", "psdc_zoom_process_device", "psdc_zoom_sync",
-    "psdc_zoom_num_stages", "psdc_zoom_stage_spectra", "psdc_zoom_psd", "psdc_zoom_stats_read", "psdc_zoom_last_error",
-    "psdc_zoomcascade_process_frames", "psdc_zoomcascade_process_frames_device", "psdc_zoomcascade_loss_read",
-    "psdc_zcsd_supported", "psdc_zcsd_create", "psdc_zcsd_create_window", "psdc_zcsd_destroy", "psdc_zcsd_reset",
-    "psdc_zcsd_set_detrend", "psdc_zcsd_set_avg", "psdc_zcsd_set_carrier", "psdc_zcsd_process", "psdc_zcsd_process_device",
-    "psdc_zcsd_sync", "psdc_zcsd_num_stages", "psdc_zcsd_stage_spectra", "psdc_zcsd_csd", "psdc_zcsd_stats_read",
-    "psdc_zcsd_last_error",
-    "psdc_zoomcsdcascade_process_frames", "psdc_zoomcsdcascade_process_frames_device", "psdc_zoomcsdcascade_loss_read",
-    "psdc_iq_create", "psdc_iq_create_window", "psdc_iq_destroy", "psdc_iq_reset", "psdc_iq_set_detrend", "psdc_iq_set_avg",
-    "psdc_iq_set_carrier", "psdc_iq_process", "psdc_iq_process_device", "psdc_iq_process_interleaved",
-    "psdc_iq_process_interleaved_device", "psdc_iq_process_frames", "psdc_iq_process_frames_device", "psdc_iq_loss_read",
-    "psdc_iq_sync", "psdc_iq_num_stages", "psdc_iq_stage_spectra", "psdc_iq_psd", "psdc_iq_stats_read", "psdc_iq_last_error",
-    "psdc_iqcsd_supported", "psdc_iqcsd_create", "psdc_iqcsd_create_window", "psdc_iqcsd_destroy", "psdc_iqcsd_reset",
-    "psdc_iqcsd_set_detrend", "psdc_iqcsd_set_avg", "psdc_iqcsd_set_carrier", "psdc_iqcsd_process", "psdc_iqcsd_process_device",
-    "psdc_iqcsd_process_interleaved", "psdc_iqcsd_process_interleaved_device", "psdc_iqcsd_process_frames",
-    "psdc_iqcsd_process_frames_device", "psdc_iqcsd_loss_read", "psdc_iqcsd_sync", "psdc_iqcsd_num_stages",
-    "psdc_iqcsd_stage_spectra", "psdc_iqcsd_csd", "psdc_iqcsd_stats_read", "psdc_iqcsd_last_error",
-    "psdc_int_zoom_process", "psdc_int_zoom_process_device", "psdc_int_zcsd_process", "psdc_int_zcsd_process_device",
-    "psdc_int_iq_process", "psdc_int_iq_process_device", "psdc_int_iqcsd_process", "psdc_int_iqcsd_process_device",
-    "psdc_sint_process", "psdc_sint_process_device", "psdc_sint_cross_process", "psdc_sint_cross_process_device",
-    "psdc_sint_csm_process", "psdc_sint_csm_process_device",
-    "psdc_sk_supported", "psdc_sk_create", "psdc_sk_create_window", "psdc_sk_destroy", "psdc_sk_reset", "psdc_sk_set_detrend",
-    "psdc_sk_set_avg", "psdc_sk_process", "psdc_sk_process_device", "psdc_sk_sync", "psdc_sk_num_stages",
-    "psdc_sk_stage_moments", "psdc_sk_psd", "psdc_sk_sk", "psdc_sk_stats_read", "psdc_sk_last_error",
-    "psdc_zsk_supported", "psdc_zsk_create", "psdc_zsk_create_window", "psdc_zsk_destroy", "psdc_zsk_reset",
-    "psdc_zsk_set_detrend", "psdc_zsk_set_avg", "psdc_zsk_set_carrier", "psdc_zsk_process", "psdc_zsk_process_device",
-    "psdc_zsk_sync", "psdc_zsk_num_stages", "psdc_zsk_stage_moments", "psdc_zsk_psd", "psdc_zsk_sk", "psdc_zsk_stats_read",
-    "psdc_zsk_last_error",
-    "psdc_iqsk_supported", "psdc_iqsk_create", "psdc_iqsk_create_window", "psdc_iqsk_destroy", "psdc_iqsk_reset",
-    "psdc_iqsk_set_detrend", "psdc_iqsk_set_avg", "psdc_iqsk_set_carrier", "psdc_iqsk_process", "psdc_iqsk_process_device",
-    "psdc_iqsk_process_interleaved", "psdc_iqsk_process_interleaved_device", "psdc_iqsk_sync", "psdc_iqsk_num_stages",
-    "psdc_iqsk_stage_moments", "psdc_iqsk_psd", "psdc_iqsk_sk", "psdc_iqsk_stats_read", "psdc_iqsk_last_error",
-    "psdc_zampm_supported", "psdc_zampm_create", "psdc_zampm_create_window", "psdc_zampm_destroy", "psdc_zampm_reset",
-    "psdc_zampm_set_detrend", "psdc_zampm_set_avg", "psdc_zampm_set_carrier", "psdc_zampm_process", "psdc_zampm_process_device",
-    "psdc_zampm_sync", "psdc_zampm_num_stages", "psdc_zampm_stage_rows", "psdc_zampm_psd", "psdc_zampm_sidebands",
-    "psdc_zampm_stats_read", "psdc_zampm_last_error",
-    "psdc_iqampm_supported", "psdc_iqampm_create", "psdc_iqampm_create_window", "psdc_iqampm_destroy", "psdc_iqampm_reset",
-    "psdc_iqampm_set_detrend", "psdc_iqampm_set_avg", "psdc_iqampm_set_carrier", "psdc_iqampm_process",
-    "psdc_iqampm_process_device", "psdc_iqampm_process_interleaved", "psdc_iqampm_process_interleaved_device", "psdc_iqampm_sync",
-    "psdc_iqampm_num_stages", "psdc_iqampm_stage_rows", "psdc_iqampm_psd", "psdc_iqampm_sidebands", "psdc_iqampm_stats_read",
-    "psdc_iqampm_last_error",
-    "psdc_zxampm_supported", "psdc_zxampm_create", "psdc_zxampm_create_window", "psdc_zxampm_destroy", "psdc_zxampm_reset",
-    "psdc_zxampm_set_detrend", "psdc_zxampm_set_avg", "psdc_zxampm_set_carrier", "psdc_zxampm_process",
-    "psdc_zxampm_process_device", "psdc_zxampm_sync", "psdc_zxampm_num_stages", "psdc_zxampm_stage_rows", "psdc_zxampm_sidebands",
-    "psdc_zxampm_stats_read", "psdc_zxampm_last_error",
-    "psdc_iqxampm_supported", "psdc_iqxampm_create", "psdc_iqxampm_create_window", "psdc_iqxampm_destroy", "psdc_iqxampm_reset",
-    "psdc_iqxampm_set_detrend", "psdc_iqxampm_set_avg", "psdc_iqxampm_set_carrier", "psdc_iqxampm_process",
-    "psdc_iqxampm_process_device", "psdc_iqxampm_process_interleaved", "psdc_iqxampm_process_interleaved_device",
-    "psdc_iqxampm_sync", "psdc_iqxampm_num_stages", "psdc_iqxampm_stage_rows", "psdc_iqxampm_sidebands", "psdc_iqxampm_stats_read",
-    "psdc_iqxampm_last_error",
-    "psdc_wf_supported", "psdc_wf_create", "psdc_wf_create_window", "psdc_wf_destroy", "psdc_wf_reset", "psdc_wf_set_detrend",
-    "psdc_wf_process", "psdc_wf_process_device", "psdc_wf_sync", "psdc_wf_num_stages", "psdc_wf_stage_blocks",
-    "psdc_wf_stage_rows", "psdc_wf_image", "psdc_wf_image_device", "psdc_wf_stats_read", "psdc_wf_last_error",
-    "psdc_zwf_supported", "psdc_zwf_create", "psdc_zwf_create_window", "psdc_zwf_destroy", "psdc_zwf_reset",
-    "psdc_zwf_set_detrend", "psdc_zwf_set_carrier", "psdc_zwf_process", "psdc_zwf_process_device", "psdc_zwf_sync",
-    "psdc_zwf_num_stages", "psdc_zwf_stage_blocks", "psdc_zwf_stage_rows", "psdc_zwf_image", "psdc_zwf_image_device",
-    "psdc_zwf_stats_read", "psdc_zwf_last_error",
-]
+def _prototypes():
+    """name -> (restype, argtypes) of every function of include/psdcascade.h.  Built without the library: lib() applies it."""
+    P = C.POINTER
+    H = vp = C.c_void_p
+    u32, u64, i32, sz, fl, text = C.c_uint32, C.c_uint64, C.c_int, C.c_size_t, C.c_float, C.c_char_p
+    fp, dp, up, p64, psz, pp = P(fl), P(C.c_double), P(u32), P(u64), P(sz), P(vp)
+    stat, brk = P(_CStageStat), P(_CBreak)
+    win = [u32, fp, fl, fl, sz]         # n and a window table: the head of every create_window
+    opts = [i32, u32, i32]              # MergeOpts
+    out = [sz, psz, brk, sz, psz]       # capacity, length written, breaks, their capacity, breaks written
+    T = {}
+
+    def f(name, res, args):
+        T[name] = (res, args)
+
+    def merged(*rows):
+        """a merged read-out of one unit: its rows between the options and the lengths"""
+        return [H, u32] + opts + list(rows) + out
+
+    # What every family has.  Per family: the prefix; how many counts create takes between the window and the device; how many
+    # sizes supported takes (0: there is no such call); which of set_avg, stats_read and set_carrier it has ("side": the carrier
+    # is one of a pair's two); the prefix of its frames pair and loss record.
+    for pre, units, sup, has, frames in (
+            ("psdc_", 1, 0, "avg", None),   # (its frames calls take no map: they follow)
+            ("psdc_cross_", 1, 0, "avg stats", "psdc_csd_"),
+            ("psdc_csm_", 2, 2, "avg stats", "psdc_csm_"),
+            ("psdc_zoom_", 1, 0, "avg stats carrier", "psdc_zoomcascade_"),
+            ("psdc_zcsd_", 1, 1, "avg stats carrier side", "psdc_zoomcsdcascade_"),
+            ("psdc_iq_", 1, 0, "avg stats carrier", "psdc_iq_"),
+            ("psdc_iqcsd_", 1, 1, "avg stats carrier side", "psdc_iqcsd_"),
+            ("psdc_sk_", 1, 1, "avg stats", None),
+            ("psdc_zsk_", 1, 1, "avg stats carrier", None),
+            ("psdc_iqsk_", 1, 1, "avg stats carrier", None),
+            ("psdc_zampm_", 1, 1, "avg stats carrier", None),
+            ("psdc_iqampm_", 1, 1, "avg stats carrier", None),
+            ("psdc_zxampm_", 1, 1, "avg stats carrier side", None),
+            ("psdc_iqxampm_", 1, 1, "avg stats carrier side", None),
+            ("psdc_wf_", 3, 1, "stats", None),
+            ("psdc_zwf_", 3, 1, "stats carrier", None)):
+        has = has.split()
+        f(pre + "create", H, [u32, i32] + [u32] * units + [i32])
+        f(pre + "create_window", H, win + [u32] * units + [i32])
+        f(pre + "destroy", None, [H])
+        f(pre + "reset", i32, [H])
+        f(pre + "set_detrend", i32, [H, i32])
+        f(pre + "sync", i32, [H])
+        f(pre + "num_stages", i32, [H, u32])
+        f(pre + "last_error", text, [H])
+        if sup:
+            f(pre + "supported", i32, [u32] * sup)
+        if "avg" in has:
+            f(pre + "set_avg", i32, [H, u32, u32])
+        if "stats" in has:
+            f(pre + "stats_read", i32, [H, p64, p64, i32])
+        if "carrier" in has:
+            f(pre + "set_carrier", i32, [H, u32] + [u32] * ("side" in has) + [u64, u64])
+        if frames:
+            f(frames + "process_frames", i32, [H, up, vp, sz, sz, psz])
+            f(frames + "process_frames_device", i32, [H, up, vp, sz, sz, psz, vp])
+            f(frames + "loss_read", i32, [H, P(_CLoss), i32])
+
+    # PsdCascadeBank, Psd and the host helpers
+    f("psdc_abi_version", i32, [])
+    f("psdc_window_get", i32, [H, P(i32), fp, fp, psz, fp])
+    f("psdc_window_table", i32, [u32, i32, fp, fp, fp, psz])
+    f("psdc_stitch", i32, [u32, i32, u32, up, up, p64, fp] + opts + [fp] + out)
+    f("psdc_stitch_window", i32, [u32, fl, fl, sz, u32, p64, up, p64, fp] + opts + [fp] + out)
+    f("psdc_readout_bytes", sz, [u32, u32])
+    f("psdc_pack_readout", i32, [H, vp, sz, psz])
+    f("psdc_pack_init", i32, [vp, sz, u32, fl, fl, sz, u32])
+    f("psdc_pack_channel", i32, [vp, sz, u32, u32, p64, up, p64, fp])
+    f("psdc_pack_pad", i32, [vp, sz, vp, sz, u32])
+    f("psdc_unpack_info", i32, [vp, sz, u32, up, up, up])
+    f("psdc_unpack_stitch", i32, [vp, sz, u32] + opts + [fp] + out)
+    f("psdc_clone", H, [H])
+    f("psdc_configure", i32, [H, i32, C.c_int64])
+    f("psdc_process", i32, [H, u32, fp, sz])
+    f("psdc_process_device", i32, [H, u32, vp, sz])
+    f("psdc_process_device_after", i32, [H, u32, vp, sz, vp])
+    f("psdc_record_consumed", i32, [H, vp])
+    for name in ("psdc_process_adcdac_frames", "psdc_process_frames", "psdc_process_frames_device",
+                 "psdc_process_adcdac_frames_device"):
+        f(name, i32, [H, vp, sz, sz, psz])
+    f("psdc_loss_read", i32, [H, P(_CLoss), i32])
+    f("psdc_flush", i32, [H])
+    f("psdc_stage_info", i32, [H, u32, u32, stat])
+    f("psdc_stage_spectrum", i32, [H, u32, u32, fp])
+    f("psdc_stage_gain", i32, [H, u32, u32, fp])
+    f("psdc_stage_buf", i32, [H, u32, u32, fp, sz, psz])
+    f("psdc_read_channel", i32, [H, u32, u32, up, stat, fp])
+    f("psdc_psd", i32, merged(fp))
+    f("psdc_rbw", fl, [H])
+    f("psdc_frequencies", sz, [brk, sz, fp, sz])
+    f("psdc_hbf_response_length", i32, [i32])
+    f("psdc_plan_counts", i32, [u32, i32, u64, u32, p64, p64, p64])
+    f("psdc_var_eval", fl, [i32, i32, fl, sz, fp, fp, sz, fl])
+    f("psdc_hbf_dec8", i32, [i32, fp, sz, fp])
+    f("psdc_fill_noise_device", i32, [i32, vp, sz, u64, u64])
+    f("psdc_profile_read", i32, [H, P(_CProfile), i32])
+    f("psdc_trace_plot", i32, [fp, fp, sz, fl, i32, fl, fl, fp, dp, sz, psz])
+    f("psdc_stage_create", H, [u32, i32, i32])
+    f("psdc_stage_create_window", H, win + [i32])
+    f("psdc_stage_destroy", None, [H])
+    f("psdc_stage_clone", H, [H])
+    f("psdc_stage_set_avg", i32, [H, u32])
+    f("psdc_stage_set_detrend", i32, [H, i32])
+    f("psdc_stage_process", i32, [H, fp, sz, fp, sz, psz])
+    f("psdc_stage_process_device", i32, [H, vp, sz, vp, sz, psz])
+    f("psdc_stage_get_spectrum", i32, [H, fp])
+    f("psdc_stage_get_count", i32, [H, up])
+    f("psdc_stage_get_gain", i32, [H, fp])
+    f("psdc_stage_get_buf", i32, [H, fp, sz, psz])
+    f("psdc_stage_last_error", text, [H])
+
+    # The feeds.  f32 streams: one real stream a unit, two (a pair), planar I and Q, interleaved (re, im); _device forms take
+    # device addresses and, last, an event to wait for.
+    for pre in ("psdc_zoom_", "psdc_sk_", "psdc_zsk_", "psdc_zampm_", "psdc_wf_", "psdc_zwf_"):
+        f(pre + "process", i32, [H, u32, fp, sz])
+        f(pre + "process_device", i32, [H, u32, vp, sz, vp])
+    for pre in ("psdc_cross_", "psdc_zcsd_", "psdc_zxampm_"):
+        f(pre + "process", i32, [H, u32, fp, fp, sz])
+        f(pre + "process_device", i32, [H, u32, vp, vp, sz, vp])
+    for pre in ("psdc_iq_", "psdc_iqsk_", "psdc_iqampm_"):
+        f(pre + "process", i32, [H, u32, fp, fp, sz])
+        f(pre + "process_device", i32, [H, u32, vp, vp, sz, vp])
+        f(pre + "process_interleaved", i32, [H, u32, fp, sz])
+        f(pre + "process_interleaved_device", i32, [H, u32, vp, sz, vp])
+    for pre in ("psdc_iqcsd_", "psdc_iqxampm_"):
+        f(pre + "process", i32, [H, u32, fp, fp, fp, fp, sz])
+        f(pre + "process_device", i32, [H, u32, vp, vp, vp, vp, sz, vp])
+        f(pre + "process_interleaved", i32, [H, u32, fp, fp, sz])
+        f(pre + "process_interleaved_device", i32, [H, u32, vp, vp, sz, vp])
+    f("psdc_csm_process", i32, [H, u32, pp, sz])
+    f("psdc_csm_process_device", i32, [H, u32, pp, sz, vp])
+    # integer streams (kind, scale): one stream a unit, two, or m behind a pointer table
+    for pre in ("psdc_sint_", "psdc_int_zoom_", "psdc_int_iq_"):
+        f(pre + "process", i32, [H, u32, vp, i32, fl, sz])
+        f(pre + "process_device", i32, [H, u32, vp, i32, fl, sz, vp])
+    for pre in ("psdc_sint_cross_", "psdc_int_zcsd_", "psdc_int_iqcsd_"):
+        f(pre + "process", i32, [H, u32, vp, vp, i32, fl, sz])
+        f(pre + "process_device", i32, [H, u32, vp, vp, i32, fl, sz, vp])
+    f("psdc_sint_csm_process", i32, [H, u32, pp, i32, fl, sz])
+    f("psdc_sint_csm_process_device", i32, [H, u32, pp, i32, fl, sz, vp])
+
+    # stage reads and read-outs, family by family
+    f("psdc_cross_stage_spectra", i32, [H, u32, u32, stat, fp, fp, fp])
+    f("psdc_cross_csd", i32, merged(fp, fp, fp))
+    f("psdc_cross_stitch", i32, [u32, fl, fl, sz, u32, p64, up, p64, fp] + opts + [fp, fp, fp] + out)
+    f("psdc_csm_stage_spectra", i32, [H, u32, u32, stat, fp])
+    f("psdc_csm_csd", i32, merged(fp))
+    f("psdc_csm_stitch", i32, [u32, u32, fl, fl, sz, u32, p64, up, p64, fp] + opts + [fp] + out)
+    for pre in ("psdc_zoom_", "psdc_iq_"):
+        f(pre + "stage_spectra", i32, [H, u32, u32, stat, fp, fp])
+        f(pre + "psd", i32, merged(fp, fp))
+    for pre in ("psdc_zcsd_", "psdc_iqcsd_"):
+        f(pre + "stage_spectra", i32, [H, u32, u32, stat, fp])
+        f(pre + "csd", i32, merged(*[fp] * 6))
+    f("psdc_sk_stage_moments", i32, [H, u32, u32, stat, dp, dp])
+    f("psdc_sk_psd", i32, merged(fp))
+    f("psdc_sk_sk", i32, merged(dp))
+    for pre in ("psdc_zsk_", "psdc_iqsk_"):
+        f(pre + "stage_moments", i32, [H, u32, u32, stat, dp, dp, dp, dp])
+        f(pre + "psd", i32, merged(fp, fp))
+        f(pre + "sk", i32, merged(dp, dp))
+    for pre in ("psdc_zampm_", "psdc_iqampm_"):
+        f(pre + "stage_rows", i32, [H, u32, u32, stat, dp, dp, dp, dp])
+        f(pre + "psd", i32, merged(fp, fp))
+        f(pre + "sidebands", i32, merged(dp, dp, dp, dp))
+    for pre in ("psdc_zxampm_", "psdc_iqxampm_"):
+        f(pre + "stage_rows", i32, [H, u32, u32, stat, dp])
+        f(pre + "sidebands", i32, merged(dp))
+    for pre, nrows in (("psdc_wf_", 2), ("psdc_zwf_", 4)):
+        f(pre + "stage_blocks", i32, [H, u32, u32, P(_CWfBlocks)])
+        f(pre + "stage_rows", i32, [H, u32, u32, u32, p64, up] + [dp] * nrows + [up])
+        f(pre + "image", i32, [H, u32, u32, u32, fp, fp, p64, up, up])
+        f(pre + "image_device", i32, [H, u32, u32, u32, vp, vp, p64, up, up])
+    return T
+
+
+_PROTOTYPES = _prototypes()
+EXPORTS = list(_PROTOTYPES)
 
 
 def _fptr(a):
@@ -701,25 +497,275 @@ def _raise(code, h=None):
     raise cls(code, msg)
 
 
-class PsdCascadeBank:
+def _stage_info(st):
+    """a _CStageStat as the info dict of the stage reads"""
+    return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
+
+
+def _carrier_words(f0, ftw, phase0):
+    """(ftw, phase0) modulo 2^64 of a carrier given as exactly one of f0 (through zoom_ftw) and ftw"""
+    if (f0 is None) == (ftw is None):
+        raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
+    if ftw is None:
+        ftw = zoom_ftw(f0)[0]
+    return int(ftw) % (1 << 64), int(phase0) % (1 << 64)
+
+
+class _Bank:
+    """What the banks share: one handle `_h` of the C ABI, made by the create or create_window of the family whose C prefix is
+    `_P`, that family's error text, and the calls every family has.  A bank class sets the attributes below, mixes in what its
+    family has beside them (_SetAvg, _Stats, _FramesFeed, a carrier mixin) and keeps its own feeds, stage reads and read-outs."""
+
+    _P = None                                                        # the family's C prefix, e.g. "psdc_zoom_"
+    _ARG_WORDS = ("must be", "out of range", "null", "window_kind")  # a failed create is ERR_ARG if its message has one
+    _IN = "samples_in"                                               # the second key of stats_read
+
+    def _open(self, n, window, device, *units):
+        """The handle, by create or, for a WindowTable, create_window; `units` are the family's counts between the window and
+        the device (channels, pairs, ...), which the frames map builder takes too."""
+        self.n, self.window, self.device, self._units = n, window, device, units
+        self._L = lib()
+        if isinstance(window, WindowTable):
+            w = np.ascontiguousarray(window.win, dtype=np.float32)
+            if w.size != n:
+                raise PsdError(ERR_ARG, "window table length != n")
+            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, *units, device)
+        else:
+            self._h = self._f("create")(n, int(window), *units, device)
+        if not self._h:
+            self._create_failed()
+        self._fresh(65536)
+
+    def _create_failed(self):
+        msg = self._f("last_error")(None)
+        msg = msg.decode() if msg else ""
+        raise PsdError(ERR_ARG if any(w in msg for w in self._ARG_WORDS) else ERR_DEVICE, msg)
+
+    def _fresh(self, most=None):
+        """What the binding keeps beside the handle (carriers, detrend), as create and reset leave it; `most` caps a table."""
+
+    def _f(self, name):
+        return getattr(self._L, self._P + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._f("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _ck(self, rc):
+        if rc < 0:
+            msg = self._f("last_error")(self._h)
+            cls = FrameError if rc in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
+            raise cls(rc, msg.decode() if msg else "")
+        return rc
+
+    def reset(self):
+        """Back to a fresh object: what the binding keeps beside the handle (the carriers: ftw = 0, phase0 = 0) too."""
+        self._ck(self._f("reset")(self._h))
+        self._fresh()
+
+    def set_detrend(self, d):
+        self._ck(self._f("set_detrend")(self._h, int(d)))
+
+    def sync(self):
+        self._ck(self._f("sync")(self._h))
+
+    def _num_stages(self, unit):
+        return self._ck(self._f("num_stages")(self._h, unit))
+
+    def _merged(self, fn, unit, opts, widths, dtype=np.float32):
+        """One merged read-out call `fn` of `unit`.  widths: per row the numbers it holds a bin (1, or 2 for a complex row of
+        (re, im)), each row behind a pointer of its own; or an int: that many rows of one number a bin as one [rows][capacity]
+        array behind one pointer.  Returns (the rows cut to the bins written, in memory of their own, the breaks)."""
+        ns = self._num_stages(unit)
+        cap = max(1, ns * (self.n // 2 + 1))
+        cp = C.POINTER(C.c_double if dtype == np.float64 else C.c_float)
+        if isinstance(widths, int):
+            rows = np.zeros((widths, cap), dtype)
+            ptrs = [rows.ctypes.data_as(cp)]
+        else:
+            rows = [np.empty(w * cap, dtype) for w in widths]
+            ptrs = [r.ctypes.data_as(cp) for r in rows]
+        br = (_CBreak * max(1, ns))()
+        plen, nb = C.c_size_t(), C.c_size_t()
+        self._ck(fn(self._h, unit, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band), *ptrs, cap,
+                    C.byref(plen), br, ns, C.byref(nb)))
+        m = plen.value
+        rows = rows[:, :m] if isinstance(widths, int) else [r[:w * m].copy() for r, w in zip(rows, widths)]
+        return rows, [Break._from_c(br[i]) for i in range(nb.value)]
+
+    def _process_iq(self, channel, z):
+        """The complex-stream process of the family: z a complex array (process_interleaved) or a pair (i, q) (process)."""
+        if isinstance(z, (tuple, list)):
+            if len(z) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
+            i = np.ascontiguousarray(z[0], dtype=np.float32)
+            q = np.ascontiguousarray(z[1], dtype=np.float32)
+            if i.ndim != 1 or i.shape != q.shape:
+                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
+            self._ck(self._f("process")(self._h, channel, _fptr(i), _fptr(q), i.size))
+            return
+        z = np.asarray(z)
+        if not np.iscomplexobj(z):
+            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
+        z = np.ascontiguousarray(z, dtype=np.complex64)
+        self._ck(self._f("process_interleaved")(self._h, channel, _fptr(z), z.size))
+
+    def _process_iq_pair(self, pair, za, zb):
+        """_process_iq for a pair: two complex arrays, or two pairs (ia, qa), (ib, qb)."""
+        planar = [isinstance(z, (tuple, list)) for z in (za, zb)]
+        if all(planar):
+            if len(za) != 2 or len(zb) != 2:
+                raise PsdError(ERR_ARG, "a planar call takes (ia, qa), (ib, qb)")
+            x = [np.ascontiguousarray(v, dtype=np.float32) for v in (*za, *zb)]
+            if any(v.ndim != 1 or v.shape != x[0].shape for v in x):
+                raise PsdError(ERR_ARG, "the four streams differ in length (" + ", ".join(str(v.size) for v in x) + ")")
+            self._ck(self._f("process")(self._h, pair, *[_fptr(v) for v in x], x[0].size))
+            return
+        if any(planar):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q), not one of each")
+        za, zb = np.asarray(za), np.asarray(zb)
+        if not (np.iscomplexobj(za) and np.iscomplexobj(zb)):
+            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q)")
+        za = np.ascontiguousarray(za, dtype=np.complex64)
+        zb = np.ascontiguousarray(zb, dtype=np.complex64)
+        if za.ndim != 1 or za.shape != zb.shape:
+            raise PsdError(ERR_ARG, f"za and zb differ in length ({za.size} and {zb.size})")
+        self._ck(self._f("process_interleaved")(self._h, pair, _fptr(za), _fptr(zb), za.size))
+
+
+class _SetAvg:
+    """set_avg, for every family but the waterfalls"""
+
+    def set_avg(self, avg):
+        self._ck(self._f("set_avg")(self._h, avg.limit, avg.count))
+
+
+class _Stats:
+    """stats_read, for every family but PsdCascadeBank (which has profile_read); `_IN` names what the family counts"""
+
+    def stats_read(self, reset=False):
+        la, si = C.c_uint64(), C.c_uint64()
+        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
+        return {"launches": la.value, self._IN: si.value}
+
+
+class _ChannelBank(_SetAvg, _Stats, _Bank):
+    """A bank of `n_channels` units fed one stream each."""
+
+    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
+        self.n_channels = n_channels
+        self._open(n, window, device, n_channels)
+
+    def num_stages(self, channel=0):
+        return self._num_stages(channel)
+
+
+class _PairBank(_SetAvg, _Stats, _Bank):
+    """A bank of `n_pairs` units fed two streams each."""
+
+    _IN = "pairs_in"
+
+    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
+        self.n_pairs = n_pairs
+        self._open(n, window, device, n_pairs)
+
+    def num_stages(self, pair=0):
+        return self._num_stages(pair)
+
+
+class _FramesFeed:
+    """The stream-frames feed of a bank.  `_FP` is the C prefix of its process_frames pair and loss record (not always the
+    family's own), `_MAP` the builder of the trace map: called with what the caller names and the bank's unit counts."""
+
+    _FP = None
+    _MAP = None
+
+    def _frames(self, data, frame_size, entries):
+        buf = np.frombuffer(data, dtype=np.uint8)
+        m = self._MAP(entries, *self._units)
+        ok = C.c_size_t(0)
+        self._ck(getattr(self._L, self._FP + "process_frames")(
+            self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p), frame_size,
+            buf.size // frame_size, C.byref(ok)))
+        return ok.value
+
+    def _frames_device(self, ptr, frame_size, n_frames, entries, after):
+        m = self._MAP(entries, *self._units)
+        ok = C.c_size_t(0)
+        self._ck(getattr(self._L, self._FP + "process_frames_device")(
+            self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr), frame_size, n_frames, C.byref(ok),
+            C.c_void_p(after) if after else None))
+        return ok.value
+
+    def loss(self, reset=False):
+        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
+        l = _CLoss()
+        self._ck(getattr(self._L, self._FP + "loss_read")(self._h, C.byref(l), int(reset)))
+        return {"received": l.received, "dropped": l.dropped}
+
+
+class _ChannelCarriers:
+    """A carrier per channel: `carriers[c]` is the (ftw, phase0) of channel c, as set."""
+
+    def _fresh(self, most=None):
+        super()._fresh(most)
+        self.carriers = {c: (0, 0) for c in range(self.n_channels if most is None else min(self.n_channels, most))}
+
+    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
+        """The channel's carrier, as f0 (cycles per sample, through zoom_ftw) or as the tuning word itself; phase0 in 2^-64
+        turn.  Only before the channel's first sample.  Returns the f0 actually used."""
+        ftw, phase0 = _carrier_words(f0, ftw, phase0)
+        self._ck(self._f("set_carrier")(self._h, channel, ftw, phase0))
+        self.carriers[channel] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+
+class _SideCarriers:
+    """A carrier per side of a pair: the table named by `_CARRIERS` holds the (ftw, phase0) of (pair, side), as set."""
+
+    _CARRIERS = "carriers"
+    _SIDES = "0: channel a, 1: channel b"
+
+    def _fresh(self, most=None):
+        super()._fresh(most)
+        if most is None:
+            keys = getattr(self, self._CARRIERS)
+        else:
+            keys = [(p, s) for p in range(min(self.n_pairs, most)) for s in (0, 1)]
+        setattr(self, self._CARRIERS, {k: (0, 0) for k in keys})
+
+    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
+        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as f0 (cycles per sample, through
+        zoom_ftw) or as the tuning word itself; phase0 in 2^-64 turn.  Only before the pair's first sample.  Returns the f0
+        actually used."""
+        ftw, phase0 = _carrier_words(f0, ftw, phase0)
+        if side is not None and side not in (0, 1):
+            raise PsdError(ERR_ARG, f"side {side} out of range ({self._SIDES})")
+        for s in ((0, 1) if side is None else (side,)):
+            self._ck(self._f("set_carrier")(self._h, pair, s, ftw, phase0))
+            getattr(self, self._CARRIERS)[(pair, s)] = (ftw, phase0)
+        return ftw / float(1 << 64)
+
+
+class PsdCascadeBank(_FramesFeed, _SetAvg, _Bank):
     """`n_channels` independent PsdCascade<N> batched on one GPU (one handle of the C ABI)."""
+
+    _P = _FP = "psdc_"
 
     def __init__(self, n, n_channels=1, window=Window.HANN, device=0, _handle=None):
         """window: a Window kind, or a caller-built WindowTable (any Window<N>, src/psd.rs:12-20).
         device: HIP device index, or -1 = the index in $PSDC_DEVICE (0 when unset)."""
-        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
-        self._L = lib()
-        if _handle is not None:
-            self._h = _handle
-        elif isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
+        self.n_channels = n_channels
+        if _handle is None:
+            self._open(n, window, device, n_channels)
         else:
-            self._h = self._L.psdc_create(n, int(window), n_channels, device)
-        if not self._h:
-            _raise(ERR_DEVICE)
+            self.n, self.window, self.device, self._L, self._h = n, window, device, lib(), _handle
+
+    def _create_failed(self):
+        _raise(ERR_DEVICE)
 
     def window_get(self):
         """(kind, WindowTable) as the library holds it: a table equal to Window::hann() is recognised as HANN."""
@@ -737,26 +783,11 @@ class PsdCascadeBank:
         assert ln.value == need
         return buf
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise(rc, self._h)
-        return rc
-
     def clone(self):
         h = self._L.psdc_clone(self._h)
         if not h:
             _raise(ERR_DEVICE)
         return PsdCascadeBank(self.n, self.n_channels, self.window, self.device, _handle=h)
-
-    def reset(self):
-        self._ck(self._L.psdc_reset(self._h))
 
     def configure(self, quantum=None, profile=None, coalesce=None, min_pairs=None, eager=None, merge=None):
         if merge is not None:
@@ -774,12 +805,6 @@ class PsdCascadeBank:
 
     def rbw(self):
         return float(self._L.psdc_rbw(self._h))
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_set_avg(self._h, avg.limit, avg.count))
 
     def process(self, channel, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -814,62 +839,40 @@ class PsdCascadeBank:
         """Record the hipEvent_t handle `event` behind the last read of every span handed over so far."""
         self._ck(self._L.psdc_record_consumed(self._h, C.c_void_p(event)))
 
+    def _ingest(self, fn, ptr, frame_size, n_frames):
+        ok = C.c_size_t(0)
+        self._ck(fn(self._h, ptr, frame_size, n_frames, C.byref(ok)))
+        return ok.value
+
     def process_adcdac_frames(self, data, frame_size):
         """data: bytes-like holding whole frames; returns the number of frames ingested."""
         buf = np.frombuffer(data, dtype=np.uint8)
-        n_frames = buf.size // frame_size
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_process_adcdac_frames(self._h, buf.ctypes.data_as(C.c_void_p), frame_size,
-                                                n_frames, C.byref(ok))
-        if rc < 0:
-            _raise(rc, self._h)
-        return ok.value
+        return self._ingest(self._L.psdc_process_adcdac_frames, buf.ctypes.data_as(C.c_void_p), frame_size, buf.size // frame_size)
 
     def process_frames(self, data, frame_size):
         """Frames of any of the four payload formats (src/de/mod.rs:12-17), each frame's own header naming its format: trace i of
         every frame goes to channel i.  data: bytes-like holding whole frames; returns the number of frames ingested."""
         buf = np.frombuffer(data, dtype=np.uint8)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_process_frames(self._h, buf.ctypes.data_as(C.c_void_p), frame_size, buf.size // frame_size, C.byref(ok))
-        if rc < 0:
-            _raise(rc, self._h)
-        return ok.value
+        return self._ingest(self._L.psdc_process_frames, buf.ctypes.data_as(C.c_void_p), frame_size, buf.size // frame_size)
 
     def process_frames_device(self, ptr, frame_size, n_frames):
         """process_frames for frames resident in device memory at address `ptr`; returns the number of frames ingested."""
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_process_frames_device(self._h, C.c_void_p(ptr), frame_size, n_frames, C.byref(ok))
-        if rc < 0:
-            _raise(rc, self._h)
-        return ok.value
+        return self._ingest(self._L.psdc_process_frames_device, C.c_void_p(ptr), frame_size, n_frames)
 
     def process_adcdac_frames_device(self, ptr, frame_size, n_frames):
         """Frames resident in device memory at address `ptr`; returns the number of frames ingested."""
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_process_adcdac_frames_device(self._h, C.c_void_p(ptr), frame_size, n_frames, C.byref(ok))
-        if rc < 0:
-            _raise(rc, self._h)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs): batches received / dropped over the ingested frames."""
-        l = _CLoss()
-        self._ck(self._L.psdc_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
+        return self._ingest(self._L.psdc_process_adcdac_frames_device, C.c_void_p(ptr), frame_size, n_frames)
 
     def flush(self):
         self._ck(self._L.psdc_flush(self._h))
 
-    def sync(self):
-        self._ck(self._L.psdc_sync(self._h))
-
     def num_stages(self, channel=0):
-        return self._ck(self._L.psdc_num_stages(self._h, channel))
+        return self._num_stages(channel)
 
     def stage_info(self, channel, stage):
         st = _CStageStat()
         self._ck(self._L.psdc_stage_info(self._h, channel, stage, C.byref(st)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
+        return _stage_info(st)
 
     def stage_spectrum(self, channel, stage):
         out = np.empty(self.n // 2 + 1, dtype=np.float32)
@@ -895,19 +898,11 @@ class PsdCascadeBank:
         st = (_CStageStat * max(1, ns.value))()
         sp = np.empty((ns.value, self.n // 2 + 1), dtype=np.float32)
         self._ck(self._L.psdc_read_channel(self._h, channel, ns.value, C.byref(ns), st, _fptr(sp) if ns.value else None))
-        info = [{"count": st[k].count, "avg": st[k].avg, "pending": st[k].pending, "processed": st[k].processed}
-                for k in range(ns.value)]
-        return info, sp
+        return [_stage_info(st[k]) for k in range(ns.value)], sp
 
     def psd(self, channel=0, opts=MergeOpts()):
-        ns = self.num_stages(channel)
-        out = np.empty(max(1, ns * (self.n // 2 + 1)), dtype=np.float32)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_psd(self._h, channel, int(opts.keep_overlap), opts.min_count,
-                                  int(opts.keep_transition_band), _fptr(out), out.size, C.byref(plen),
-                                  br, ns, C.byref(nb)))
-        return out[:plen.value].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+        (p,), br = self._merged(self._L.psdc_psd, channel, opts, (1,))
+        return p, br
 
     def profile_read(self, reset=False):
         p = _CProfile()
@@ -916,7 +911,110 @@ class PsdCascadeBank:
                 "stage0_samples": p.stage0_samples}
 
 
-class PsdCascade:
+class _Cascade:
+    """What the single objects share: a bank `_b` of the class `_BANK` with one unit, and the calls that name no unit."""
+
+    _BANK = None
+
+    def __init__(self, n, window=Window.HANN, device=0):
+        self.n = n
+        self._b = self._BANK(n, 1, window, device)
+
+    def set_detrend(self, d):
+        self._b.set_detrend(d)
+
+    def num_stages(self):
+        return self._b.num_stages(0)
+
+    def sync(self):
+        self._b.sync()
+
+    def close(self):
+        self._b.close()
+
+
+class _UnitCascade(_Cascade):
+    """The single object of every bank but PsdCascadeBank and the waterfalls: set_avg, reset and stats_read beside the above."""
+
+    def set_avg(self, avg):
+        self._b.set_avg(avg)
+
+    def reset(self):
+        self._b.reset()
+
+    def stats_read(self, reset=False):
+        return self._b.stats_read(reset)
+
+
+class _KeepsCarrier:
+    """A single object around one carrier, over a bank with _ChannelCarriers: `f0` is the frequency in use (ftw / 2^64), and
+    reset() keeps the carrier."""
+
+    def _tune(self, f0, ftw, phase0):
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0):
+        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
+        self.ftw, self.phase0 = self._b.carriers[0]
+        return self.f0
+
+    def reset(self):
+        self._b.reset()
+        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
+
+
+class _CarrierCascade(_KeepsCarrier, _UnitCascade):
+    """One stream around one carrier: the single object of the zoom and IQ banks."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        super().__init__(n, window, device)
+        self._tune(f0, ftw, phase0)
+
+    def process(self, x):
+        self._b.process(0, x)
+
+    def process_device(self, ptr, length, after=None):
+        self._b.process_device(0, ptr, length, after)
+
+    def psd(self, opts=MergeOpts()):
+        return self._b.psd(0, opts)
+
+
+class _PairCarrierCascade(_UnitCascade):
+    """One pair around a carrier a side, over a bank with _SideCarriers: the constructor's carrier goes to both sides, and
+    reset() keeps both."""
+
+    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
+        super().__init__(n, window, device)
+        if f0 is None and ftw is None:
+            ftw = 0
+        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
+
+    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
+        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
+        table = getattr(self._b, self._BANK._CARRIERS)
+        setattr(self, self._BANK._CARRIERS, [table[(0, 0)], table[(0, 1)]])
+        return f
+
+    def process(self, x, y):
+        self._b.process(0, x, y)
+
+    def process_device(self, px, py, length, after=None):
+        self._b.process_device(0, px, py, length, after)
+
+    def csd(self, opts=MergeOpts()):
+        return self._b.csd(0, opts)
+
+    def reset(self):
+        car = list(getattr(self, self._BANK._CARRIERS))
+        self._b.reset()
+        for s, (ftw, ph) in enumerate(car):
+            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
+
+
+class PsdCascade(_Cascade):
     """Online cascaded PSD estimator, one trace (src/psd.rs:399-544)."""
 
     def __init__(self, n, window=Window.HANN, device=0, _bank=None):
@@ -931,9 +1029,6 @@ class PsdCascade:
 
     def set_avg(self, avg):
         self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
 
     def process(self, x):
         self._b.process(0, x)
@@ -951,9 +1046,6 @@ class PsdCascade:
         return self._b.psd(0, opts)
 
     # PsdStage accessors of stage i (src/psd.rs:271-287)
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_spectrum(self, i):
         return self._b.stage_spectrum(0, i)
 
@@ -971,18 +1063,6 @@ class PsdCascade:
 
     def configure(self, **kw):
         self._b.configure(**kw)
-
-    def sync(self):
-        self._b.sync()
-
-    def close(self):
-        self._b.close()
-
-
-def _raise_cross(code, h=None):
-    msg = lib().psdc_cross_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
 
 
 TRACE_NONE = 0xFFFFFFFF
@@ -1010,48 +1090,12 @@ def pair_map(pairs, n_pairs):
     return m
 
 
-class CsdCascadeBank:
+class CsdCascadeBank(_FramesFeed, _PairBank):
     """`n_pairs` independent cross-spectral cascades (psdc_cross_*): pairs of streams x, y fed together.  Per stage the
     accumulators Sxx, Syy and Sxy = sum conj(X) Y (scipy.signal.csd's convention: H1 = Sxy / Sxx); the read-out is
     PsdCascade::psd (src/psd.rs:479-543) applied to each row, so Sxx is the psd() of a PsdCascade fed x."""
 
-    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
-        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_cross_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs,
-                                                       device)
-        else:
-            self._h = self._L.psdc_cross_create(n, int(window), n_pairs, device)
-        if not self._h:
-            msg = self._L.psdc_cross_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_cross_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_cross(rc, self._h)
-        return rc
-
-    def reset(self):
-        self._ck(self._L.psdc_cross_reset(self._h))
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_cross_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_cross_set_avg(self._h, avg.limit, avg.count))
+    _P, _FP, _MAP = "psdc_cross_", "psdc_csd_", staticmethod(pair_map)
 
     def process(self, pair, x, y):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -1085,35 +1129,12 @@ class CsdCascadeBank:
         """Stream frames of any of the four payload formats (bytes-like holding whole frames) into the pairs: pairs[p] = (x, y)
         feeds pair p with traces x and y of every frame (indices or TRACE_NAMES labels), None leaves it unfed.  Returns the
         number of frames ingested; a bad frame raises FrameError after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        m = pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_csd_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
-                                             frame_size, buf.size // frame_size, C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, pairs)
 
     def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
         """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
         their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
-        m = pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_csd_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
-                                                    frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
-        l = _CLoss()
-        self._ck(self._L.psdc_csd_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_cross_sync(self._h))
-
-    def num_stages(self, pair=0):
-        return self._ck(self._L.psdc_cross_num_stages(self._h, pair))
+        return self._frames_device(ptr, frame_size, n_frames, pairs, after)
 
     def stage_spectra(self, pair, stage):
         """(info, sxx, syy, sxy) of one stage's raw accumulators; sxy complex64."""
@@ -1121,41 +1142,18 @@ class CsdCascadeBank:
         st = _CStageStat()
         xx, yy, xy = np.empty(b, np.float32), np.empty(b, np.float32), np.empty(2 * b, np.float32)
         self._ck(self._L.psdc_cross_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(xx), _fptr(yy), _fptr(xy)))
-        info = {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
-        return info, xx, yy, xy.view(np.complex64)
+        return _stage_info(st), xx, yy, xy.view(np.complex64)
 
     def csd(self, pair=0, opts=MergeOpts()):
         """(sxx, syy, sxy complex64, breaks): PsdCascade::psd of each row."""
-        ns = self.num_stages(pair)
-        cap = max(1, ns * (self.n // 2 + 1))
-        xx, yy, xy = np.empty(cap, np.float32), np.empty(cap, np.float32), np.empty(2 * cap, np.float32)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_cross_csd(self._h, pair, int(opts.keep_overlap), opts.min_count,
-                                        int(opts.keep_transition_band), _fptr(xx), _fptr(yy), _fptr(xy), cap,
-                                        C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        return (xx[:m].copy(), yy[:m].copy(), xy[:2 * m].view(np.complex64).copy(),
-                [Break._from_c(br[i]) for i in range(nb.value)])
-
-    def stats_read(self, reset=False):
-        la, pi = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_cross_stats_read(self._h, C.byref(la), C.byref(pi), int(reset)))
-        return {"launches": la.value, "pairs_in": pi.value}
+        (xx, yy, xy), br = self._merged(self._L.psdc_cross_csd, pair, opts, (1, 1, 2))
+        return xx, yy, xy.view(np.complex64), br
 
 
-class CsdCascade:
+class CsdCascade(_UnitCascade):
     """One pair of streams: the cross-spectral form of PsdCascade (src/psd.rs:393 names `csdl` as its model)."""
 
-    def __init__(self, n, window=Window.HANN, device=0):
-        self.n = n
-        self._b = CsdCascadeBank(n, 1, window, device)
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
+    _BANK = CsdCascadeBank
 
     def process(self, x, y):
         self._b.process(0, x, y)
@@ -1182,23 +1180,8 @@ class CsdCascade:
     def csd(self, opts=MergeOpts()):
         return self._b.csd(0, opts)
 
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_spectra(self, i):
         return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        self._b.reset()
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
 
 
 def group_map(groups, m, n_groups):
@@ -1214,12 +1197,6 @@ def group_map(groups, m, n_groups):
             raise PsdError(ERR_ARG, f"group {g} names {len(tr)} traces for m = {m}")
         out[m * g:m * g + m] = [trace_index(t) for t in tr]
     return out
-
-
-def _raise_csm(code, h=None):
-    msg = lib().psdc_csm_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
 
 
 def csm_supported(n, m):
@@ -1240,50 +1217,20 @@ def csm_matrix(rows, m):
     return S
 
 
-class CsmCascadeBank:
+class CsmCascadeBank(_FramesFeed, _SetAvg, _Stats, _Bank):
     """`n_groups` independent cross-spectral MATRIX cascades (psdc_csm_*): groups of m = 2 ... 4 streams fed together, each
     transformed and decimated once a segment; per stage the Hermitian matrix S_ab = sum conj(X_a) X_b (the pair object's
     convention).  The read-out is PsdCascade::psd applied to each real row: S[a, a] is the psd() of a PsdCascade fed channel a."""
 
+    _P, _FP, _MAP = "psdc_csm_", "psdc_csm_", staticmethod(group_map)
+    _ARG_WORDS = _Bank._ARG_WORDS + ("not supported",)
+    _IN = "sample_times_in"
+
     def __init__(self, n, m, n_groups=1, window=Window.HANN, device=0):
-        self.n, self.m, self.n_groups, self.window, self.device = n, m, n_groups, window, device
-        self._L = lib()
+        self.m, self.n_groups = m, n_groups
         if not (0 <= n < 2 ** 32 and 0 <= m < 2 ** 32):
             raise PsdError(ERR_ARG, f"n = {n} with m = {m} is not supported")
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_csm_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, m, n_groups,
-                                                     device)
-        else:
-            self._h = self._L.psdc_csm_create(n, int(window), m, n_groups, device)
-        if not self._h:
-            msg = self._L.psdc_csm_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_csm_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_csm(rc, self._h)
-        return rc
-
-    def reset(self):
-        self._ck(self._L.psdc_csm_reset(self._h))
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_csm_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_csm_set_avg(self._h, avg.limit, avg.count))
+        self._open(n, window, device, m, n_groups)
 
     def _ptrs(self, ptrs):
         if len(ptrs) != self.m:
@@ -1329,71 +1276,34 @@ class CsmCascadeBank:
         """Stream frames (bytes-like holding whole frames) into the groups: groups[g] = m traces (indices or TRACE_NAMES
         labels) feeds group g, None leaves it unfed.  Returns the number of frames ingested; a bad frame raises FrameError
         after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        gm = group_map(groups, self.m, self.n_groups)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_csm_process_frames(self._h, gm.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
-                                             frame_size, buf.size // frame_size, C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, groups)
 
     def process_frames_device(self, ptr, frame_size, n_frames, groups, after=None):
         """process_frames for frames resident in device memory at address `ptr` (CsdCascadeBank.process_frames_device)."""
-        gm = group_map(groups, self.m, self.n_groups)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_csm_process_frames_device(self._h, gm.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
-                                                    frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        l = _CLoss()
-        self._ck(self._L.psdc_csm_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_csm_sync(self._h))
+        return self._frames_device(ptr, frame_size, n_frames, groups, after)
 
     def num_stages(self, group=0):
-        return self._ck(self._L.psdc_csm_num_stages(self._h, group))
+        return self._num_stages(group)
 
     def stage_spectra(self, group, stage):
         """(info, S) of one stage's raw accumulators; S complex64 (m, m, n/2 + 1), Hermitian."""
         st = _CStageStat()
         rows = np.empty(self.m * self.m * (self.n // 2 + 1), np.float32)
         self._ck(self._L.psdc_csm_stage_spectra(self._h, group, stage, C.byref(st), _fptr(rows)))
-        info = {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}
-        return info, csm_matrix(rows, self.m)
+        return _stage_info(st), csm_matrix(rows, self.m)
 
     def csd(self, group=0, opts=MergeOpts()):
         """(S, breaks): S complex64 (m, m, bins), Hermitian and filled on both sides; PsdCascade::psd of each real row."""
-        ns = self.num_stages(group)
-        cap = max(1, ns * (self.n // 2 + 1))
-        rows = np.empty((self.m * self.m, cap), np.float32)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_csm_csd(self._h, group, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                      _fptr(rows), cap, C.byref(plen), br, ns, C.byref(nb)))
-        return csm_matrix(rows[:, :plen.value], self.m), [Break._from_c(br[i]) for i in range(nb.value)]
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_csm_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "sample_times_in": si.value}
+        rows, br = self._merged(self._L.psdc_csm_csd, group, opts, self.m * self.m)
+        return csm_matrix(rows, self.m), br
 
 
-class CsmCascade:
+class CsmCascade(_UnitCascade):
     """One group of m streams (CsmCascadeBank with n_groups = 1)."""
 
     def __init__(self, n, m, window=Window.HANN, device=0):
         self.n, self.m = n, m
         self._b = CsmCascadeBank(n, m, 1, window, device)
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
 
     def process(self, xs):
         self._b.process(0, xs)
@@ -1419,23 +1329,8 @@ class CsmCascade:
     def csd(self, opts=MergeOpts()):
         return self._b.csd(0, opts)
 
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_spectra(self, i):
         return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        self._b.reset()
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
 
 
 def zoom_ftw(f0):
@@ -1458,12 +1353,6 @@ def two_sided(upper, lower, breaks):
     return np.concatenate([-f[neg][::-1], f]), np.concatenate([lo[neg][::-1], up])
 
 
-def _raise_zoom(code, h=None):
-    msg = lib().psdc_zoom_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
-
-
 def channel_map(traces, n_channels):
     """The map psdc_zoomcascade_process_frames[_device] take, from `traces`: entry c is the trace channel c takes -- an index or a TRACE_NAMES label (trace_index, as
     pair_map resolves its pairs) -- or None (channel c not fed); channels past the end of the list are not fed.  A map that
@@ -1484,64 +1373,13 @@ def channel_map(traces, n_channels):
     return m
 
 
-class ZoomCascadeBank:
+class ZoomCascadeBank(_ChannelCarriers, _FramesFeed, _ChannelBank):
     """`n_channels` independent zoom cascades (psdc_zoom_*): each real stream is mixed down from its own carrier (a 64-bit
     tuning word and start phase, exact in integers) to I + i Q in front of the cascade, and every stage keeps the two-sided
     |Z|^2 of it as two rows: `upper` at offset f is the PSD of x at f0 + f, `lower` that at f0 - f, both scaled as
     PsdCascade::psd scales its one-sided spectrum (white noise of variance 1 reads 2)."""
 
-    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
-        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_zoom_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels,
-                                                      device)
-        else:
-            self._h = self._L.psdc_zoom_create(n, int(window), n_channels, device)
-        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
-        if not self._h:
-            msg = self._L.psdc_zoom_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_zoom_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_zoom(rc, self._h)
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        self._ck(self._L.psdc_zoom_reset(self._h))
-        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_zoom_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_zoom_set_avg(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
-        """The channel's carrier, as f0 (cycles per sample, through zoom_ftw) or as the tuning word itself; phase0 in 2^-64
-        turn.  Only before the channel's first sample.  Returns the f0 actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        self._ck(self._L.psdc_zoom_set_carrier(self._h, channel, ftw, phase0))
-        self.carriers[channel] = (ftw, phase0)
-        return ftw / float(1 << 64)
+    _P, _FP, _MAP = "psdc_zoom_", "psdc_zoomcascade_", staticmethod(channel_map)
 
     def process(self, channel, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -1571,90 +1409,33 @@ class ZoomCascadeBank:
         trace channel c takes of every frame (an index or a TRACE_NAMES label), None leaves it unfed; a trace may feed several
         channels.  The frames are decoded and mixed on the device in one kernel.  Returns the number of frames ingested; a bad
         frame raises FrameError after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        m = channel_map(traces, self.n_channels)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_zoomcascade_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
-                                              frame_size, buf.size // frame_size, C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, traces)
 
     def process_frames_device(self, ptr, frame_size, n_frames, traces, after=None):
         """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
         their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
-        m = channel_map(traces, self.n_channels)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_zoomcascade_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
-                                                     frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
-        l = _CLoss()
-        self._ck(self._L.psdc_zoomcascade_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_zoom_sync(self._h))
-
-    def num_stages(self, channel=0):
-        return self._ck(self._L.psdc_zoom_num_stages(self._h, channel))
+        return self._frames_device(ptr, frame_size, n_frames, traces, after)
 
     def stage_spectra(self, channel, stage):
         """(info, upper, lower) of one stage's raw accumulators."""
         b = self.n // 2 + 1
         st = _CStageStat()
         up, lo = np.empty(b, np.float32), np.empty(b, np.float32)
-        self._ck(self._L.psdc_zoom_stage_spectra(self._h, channel, stage, C.byref(st), _fptr(up), _fptr(lo)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, up, lo
+        self._ck(self._f("stage_spectra")(self._h, channel, stage, C.byref(st), _fptr(up), _fptr(lo)))
+        return _stage_info(st), up, lo
 
     def psd(self, channel=0, opts=MergeOpts()):
-        """(upper, lower, breaks): PsdCascade::psd of each row; Break.frequencies(breaks) are the offsets of both."""
-        ns = self.num_stages(channel)
-        cap = max(1, ns * (self.n // 2 + 1))
-        up, lo = np.empty(cap, np.float32), np.empty(cap, np.float32)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_zoom_psd(self._h, channel, int(opts.keep_overlap), opts.min_count,
-                                       int(opts.keep_transition_band), _fptr(up), _fptr(lo), cap, C.byref(plen), br, ns,
-                                       C.byref(nb)))
-        m = plen.value
-        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_zoom_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
+        """(upper, lower, breaks): PsdCascade::psd of each row; Break.frequencies(breaks) are the offsets of both, and
+        two_sided(upper, lower, breaks) is the spectrum over (-0.5, 0.5]."""
+        (up, lo), br = self._merged(self._f("psd"), channel, opts, (1, 1))
+        return up, lo, br
 
 
-class ZoomCascade:
+class ZoomCascade(_CarrierCascade):
     """One stream around one carrier: ZoomCascade(n, f0=0.2) or ZoomCascade(n, ftw=...).  `f0` is the frequency in use
     (ftw / 2^64).  reset() keeps the object's carrier."""
 
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = ZoomCascadeBank(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0):
-        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
-        self.ftw, self.phase0 = self._b.carriers[0]
-        return self.f0
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
-
-    def process(self, x):
-        self._b.process(0, x)
-
-    def process_device(self, ptr, length, after=None):
-        self._b.process_device(0, ptr, length, after)
+    _BANK = ZoomCascadeBank
 
     def process_int(self, x, scale=None):
         self._b.process_int(0, x, scale)
@@ -1672,27 +1453,8 @@ class ZoomCascade:
     def loss(self, reset=False):
         return self._b.loss(reset)
 
-    def psd(self, opts=MergeOpts()):
-        return self._b.psd(0, opts)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_spectra(self, i):
         return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        self._b.reset()
-        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
 
 
 def sk_supported(n):
@@ -1721,52 +1483,12 @@ def sk_sigma(count):
     return 2.0 / float(np.sqrt(float(count)))
 
 
-def _raise_sk(code, h=None):
-    msg = lib().psdc_sk_last_error(h)
-    raise PsdError(code, msg.decode() if msg else "")
-
-
-class SkCascadeBank:
+class SkCascadeBank(_ChannelBank):
     """`n_channels` independent spectral kurtosis cascades (psdc_sk_*): every stage of a real stream keeps S1 = sum P, the
     spectrum PsdCascade keeps, and S2 = sum P^2 beside it.  psd() is PsdCascade's; sk() is the per-bin estimator
     sk_from_moments of the same stages and bins: 1 where the bin holds stationary Gaussian noise."""
 
-    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
-        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_sk_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
-        else:
-            self._h = self._L.psdc_sk_create(n, int(window), n_channels, device)
-        if not self._h:
-            msg = self._L.psdc_sk_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_sk_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_sk(rc, self._h)
-        return rc
-
-    def reset(self):
-        self._ck(self._L.psdc_sk_reset(self._h))
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_sk_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_sk_set_avg(self._h, avg.limit, avg.count))
+    _P = "psdc_sk_"
 
     def process(self, channel, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -1777,12 +1499,6 @@ class SkCascadeBank:
         when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
         self._ck(self._L.psdc_sk_process_device(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
 
-    def sync(self):
-        self._ck(self._L.psdc_sk_sync(self._h))
-
-    def num_stages(self, channel=0):
-        return self._ck(self._L.psdc_sk_num_stages(self._h, channel))
-
     def stage_moments(self, channel, stage):
         """(info, s1, s2) of one stage: its raw f64 accumulators sum w P and sum w P^2"""
         b = self.n // 2 + 1
@@ -1790,46 +1506,25 @@ class SkCascadeBank:
         s1, s2 = np.empty(b, np.float64), np.empty(b, np.float64)
         dp = C.POINTER(C.c_double)
         self._ck(self._L.psdc_sk_stage_moments(self._h, channel, stage, C.byref(st), s1.ctypes.data_as(dp), s2.ctypes.data_as(dp)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, s1, s2
-
-    def _merged(self, fn, dtype, ctype, channel, opts):
-        ns = self.num_stages(channel)
-        cap = max(1, ns * (self.n // 2 + 1))
-        out = np.empty(cap, dtype)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(fn(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                    out.ctypes.data_as(C.POINTER(ctype)), cap, C.byref(plen), br, ns, C.byref(nb)))
-        return out[:plen.value].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
+        return _stage_info(st), s1, s2
 
     def psd(self, channel=0, opts=MergeOpts()):
         """(psd, breaks): PsdCascade::psd of row 0, as PsdCascade.psd() returns it"""
-        return self._merged(self._L.psdc_sk_psd, np.float32, C.c_float, channel, opts)
+        (p,), br = self._merged(self._L.psdc_sk_psd, channel, opts, (1,))
+        return p, br
 
     def sk(self, channel=0, opts=MergeOpts()):
         """(sk, breaks): float64 SK of every bin of psd(), from the stage and bin psd() took it from; the same breaks"""
-        return self._merged(self._L.psdc_sk_sk, np.float64, C.c_double, channel, opts)
+        (s,), br = self._merged(self._L.psdc_sk_sk, channel, opts, (1,), np.float64)
+        return s, br
 
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_sk_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
-
-    stats = stats_read
+    stats = _Stats.stats_read
 
 
-class SkCascade:
+class SkCascade(_UnitCascade):
     """One stream: SkCascade(n).  psd() beside sk(), the per-bin spectral kurtosis."""
 
-    def __init__(self, n, window=Window.HANN, device=0):
-        self.n = n
-        self._b = SkCascadeBank(n, 1, window, device)
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
+    _BANK = SkCascadeBank
 
     def process(self, x):
         self._b.process(0, x)
@@ -1843,31 +1538,10 @@ class SkCascade:
     def sk(self, opts=MergeOpts()):
         return self._b.sk(0, opts)
 
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_moments(self, i):
         return self._b.stage_moments(0, i)
 
-    def reset(self):
-        self._b.reset()
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    stats = stats_read
-
-    def close(self):
-        self._b.close()
-
-
-def _raise_iq(code, h=None):
-    msg = lib().psdc_iq_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
+    stats = _UnitCascade.stats_read
 
 
 def iq_map(pairs, n_channels):
@@ -1894,81 +1568,18 @@ def iq_map(pairs, n_channels):
     return m
 
 
-class IqCascadeBank:
+class IqCascadeBank(ZoomCascadeBank):
     """`n_channels` independent IQ cascades (psdc_iq_*): each stream is complex already, z = I + i Q, and is turned by its own
     carrier (default none: ftw = 0, phase0 = 0) in front of the zoom object's cascade.  Every stage keeps the two-sided |Z|^2 as
     two rows, `upper` at offsets f >= 0 and `lower` at -f, scaled as PsdCascade::psd scales its one-sided spectrum: complex
     white noise with E|z|^2 = 1 reads 2, and row / 2 is the two-sided density of z (two_sided() lays the rows out)."""
 
-    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
-        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_iq_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
-        else:
-            self._h = self._L.psdc_iq_create(n, int(window), n_channels, device)
-        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
-        if not self._h:
-            msg = self._L.psdc_iq_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_iq_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_iq(rc, self._h)
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        self._ck(self._L.psdc_iq_reset(self._h))
-        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_iq_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_iq_set_avg(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
-        """The channel's carrier, as f0 (cycles per sample, through zoom_ftw) or as the tuning word itself; phase0 in 2^-64
-        turn.  Only before the channel's first sample.  Returns the f0 actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        self._ck(self._L.psdc_iq_set_carrier(self._h, channel, ftw, phase0))
-        self.carriers[channel] = (ftw, phase0)
-        return ftw / float(1 << 64)
+    _P, _FP, _MAP = "psdc_iq_", "psdc_iq_", staticmethod(iq_map)
 
     def process(self, channel, z):
         """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
         real arrays of one length (the planar route)."""
-        if isinstance(z, (tuple, list)):
-            if len(z) != 2:
-                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
-            i = np.ascontiguousarray(z[0], dtype=np.float32)
-            q = np.ascontiguousarray(z[1], dtype=np.float32)
-            if i.ndim != 1 or i.shape != q.shape:
-                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
-            self._ck(self._L.psdc_iq_process(self._h, channel, _fptr(i), _fptr(q), i.size))
-            return
-        z = np.asarray(z)
-        if not np.iscomplexobj(z):
-            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
-        z = np.ascontiguousarray(z, dtype=np.complex64)
-        self._ck(self._L.psdc_iq_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+        self._process_iq(channel, z)
 
     def process_device(self, channel, ptr, length, after=None):
         """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); after: a hipEvent_t
@@ -2002,97 +1613,26 @@ class IqCascadeBank:
         (i_trace, q_trace) channel c takes of every frame (indices or TRACE_NAMES labels, e.g. ("BI", "BQ")), None leaves it
         unfed; a trace may feed several channels.  The frames are decoded and mixed on the device in one kernel.  Returns the
         number of frames ingested; a bad frame raises FrameError after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        m = iq_map(pairs, self.n_channels)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_iq_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
-                                            frame_size, buf.size // frame_size, C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, pairs)
 
     def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
         """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
         their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
-        m = iq_map(pairs, self.n_channels)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_iq_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr), frame_size,
-                                                   n_frames, C.byref(ok), C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
-        l = _CLoss()
-        self._ck(self._L.psdc_iq_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_iq_sync(self._h))
-
-    def num_stages(self, channel=0):
-        return self._ck(self._L.psdc_iq_num_stages(self._h, channel))
-
-    def stage_spectra(self, channel, stage):
-        """(info, upper, lower) of one stage's raw accumulators."""
-        b = self.n // 2 + 1
-        st = _CStageStat()
-        up, lo = np.empty(b, np.float32), np.empty(b, np.float32)
-        self._ck(self._L.psdc_iq_stage_spectra(self._h, channel, stage, C.byref(st), _fptr(up), _fptr(lo)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, up, lo
-
-    def psd(self, channel=0, opts=MergeOpts()):
-        """(upper, lower, breaks): PsdCascade::psd of each row; Break.frequencies(breaks) are the offsets of both, and
-        two_sided(upper, lower, breaks) is the spectrum over (-0.5, 0.5]."""
-        ns = self.num_stages(channel)
-        cap = max(1, ns * (self.n // 2 + 1))
-        up, lo = np.empty(cap, np.float32), np.empty(cap, np.float32)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_iq_psd(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                     _fptr(up), _fptr(lo), cap, C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_iq_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
+        return self._frames_device(ptr, frame_size, n_frames, pairs, after)
 
 
-class IqCascade:
+class IqCascade(ZoomCascade):
     """One complex stream: IqCascade(n) analyses it as it is, IqCascade(n, f0=0.2) or IqCascade(n, ftw=...) retunes it first.
     `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
 
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = IqCascadeBank(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0):
-        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
-        self.ftw, self.phase0 = self._b.carriers[0]
-        return self.f0
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
+    _BANK = IqCascadeBank
 
     def process(self, z):
         """z: a complex array, or a pair (i, q) (IqCascadeBank.process)"""
         self._b.process(0, z)
 
-    def process_device(self, ptr, length, after=None):
-        self._b.process_device(0, ptr, length, after)
-
     def process_int(self, z, scale=None):
         self._b.process_int(0, z, scale)
-
-    def process_int_device(self, ptr, length, kind, scale=None, after=None):
-        self._b.process_int_device(0, ptr, length, kind, scale, after)
 
     def process_device_planar(self, pi, pq, length, after=None):
         self._b.process_device_planar(0, pi, pq, length, after)
@@ -2104,125 +1644,13 @@ class IqCascade:
     def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
         return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
 
-    def loss(self, reset=False):
-        return self._b.loss(reset)
-
-    def psd(self, opts=MergeOpts()):
-        return self._b.psd(0, opts)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
-
-    def stage_spectra(self, i):
-        return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        self._b.reset()
-        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
-
 
 def zoom_sk_supported(n):
     """Whether ZoomSkCascade[Bank] and IqSkCascade[Bank] take the size n: a power of two 64 ... 4096 (sk_supported)"""
     return 0 <= n < (1 << 32) and bool(lib().psdc_zsk_supported(n))
 
 
-class _CarrierRowsBank:
-    """What the banks of four-row objects around a carrier share (ZoomSkCascadeBank, ZoomAmPmCascadeBank and their IQ
-    siblings): creation, settings, the carrier, and the merged read-out of two rows.  `_P` is the C prefix."""
-
-    _P = None
-
-    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
-        self.n, self.n_channels, self.window, self.device = n, n_channels, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, device)
-        else:
-            self._h = self._f("create")(n, int(window), n_channels, device)
-        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}  # (ftw, phase0) of every channel, as set
-        if not self._h:
-            msg = self._f("last_error")(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def _f(self, name):
-        return getattr(self._L, self._P + name)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._f("destroy")(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            msg = self._f("last_error")(self._h)
-            raise PsdError(rc, msg.decode() if msg else "")
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        self._ck(self._f("reset")(self._h))
-        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
-
-    def set_detrend(self, d):
-        self._ck(self._f("set_detrend")(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._f("set_avg")(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, channel, f0=None, ftw=None, phase0=0):
-        """The channel's carrier, as ZoomCascadeBank.set_carrier takes it.  Returns the f0 actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        self._ck(self._f("set_carrier")(self._h, channel, ftw, phase0))
-        self.carriers[channel] = (ftw, phase0)
-        return ftw / float(1 << 64)
-
-    def sync(self):
-        self._ck(self._f("sync")(self._h))
-
-    def num_stages(self, channel=0):
-        return self._ck(self._f("num_stages")(self._h, channel))
-
-    def _merged(self, fn, dtype, ctype, channel, opts):
-        ns = self.num_stages(channel)
-        cap = max(1, ns * (self.n // 2 + 1))
-        up, lo = np.empty(cap, dtype), np.empty(cap, dtype)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        cp = C.POINTER(ctype)
-        self._ck(fn(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band), up.ctypes.data_as(cp),
-                    lo.ctypes.data_as(cp), cap, C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        return up[:m].copy(), lo[:m].copy(), [Break._from_c(br[i]) for i in range(nb.value)]
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
-
-    stats = stats_read
-
-
-class ZoomSkCascadeBank(_CarrierRowsBank):
+class ZoomSkCascadeBank(_ChannelCarriers, _ChannelBank):
     """`n_channels` independent zoom spectral kurtosis cascades (psdc_zsk_*): ZoomCascadeBank's carrier, mixer and two-sided
     cascade, with S2 = sum |Z|^4 kept beside S1 = sum |Z|^2 on both sides.  psd() is ZoomCascadeBank's; sk() is sk_from_moments
     of the same stages and bins, per side: 1 where the sideband holds stationary (circular) Gaussian noise, at every bin --
@@ -2248,15 +1676,19 @@ class ZoomSkCascadeBank(_CarrierRowsBank):
         rows = [np.empty(b, np.float64) for _ in range(4)]
         dp = C.POINTER(C.c_double)
         self._ck(self._f("stage_moments")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
-        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, *rows)
+        return (_stage_info(st), *rows)
 
     def psd(self, channel=0, opts=MergeOpts()):
         """(upper, lower, breaks): the zoom read-out of the S1 rows, as ZoomCascadeBank.psd() returns it"""
-        return self._merged(self._f("psd"), np.float32, C.c_float, channel, opts)
+        rows, br = self._merged(self._f("psd"), channel, opts, (1, 1))
+        return (*rows, br)
 
     def sk(self, channel=0, opts=MergeOpts()):
         """(sk_upper, sk_lower, breaks): float64 SK of every bin of psd(), from the stage and bin psd() took it from"""
-        return self._merged(self._f("sk"), np.float64, C.c_double, channel, opts)
+        rows, br = self._merged(self._f("sk"), channel, opts, (1, 1), np.float64)
+        return (*rows, br)
+
+    stats = _Stats.stats_read
 
 
 class IqSkCascadeBank(ZoomSkCascadeBank):
@@ -2269,20 +1701,7 @@ class IqSkCascadeBank(ZoomSkCascadeBank):
     def process(self, channel, z):
         """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
         real arrays of one length (the planar route)."""
-        if isinstance(z, (tuple, list)):
-            if len(z) != 2:
-                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
-            i = np.ascontiguousarray(z[0], dtype=np.float32)
-            q = np.ascontiguousarray(z[1], dtype=np.float32)
-            if i.ndim != 1 or i.shape != q.shape:
-                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
-            self._ck(self._L.psdc_iqsk_process(self._h, channel, _fptr(i), _fptr(q), i.size))
-            return
-        z = np.asarray(z)
-        if not np.iscomplexobj(z):
-            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
-        z = np.ascontiguousarray(z, dtype=np.complex64)
-        self._ck(self._L.psdc_iqsk_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+        self._process_iq(channel, z)
 
     def process_device(self, channel, ptr, length, after=None):
         """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); the rest as
@@ -2296,62 +1715,12 @@ class IqSkCascadeBank(ZoomSkCascadeBank):
                                                   C.c_void_p(after) if after else None))
 
 
-class _CarrierRowsCascade:
-    """What the single-channel objects over a _CarrierRowsBank share; `_BANK` is the bank's class."""
-
-    _BANK = None
-
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = self._BANK(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0):
-        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
-        self.ftw, self.phase0 = self._b.carriers[0]
-        return self.f0
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
-
-    def process(self, x):
-        self._b.process(0, x)
-
-    def process_device(self, ptr, length, after=None):
-        self._b.process_device(0, ptr, length, after)
-
-    def psd(self, opts=MergeOpts()):
-        return self._b.psd(0, opts)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
-
-    def reset(self):
-        self._b.reset()
-        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    stats = stats_read
-
-    def close(self):
-        self._b.close()
-
-
-class ZoomSkCascade(_CarrierRowsCascade):
+class ZoomSkCascade(_CarrierCascade):
     """One real stream around one carrier: ZoomSkCascade(n, f0=0.2) or ZoomSkCascade(n, ftw=...): psd() beside sk(), both
     two-sided.  `f0` is the frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
 
     _BANK = ZoomSkCascadeBank
+    stats = _UnitCascade.stats_read
 
     def sk(self, opts=MergeOpts()):
         return self._b.sk(0, opts)
@@ -2388,7 +1757,7 @@ def waterfall_block_span(n, overlap, block, stage, b):
     return range(b * block * hop * d, ((b + 1) * block - 1) * hop * d + n * d)
 
 
-class WaterfallCascadeBank:
+class WaterfallCascadeBank(_Stats, _Bank):
     """`n_channels` independent waterfall cascades (psdc_wf_*): SkCascadeBank's stages, but every stage keeps a ring of its
     `depth` most recent blocks of `block` segments, each with its own S1 = sum P and S2 = sum P^2, where SkCascadeBank keeps one
     average.  image() gives a stage's PSD and spectral kurtosis against time, oldest block first; stage k's blocks are 8^k times
@@ -2398,52 +1767,17 @@ class WaterfallCascadeBank:
     _ROWS = 2
 
     def __init__(self, n, n_channels=1, block=64, depth=64, window=Window.HANN, device=0):
-        self.n, self.n_channels, self.block, self.depth, self.window, self.device = n, n_channels, block, depth, window, device
-        self._L = lib()
+        self.n_channels, self.block, self.depth = n_channels, block, depth
         bad = [k for k, v in (("n", n), ("n_channels", n_channels), ("block", block), ("depth", depth)) if not 0 <= v <= U32_MAX]
         if bad:
             raise PsdError(ERR_ARG, f"{self._P}create: {bad[0]} must be in [0, 2^32)")
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._wt = window
-            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_channels, block, depth, device)
-        else:
-            self._wt = None
-            self._h = self._f("create")(n, int(window), n_channels, block, depth, device)
-        if not self._h:
-            msg = self._f("last_error")(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def _f(self, name):
-        return getattr(self._L, self._P + name)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._f("destroy")(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            msg = self._f("last_error")(self._h)
-            raise PsdError(rc, msg.decode() if msg else "")
-        return rc
+        self._open(n, window, device, n_channels, block, depth)
+        self._wt = window if isinstance(window, WindowTable) else None
 
     def _table(self):
         if self._wt is None:
             self._wt = WindowTable._kind(self.n, self.window)
         return self._wt
-
-    def reset(self):
-        self._ck(self._f("reset")(self._h))
-
-    def set_detrend(self, d):
-        self._ck(self._f("set_detrend")(self._h, int(d)))
 
     def process(self, channel, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -2454,11 +1788,8 @@ class WaterfallCascadeBank:
         when it has completed.  The samples must stay unchanged until sync() or a read-out returns."""
         self._ck(self._f("process_device")(self._h, channel, C.c_void_p(ptr), length, C.c_void_p(after) if after else None))
 
-    def sync(self):
-        self._ck(self._f("sync")(self._h))
-
     def num_stages(self, channel=0):
-        return self._ck(self._f("num_stages")(self._h, channel))
+        return self._num_stages(channel)
 
     def stage_blocks(self, channel, stage):
         """dict(block, depth, started, rows_valid, newest_count, pending) of one stage's ring"""
@@ -2537,15 +1868,10 @@ class WaterfallCascadeBank:
         p, br = self._recent(channel, blocks, opts, 1)
         return p[0], br
 
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "samples_in": si.value}
-
-    stats = stats_read
+    stats = _Stats.stats_read
 
 
-class ZoomWaterfallCascadeBank(WaterfallCascadeBank):
+class ZoomWaterfallCascadeBank(_ChannelCarriers, WaterfallCascadeBank):
     """`n_channels` independent zoom waterfall cascades (psdc_zwf_*): ZoomSkCascadeBank's carrier, mixer and two-sided stages with
     a ring of blocks a stage.  Fed as ZoomCascadeBank is.  Rows come per side, images as [rows][2][n/2 + 1] with side 0 the
     upper and side 1 the lower sideband."""
@@ -2555,17 +1881,9 @@ class ZoomWaterfallCascadeBank(WaterfallCascadeBank):
 
     def __init__(self, n, n_channels=1, f0=None, ftw=None, block=64, depth=64, window=Window.HANN, device=0):
         super().__init__(n, n_channels, block, depth, window, device)
-        self.carriers = {c: (0, 0) for c in range(min(n_channels, 65536))}
         if f0 is not None or ftw is not None:
             for c in range(n_channels):
                 self.set_carrier(c, f0=f0, ftw=ftw)
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        super().reset()
-        self.carriers = {c: (0, 0) for c in range(self.n_channels)}
-
-    set_carrier = _CarrierRowsBank.set_carrier
 
     def stage_rows(self, channel, stage, max_rows=None):
         """(block_index, counts, s1_upper, s1_lower, s2_upper, s2_lower), as WaterfallCascadeBank.stage_rows per side"""
@@ -2580,7 +1898,7 @@ class ZoomWaterfallCascadeBank(WaterfallCascadeBank):
         return p[0], p[1], br
 
 
-class WaterfallCascade:
+class WaterfallCascade(_Cascade):
     """One real stream: WaterfallCascade(n, block=64, depth=64).  image(stage) is that stage's PSD and SK against time."""
 
     _BANK = WaterfallCascadeBank
@@ -2589,17 +1907,11 @@ class WaterfallCascade:
         self.n, self.block, self.depth = n, block, depth
         self._b = self._BANK(n, 1, block=block, depth=depth, window=window, device=device)
 
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
-
     def process(self, x):
         self._b.process(0, x)
 
     def process_device(self, ptr, length, after=None):
         self._b.process_device(0, ptr, length, after)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
 
     def stage_blocks(self, stage):
         return self._b.stage_blocks(0, stage)
@@ -2622,37 +1934,21 @@ class WaterfallCascade:
     def reset(self):
         self._b.reset()
 
-    def sync(self):
-        self._b.sync()
-
     def stats_read(self, reset=False):
         return self._b.stats_read(reset)
 
     stats = stats_read
 
-    def close(self):
-        self._b.close()
 
-
-class ZoomWaterfallCascade(WaterfallCascade):
+class ZoomWaterfallCascade(_KeepsCarrier, WaterfallCascade):
     """One real stream around one carrier: ZoomWaterfallCascade(n, f0=0.2, block=64, depth=64) or (n, ftw=...).  `f0` is the
     frequency in use (ftw / 2^64).  reset() keeps the object's carrier."""
 
+    _BANK = ZoomWaterfallCascadeBank
+
     def __init__(self, n, f0=None, ftw=None, phase0=0, block=64, depth=64, window=Window.HANN, device=0):
-        self.n, self.block, self.depth = n, block, depth
-        self._b = ZoomWaterfallCascadeBank(n, 1, block=block, depth=depth, window=window, device=device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0):
-        self.f0 = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0)
-        self.ftw, self.phase0 = self._b.carriers[0]
-        return self.f0
-
-    def reset(self):
-        self._b.reset()
-        self._b.set_carrier(0, ftw=self.ftw, phase0=self.phase0)
+        super().__init__(n, block, depth, window, device)
+        self._tune(f0, ftw, phase0)
 
 
 def zoom_ampm_supported(n):
@@ -2691,7 +1987,7 @@ def carrier_from_rows(n, window_power, count, upper0, lower0, comp0):
     return mag / (float(count) * float(n) ** 2 * float(window_power)), c / mag, mag / float(np.sqrt(float(upper0) * float(lower0)))
 
 
-class ZoomAmPmCascadeBank(_CarrierRowsBank):
+class ZoomAmPmCascadeBank(_ChannelCarriers, _ChannelBank):
     """`n_channels` independent AM/PM cascades (psdc_zampm_*): ZoomCascadeBank's carrier, mixer and two-sided cascade, with the
     complementary spectrum comp[k] = sum Z_k Z_(N-k) kept beside upper and lower.  psd() is ZoomCascadeBank's; sidebands() adds
     comp, all in f64; am_pm() separates them into the amplitude noise, phase noise and AM-PM cross spectra of the carrier.
@@ -2702,12 +1998,8 @@ class ZoomAmPmCascadeBank(_CarrierRowsBank):
 
     _P = "psdc_zampm_"
 
-    def __init__(self, n, n_channels=1, window=Window.HANN, device=0):
-        super().__init__(n, n_channels, window, device)
-        self.detrend = Detrend.NONE
-
-    def reset(self):
-        super().reset()
+    def _fresh(self, most=None):
+        super()._fresh(most)
         self.detrend = Detrend.NONE
 
     def set_detrend(self, d):
@@ -2730,25 +2022,17 @@ class ZoomAmPmCascadeBank(_CarrierRowsBank):
         rows = [np.empty(b, np.float64) for _ in range(4)]
         dp = C.POINTER(C.c_double)
         self._ck(self._f("stage_rows")(self._h, channel, stage, C.byref(st), *(r.ctypes.data_as(dp) for r in rows)))
-        return ({"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows[0], rows[1],
-                rows[2] + 1j * rows[3])
+        return _stage_info(st), rows[0], rows[1], rows[2] + 1j * rows[3]
 
     def psd(self, channel=0, opts=MergeOpts()):
         """(upper, lower, breaks): the zoom read-out of rows 0 and 1, as ZoomCascadeBank.psd() returns it"""
-        return self._merged(self._f("psd"), np.float32, C.c_float, channel, opts)
+        rows, br = self._merged(self._f("psd"), channel, opts, (1, 1))
+        return (*rows, br)
 
     def sidebands(self, channel=0, opts=MergeOpts()):
         """(upper, lower, comp, breaks): all four rows merged as psd() merges, in f64 (comp complex128)"""
-        ns = self.num_stages(channel)
-        cap = max(1, ns * (self.n // 2 + 1))
-        rows = [np.empty(cap, np.float64) for _ in range(4)]
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        dp = C.POINTER(C.c_double)
-        self._ck(self._f("sidebands")(self._h, channel, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                      *(r.ctypes.data_as(dp) for r in rows), cap, C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        return rows[0][:m].copy(), rows[1][:m].copy(), rows[2][:m] + 1j * rows[3][:m], [Break._from_c(br[i]) for i in range(nb.value)]
+        rows, br = self._merged(self._f("sidebands"), channel, opts, (1, 1, 1, 1), np.float64)
+        return rows[0], rows[1], rows[2] + 1j * rows[3], br
 
     def _window_power(self):
         return self.window.power if isinstance(self.window, WindowTable) else WindowTable._kind(self.n, self.window).power
@@ -2773,6 +2057,8 @@ class ZoomAmPmCascadeBank(_CarrierRowsBank):
         up, lo, comp, br = self.sidebands(channel, opts)
         return (*am_pm_from_sidebands(up, lo, comp, carrier), br)
 
+    stats = _Stats.stats_read
+
 
 class IqAmPmCascadeBank(ZoomAmPmCascadeBank):
     """`n_channels` independent IQ AM/PM cascades (psdc_iqampm_*): ZoomAmPmCascadeBank for streams that are complex already (a
@@ -2784,20 +2070,7 @@ class IqAmPmCascadeBank(ZoomAmPmCascadeBank):
     def process(self, channel, z):
         """z: a complex array (converted to complex64 and fed as (re, im) pairs: the interleaved route), or a pair (i, q) of
         real arrays of one length (the planar route)."""
-        if isinstance(z, (tuple, list)):
-            if len(z) != 2:
-                raise PsdError(ERR_ARG, "a planar call takes (i, q)")
-            i = np.ascontiguousarray(z[0], dtype=np.float32)
-            q = np.ascontiguousarray(z[1], dtype=np.float32)
-            if i.ndim != 1 or i.shape != q.shape:
-                raise PsdError(ERR_ARG, f"i and q differ in length ({i.size} and {q.size})")
-            self._ck(self._L.psdc_iqampm_process(self._h, channel, _fptr(i), _fptr(q), i.size))
-            return
-        z = np.asarray(z)
-        if not np.iscomplexobj(z):
-            raise PsdError(ERR_ARG, "process takes a complex array or a pair (i, q)")
-        z = np.ascontiguousarray(z, dtype=np.complex64)
-        self._ck(self._L.psdc_iqampm_process_interleaved(self._h, channel, z.ctypes.data_as(C.POINTER(C.c_float)), z.size))
+        self._process_iq(channel, z)
 
     def process_device(self, channel, ptr, length, after=None):
         """ptr: device address of `length` (re, im) pairs of f32 (a complex64 tensor's memory; 8-byte aligned); the rest as
@@ -2811,12 +2084,13 @@ class IqAmPmCascadeBank(ZoomAmPmCascadeBank):
                                                     C.c_void_p(after) if after else None))
 
 
-class ZoomAmPmCascade(_CarrierRowsCascade):
+class ZoomAmPmCascade(_CarrierCascade):
     """One real stream around one carrier: ZoomAmPmCascade(n, f0=0.2) or ZoomAmPmCascade(n, ftw=...): psd() and sidebands(),
     carrier() and am_pm() (ZoomAmPmCascadeBank has the definitions and the limits).  `f0` is the frequency in use
     (ftw / 2^64).  reset() keeps the object's carrier."""
 
     _BANK = ZoomAmPmCascadeBank
+    stats = _UnitCascade.stats_read
 
     def sidebands(self, opts=MergeOpts()):
         return self._b.sidebands(0, opts)
@@ -2849,13 +2123,7 @@ def zcsd_supported(n):
     return 0 <= n < (1 << 32) and bool(lib().psdc_zcsd_supported(n))
 
 
-def _raise_zcsd(code, h=None):
-    msg = lib().psdc_zcsd_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
-
-
-class ZoomCsdCascadeBank:
+class ZoomCsdCascadeBank(_SideCarriers, _FramesFeed, _PairBank):
     """`n_pairs` independent zoom cross cascades (psdc_zcsd_*): a pair is two real streams a and b, each mixed down from a
     carrier of its own (ZoomCascadeBank's tuning word and start phase) to I + i Q in front of the cascade.  Every stage keeps the
     two-sided auto spectra of both and their cross spectrum S_ab = conj(Z_a) Z_b (CsdCascade's sign), each as an `upper` row
@@ -2865,62 +2133,8 @@ class ZoomCsdCascadeBank:
     Recipe (AM / PM separation): feed the SAME stream to both sides with the carriers ftw and -ftw, phase0 = 0.  S_bb upper is
     then S_aa lower and S_ab upper is conj(Z_k Z_-k), the term that separates amplitude from phase noise."""
 
-    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
-        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_zcsd_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
-        else:
-            self._h = self._L.psdc_zcsd_create(n, int(window), n_pairs, device)
-        # (ftw, phase0) of both sides of every pair, as set
-        self.carriers = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
-        if not self._h:
-            msg = self._L.psdc_zcsd_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_zcsd_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_zcsd(rc, self._h)
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        self._ck(self._L.psdc_zcsd_reset(self._h))
-        self.carriers = {k: (0, 0) for k in self.carriers}
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_zcsd_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_zcsd_set_avg(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
-        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as f0 (cycles per sample, through
-        zoom_ftw) or as the tuning word itself; phase0 in 2^-64 turn.  Only before the pair's first sample.  Returns the f0
-        actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        if side is not None and side not in (0, 1):
-            raise PsdError(ERR_ARG, f"side {side} out of range (0: channel a, 1: channel b)")
-        for s in ((0, 1) if side is None else (side,)):
-            self._ck(self._L.psdc_zcsd_set_carrier(self._h, pair, s, ftw, phase0))
-            self.carriers[(pair, s)] = (ftw, phase0)
-        return ftw / float(1 << 64)
+    _P, _FP, _MAP = "psdc_zcsd_", "psdc_zoomcsdcascade_", staticmethod(pair_map)
+    _ARG_WORDS = _Bank._ARG_WORDS + ("not supported",)
 
     def process(self, pair, x, y):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -2954,94 +2168,33 @@ class ZoomCsdCascadeBank:
         pair unfed; a trace may feed several sides, both sides of one pair included.  The frames are decoded and mixed on the
         device in one kernel; two sides with one carrier share the oscillator.  Returns the number of frames ingested; a bad
         frame raises FrameError after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        m = pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_zoomcsdcascade_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                        buf.ctypes.data_as(C.c_void_p), frame_size, buf.size // frame_size,
-                                                        C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, pairs)
 
     def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
         """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
         their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
-        m = pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_zoomcsdcascade_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
-                                                               frame_size, n_frames, C.byref(ok),
-                                                               C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
-        l = _CLoss()
-        self._ck(self._L.psdc_zoomcsdcascade_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_zcsd_sync(self._h))
-
-    def num_stages(self, pair=0):
-        return self._ck(self._L.psdc_zcsd_num_stages(self._h, pair))
+        return self._frames_device(ptr, frame_size, n_frames, pairs, after)
 
     def stage_spectra(self, pair, stage):
         """(info, rows) of one stage's raw accumulators: rows (8, n/2 + 1) in the layout of include/psdcascade.h -- S_aa upper,
         lower; S_bb upper, lower; Re S_ab upper, lower; Im S_ab upper, lower."""
         st = _CStageStat()
         rows = np.empty((8, self.n // 2 + 1), np.float32)
-        self._ck(self._L.psdc_zcsd_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(rows)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
+        self._ck(self._f("stage_spectra")(self._h, pair, stage, C.byref(st), _fptr(rows)))
+        return _stage_info(st), rows
 
     def csd(self, pair=0, opts=MergeOpts()):
         """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): PsdCascade::psd of every row, sab complex;
         Break.frequencies(breaks) are the offsets of all."""
-        ns = self.num_stages(pair)
-        cap = max(1, ns * (self.n // 2 + 1))
-        real = [np.empty(cap, np.float32) for _ in range(4)]
-        cplx = [np.empty(2 * cap, np.float32) for _ in range(2)]
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_zcsd_csd(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                       *[_fptr(a) for a in real + cplx], cap, C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        out = [a[:m].copy() for a in real] + [(a[0:2 * m:2] + 1j * a[1:2 * m:2]).astype(np.complex64) for a in cplx]
-        return (*out, [Break._from_c(br[i]) for i in range(nb.value)])
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_zcsd_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "pairs_in": si.value}
+        rows, br = self._merged(self._f("csd"), pair, opts, (1, 1, 1, 1, 2, 2))
+        return (*rows[:4], *((a[0::2] + 1j * a[1::2]).astype(np.complex64) for a in rows[4:]), br)
 
 
-class ZoomCsdCascade:
+class ZoomCsdCascade(_PairCarrierCascade):
     """One pair around a carrier: ZoomCsdCascade(n, f0=0.2) or ZoomCsdCascade(n, ftw=...) sets both sides; set_carrier(side=...)
     sets one.  reset() keeps the object's carriers."""
 
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = ZoomCsdCascadeBank(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
-        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
-        self.carriers = [self._b.carriers[(0, 0)], self._b.carriers[(0, 1)]]
-        return f
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
-
-    def process(self, x, y):
-        self._b.process(0, x, y)
-
-    def process_device(self, px, py, length, after=None):
-        self._b.process_device(0, px, py, length, after)
+    _BANK = ZoomCsdCascadeBank
 
     def process_int(self, x, y, scale=None):
         self._b.process_int(0, x, y, scale)
@@ -3059,29 +2212,8 @@ class ZoomCsdCascade:
     def loss(self, reset=False):
         return self._b.loss(reset)
 
-    def csd(self, opts=MergeOpts()):
-        return self._b.csd(0, opts)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_spectra(self, i):
         return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        car = list(self.carriers)
-        self._b.reset()
-        for s, (ftw, ph) in enumerate(car):
-            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
 
 
 IQCSD_STEADY_LAUNCHES = 4  # PSDC_IQCSD_STEADY_LAUNCHES: pair mixer; segments, decimators, fold + tails
@@ -3090,12 +2222,6 @@ IQCSD_STEADY_LAUNCHES = 4  # PSDC_IQCSD_STEADY_LAUNCHES: pair mixer; segments, d
 def iqcsd_supported(n):
     """True if an IqCsdCascadeBank of size n can be created (psdc_iqcsd_supported: the zoom cross object's sizes).  Needs no GPU."""
     return 0 <= n < (1 << 32) and bool(lib().psdc_iqcsd_supported(n))
-
-
-def _raise_iqcsd(code, h=None):
-    msg = lib().psdc_iqcsd_last_error(h)
-    cls = FrameError if code in (ERR_FRAME_HEADER, ERR_FRAME_FORMAT, ERR_FRAME_SIZE) else PsdError
-    raise cls(code, msg.decode() if msg else "")
 
 
 def iq_pair_map(pairs, n_pairs):
@@ -3130,93 +2256,20 @@ def iq_pair_map(pairs, n_pairs):
     return m
 
 
-class IqCsdCascadeBank:
+class IqCsdCascadeBank(ZoomCsdCascadeBank):
     """`n_pairs` independent IQ cross cascades (psdc_iqcsd_*): a pair is two streams that are complex already, a = I_a + i Q_a
     and b = I_b + i Q_b, each turned by a carrier of its own (default none: ftw = 0, phase0 = 0) in one pair mixer launch in front
     of the zoom cross object's cascade.  Every stage keeps the two-sided auto spectra of both and their cross spectrum
     S_ab = conj(Z_a) Z_b, each as an `upper` row (offsets f >= 0) and a `lower` row (-f, the value at bin N - k, not
     conjugated), exactly as ZoomCsdCascadeBank does.  coherence(), transfer() and two_sided() take the rows of csd() as they are."""
 
-    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
-        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._L.psdc_iqcsd_create_window(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
-        else:
-            self._h = self._L.psdc_iqcsd_create(n, int(window), n_pairs, device)
-        # (ftw, phase0) of both sides of every pair, as set
-        self.carriers = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
-        if not self._h:
-            msg = self._L.psdc_iqcsd_last_error(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.psdc_iqcsd_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            _raise_iqcsd(rc, self._h)
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers too (ftw = 0, phase0 = 0)."""
-        self._ck(self._L.psdc_iqcsd_reset(self._h))
-        self.carriers = {k: (0, 0) for k in self.carriers}
-
-    def set_detrend(self, d):
-        self._ck(self._L.psdc_iqcsd_set_detrend(self._h, int(d)))
-
-    def set_avg(self, avg):
-        self._ck(self._L.psdc_iqcsd_set_avg(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
-        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as f0 (cycles per sample, through
-        zoom_ftw) or as the tuning word itself; phase0 in 2^-64 turn.  Only before the pair's first sample.  Returns the f0
-        actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        if side is not None and side not in (0, 1):
-            raise PsdError(ERR_ARG, f"side {side} out of range (0: stream a, 1: stream b)")
-        for s in ((0, 1) if side is None else (side,)):
-            self._ck(self._L.psdc_iqcsd_set_carrier(self._h, pair, s, ftw, phase0))
-            self.carriers[(pair, s)] = (ftw, phase0)
-        return ftw / float(1 << 64)
+    _P, _FP, _MAP = "psdc_iqcsd_", "psdc_iqcsd_", staticmethod(iq_pair_map)
+    _SIDES = "0: stream a, 1: stream b"
 
     def process(self, pair, za, zb):
         """za, zb: two complex arrays of one length (converted to complex64 and fed as (re, im) pairs: the interleaved route), or
         two pairs (ia, qa), (ib, qb) of real arrays of one length (the planar route)."""
-        planar = [isinstance(z, (tuple, list)) for z in (za, zb)]
-        if all(planar):
-            if len(za) != 2 or len(zb) != 2:
-                raise PsdError(ERR_ARG, "a planar call takes (ia, qa), (ib, qb)")
-            x = [np.ascontiguousarray(v, dtype=np.float32) for v in (*za, *zb)]
-            if any(v.ndim != 1 or v.shape != x[0].shape for v in x):
-                raise PsdError(ERR_ARG, "the four streams differ in length (" + ", ".join(str(v.size) for v in x) + ")")
-            self._ck(self._L.psdc_iqcsd_process(self._h, pair, *[_fptr(v) for v in x], x[0].size))
-            return
-        if any(planar):
-            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q), not one of each")
-        za, zb = np.asarray(za), np.asarray(zb)
-        if not (np.iscomplexobj(za) and np.iscomplexobj(zb)):
-            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q)")
-        za = np.ascontiguousarray(za, dtype=np.complex64)
-        zb = np.ascontiguousarray(zb, dtype=np.complex64)
-        if za.ndim != 1 or za.shape != zb.shape:
-            raise PsdError(ERR_ARG, f"za and zb differ in length ({za.size} and {zb.size})")
-        self._ck(self._L.psdc_iqcsd_process_interleaved(self._h, pair, za.ctypes.data_as(C.POINTER(C.c_float)),
-                                                        zb.ctypes.data_as(C.POINTER(C.c_float)), za.size))
+        self._process_iq_pair(pair, za, zb)
 
     def process_device(self, pair, pa, pb, length, after=None):
         """pa, pb: device addresses of `length` (re, im) pairs of f32 each (two complex64 tensors' memory; 8-byte aligned); after:
@@ -3251,88 +2304,16 @@ class IqCsdCascadeBank:
         iq_pair_map), or None to leave the pair unfed; a trace may feed any number of sides.  The frames are decoded and mixed on
         the device in one kernel; two sides with one carrier share the oscillator.  Returns the number of frames ingested; a
         bad frame raises FrameError after the frames before it were ingested."""
-        buf = np.frombuffer(data, dtype=np.uint8)
-        m = iq_pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_iqcsd_process_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), buf.ctypes.data_as(C.c_void_p),
-                                               frame_size, buf.size // frame_size, C.byref(ok))
-        self._ck(rc)
-        return ok.value
+        return self._frames(data, frame_size, pairs)
 
-    def process_frames_device(self, ptr, frame_size, n_frames, pairs, after=None):
-        """process_frames for frames resident in device memory at address `ptr`; after: a hipEvent_t handle recorded behind
-        their producer, or None when it has completed.  The payloads must stay unchanged until sync() or a read-out returns."""
-        m = iq_pair_map(pairs, self.n_pairs)
-        ok = C.c_size_t(0)
-        rc = self._L.psdc_iqcsd_process_frames_device(self._h, m.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(ptr),
-                                                      frame_size, n_frames, C.byref(ok), C.c_void_p(after) if after else None)
-        self._ck(rc)
-        return ok.value
-
-    def loss(self, reset=False):
-        """Loss counters (src/loss.rs) over the frames ingested: batches received / dropped."""
-        l = _CLoss()
-        self._ck(self._L.psdc_iqcsd_loss_read(self._h, C.byref(l), int(reset)))
-        return {"received": l.received, "dropped": l.dropped}
-
-    def sync(self):
-        self._ck(self._L.psdc_iqcsd_sync(self._h))
-
-    def num_stages(self, pair=0):
-        return self._ck(self._L.psdc_iqcsd_num_stages(self._h, pair))
-
-    def stage_spectra(self, pair, stage):
-        """(info, rows) of one stage's raw accumulators: rows (8, n/2 + 1) in the layout of include/psdcascade.h -- S_aa upper,
-        lower; S_bb upper, lower; Re S_ab upper, lower; Im S_ab upper, lower."""
-        st = _CStageStat()
-        rows = np.empty((8, self.n // 2 + 1), np.float32)
-        self._ck(self._L.psdc_iqcsd_stage_spectra(self._h, pair, stage, C.byref(st), _fptr(rows)))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
-
-    def csd(self, pair=0, opts=MergeOpts()):
-        """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): PsdCascade::psd of every row, sab complex;
-        Break.frequencies(breaks) are the offsets of all."""
-        ns = self.num_stages(pair)
-        cap = max(1, ns * (self.n // 2 + 1))
-        real = [np.empty(cap, np.float32) for _ in range(4)]
-        cplx = [np.empty(2 * cap, np.float32) for _ in range(2)]
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._L.psdc_iqcsd_csd(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                        *[_fptr(a) for a in real + cplx], cap, C.byref(plen), br, ns, C.byref(nb)))
-        m = plen.value
-        out = [a[:m].copy() for a in real] + [(a[0:2 * m:2] + 1j * a[1:2 * m:2]).astype(np.complex64) for a in cplx]
-        return (*out, [Break._from_c(br[i]) for i in range(nb.value)])
-
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._L.psdc_iqcsd_stats_read(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "pairs_in": si.value}
-
-    stats = stats_read
+    stats = _Stats.stats_read
 
 
-class IqCsdCascade:
+class IqCsdCascade(ZoomCsdCascade):
     """One pair of complex streams: IqCsdCascade(n) analyses them as they are, IqCsdCascade(n, f0=0.2) or IqCsdCascade(n, ftw=...)
     retunes both sides first; set_carrier(side=...) sets one.  reset() keeps the object's carriers."""
 
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = IqCsdCascadeBank(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
-        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
-        self.carriers = [self._b.carriers[(0, 0)], self._b.carriers[(0, 1)]]
-        return f
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
+    _BANK = IqCsdCascadeBank
 
     def process(self, za, zb):
         """za, zb: two complex arrays, or two pairs (i, q) (IqCsdCascadeBank.process)"""
@@ -3354,37 +2335,7 @@ class IqCsdCascade:
         """pair: ((ia, qa), (ib, qb)), the traces of the frames the two streams are (IqCsdCascadeBank.process_frames)"""
         return self._b.process_frames(data, frame_size, [pair])
 
-    def process_frames_device(self, ptr, frame_size, n_frames, pair, after=None):
-        return self._b.process_frames_device(ptr, frame_size, n_frames, [pair], after)
-
-    def loss(self, reset=False):
-        return self._b.loss(reset)
-
-    def csd(self, opts=MergeOpts()):
-        return self._b.csd(0, opts)
-
-    def num_stages(self):
-        return self._b.num_stages(0)
-
-    def stage_spectra(self, i):
-        return self._b.stage_spectra(0, i)
-
-    def reset(self):
-        car = list(self.carriers)
-        self._b.reset()
-        for s, (ftw, ph) in enumerate(car):
-            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    stats = stats_read
-
-    def close(self):
-        self._b.close()
+    stats = _UnitCascade.stats_read
 
 
 def zoom_ampm_cross_supported(n):
@@ -3427,7 +2378,7 @@ def am_pm_cross_from_sidebands(sab_up, sab_lo, cab, cba, p_ab, w, q):
             1j * (t1 + t2 - t3 - t4) / (4.0 * P))
 
 
-class ZoomAmPmCsdCascadeBank:
+class ZoomAmPmCsdCascadeBank(_SideCarriers, _PairBank):
     """`n_pairs` independent AM/PM cross cascades (psdc_zxampm_*): ZoomCsdCascadeBank's pair -- two real streams a and b, each
     mixed down from a carrier of its own -- on one transform a channel and segment, with the two complementary cross spectra
     cab[k] = sum Z_a[k] Z_b[N-k] and cba[k] = sum Z_a[N-k] Z_b[k] (products WITHOUT a conjugate) kept beside the zoom cross
@@ -3440,69 +2391,16 @@ class ZoomAmPmCsdCascadeBank:
     loss record or integer feeds."""
 
     _P = "psdc_zxampm_"
+    _ARG_WORDS = _Bank._ARG_WORDS + ("not supported",)
+    _CARRIERS = "carriers_set"   # (carriers() is the read-out of the carriers themselves)
 
-    def __init__(self, n, n_pairs=1, window=Window.HANN, device=0):
-        self.n, self.n_pairs, self.window, self.device = n, n_pairs, window, device
-        self._L = lib()
-        if isinstance(window, WindowTable):
-            w = np.ascontiguousarray(window.win, dtype=np.float32)
-            if w.size != n:
-                raise PsdError(ERR_ARG, "window table length != n")
-            self._h = self._f("create_window")(n, _fptr(w), window.power, window.nenbw, window.overlap, n_pairs, device)
-        else:
-            self._h = self._f("create")(n, int(window), n_pairs, device)
-        # (ftw, phase0) of both sides of every pair, as set
-        self.carriers_set = {(p, s): (0, 0) for p in range(min(n_pairs, 65536)) for s in (0, 1)}
-        self.detrend = Detrend.NONE
-        if not self._h:
-            msg = self._f("last_error")(None)
-            msg = msg.decode() if msg else ""
-            arg = any(w in msg for w in ("must be", "out of range", "null", "window_kind", "not supported"))
-            raise PsdError(ERR_ARG if arg else ERR_DEVICE, msg)
-
-    def _f(self, name):
-        return getattr(self._L, self._P + name)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._f("destroy")(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _ck(self, rc):
-        if rc < 0:
-            msg = self._f("last_error")(self._h)
-            raise PsdError(rc, msg.decode() if msg else "")
-        return rc
-
-    def reset(self):
-        """Back to a fresh object: the carriers (ftw = 0, phase0 = 0) and the detrend too."""
-        self._ck(self._f("reset")(self._h))
-        self.carriers_set = {k: (0, 0) for k in self.carriers_set}
+    def _fresh(self, most=None):
+        super()._fresh(most)
         self.detrend = Detrend.NONE
 
     def set_detrend(self, d):
-        self._ck(self._f("set_detrend")(self._h, int(d)))
+        super().set_detrend(d)
         self.detrend = Detrend(int(d))
-
-    def set_avg(self, avg):
-        self._ck(self._f("set_avg")(self._h, avg.limit, avg.count))
-
-    def set_carrier(self, pair, f0=None, ftw=None, phase0=0, side=None):
-        """The carrier of one side of a pair (side 0: a, 1: b) or, with side=None, of both; as ZoomCsdCascadeBank.set_carrier.
-        Returns the f0 actually used."""
-        if (f0 is None) == (ftw is None):
-            raise PsdError(ERR_ARG, "give exactly one of f0 and ftw")
-        if ftw is None:
-            ftw = zoom_ftw(f0)[0]
-        ftw, phase0 = int(ftw) % (1 << 64), int(phase0) % (1 << 64)
-        if side is not None and side not in (0, 1):
-            raise PsdError(ERR_ARG, f"side {side} out of range (0: channel a, 1: channel b)")
-        for s in ((0, 1) if side is None else (side,)):
-            self._ck(self._f("set_carrier")(self._h, pair, s, ftw, phase0))
-            self.carriers_set[(pair, s)] = (ftw, phase0)
-        return ftw / float(1 << 64)
 
     def process(self, pair, x, y):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -3517,41 +2415,28 @@ class ZoomAmPmCsdCascadeBank:
         self._ck(self._L.psdc_zxampm_process_device(self._h, pair, C.c_void_p(px), C.c_void_p(py), length,
                                                     C.c_void_p(after) if after else None))
 
-    def sync(self):
-        self._ck(self._f("sync")(self._h))
-
-    def num_stages(self, pair=0):
-        return self._ck(self._f("num_stages")(self._h, pair))
-
     def stage_rows(self, pair, stage):
         """(info, rows) of one stage's raw f64 accumulators: rows (12, n/2 + 1) in the layout of include/psdcascade.h -- the zoom
         cross object's eight, then Re cab, Im cab, Re cba, Im cba"""
         st = _CStageStat()
         rows = np.empty((12, self.n // 2 + 1), np.float64)
         self._ck(self._f("stage_rows")(self._h, pair, stage, C.byref(st), rows.ctypes.data_as(C.POINTER(C.c_double))))
-        return {"count": st.count, "avg": st.avg, "pending": st.pending, "processed": st.processed}, rows
+        return _stage_info(st), rows
 
-    def _merged(self, pair, opts):
-        ns = self.num_stages(pair)
-        cap = max(1, ns * (self.n // 2 + 1))
-        rows = np.zeros((12, cap), np.float64)
-        br = (_CBreak * max(1, ns))()
-        plen, nb = C.c_size_t(), C.c_size_t()
-        self._ck(self._f("sidebands")(self._h, pair, int(opts.keep_overlap), opts.min_count, int(opts.keep_transition_band),
-                                      rows.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(plen), br, ns, C.byref(nb)))
-        return rows[:, :plen.value], [Break._from_c(br[i]) for i in range(nb.value)]
+    def _twelve(self, pair, opts):
+        return self._merged(self._f("sidebands"), pair, opts, 12, np.float64)
 
     def sidebands(self, pair=0, opts=MergeOpts()):
         """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, cab, cba, breaks): all twelve rows merged with one set of Breaks, in
         f64 (the last four complex128)"""
-        r, br = self._merged(pair, opts)
+        r, br = self._twelve(pair, opts)
         return (r[0].copy(), r[1].copy(), r[2].copy(), r[3].copy(), r[4] + 1j * r[6], r[5] + 1j * r[7], r[8] + 1j * r[9],
                 r[10] + 1j * r[11], br)
 
     def csd(self, pair=0, opts=MergeOpts()):
         """(saa_up, saa_lo, sbb_up, sbb_lo, sab_up, sab_lo, breaks): ZoomCsdCascadeBank.csd()'s tuple (f32, sab complex64), taken
         from rows 0 ... 7"""
-        r, br = self._merged(pair, opts)
+        r, br = self._twelve(pair, opts)
         return (*(r[i].astype(np.float32) for i in range(4)), (r[4] + 1j * r[6]).astype(np.complex64),
                 (r[5] + 1j * r[7]).astype(np.complex64), br)
 
@@ -3578,11 +2463,6 @@ class ZoomAmPmCsdCascadeBank:
         sb = self.sidebands(pair, opts)
         return (*am_pm_cross_from_sidebands(sb[4], sb[5], sb[6], sb[7], p_ab, w, q), sb[8])
 
-    def stats_read(self, reset=False):
-        la, si = C.c_uint64(), C.c_uint64()
-        self._ck(self._f("stats_read")(self._h, C.byref(la), C.byref(si), int(reset)))
-        return {"launches": la.value, "pairs_in": si.value}
-
 
 class IqAmPmCsdCascadeBank(ZoomAmPmCsdCascadeBank):
     """`n_pairs` independent IQ AM/PM cross cascades (psdc_iqxampm_*): ZoomAmPmCsdCascadeBank for two streams that are complex
@@ -3593,26 +2473,7 @@ class IqAmPmCsdCascadeBank(ZoomAmPmCsdCascadeBank):
     def process(self, pair, za, zb):
         """za, zb: two complex arrays of one length (converted to complex64 and fed as (re, im) pairs: the interleaved route), or
         two pairs (ia, qa), (ib, qb) of real arrays of one length (the planar route)."""
-        planar = [isinstance(z, (tuple, list)) for z in (za, zb)]
-        if all(planar):
-            if len(za) != 2 or len(zb) != 2:
-                raise PsdError(ERR_ARG, "a planar call takes (ia, qa), (ib, qb)")
-            x = [np.ascontiguousarray(v, dtype=np.float32) for v in (*za, *zb)]
-            if any(v.ndim != 1 or v.shape != x[0].shape for v in x):
-                raise PsdError(ERR_ARG, "the four streams differ in length (" + ", ".join(str(v.size) for v in x) + ")")
-            self._ck(self._L.psdc_iqxampm_process(self._h, pair, *[_fptr(v) for v in x], x[0].size))
-            return
-        if any(planar):
-            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q), not one of each")
-        za, zb = np.asarray(za), np.asarray(zb)
-        if not (np.iscomplexobj(za) and np.iscomplexobj(zb)):
-            raise PsdError(ERR_ARG, "process takes two complex arrays or two pairs (i, q)")
-        za = np.ascontiguousarray(za, dtype=np.complex64)
-        zb = np.ascontiguousarray(zb, dtype=np.complex64)
-        if za.ndim != 1 or za.shape != zb.shape:
-            raise PsdError(ERR_ARG, f"za and zb differ in length ({za.size} and {zb.size})")
-        self._ck(self._L.psdc_iqxampm_process_interleaved(self._h, pair, za.ctypes.data_as(C.POINTER(C.c_float)),
-                                                          zb.ctypes.data_as(C.POINTER(C.c_float)), za.size))
+        self._process_iq_pair(pair, za, zb)
 
     def process_device(self, pair, pa, pb, length, after=None):
         """pa, pb: device addresses of `length` (re, im) pairs of f32 each (two complex64 tensors' memory; 8-byte aligned); the
@@ -3626,39 +2487,12 @@ class IqAmPmCsdCascadeBank(ZoomAmPmCsdCascadeBank):
                                                      C.c_void_p(pqb), length, C.c_void_p(after) if after else None))
 
 
-class ZoomAmPmCsdCascade:
+class ZoomAmPmCsdCascade(_PairCarrierCascade):
     """One pair around a carrier: ZoomAmPmCsdCascade(n, f0=0.2) or ZoomAmPmCsdCascade(n, ftw=...) sets both sides;
     set_carrier(side=...) sets one.  csd(), sidebands(), carriers() and am_pm_cross() (ZoomAmPmCsdCascadeBank has the definitions
     and the limits).  reset() keeps the object's carriers."""
 
     _BANK = ZoomAmPmCsdCascadeBank
-
-    def __init__(self, n, f0=None, ftw=None, phase0=0, window=Window.HANN, device=0):
-        self.n = n
-        self._b = self._BANK(n, 1, window, device)
-        if f0 is None and ftw is None:
-            ftw = 0
-        self.set_carrier(f0=f0, ftw=ftw, phase0=phase0)
-
-    def set_carrier(self, f0=None, ftw=None, phase0=0, side=None):
-        f = self._b.set_carrier(0, f0=f0, ftw=ftw, phase0=phase0, side=side)
-        self.carriers_set = [self._b.carriers_set[(0, 0)], self._b.carriers_set[(0, 1)]]
-        return f
-
-    def set_avg(self, avg):
-        self._b.set_avg(avg)
-
-    def set_detrend(self, d):
-        self._b.set_detrend(d)
-
-    def process(self, x, y):
-        self._b.process(0, x, y)
-
-    def process_device(self, px, py, length, after=None):
-        self._b.process_device(0, px, py, length, after)
-
-    def csd(self, opts=MergeOpts()):
-        return self._b.csd(0, opts)
 
     def sidebands(self, opts=MergeOpts()):
         return self._b.sidebands(0, opts)
@@ -3669,26 +2503,8 @@ class ZoomAmPmCsdCascade:
     def am_pm_cross(self, carriers=None, opts=MergeOpts()):
         return self._b.am_pm_cross(0, carriers, opts)
 
-    def num_stages(self):
-        return self._b.num_stages(0)
-
     def stage_rows(self, i):
         return self._b.stage_rows(0, i)
-
-    def reset(self):
-        car = list(self.carriers_set)
-        self._b.reset()
-        for s, (ftw, ph) in enumerate(car):
-            self._b.set_carrier(0, ftw=ftw, phase0=ph, side=s)
-
-    def sync(self):
-        self._b.sync()
-
-    def stats_read(self, reset=False):
-        return self._b.stats_read(reset)
-
-    def close(self):
-        self._b.close()
 
 
 class IqAmPmCsdCascade(ZoomAmPmCsdCascade):
