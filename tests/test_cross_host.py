@@ -25,9 +25,10 @@ def _window(ora, n, window):
     return np.asarray(w, np.float32).astype(np.float64), p, e, ov, None
 
 
-def restate(ora, x, y, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64"):
+def restate(ora, x, y, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", schedule=None):
     """Cross cascade of the streams x, y: per stage dict(count, avg, pending, sxx, syy, sxy complex), stage 0 first.
-    prec "f64": truth; "f32": the reference's arithmetic (f32 detrend / FFT / decimator, f32 accumulation)."""
+    prec "f64": truth; "f32": the reference's arithmetic (f32 detrend / FFT / decimator, f32 accumulation).
+    schedule: a settings_schedule.Schedule of mid-stream set_detrend / set_avg calls; it then replaces detrend and avg."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     h = n // 2 + 1
@@ -51,6 +52,8 @@ def restate(ora, x, y, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX),
             return ora.fft_forward(c.astype(ct), prec)[:h].astype(ct)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             X, Y = spec(xs[j * hop:j * hop + n]), spec(ys[j * hop:j * hop + n])
             g = 1.0
             if count > a:
@@ -61,6 +64,8 @@ def restate(ora, x, y, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX),
             syy = ft(g) * syy + (Y.real * Y.real + Y.imag * Y.imag).astype(ft)
             sxy = ft(g) * sxy + (np.conj(X) * Y).astype(ct)
         pending = xs.size if nseg == 0 else xs.size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, sxx=sxx, syy=syy, sxy=sxy))
         p = nseg * hop + overlap if nseg else 0
         xs = ora.hbf_dec8(xs[:p], prec)[DRAIN:].astype(ft)  # (the f64 oracle carries its stages in f64)

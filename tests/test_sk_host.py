@@ -25,10 +25,11 @@ SK_SYMBOLS = ["psdc_sk_supported", "psdc_sk_create", "psdc_sk_create_window", "p
               "psdc_sk_last_error"]
 
 
-def restate_sk(ora, x, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", max_stages=None):
+def restate_sk(ora, x, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", max_stages=None, schedule=None):
     """Spectral kurtosis cascade of the stream x: per stage dict(count, avg, pending, s1, s2), stage 0 first.
     prec "f64": truth; "f32": the reference's arithmetic (f32 detrend / FFT / decimator, f32 accumulation).
-    max_stages: stop after that many stages (the property tests look at the first ones only)."""
+    max_stages: stop after that many stages (the property tests look at the first ones only).
+    schedule: a settings_schedule.Schedule of mid-stream set_detrend / set_avg calls; it then replaces detrend and avg."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     h = n // 2 + 1
@@ -52,6 +53,8 @@ def restate_sk(ora, x, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX),
             return ora.fft_forward(c.astype(ct), prec)[:h].astype(ct)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             X = spec(xs[j * hop:j * hop + n])
             g = 1.0
             if count > a:
@@ -62,6 +65,8 @@ def restate_sk(ora, x, n, window="hann", detrend="none", avg=(U32_MAX, U32_MAX),
             s1 = ft(g) * s1 + p
             s2 = ft(g) * s2 + (p * p).astype(ft)
         pending = xs.size if nseg == 0 else xs.size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, s1=s1, s2=s2))
         p = nseg * hop + overlap if nseg else 0
         xs = ora.hbf_dec8(xs[:p], prec)[DRAIN:].astype(ft)  # (the f64 oracle carries its stages in f64)

@@ -35,10 +35,11 @@ ZWF_ROWS = ("upper", "lower", "s2_upper", "s2_lower")
 
 # ---- the restatements ----
 
-def _restate_blocks(ora, streams, n, block, window, detrend, prec, max_stages, rows_of):
+def _restate_blocks(ora, streams, n, block, window, detrend, prec, max_stages, rows_of, schedule=None):
     """The cascade of the m streams (one for the real kind; I and Q for the zoom kind): per stage
     dict(segs, pending, blocks=[dict(index, count, rows...)]), stage 0 first, EVERY block since the stream's start (a ring keeps the
-    newest K of them).  rows_of(specs of one segment) -> {row name: its periodogram term}.  Stage bookkeeping as restate_sk."""
+    newest K of them).  rows_of(specs of one segment) -> {row name: its periodogram term}.  Stage bookkeeping as restate_sk.
+    schedule: a settings_schedule.Schedule of mid-stream set_detrend calls; it then replaces detrend."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     ft = np.float64 if prec == "f64" else np.float32
@@ -56,6 +57,8 @@ def _restate_blocks(ora, streams, n, block, window, detrend, prec, max_stages, r
 
         blocks = []
         for j in range(nseg):
+            if schedule is not None:  # the detrend in force when segment j of stage k completed
+                detrend = schedule.stage(k, j)[0]
             terms = rows_of([prep(x[j * hop:j * hop + n]) for x in xs])
             if j % block == 0:
                 blocks.append(dict(index=j // block, count=0, **{name: np.zeros(n // 2 + 1, ft) for name in terms}))
@@ -71,7 +74,7 @@ def _restate_blocks(ora, streams, n, block, window, detrend, prec, max_stages, r
     return stages
 
 
-def restate_waterfall(ora, x, n, block, window="hann", detrend="none", prec="f64", max_stages=None):
+def restate_waterfall(ora, x, n, block, window="hann", detrend="none", prec="f64", max_stages=None, schedule=None):
     """Waterfall cascade of the real stream x: per block the rows s1 = sum P and s2 = sum P^2 of its segments, with restate_sk's
     segment arithmetic (prec "f64": truth; "f32": the reference's arithmetic with f32 accumulation inside a block)"""
     h = n // 2 + 1
@@ -83,10 +86,11 @@ def restate_waterfall(ora, x, n, block, window="hann", detrend="none", prec="f64
         p = (X.real * X.real + X.imag * X.imag).astype(ft)
         return {"s1": p, "s2": (p * p).astype(ft)}
 
-    return _restate_blocks(ora, [x], n, block, window, detrend, prec, max_stages, rows_of)
+    return _restate_blocks(ora, [x], n, block, window, detrend, prec, max_stages, rows_of, schedule)
 
 
-def restate_zoom_waterfall(ora, x, n, ftw, block, window="hann", detrend="none", prec="f64", iq=None, max_stages=None):
+def restate_zoom_waterfall(ora, x, n, ftw, block, window="hann", detrend="none", prec="f64", iq=None, max_stages=None,
+                           schedule=None):
     """Zoom waterfall cascade of the real stream x around the carrier ftw: per block the four rows of restate_zoom_sk (upper,
     lower, s2_upper, s2_lower).  prec and iq as restate_zoom_sk takes them."""
     h = n // 2 + 1
@@ -102,7 +106,7 @@ def restate_zoom_waterfall(ora, x, n, ftw, block, window="hann", detrend="none",
         p2 = (p * p).astype(ft)
         return {"upper": p[:h], "lower": p[lower_idx], "s2_upper": p2[:h], "s2_lower": p2[lower_idx]}
 
-    return _restate_blocks(ora, [si, sq], n, block, window, detrend, prec, max_stages, rows_of)
+    return _restate_blocks(ora, [si, sq], n, block, window, detrend, prec, max_stages, rows_of, schedule)
 
 
 def ring_of(stage, depth):

@@ -35,9 +35,9 @@ IQXAMPM_SYMBOLS = ["psdc_iqxampm_" + s for s in _COMMON + ["process", "process_d
 
 
 def restate_zoom_ampm_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64",
-                            iq=None, max_stages=None):
+                            iq=None, max_stages=None, schedule=None):
     """AM/PM cross cascade of the streams xa, xb with the carriers ftw = (ftw_a, ftw_b): per stage dict(count, avg, pending,
-    rows (8, n/2 + 1) computed as restate_zoom_cross computes them, cab, cba complex), stage 0 first.  prec / iq as
+    rows (8, n/2 + 1) computed as restate_zoom_cross computes them, cab, cba complex), stage 0 first.  prec / iq / schedule as
     restate_zoom_cross takes them.  max_stages: stop after that many stages (the property tests look at stage 0 only)."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
@@ -69,6 +69,8 @@ def restate_zoom_ampm_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", d
             return np.fft.fft(z) if prec == "f64" else ora.fft_forward(z, "f32").astype(ct)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             Za, Zb = spec(s[0], s[1], j), spec(s[2], s[3], j)
             pa = (Za.real * Za.real + Za.imag * Za.imag).astype(ft)
             pb = (Zb.real * Zb.real + Zb.imag * Zb.imag).astype(ft)
@@ -84,6 +86,8 @@ def restate_zoom_ampm_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", d
             cab = (ft(g) * cab + (Za[:h] * Zb[lower_idx]).astype(ct)).astype(ct)
             cba = (ft(g) * cba + (Za[lower_idx] * Zb[:h]).astype(ct)).astype(ct)
         pending = size if nseg == 0 else size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, rows=rows, cab=cab, cba=cba))
         p = nseg * hop + overlap if nseg else 0
         s = [ora.hbf_dec8(v[:p], prec)[DRAIN:].astype(ft) for v in s]

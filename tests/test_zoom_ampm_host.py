@@ -31,10 +31,10 @@ IQAMPM_SYMBOLS = ["psdc_iqampm_" + s for s in _COMMON + ["process", "process_dev
 
 
 def restate_zoom_ampm(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", iq=None,
-                      max_stages=None):
+                      max_stages=None, schedule=None):
     """AM/PM cascade of the stream x: per stage dict(count, avg, pending, upper, lower, comp), stage 0 first; upper / lower are
-    computed as restate_zoom computes them, comp[k] = sum w Z[k] Z[(N - k) mod N] is complex.  prec and iq as restate_zoom takes
-    them.  max_stages: stop after that many stages (the property tests look at stage 0 only)."""
+    computed as restate_zoom computes them, comp[k] = sum w Z[k] Z[(N - k) mod N] is complex.  prec, iq and schedule as restate_zoom
+    takes them.  max_stages: stop after that many stages (the property tests look at stage 0 only)."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     h = n // 2 + 1
@@ -58,6 +58,8 @@ def restate_zoom_ampm(ora, x, n, ftw, phase0=0, window="hann", detrend="none", a
             return ora.detrend_apply(seg, detrend, "rect", prec).real * win.astype(ft)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             z = (prep(si[j * hop:j * hop + n]) + 1j * prep(sq[j * hop:j * hop + n])).astype(ct)
             Z = np.fft.fft(z) if prec == "f64" else ora.fft_forward(z, "f32").astype(ct)
             p = (Z.real * Z.real + Z.imag * Z.imag).astype(ft)
@@ -71,6 +73,8 @@ def restate_zoom_ampm(ora, x, n, ftw, phase0=0, window="hann", detrend="none", a
             lower = ft(g) * lower + p[lower_idx]
             comp = (ft(g) * comp + c).astype(ct)
         pending = si.size if nseg == 0 else si.size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, upper=upper, lower=lower, comp=comp))
         p = nseg * hop + overlap if nseg else 0
         si = ora.hbf_dec8(si[:p], prec)[DRAIN:].astype(ft)

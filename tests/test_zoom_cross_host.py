@@ -24,10 +24,10 @@ ROWS = ("saa_up", "saa_lo", "sbb_up", "sbb_lo", "re_up", "re_lo", "im_up", "im_l
 
 
 def restate_zoom_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64",
-                       iq=None):
+                       iq=None, schedule=None):
     """Zoom cross cascade of the streams xa, xb with the carriers ftw = (ftw_a, ftw_b): per stage dict(count, avg, pending,
     rows (8, n/2 + 1) in the header's order), stage 0 first.  prec / iq as restate_zoom: "f64" is truth; "f32" the complex64
-    sibling with iq = ((I_a, Q_a), (I_b, Q_b)) from mix_f32."""
+    sibling with iq = ((I_a, Q_a), (I_b, Q_b)) from mix_f32.  schedule as restate_zoom takes it."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     h = n // 2 + 1
@@ -57,6 +57,8 @@ def restate_zoom_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", detren
             return np.fft.fft(z) if prec == "f64" else ora.fft_forward(z, "f32").astype(ct)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             Za, Zb = spec(s[0], s[1], j), spec(s[2], s[3], j)
             pa = (Za.real * Za.real + Za.imag * Za.imag).astype(ft)
             pb = (Zb.real * Zb.real + Zb.imag * Zb.imag).astype(ft)
@@ -70,6 +72,8 @@ def restate_zoom_cross(ora, xa, xb, n, ftw, phase0=(0, 0), window="hann", detren
             new = np.stack([v[idx] for v in vals for idx in (slice(0, h), lower_idx)])
             rows = ft(g) * rows + new
         pending = size if nseg == 0 else size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, rows=rows))
         p = nseg * hop + overlap if nseg else 0
         s = [ora.hbf_dec8(v[:p], prec)[DRAIN:].astype(ft) for v in s]

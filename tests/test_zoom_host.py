@@ -63,9 +63,11 @@ def mix_f32(emul, x, ftw, phase0=0):
     return iq[:x.size].copy(), iq[x.size:].copy()
 
 
-def restate_zoom(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", iq=None):
+def restate_zoom(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", iq=None,
+                 schedule=None):
     """Zoom cascade of the stream x: per stage dict(count, avg, pending, upper, lower), stage 0 first.  prec "f64": truth (f64
-    LO, numpy FFT); "f32": the complex64 sibling -- iq = (I, Q) from mix_f32, f32 detrend / decimator, complex64 FFT, f32 rows."""
+    LO, numpy FFT); "f32": the complex64 sibling -- iq = (I, Q) from mix_f32, f32 detrend / decimator, complex64 FFT, f32 rows.
+    schedule: a settings_schedule.Schedule of mid-stream set_detrend / set_avg calls; it then replaces detrend and avg."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
     h = n // 2 + 1
@@ -89,6 +91,8 @@ def restate_zoom(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U
             return ora.detrend_apply(seg, detrend, "rect", prec).real * win.astype(ft)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             z = (prep(si[j * hop:j * hop + n]) + 1j * prep(sq[j * hop:j * hop + n])).astype(ct)
             Z = np.fft.fft(z) if prec == "f64" else ora.fft_forward(z, "f32").astype(ct)
             p = (Z.real * Z.real + Z.imag * Z.imag).astype(ft)
@@ -100,6 +104,8 @@ def restate_zoom(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U
             upper = ft(g) * upper + p[:h]
             lower = ft(g) * lower + p[lower_idx]
         pending = si.size if nseg == 0 else si.size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, upper=upper, lower=lower))
         p = nseg * hop + overlap if nseg else 0
         si = ora.hbf_dec8(si[:p], prec)[DRAIN:].astype(ft)

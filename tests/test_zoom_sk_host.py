@@ -32,9 +32,9 @@ IQSK_SYMBOLS = ["psdc_iqsk_" + s for s in _COMMON + ["process", "process_device"
 
 
 def restate_zoom_sk(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg=(U32_MAX, U32_MAX), prec="f64", iq=None,
-                    max_stages=None):
+                    max_stages=None, schedule=None):
     """Zoom spectral kurtosis cascade of the stream x: per stage dict(count, avg, pending, upper, lower, s2_upper, s2_lower), stage 0
-    first; upper / lower are the S1 rows, computed as restate_zoom computes them.  prec and iq as restate_zoom takes them.
+    first; upper / lower are the S1 rows, computed as restate_zoom computes them.  prec, iq and schedule as restate_zoom takes them.
     max_stages: stop after that many stages (the property tests look at the first ones only)."""
     win, _, _, overlap, kind = _window(ora, n, window)
     hop = n - overlap
@@ -60,6 +60,8 @@ def restate_zoom_sk(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg
             return ora.detrend_apply(seg, detrend, "rect", prec).real * win.astype(ft)
 
         for j in range(nseg):
+            if schedule is not None:  # the settings in force when segment j of stage k completed
+                detrend, a = schedule.stage(k, j)
             z = (prep(si[j * hop:j * hop + n]) + 1j * prep(sq[j * hop:j * hop + n])).astype(ct)
             Z = np.fft.fft(z) if prec == "f64" else ora.fft_forward(z, "f32").astype(ct)
             p = (Z.real * Z.real + Z.imag * Z.imag).astype(ft)
@@ -74,6 +76,8 @@ def restate_zoom_sk(ora, x, n, ftw, phase0=0, window="hann", detrend="none", avg
             u2 = ft(g) * u2 + p2[:h]
             l2 = ft(g) * l2 + p2[lower_idx]
         pending = si.size if nseg == 0 else si.size - nseg * hop
+        if schedule is not None:
+            a = schedule.final_avg(k)  # the stitchers take the value in force at the end
         stages.append(dict(count=count, avg=a, pending=pending, upper=upper, lower=lower, s2_upper=u2, s2_lower=l2))
         p = nseg * hop + overlap if nseg else 0
         si = ora.hbf_dec8(si[:p], prec)[DRAIN:].astype(ft)
