@@ -8,7 +8,7 @@
 //                      fixed order and carries the stream tails into the other buffer.
 // The /8 decimator is hbf_dec8_kernel (kernels.hip) through launch_dec, one job per channel.
 #include "cross.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 
 namespace psdk {
 
@@ -23,9 +23,8 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void cross_kernel(const CrossBa
     __shared__ cf frames[TEAMS * 2 * Cfg::FRAME];
     __shared__ float red[Cfg::WAVES * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CrossJob &j) { return j.block_begin; });
-    const CrossJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CrossJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     cf *fx = frames + team * 2 * Cfg::FRAME;
@@ -34,16 +33,16 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void cross_kernel(const CrossBa
     const int detrend = batch.detrend;
 
     float acc[XB][4];
-#pragma unroll
-    for (int r = 0; r < XB; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            acc[r][c] = 0.0f;
+    zero_rows(acc);
 
     for (int lt = wb; lt < job.ntiles; lt += job.nblocks) {
         const int seg_lo = lt * SPT;
         const int seg_hi = min(job.nseg, seg_lo + SPT);
         const int npairs = (seg_hi - seg_lo + 1) >> 1;
+        // This kernel keeps its own spelling of seg_pair and of OwnedCombine<H, 4, 4, TEAMS, TEAM> (segment_kernel.h; the host
+        // check walks that layout as "cross").  Its speed follows its register allocation, at the limit of one wavefront a SIMD: with
+        // the shared functions, or without the one-turn p0 loop, it computed the same bits 18 ... 24 % slower at N = 1024 ... 4096
+        // (profiles/segment_skeleton_probe.json).
         for (int p0 = 0; p0 < npairs; p0 += TEAMS) {
             const int la = seg_lo + 2 * (p0 + team);
             const bool act_a = la < seg_hi, act_b = la + 1 < seg_hi;
@@ -140,67 +139,15 @@ __global__ __launch_bounds__(POST_THREADS) void cross_post_kernel(const CrossPos
 
 int cross_fold_blocks(int nrows, int nbins) { return (nrows * nbins + FOLD_ELEMS - 1) / FOLD_ELEMS; }
 
-int cross_block_threads(int n)
-{
-    switch (n) {
-#define PSDK_CASE(NN) \
-    case NN:          \
-        return CrossCfg<NN>::BLOCK;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return 0;
-    }
-}
+int cross_block_threads(int n) { return seg_supported(n) ? seg_block(n) : 0; }
 
-bool cross_supported(int n) { return n >= 64 && n <= 4096 && (n & (n - 1)) == 0; }
+bool cross_supported(int n) { return seg_supported(n); }
 
-int cross_segments_per_tile(int n)
-{
-    switch (n) {
-#define PSDK_CASE(NN) \
-    case NN:          \
-        return CrossCfg<NN>::SPT;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return 0;
-    }
-}
+int cross_segments_per_tile(int n) { return seg_supported(n) ? seg_spt(n) : 0; }
 
 hipError_t launch_cross(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s)
 {
-    if (b.nblocks <= 0)
-        return hipSuccess;
-    switch (n) {
-#define PSDK_CASE(NN)                                                                                                   \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL(cross_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw);        \
-        break;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return seg_launch(n, b, win, tw, s, [](auto N) { return cross_kernel<decltype(N)::value>; });
 }
 
 hipError_t launch_cross_post(const CrossPostBatch &b, hipStream_t s)

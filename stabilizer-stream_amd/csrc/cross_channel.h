@@ -2,27 +2,41 @@
 // zoom.hip / zoom_cross.hip (the I / Q pair of a mixed-down channel):
 // load, detrend and window two consecutive segments of a channel, transform them as one complex signal and leave the spectrum
 // in natural order in an LDS frame (cross_fft.h) -- or, for the zoom kernels, leave nothing in the frame and add |Z|^2 of the
-// thread's bins to its registers, or hand the bins themselves back.  Device code only.
+// thread's bins to its registers, or hand the bins themselves back.  The workgroup shape (CrossCfg) is plain constants; the rest
+// is device code.
 #pragma once
 #include "cross_fft.h"
 
 namespace psdk {
 
+// The workgroup of a segment kernel as closed formulas of n (a power of two, 64 ... 4096): a team of n / 16 threads transforms a
+// segment, a workgroup is as many teams as fill 128 threads (one team from n = 2048 up), and a tile gives every team one
+// segment pair.  The host side reads them too (cross_block_threads, *_segments_per_tile).
+constexpr bool seg_supported(int n) { return n >= 64 && n <= 4096 && (n & (n - 1)) == 0; }
+constexpr int seg_team(int n) { return n / 16; }
+constexpr int seg_block(int n) { return seg_team(n) > 128 ? seg_team(n) : 128; }
+constexpr int seg_teams(int n) { return seg_block(n) / seg_team(n); }
+constexpr int seg_spt(int n) { return 2 * seg_teams(n); } // fine tiles keep the workgroups of a launch even
+
 template <int N>
 struct CrossCfg {
     using Plan = FftPlan<N>;
     static constexpr int E = Plan::E;
-    static constexpr int TEAM = Plan::TEAM;
-    static constexpr int BLOCK = TEAM > 128 ? TEAM : 128;
-    static constexpr int TEAMS = BLOCK / TEAM;
-    static constexpr int SPT = 2 * TEAMS; // segments per tile: one pair a team (fine tiles keep the workgroups of a launch even)
+    static constexpr int TEAM = seg_team(N);
+    static constexpr int BLOCK = seg_block(N);
+    static constexpr int TEAMS = seg_teams(N);
+    static constexpr int SPT = seg_spt(N); // segments per tile: one pair a team
     static constexpr int WAVES = BLOCK / 64;
     static constexpr int H = N / 2 + 1;
     static constexpr int FRAME = LdsFrame<N>::SIZE;
-    static_assert(E == 16, "cross kernel: sixteen elements a thread");
+    static_assert(E == 16 && TEAM == Plan::TEAM, "cross kernel: sixteen elements a thread");
     static_assert(H <= FRAME, "partial rows reuse the frames' LDS");
 };
+static_assert(CrossCfg<64>::TEAMS == 32 && CrossCfg<128>::TEAMS == 16 && CrossCfg<256>::TEAMS == 8 && CrossCfg<512>::TEAMS == 4 &&
+                  CrossCfg<1024>::TEAMS == 2 && CrossCfg<2048>::TEAMS == 1 && CrossCfg<4096>::TEAMS == 1 && CrossCfg<4096>::BLOCK == 256,
+              "the seven sizes: 128 threads a workgroup, one team of 256 at n = 4096");
 
+#ifdef __HIPCC__
 template <class Job>
 __device__ __forceinline__ float cross_amp(const Job &job, int step)
 {
@@ -174,5 +188,6 @@ __device__ __forceinline__ void cross_channel(const float *__restrict__ src, lon
         store_natural<N>(t, v, frame);
     }
 }
+#endif // __HIPCC__
 
 } // namespace psdk

@@ -15,7 +15,7 @@
 // tile (frames complete / frames free) in place of the pair kernel's wavefront-local ones.
 // The fold, the stream tails and the decimator are the pair object's kernels (cross.hip, kernels.hip).
 #include "csm.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 #include "csm_fft.h"
 
 namespace psdk {
@@ -31,9 +31,8 @@ __global__ __launch_bounds__((CsmShape<N, M>::BLOCK)) void csm_kernel(const CsmB
     __shared__ cf frames[TEAMS * M * FRAME];
     __shared__ float red[(BLOCK / 64) * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CsmJob &j) { return j.block_begin; });
-    const CsmJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CsmJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     const int pg = threadIdx.x / GS;
@@ -43,29 +42,21 @@ __global__ __launch_bounds__((CsmShape<N, M>::BLOCK)) void csm_kernel(const CsmB
     const int detrend = batch.detrend;
 
     float acc[XB][ROWS];
-#pragma unroll
-    for (int r = 0; r < XB; ++r)
-#pragma unroll
-        for (int c = 0; c < ROWS; ++c)
-            acc[r][c] = 0.0f;
+    zero_rows(acc);
 
-    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) {
+    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment pair a team
         const int seg_lo = lt * SPT;
         const int seg_hi = min(job.nseg, seg_lo + SPT);
-        const int la = seg_lo + 2 * team;
-        const bool act_a = la < seg_hi, act_b = la + 1 < seg_hi;
-        // lanes without a segment read the job's first one (always inside the stream) and drop it
-        const long long ofs_safe = job.seg0 * (long long)hop - job.src_base;
-        const long long ofs_a = (job.seg0 + la) * (long long)hop - job.src_base;
-        const long long ofs_la = act_a ? ofs_a : ofs_safe, ofs_lb = act_b ? ofs_a + hop : ofs_safe;
+        const SegPair sp = seg_pair(job, hop, seg_hi, seg_lo + 2 * team);
         float ampa = 1.0f, ampb = 1.0f;
         if (job.ewma) {
-            ampa = cross_amp(job, job.step0 + la);
-            ampb = cross_amp(job, job.step0 + la + 1);
+            ampa = cross_amp(job, job.step0 + sp.seg);
+            ampb = cross_amp(job, job.step0 + sp.seg + 1);
         }
 #pragma unroll
         for (int c = 0; c < M; ++c)
-            cross_channel<N>(job.src[c], ofs_la, ofs_lb, act_a, act_b, detrend, ampa, ampb, t, team, fteam + c * FRAME, red, win, tw);
+            cross_channel<N>(job.src[c], sp.ofs_a, sp.ofs_b, sp.act_a, sp.act_b, detrend, ampa, ampb, t, team, fteam + c * FRAME, red,
+                             win, tw);
         __syncthreads(); // every team's frames stand
         for (int g = pg; g < TEAMS; g += PG) { // fixed order: the same calls give the same bits
             const int lg = seg_lo + 2 * g;
@@ -93,24 +84,8 @@ __global__ __launch_bounds__((CsmShape<N, M>::BLOCK)) void csm_kernel(const CsmB
                 for (int c = 0; c < ROWS; ++c)
                     out[c * H + k] = acc[r][c];
         }
-    } else { // combine the product groups (fixed order) through the frames' LDS
-        float *fq = reinterpret_cast<float *>(frames);
-#pragma unroll
-        for (int r = 0; r < XB; ++r) {
-            const int k = pt + GS * r;
-            if (k < H)
-#pragma unroll
-                for (int c = 0; c < ROWS; ++c)
-                    fq[(pg * ROWS + c) * H + k] = acc[r][c];
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < ROWS * H; e += BLOCK) {
-            float s = 0.0f;
-#pragma unroll
-            for (int g = 0; g < PG; ++g)
-                s += fq[g * ROWS * H + e];
-            out[e] = s;
-        }
+    } else { // combine the product groups (fixed order) through the frames' LDS, as the other kernels combine their teams
+        seg_combine<OwnedCombine<H, ROWS, ROWS, PG, GS>, BLOCK>(frames, pg, pt, acc, out);
     }
 }
 

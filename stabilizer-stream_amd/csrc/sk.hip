@@ -8,7 +8,7 @@
 // Fold and stream tails are cross_post_kernel with nrows = 2 (cross.hip), the /8 decimator is hbf_dec8_kernel (kernels.hip),
 // one job a channel.  One frame a team: half the LDS of cross_kernel<N>.
 #include "sk.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 #include "sk_fft.h"
 
 namespace psdk {
@@ -25,9 +25,8 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void sk_kernel(const CrossBatch
     __shared__ cf frames[TEAMS * Cfg::FRAME];
     __shared__ float red[Cfg::WAVES * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CrossJob &j) { return j.block_begin; });
-    const CrossJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CrossJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     cf *frame = frames + team * Cfg::FRAME;
@@ -35,81 +34,35 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void sk_kernel(const CrossBatch
     const int detrend = batch.detrend;
 
     float acc[XB][SK_ROWS];
-#pragma unroll
-    for (int r = 0; r < XB; ++r)
-#pragma unroll
-        for (int c = 0; c < SK_ROWS; ++c)
-            acc[r][c] = 0.0f;
+    zero_rows(acc);
 
     for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment pair a team
         const int seg_lo = lt * SPT;
-        const int seg_hi = min(job.nseg, seg_lo + SPT);
-        const int la = seg_lo + 2 * team;
-        const bool act_a = la < seg_hi, act_b = la + 1 < seg_hi;
-        // lanes without a segment read the job's first one (always inside the stream) and drop it
-        const long long ofs_safe = job.seg0 * (long long)hop - job.src_base;
-        const long long ofs_a = (job.seg0 + la) * (long long)hop - job.src_base;
-        const long long ofs_la = act_a ? ofs_a : ofs_safe, ofs_lb = act_b ? ofs_a + hop : ofs_safe;
+        const SegPair sp = seg_pair(job, hop, min(job.nseg, seg_lo + SPT), seg_lo + 2 * team);
         float wa = 1.0f, wbw = 1.0f;
         if (job.ewma) {
-            wa = sk_weight(job, job.step0 + la);
-            wbw = sk_weight(job, job.step0 + la + 1);
+            wa = sk_weight(job, job.step0 + sp.seg);
+            wbw = sk_weight(job, job.step0 + sp.seg + 1);
         }
-        cross_channel<N>(job.src[0], ofs_la, ofs_lb, act_a, act_b, detrend, 1.0f, 1.0f, t, team, frame, red, win, tw);
+        cross_channel<N>(job.src[0], sp.ofs_a, sp.ofs_b, sp.act_a, sp.act_b, detrend, 1.0f, 1.0f, t, team, frame, red, win, tw);
         xteam_sync<TEAM>();
 #pragma unroll
         for (int r = 0; r < XB; ++r) {
             const int k = t + TEAM * r;
             if (k < H)
-                sk_bin<N>(k, frame, wa, wbw, act_b, acc[r]);
+                sk_bin<N>(k, frame, wa, wbw, sp.act_b, acc[r]);
         }
     }
 
-    // combine the teams (fixed order) and write the workgroup's partial rows
-    float *fq = reinterpret_cast<float *>(frames);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < XB; ++r) {
-        const int k = t + TEAM * r;
-        if (k < H)
-#pragma unroll
-            for (int c = 0; c < SK_ROWS; ++c)
-                fq[team * SK_ROWS * H + sk_row_at<N>(c, k)] = acc[r][c];
-    }
-    __syncthreads();
-    float *out = job.partial + (size_t)wb * SK_ROWS * H;
-    for (int e = threadIdx.x; e < SK_ROWS * H; e += Cfg::BLOCK) {
-        float s = 0.0f;
-#pragma unroll
-        for (int g = 0; g < TEAMS; ++g)
-            s += fq[g * SK_ROWS * H + e];
-        out[e] = s;
-    }
+    // combine the teams (fixed order) and write the workgroup's partial rows: element sk_row_at<N>(row, k)
+    combine_owned<N, SK_ROWS, SK_ROWS>(frames, team, t, acc, job.partial + (size_t)wb * SK_ROWS * H);
 }
 
 int sk_segments_per_tile(int n) { return cross_segments_per_tile(n); }
 
 hipError_t launch_sk(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s)
 {
-    if (b.nblocks <= 0)
-        return hipSuccess;
-    switch (n) {
-#define PSDK_CASE(NN)                                                                                                   \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL(sk_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw);            \
-        break;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return seg_launch(n, b, win, tw, s, [](auto N) { return sk_kernel<decltype(N)::value>; });
 }
 
 } // namespace psdk

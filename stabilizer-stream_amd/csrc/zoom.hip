@@ -11,7 +11,7 @@
 // Fold and stream tails are cross_post_kernel with nrows = 2 (cross.hip), the /8 decimator is hbf_dec8_kernel (kernels.hip),
 // one job for I and one for Q.
 #include "zoom.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 #include "zoom_lo.h"
 
 namespace psdk {
@@ -27,45 +27,26 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_kernel(const CrossBat
     __shared__ cf frames[TEAMS * Cfg::FRAME];
     __shared__ float red[Cfg::WAVES * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CrossJob &j) { return j.block_begin; });
-    const CrossJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CrossJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     cf *frame = frames + team * Cfg::FRAME;
     const int hop = batch.hop;
     const int detrend = batch.detrend;
 
-    float acc[E];
-#pragma unroll
-    for (int s = 0; s < E; ++s)
-        acc[s] = 0.0f;
+    float acc[1][E];
+    zero_rows(acc);
 
     for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment a team
-        const int seg = lt * TEAMS + team;
-        const bool act = seg < job.nseg;
-        // a team without a segment reads the job's first one (always inside the stream) and drops it
-        const long long ofs = (job.seg0 + (act ? seg : 0)) * (long long)hop - job.src_base;
-        const float amp = job.ewma ? cross_amp(job, job.step0 + seg) : 1.0f;
-        cross_channel<N, true>(job.src[0], ofs, ofs, act, act, detrend, amp, amp, t, team, frame, red, win, tw, job.src[1], acc);
+        const OneSeg sg = one_seg<TEAMS>(job, hop, lt, team);
+        const float amp = job.ewma ? cross_amp(job, job.step0 + sg.seg) : 1.0f;
+        cross_channel<N, true>(job.src[0], sg.ofs, sg.ofs, sg.act, sg.act, detrend, amp, amp, t, team, frame, red, win, tw, job.src[1],
+                               acc[0]);
     }
 
     // the teams' rows through the frames' LDS in bin order, then combined in a fixed order into the two partial rows
-    float *fq = reinterpret_cast<float *>(frames);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < E; ++s)
-        fq[team * N + freq_of_slot<N>(t, s)] = acc[s];
-    __syncthreads();
-    float *out = job.partial + (size_t)wb * 2 * H;
-    for (int e = threadIdx.x; e < 2 * H; e += Cfg::BLOCK) {
-        const int k = e < H ? e : (N - (e - H)) & (N - 1);
-        float s = 0.0f;
-#pragma unroll
-        for (int g = 0; g < TEAMS; ++g)
-            s += fq[g * N + k];
-        out[e] = s;
-    }
+    combine_slots<N, 1, 1>(frames, team, t, acc, job.partial + (size_t)wb * 2 * H);
 }
 
 // A thread takes MIX_Q consecutive samples that start on a 16-byte boundary of the destination streams: one 16-byte store to
@@ -104,31 +85,13 @@ __global__ __launch_bounds__(MIX_BLOCK) void zoom_mix_kernel(const ZoomMixJob jo
         zoom_mix(job.x[i], ph, job.dst_i[i], job.dst_q[i]);
 }
 
-int zoom_segments_per_tile(int n) { return cross_supported(n) ? cross_block_threads(n) / (n / 16) : 0; }
+int zoom_segments_per_tile(int n) { return seg_supported(n) ? seg_teams(n) : 0; }
 
 int zoom_block_threads(int n) { return cross_block_threads(n); }
 
 hipError_t launch_zoom(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s)
 {
-    if (b.nblocks <= 0)
-        return hipSuccess;
-    switch (n) {
-#define PSDK_CASE(NN)                                                                                                   \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL(zoom_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw);          \
-        break;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return seg_launch(n, b, win, tw, s, [](auto N) { return zoom_kernel<decltype(N)::value>; });
 }
 
 hipError_t launch_zoom_mix(const ZoomMixJob &j, hipStream_t s)

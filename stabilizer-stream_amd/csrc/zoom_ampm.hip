@@ -12,7 +12,7 @@
 // The LDS is zoom_kernel<N>'s.  Mixers are zoom_mix_kernel (zoom.hip) and iq_mix_kernel (iq.hip), fold and stream tails
 // cross_post_kernel with nrows = 4 (cross.hip), the /8 decimator hbf_dec8_kernel (kernels.hip), one job for I and one for Q.
 #include "zoom_ampm.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 #include "zoom_ampm_fft.h"
 
 namespace psdk {
@@ -29,9 +29,8 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_kernel(const Cro
     __shared__ cf frames[TEAMS * Cfg::FRAME];
     __shared__ float red[Cfg::WAVES * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CrossJob &j) { return j.block_begin; });
-    const CrossJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CrossJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     cf *frame = frames + team * Cfg::FRAME;
@@ -39,21 +38,14 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_kernel(const Cro
     const int detrend = batch.detrend;
 
     float acc[XB][ZAMPM_ROWS];
-#pragma unroll
-    for (int r = 0; r < XB; ++r)
-#pragma unroll
-        for (int c = 0; c < ZAMPM_ROWS; ++c)
-            acc[r][c] = 0.0f;
+    zero_rows(acc);
 
-    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment a team
-        const int seg = lt * TEAMS + team;
-        const bool act = seg < job.nseg;
-        // a team without a segment reads the job's first one (always inside the stream) and drops it: its bins are zeros
-        const long long ofs = (job.seg0 + (act ? seg : 0)) * (long long)hop - job.src_base;
-        const float amp = job.ewma ? cross_amp(job, job.step0 + seg) : 1.0f;
+    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment a team (an idle team's bins are zeros)
+        const OneSeg sg = one_seg<TEAMS>(job, hop, lt, team);
+        const float amp = job.ewma ? cross_amp(job, job.step0 + sg.seg) : 1.0f;
         cf z[E];
-        cross_channel<N, true, true>(job.src[0], ofs, ofs, act, act, detrend, amp, amp, t, team, frame, red, win, tw, job.src[1],
-                                     nullptr, z);
+        cross_channel<N, true, true>(job.src[0], sg.ofs, sg.ofs, sg.act, sg.act, detrend, amp, amp, t, team, frame, red, win, tw,
+                                     job.src[1], nullptr, z);
         // the team is past the last pass's reads of the frame (xfft_run ends on a team sync); the next segment's pass 0 waits
         // for the readers below
         store_natural<N>(t, z, frame);
@@ -67,51 +59,12 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_kernel(const Cro
     }
 
     // the teams' values through the frames' LDS, rows 2 p and 2 p + 1 in turn p, then combined in a fixed order
-    float *fq = reinterpret_cast<float *>(frames);
-    float *out = job.partial + (size_t)wb * ZAMPM_ROWS * H;
-#pragma unroll
-    for (int p = 0; p < ZAMPM_ROWS / 2; ++p) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < XB; ++r) {
-            const int k = t + TEAM * r;
-            if (k < H) {
-                fq[(team * 2 + 0) * H + k] = acc[r][2 * p];
-                fq[(team * 2 + 1) * H + k] = acc[r][2 * p + 1];
-            }
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < 2 * H; e += Cfg::BLOCK) {
-            float s = 0.0f;
-#pragma unroll
-            for (int g = 0; g < TEAMS; ++g)
-                s += fq[g * 2 * H + e];
-            out[2 * p * H + e] = s;
-        }
-    }
+    combine_owned<N, ZAMPM_ROWS, 2>(frames, team, t, acc, job.partial + (size_t)wb * ZAMPM_ROWS * H);
 }
 
 hipError_t launch_zoom_ampm(int n, const CrossBatch &b, const float *win, const cf *tw, hipStream_t s)
 {
-    if (b.nblocks <= 0)
-        return hipSuccess;
-    switch (n) {
-#define PSDK_CASE(NN)                                                                                                   \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL(zoom_ampm_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw);     \
-        break;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return seg_launch(n, b, win, tw, s, [](auto N) { return zoom_ampm_kernel<decltype(N)::value>; });
 }
 
 } // namespace psdk

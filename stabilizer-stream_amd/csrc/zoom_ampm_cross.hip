@@ -16,7 +16,7 @@
 // The launcher is reached through launch_zoom_cross (zoom_cross.hip) on CsmBatch::variant; mixers, the fold and stream tails
 // (cross_post_kernel with nrows = 12) and the /8 decimator are the zoom cross / IQ cross objects'.
 #include "zoom_ampm_cross.h"
-#include "cross_channel.h"
+#include "segment_kernel.h"
 #include "zoom_ampm_cross_fft.h"
 
 namespace psdk {
@@ -34,9 +34,8 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_cross_kernel(con
     __shared__ cf frames[TEAMS * 2 * Cfg::FRAME];
     __shared__ float red[Cfg::WAVES * 2];
 
-    const int ji = job_of_unit(batch, (int)blockIdx.x, [](const CsmJob &j) { return j.block_begin; });
-    const CsmJob &job = batch.jobs[ji];
-    const int wb = blockIdx.x - job.block_begin;
+    int wb;
+    const CsmJob &job = seg_job(batch, wb);
     const int team = threadIdx.x / TEAM;
     const int t = threadIdx.x % TEAM;
     cf *fa = frames + team * 2 * Cfg::FRAME;
@@ -45,30 +44,23 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_cross_kernel(con
     const int detrend = batch.detrend;
 
     float acc[XB][ZXAMPM_ROWS];
-#pragma unroll
-    for (int r = 0; r < XB; ++r)
-#pragma unroll
-        for (int c = 0; c < ZXAMPM_ROWS; ++c)
-            acc[r][c] = 0.0f;
+    zero_rows(acc);
 
-    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment a team
-        const int seg = lt * TEAMS + team;
-        const bool act = seg < job.nseg;
-        // a team without a segment reads the job's first one (always inside the streams) and drops it: its bins are zeros
-        const long long ofs = (job.seg0 + (act ? seg : 0)) * (long long)hop - job.src_base;
-        const float amp = job.ewma ? cross_amp(job, job.step0 + seg) : 1.0f;
+    for (int lt = wb; lt < job.ntiles; lt += job.nblocks) { // a tile: one segment a team (an idle team's bins are zeros)
+        const OneSeg sg = one_seg<TEAMS>(job, hop, lt, team);
+        const float amp = job.ewma ? cross_amp(job, job.step0 + sg.seg) : 1.0f;
         {
             cf z[E];
-            cross_channel<N, true, true>(job.src[0], ofs, ofs, act, act, detrend, amp, amp, t, team, fa, red, win, tw, job.src[1],
-                                         nullptr, z);
+            cross_channel<N, true, true>(job.src[0], sg.ofs, sg.ofs, sg.act, sg.act, detrend, amp, amp, t, team, fa, red, win, tw,
+                                         job.src[1], nullptr, z);
             // the team is past the last pass's reads of frame A (xfft_run ends on a team sync)
             store_natural<N>(t, z, fa);
         }
         {
             cf z[E];
             // (pass 0 of this transform waits for the readers of frame B below, as the next segment's waits for those of frame A)
-            cross_channel<N, true, true>(job.src[2], ofs, ofs, act, act, detrend, amp, amp, t, team, fb, red, win, tw, job.src[3],
-                                         nullptr, z);
+            cross_channel<N, true, true>(job.src[2], sg.ofs, sg.ofs, sg.act, sg.act, detrend, amp, amp, t, team, fb, red, win, tw,
+                                         job.src[3], nullptr, z);
             store_natural<N>(t, z, fb);
         }
         xteam_sync<TEAM>();
@@ -81,51 +73,12 @@ __global__ __launch_bounds__(CrossCfg<N>::BLOCK) void zoom_ampm_cross_kernel(con
     }
 
     // the teams' values through the frames' LDS, rows ZXAMPM_TURN p ... ZXAMPM_TURN p + 3 in turn p, then combined in a fixed order
-    float *fq = reinterpret_cast<float *>(frames);
-    float *out = job.partial + (size_t)wb * ZXAMPM_ROWS * H;
-#pragma unroll
-    for (int p = 0; p < ZXAMPM_ROWS / ZXAMPM_TURN; ++p) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < XB; ++r) {
-            const int k = t + TEAM * r;
-            if (k < H)
-#pragma unroll
-                for (int c = 0; c < ZXAMPM_TURN; ++c)
-                    fq[(team * ZXAMPM_TURN + c) * H + k] = acc[r][ZXAMPM_TURN * p + c];
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < ZXAMPM_TURN * H; e += Cfg::BLOCK) {
-            float s = 0.0f;
-#pragma unroll
-            for (int g = 0; g < TEAMS; ++g)
-                s += fq[g * ZXAMPM_TURN * H + e];
-            out[ZXAMPM_TURN * p * H + e] = s;
-        }
-    }
+    combine_owned<N, ZXAMPM_ROWS, ZXAMPM_TURN>(frames, team, t, acc, job.partial + (size_t)wb * ZXAMPM_ROWS * H);
 }
 
 hipError_t launch_zoom_ampm_cross(int n, const CsmBatch &b, const float *win, const cf *tw, hipStream_t s)
 {
-    if (b.nblocks <= 0)
-        return hipSuccess;
-    switch (n) {
-#define PSDK_CASE(NN)                                                                                                        \
-    case NN:                                                                                                                 \
-        hipLaunchKernelGGL(zoom_ampm_cross_kernel<NN>, dim3(b.nblocks), dim3(CrossCfg<NN>::BLOCK), 0, s, b, win, tw);    \
-        break;
-        PSDK_CASE(64)
-        PSDK_CASE(128)
-        PSDK_CASE(256)
-        PSDK_CASE(512)
-        PSDK_CASE(1024)
-        PSDK_CASE(2048)
-        PSDK_CASE(4096)
-#undef PSDK_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return seg_launch(n, b, win, tw, s, [](auto N) { return zoom_ampm_cross_kernel<decltype(N)::value>; });
 }
 
 } // namespace psdk

@@ -7,6 +7,7 @@
 // or at f0 - (N - j) / N, and the row layout below only says where bin j is read out.
 // Row layout of a workgroup partial and of a stage's accumulators, eight rows of N/2 + 1 (include/psdcascade.h):
 //     row 2 q + 0 (upper): bin k,    row 2 q + 1 (lower): bin (N - k) mod N, not conjugated;    q = 0 S_aa, 1 S_bb, 2 Re S_ab, 3 Im S_ab
+// (two_sided_bin, two_sided_value of segment_kernel.h; q is acc's index below)
 //
 // Everything here is __host__ __device__: tests/host/zoom_cross_emul.cpp runs it against an f64 DFT.
 #pragma once
@@ -26,15 +27,5 @@ PSDK_HD void zoom_cross_bin(cf za, cf zb, float *acc, int stride)
     acc[2 * stride] += za.re * zb.re + za.im * zb.im;
     acc[3 * stride] += za.re * zb.im - za.im * zb.re;
 }
-
-// the transform bin that row `row` (0 ... 7) shows at index k (0 ... N/2)
-template <int N>
-PSDK_HD int zoom_cross_row_bin(int row, int k)
-{
-    return (row & 1) ? (N - k) & (N - 1) : k;
-}
-
-// the value (0 ... 3, as acc above) row `row` belongs to
-PSDK_HD int zoom_cross_row_value(int row) { return row >> 1; }
 
 } // namespace psdk

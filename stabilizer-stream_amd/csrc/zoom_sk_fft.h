@@ -9,7 +9,7 @@
 // noise reads SK = 1 at offset 0 and at Nyquist as well -- the "2 at the real-valued bins" of the real object does not occur.
 // Row layout of a workgroup partial and of a stage's accumulators, four rows of N/2 + 1 (include/psdcascade.h):
 //     row 2 q + 0 (upper): bin k,    row 2 q + 1 (lower): bin (N - k) mod N;    q = 0 S1 = sum w P, 1 S2 = sum w P^2
-// so rows 0 and 1 are zoom_kernel's upper and lower.
+// so rows 0 and 1 are zoom_kernel's upper and lower (two_sided_bin, two_sided_value of segment_kernel.h).
 // Range: a workgroup's partial rows are f32, so the sum of P^2 over its segments must stay below f32 max.
 //
 // Everything here is __host__ __device__: tests/host/zoom_sk_emul.cpp runs it lane by lane against an f64 DFT.
@@ -29,15 +29,5 @@ PSDK_HD void zoom_sk_slot(cf z, float w, float &a1, float &a2)
     a1 += wp;
     a2 += wp * p;
 }
-
-// the transform bin that row `row` (0 ... 3) shows at index k (0 ... N/2)
-template <int N>
-PSDK_HD int zoom_sk_row_bin(int row, int k)
-{
-    return (row & 1) ? (N - k) & (N - 1) : k;
-}
-
-// the moment (0: S1, 1: S2) row `row` belongs to
-PSDK_HD int zoom_sk_row_moment(int row) { return row >> 1; }
 
 } // namespace psdk

@@ -2,7 +2,7 @@
 // transform of cross_fft.h leaves (no natural-order store, as the kernel), against a direct f64 DFT of the same complex inputs,
 // for N = 64 and 1024.  Two channels of random complex samples, channel b = 0.6 a + noise at another scale, so S_ab is neither
 // 0 nor sqrt(S_aa S_bb).  Each of the four values of every bin j = 0 ... N - 1 is compared with the f64 product, and the eight
-// rows are then read through zoom_cross_row_bin / zoom_cross_row_value and compared with the row table of include/psdcascade.h
+// rows are then read through two_sided_bin / two_sided_value (segment_kernel.h) and compared with the row table of include/psdcascade.h
 // written out here: S_aa, S_bb, Re S_ab, Im S_ab, each upper (bin k) and lower (bin (N - k) mod N, not conjugated).
 //
 // Bound.  With eps = 2^-23 and R_a, R_b the rms of |Z_a|, |Z_b| over the bins (what an averaged S_aa, S_bb of this input reads:
@@ -12,6 +12,7 @@
 // give 2 x 3 eps sqrt(log2 N) R x 4 R = 24 sqrt(log2 N) eps R_a R_b: 76 eps at N = 1024.  Asserted: 8 log2 N eps R_a R_b
 // (48 eps at N = 64, 80 eps at N = 1024) for every value; the auto values use R_a R_a and R_b R_b.
 // Build: g++ -O2 -std=c++17 -I<csrc> zoom_cross_emul.cpp (tests/test_zoom_cross_host.py does).
+#include "segment_kernel.h"
 #include "zoom_cross_fft.h"
 
 #include <algorithm>
@@ -112,7 +113,7 @@ static bool check(std::mt19937_64 &rng, double scale_b)
     bool rows_ok = true;
     for (int row = 0; row < ZCROSS_ROWS; ++row)
         for (int k = 0; k < H; ++k) {
-            const float got = val[(size_t)zoom_cross_row_value(row) * N + zoom_cross_row_bin<N>(row, k)];
+            const float got = val[(size_t)two_sided_value(row) * N + two_sided_bin<N>(row, k)];
             const int j = (row % 2 == 0) ? k : (N - k) % N; // upper: bin k; lower: bin N - k
             const int q = row / 2;                          // rows 0, 1 S_aa; 2, 3 S_bb; 4, 5 Re S_ab; 6, 7 Im S_ab
             rows_ok = rows_ok && got == val[(size_t)q * N + j];

@@ -10,6 +10,7 @@
 // segment's bins.
 // Build: g++ -O2 -std=c++17 -I<csrc> zoom_sk_emul.cpp (tests/test_zoom_sk_host.py does, and once more with
 // -fsanitize=address,undefined).
+#include "segment_kernel.h"
 #include "zoom_sk_fft.h"
 
 #include <algorithm>
@@ -109,8 +110,8 @@ static bool check(std::mt19937_64 &rng, float w, bool active, double scale, Wors
     std::vector<int> seen((size_t)ZSK_ROWS * H, 0), src((size_t)ZSK_ROWS * H, -1);
     for (int e = 0; e < ZSK_ROWS * H; ++e) {
         const int row = e / H;
-        const int k = zoom_sk_row_bin<N>(row, e - row * H);
-        const int q = zoom_sk_row_moment(row);
+        const int k = two_sided_bin<N>(row, e - row * H);
+        const int q = two_sided_value(row);
         if (k < 0 || k >= N || q < 0 || q >= ZSK_Q)
             return false;
         part[e] = fq[(size_t)q * N + k];
