@@ -1,18 +1,23 @@
 // Host check of stabilizer-stream_amd/csrc/segment_kernel.h: the skeleton the eight segment kernels share, off the GPU.
 //
-// Tile addressing.  For N = 64 (32 teams), 1024 (2 teams) and 4096 (one team of 256), nseg in {1, 2, SPT - 1, SPT, SPT + 1,
-// 3 SPT + 1} and nblocks in {1, 2, ntiles}, every (workgroup, tile, team) is walked as the kernels' loops walk them, through
-// seg_pair (cross, sk, csm) and through one_seg (the zoom kernels).  The segment a lane reads is taken from its OFFSET, not from
+// Tile addressing.  For every N = 64 ... 4096 in the shape of the team kernels (CrossCfg<N>: 32 ... 1 teams), and for every
+// (N, M) of csm_kernel in its own shape (CsmShape<N, M>: up to 64 teams), nseg in {1, 2, SPT - 1, SPT, SPT + 1, 3 SPT + 1} and
+// nblocks in {1, 2, ntiles}, every (workgroup, tile, team) is walked as the kernels' loops walk them, through seg_pair (cross, sk,
+// csm) and through one_seg (the zoom kernels).  The segment a lane reads is taken from its OFFSET, not from
 // the loop indices: every segment of the job must come exactly once, at (seg0 + j) hop - src_base, with the EWMA step step0 + j;
 // a lane without a segment must read N samples that start inside the job's first segment and end inside the job's span.
+// csm's product loop is walked beside it, thread by thread: every bin 0 ... N/2 of every team that holds a segment must be taken
+// by exactly one thread, with b_live as seg_pair says, and where there is one product group every partial element is stored once.
 //
-// Combine.  For each kernel's parameter set (the kernels' own constants; csm at every N with more than one product group) every
+// Combine.  For each kernel's parameter set at every size (the kernels' own constants; csm at every shape with more than one
+// product group) every
 // thread's accumulators hold a value that is a function of (group, row, bin) alone -- random mantissas over 24 binades, so an f32
 // sum depends on its order -- and accumulators of bins a thread does not own hold NaN.  Turn by turn, on an array of the size of
 // the kernel's LDS with guards around it and NaN inside it, every thread runs the store phase, then every partial element the sum
 // phase: each [row][k], k <= N/2, must be written exactly once with the groups' values of that (row, bin) summed in ascending
 // group order, the two-sided rows reading bin (N - k) mod N in their odd rows; the guards must stay as they were.
 //
+// `--shapes` prints the workgroup shape of every instance instead (tests/test_segment_instances_host.py holds its table to it).
 // -DSEGK_SEED=1 / 2 seeds one mistake into the way THIS program calls the header (1: a lane without a segment takes its offset
 // from the previous job's base; 2: the sum phase is always handed turn 0) and the program must then fail: tests/test_segment_kernel_host.py
 // builds both, beside the plain build and one with -fsanitize=address,undefined.
@@ -93,18 +98,16 @@ struct Walk {
     }
 };
 
-template <int N>
-static void check_addressing(long long &lanes, long long &idle)
+// TEAMS teams a workgroup, SPT segments a pair tile; zoom: walk the one-segment form beside the pair form (the team kernels' shape)
+template <int N, int TEAMS, int SPT>
+static void walk_addressing(bool zoom, long long &lanes, long long &idle)
 {
-    using Cfg = CrossCfg<N>;
-    constexpr int TEAMS = Cfg::TEAMS, SPT = Cfg::SPT;
-    static_assert(TEAMS == seg_teams(N) && SPT == seg_spt(N) && Cfg::BLOCK == seg_block(N) && Cfg::TEAM == seg_team(N), "one shape");
     const int hop = N / 2 + 3; // no multiple of anything
     const Job prev = {1000, 40, 9, 1, 1, 3};
     for (int nseg : {1, 2, SPT - 1, SPT, SPT + 1, 3 * SPT + 1}) {
         if (nseg < 1)
             continue;
-        for (int form = 0; form < 2; ++form) {
+        for (int form = 0; form < (zoom ? 2 : 1); ++form) {
             const int per_tile = form == 0 ? SPT : TEAMS;
             const int ntiles = (nseg + per_tile - 1) / per_tile;
             for (int nblocks : {1, 2, ntiles}) {
@@ -146,6 +149,14 @@ static void check_addressing(long long &lanes, long long &idle)
             }
         }
     }
+}
+
+template <int N>
+static void check_addressing(long long &lanes, long long &idle)
+{
+    using Cfg = CrossCfg<N>;
+    static_assert(Cfg::TEAMS == seg_teams(N) && Cfg::SPT == seg_spt(N) && Cfg::BLOCK == seg_block(N) && Cfg::TEAM == seg_team(N), "one shape");
+    walk_addressing<N, Cfg::TEAMS, Cfg::SPT>(true, lanes, idle);
 }
 
 // ---- combine ---------------------------------------------------------------------------------------------------------------------
@@ -278,35 +289,84 @@ static void check_combines()
                 fail("sk_row_at N=%d", N);
 }
 
+// csm_kernel<N, M>: its tiles, its product loop thread by thread (csm.hip: thread pt of product group pg takes the bins
+// pt + GS r of the teams pg, pg + PG, ... that hold a segment), and the combine of its product groups where it has more than one
 template <int N, int M>
-static void check_csm()
+static int check_csm(long long &lanes, long long &idle)
 {
     using S = CsmShape<N, M>;
-    static_assert(S::PG > 1, "the shapes that combine product groups");
-    check_owned<S::H, S::ROWS, S::ROWS, S::PG, S::GS>(M == 2 ? "csm m=2" : M == 3 ? "csm m=3" : "csm m=4", N, S::TEAMS * M * S::FRAME * 2);
+    static_assert(S::TEAM == seg_team(N) && S::TEAMS * S::TEAM == S::BLOCK && S::PG * S::GS == S::BLOCK, "whole teams, whole groups");
+    char name[32];
+    snprintf(name, sizeof name, "csm m=%d", M);
+    walk_addressing<N, S::TEAMS, S::SPT>(false, lanes, idle);
+    for (int nseg : {1, 2, S::SPT - 1, S::SPT}) { // one tile: the teams with a segment, and the odd last one
+        std::vector<int> taken((size_t)S::TEAMS * S::H, 0);
+        const Job job = {0, 0, nseg, 1, 1, 0};
+        for (int tid = 0; tid < S::BLOCK; ++tid) {
+            const int pg = tid / S::GS, pt = tid % S::GS;
+            for (int g = pg; g < S::TEAMS; g += S::PG) {
+                const int lg = 2 * g;
+                if (lg >= nseg)
+                    break;
+                const SegPair sp = seg_pair(job, N / 2, nseg, 2 * g);
+                if (!sp.act_a || sp.act_b != (lg + 1 < nseg))
+                    fail("%s N=%d nseg=%d: the product loop and the tile disagree on team %d", name, N, nseg, g);
+                for (int r = 0; r < S::XB; ++r)
+                    if (pt + S::GS * r < S::H)
+                        ++taken[(size_t)g * S::H + pt + S::GS * r];
+            }
+        }
+        for (int g = 0; g < S::TEAMS; ++g)
+            for (int k = 0; k < S::H; ++k)
+                if (taken[(size_t)g * S::H + k] != (2 * g < nseg ? 1 : 0))
+                    fail("%s N=%d nseg=%d: bin %d of team %d taken %d times", name, N, nseg, k, g, taken[(size_t)g * S::H + k]);
+    }
+    if constexpr (S::PG > 1)
+        check_owned<S::H, S::ROWS, S::ROWS, S::PG, S::GS>(name, N, S::TEAMS * M * S::FRAME * 2);
+    return S::PG > 1;
 }
 
-int main()
+#define SEGK_SIZES(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
+#define SEGK_CSM(X) \
+    X(64, 2) X(64, 3) X(64, 4) X(128, 2) X(128, 3) X(128, 4) X(256, 2) X(256, 3) X(256, 4) X(512, 2) X(512, 3) X(512, 4) \
+    X(1024, 2) X(1024, 3) X(1024, 4) X(2048, 2) X(2048, 3) X(2048, 4) X(4096, 2) X(4096, 3)
+
+static void print_shapes()
 {
+#define X(NN) printf("team %d teams %d block %d\n", NN, seg_teams(NN), seg_block(NN));
+    SEGK_SIZES(X)
+#undef X
+#define X(NN, MM)                                                                                                          \
+    printf("csm %d %d block %d teams %d spt %d pg %d gs %d\n", NN, MM, CsmShape<NN, MM>::BLOCK, CsmShape<NN, MM>::TEAMS, \
+           CsmShape<NN, MM>::SPT, CsmShape<NN, MM>::PG, CsmShape<NN, MM>::GS);
+    SEGK_CSM(X)
+#undef X
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && !std::strcmp(argv[1], "--shapes")) {
+        print_shapes();
+        return 0;
+    }
     long long lanes = 0, idle = 0;
-    check_addressing<64>(lanes, idle);
-    check_addressing<1024>(lanes, idle);
-    check_addressing<4096>(lanes, idle);
+    int sizes = 0, shapes = 0, grouped = 0;
+#define X(NN) check_addressing<NN>(lanes, idle);
+    SEGK_SIZES(X)
+#undef X
+#define X(NN)             \
+    check_combines<NN>(); \
+    ++sizes;
+    SEGK_SIZES(X)
+#undef X
+#define X(NN, MM)                               \
+    grouped += check_csm<NN, MM>(lanes, idle); \
+    ++shapes;
+    SEGK_CSM(X)
+#undef X
     printf("addressing: %lld lanes walked, %lld without a segment\n", lanes, idle);
-    check_combines<64>();
-    check_combines<1024>();
-    check_combines<4096>();
-    check_csm<64, 2>();
-    check_csm<64, 3>();
-    check_csm<64, 4>();
-    check_csm<128, 2>();
-    check_csm<128, 3>();
-    check_csm<128, 4>();
-    check_csm<256, 2>();
-    check_csm<256, 3>();
-    check_csm<256, 4>();
-    static_assert(CsmShape<512, 2>::PG == 1 && CsmShape<4096, 3>::PG == 1, "no product groups to combine from N = 512 up");
-    printf("combine: 7 team kernels at N = 64, 1024, 4096 and csm at N = 64, 128, 256 with m = 2, 3, 4\n");
+    printf("combine: 7 team kernels at %d sizes, N = 64 ... 4096, and csm at %d shapes (N, M), %d of them with product groups\n", sizes,
+           shapes, grouped);
     if (g_fail) {
         printf("segment_kernel_check: %d failure(s)\n", g_fail);
         return 1;

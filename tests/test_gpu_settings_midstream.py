@@ -40,7 +40,7 @@ from test_zoom_sk_host import restate_zoom_sk
 pytestmark = pytest.mark.gpu
 
 F0 = (0.2345678901234567, 0.3141592653589793)  # carriers off the bin grid, as the parity cases of the zoom and IQ families have them
-CSM_M = 3
+CSM_M = 3  # the channels of a matrix unit in the walks of this file; a Case may say otherwise (tests/test_gpu_segment_instances.py)
 
 
 class Unit:
@@ -58,10 +58,11 @@ class Unit:
 class Case:
     """what the steps of one walk share: the window in its three spellings, the carriers, the units' streams behind the mixer"""
 
-    def __init__(self, pkg, ora, kind, n, wkind, emuls):
+    def __init__(self, pkg, ora, kind, n, wkind, emuls, m=CSM_M):
         self.pkg, self.ora, self.kind, self.n, self.wkind, self.emuls = pkg, ora, kind, n, wkind, emuls
+        self.m = m  # the channels of a matrix unit (csm alone reads it)
         self.pwin, self.owin = windows_of(pkg, n, wkind)
-        self.wt = pkg.WindowTable._kind(n, self.pwin)
+        self.wt = self.pwin if isinstance(self.pwin, pkg.WindowTable) else pkg.WindowTable._kind(n, self.pwin)  # (a caller's table)
         self.overlap = self.wt.overlap
         self.ftw = tuple(pkg.zoom_ftw(f)[0] for f in F0)
         self.mixed = {}
@@ -118,6 +119,9 @@ class Family:
     cls = None
     sides = 1          # streams a unit takes (complex kinds: complex streams)
     list_feed = False  # the matrix object takes its channels as one list
+
+    def sides_of(self, c):
+        return self.sides
 
     def make(self, c):
         return getattr(c.pkg, self.cls)(c.n, UNITS, window=c.pwin)
@@ -180,23 +184,28 @@ class Cross(Family):
 
 class Csm(Cross):
     cls = "CsmCascadeBank"
-    sides = CSM_M
+    sides = None  # the case's channel count
     list_feed = True
-    PAIRS = [(a, b) for a in range(CSM_M) for b in range(a + 1, CSM_M)]
+
+    def sides_of(self, c):
+        return c.m
+
+    def pairs(self, c):
+        return [(a, b) for a in range(c.m) for b in range(a + 1, c.m)]
 
     def make(self, c):
-        return c.pkg.CsmCascadeBank(c.n, CSM_M, UNITS, window=c.pwin)
+        return c.pkg.CsmCascadeBank(c.n, c.m, UNITS, window=c.pwin)
 
     def input(self, c, length, seed):
-        return channels(CSM_M, length, seed)
+        return channels(c.m, length, seed)
 
     def restate(self, c, u, planes, prec, sched):
-        return {p: restate(c.ora, planes[p[0]], planes[p[1]], c.n, c.owin, prec=prec, schedule=sched) for p in self.PAIRS}
+        return {p: restate(c.ora, planes[p[0]], planes[p[1]], c.n, c.owin, prec=prec, schedule=sched) for p in self.pairs(c)}
 
     def check(self, c, bank, u, sched, segs, planes, st64, st32, what):
         got = [bank.stage_spectra(u, k) for k in range(bank.num_stages(u))]
         S, br = bank.csd(u)
-        for a, b in self.PAIRS:
+        for a, b in self.pairs(c):
             exact([g[0] for g in got], st64[a, b], what)
             self.pair(c, sched, segs, [planes[a], planes[b]], st64[a, b], st32[a, b],
                       lambda k: (got[k][1][a, a].real, got[k][1][b, b].real, got[k][1][a, b]),
@@ -483,7 +492,7 @@ def test_settings_midstream(pkg, ora, gpu_required, emul, iq_emul, kind, n, seed
     walk = make_walk(kind, n, seed, wkind)
     totals = [unit_events(walk, u)[1] for u in range(UNITS)]
     planes = [fam.input(c, totals[u], 10 * seed + u) for u in range(UNITS)]
-    assert all(len(p) == fam.sides * (2 if complex_in else 1) and all(v.size == totals[u] for v in p) for u, p in enumerate(planes))
+    assert all(len(p) == fam.sides_of(c) * (2 if complex_in else 1) and all(v.size == totals[u] for v in p) for u, p in enumerate(planes))
     keep, ptrs = device_buffers(walk, planes, complex_in)
     bank = fam.make(c)
     fam.carriers(c, bank)

@@ -40,10 +40,10 @@ def run(exe):
 def passes(r):
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), (r.stdout + r.stderr)[-3000:]
     assert "FAIL" not in r.stdout
-    # both tile forms at the three sizes: lanes with and without a segment were walked
+    # both tile forms at the seven sizes and csm's tiles at its 20 shapes: lanes with and without a segment were walked
     lanes, idle = [int(v) for v in r.stdout.split("addressing: ")[1].split(" without")[0].replace(" lanes walked,", "").split()]
-    assert lanes > 3000 and 0 < idle < lanes
-    assert "7 team kernels at N = 64, 1024, 4096 and csm at N = 64, 128, 256 with m = 2, 3, 4" in r.stdout
+    assert lanes > 20000 and 0 < idle < lanes
+    assert "7 team kernels at 7 sizes, N = 64 ... 4096, and csm at 20 shapes (N, M), 9 of them with product groups" in r.stdout
 
 
 def test_segment_skeleton(segk_dir):
