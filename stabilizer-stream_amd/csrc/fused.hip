@@ -1313,27 +1313,24 @@ hipError_t launch_fused(int n, const FusedBatch &b, const float *win, const cf *
         return hipSuccess;
     // N = 2048 / 4096: the three-pass kernels (bigfused3_impl.h), unless the caller passes no seeds (PSDC_FFT3=0, A/B aid: the
     // four-pass kernels)
-    if (tw3g) {
-        if (n == 2048)
-            return launch_bigfused3_2048(b, win, tw3g, s, ea, eb);
-        if (n == 4096)
-            return launch_bigfused3_4096(b, win, tw3g, s, ea, eb);
-    }
-    switch (n) {
-    case 256:
-        return launch_fused_n<256>(b, win, s, ea, eb, aux);
-    case 512:
-        return launch_fused_n<512>(b, win, s, ea, eb, aux);
-    case 1024:
-        return launch_fused_n<1024>(b, win, s, ea, eb, aux);
-    case 2048:
-        return launch_bigfused_2048(b, win, tw0g, twag, s, ea, eb);
-    case 4096:
-        return launch_bigfused_4096(b, win, tw0g, twag, s, ea, eb);
-    case 8192:
-        return launch_bigfused_8192(b, win, tw0g, twag, s, ea, eb);
-    case 16384:
-        return launch_bigfused_16384(b, win, tw0g, twag, s, ea, eb);
+    switch (fused_family(n, tw3g != nullptr)) {
+    case FUSED_FAMILY_BIG3:
+        return n == 2048 ? launch_bigfused3_2048(b, win, tw3g, s, ea, eb) : launch_bigfused3_4096(b, win, tw3g, s, ea, eb);
+    case FUSED_FAMILY_TEAM:
+        return n == 256 ? launch_fused_n<256>(b, win, s, ea, eb, aux)
+               : n == 512 ? launch_fused_n<512>(b, win, s, ea, eb, aux)
+                          : launch_fused_n<1024>(b, win, s, ea, eb, aux);
+    case FUSED_FAMILY_BIG:
+        switch (n) {
+        case 2048:
+            return launch_bigfused_2048(b, win, tw0g, twag, s, ea, eb);
+        case 4096:
+            return launch_bigfused_4096(b, win, tw0g, twag, s, ea, eb);
+        case 8192:
+            return launch_bigfused_8192(b, win, tw0g, twag, s, ea, eb);
+        default:
+            return launch_bigfused_16384(b, win, tw0g, twag, s, ea, eb);
+        }
     default:
         return hipErrorInvalidValue;
     }

@@ -156,7 +156,7 @@ struct FusedBatch {
     // segment seg_a + i = samples src[N i + N/2 .. N i + 3N/2), transformed with a zero imaginary part: exactly the N samples the
     // pair decimates, as ever; src points HALF A SEGMENT IN FRONT of segment seg_a (that half chunk is read for the decimator's
     // history only), so the stream is consumed as with half-overlapped pairs (the SINGLE kernels).
-    // 2 (N <= 1024): as 1, but segments 2i and 2i + 1 share ONE transform (the two-for-one of two disjoint segments); every job
+    // 2 (every fused size: fused_double_supported): as 1, but segments 2i and 2i + 1 share ONE transform (the two-for-one of two disjoint segments); every job
     // then holds an even number of pairs and `run` is even
     int single;
     // frame jobs come first in the launch, four by four (the traces of one span, equal workgroup counts): group g
@@ -250,6 +250,31 @@ void fused_big_tables(int n, std::vector<cf> &tw0, std::vector<cf> &twa);
 // twiddle seeds of the three-pass kernels (N = 2048, 4096: fft_block3.h) [2][N/16]: W_N^tl, W_N^(4 tl); empty otherwise
 void fused_big3_table(int n, std::vector<cf> &tw3);
 // tw3g == nullptr: N = 2048 / 4096 on the four-pass kernels (PSDC_FFT3=0)
+// The kernel family a fused launch of size n goes to: the team kernels (fused_kernel, N <= 1024), the three-pass kernels
+// (bigfused3_kernel: N = 2048 / 4096 with their twiddle seeds) or the four-pass ones (bigfused_kernel).  launch_fused switches on it
+// and the PSDC_DBG_PLAN line of planner.cpp prints it, so the two cannot drift apart.
+enum FusedFamily { FUSED_FAMILY_NONE = 0, FUSED_FAMILY_TEAM, FUSED_FAMILY_BIG3, FUSED_FAMILY_BIG };
+inline FusedFamily fused_family(int n, bool have_tw3)
+{
+    switch (n) {
+    case 256:
+    case 512:
+    case 1024:
+        return FUSED_FAMILY_TEAM;
+    case 2048:
+    case 4096:
+        return have_tw3 ? FUSED_FAMILY_BIG3 : FUSED_FAMILY_BIG;
+    case 8192:
+    case 16384:
+        return FUSED_FAMILY_BIG;
+    default:
+        return FUSED_FAMILY_NONE;
+    }
+}
+inline const char *fused_family_name(FusedFamily f)
+{
+    return f == FUSED_FAMILY_TEAM ? "fused" : f == FUSED_FAMILY_BIG3 ? "bigfused3" : f == FUSED_FAMILY_BIG ? "bigfused" : "none";
+}
 // ev_a / ev_b (both or neither): events that receive the kernel's own start and stop times
 // (hipExtLaunchKernelGGL), for PSDC_OPT_PROFILE
 hipError_t launch_fused(int n, const FusedBatch &b, const float *win, const cf *tw0g, const cf *twag, const cf *tw3g,

@@ -673,6 +673,7 @@ int Round::launch(const FusedAux *aux)
         fb.detrend = h->detrend;
         fb.single = dbl ? 2 : single ? 1 : 0;
         FspanMap fm(fb.fspans);
+        const size_t first_job = i;
         for (; i < fjobs.size() && fb.njobs < (int)fused_jpl; ++i) {
             FusedJob j = fjobs[i].j;
             j.block_begin = fb.nblocks;
@@ -711,13 +712,24 @@ int Round::launch(const FusedAux *aux)
             ++fb.n_fgroups;
             a += 4;
         }
+        const cf *const tw3g = h->knobs.fft3 ? h->d_tw3g : nullptr; // (no seeds: N = 2048 / 4096 on the four-pass kernels)
         if (h->knobs.plan) { // (PSDC_DBG_PLAN, debugging aid: what each fused launch holds)
             long long np = 0;
             for (int q = 0; q < fb.njobs; ++q)
                 np += fb.jobs[q].npairs;
             fprintf(stderr, "fused launch: %d jobs, %d workgroups (+%d aux), %lld pairs:", fb.njobs, fb.nblocks, aux ? aux->nblocks : 0, np);
+            // per job: pairs / workgroups / run, `s` behind a seam prologue, then @<stage>.<step0> (the stage of the channel's cascade
+            // the job belongs to and the EWMA step of its first segment) and `f` for a job that reads frames
             for (int q = 0; q < fb.njobs; ++q)
-                fprintf(stderr, " %dp/%dwg/r%d%s", fb.jobs[q].npairs, fb.jobs[q].nblocks, fb.jobs[q].run, fb.jobs[q].pre_count ? "s" : "");
+                fprintf(stderr, " %dp/%dwg/r%d%s@%u.%d%s", fb.jobs[q].npairs, fb.jobs[q].nblocks, fb.jobs[q].run, fb.jobs[q].pre_count ? "s" : "",
+                        works[fjobs[first_job + (size_t)q].work].k, fb.jobs[q].step0, fb.jobs[q].fspan >= 0 ? "f" : "");
+            // the kernel the launch goes to, as launch_fused chooses it, and the workgroups of each four-trace frame group
+            fprintf(stderr, " | kernel %s n=%d detrend=%d ewma=%d frames=%d single=%d groups=[",
+                    fused_family_name(fused_family((int)h->n, tw3g != nullptr)), (int)h->n, fb.detrend, fb.any_ewma ? 1 : 0,
+                    fb.any_frames ? 1 : 0, fb.single);
+            for (int a = 0; a < fb.n_fgroups; ++a)
+                fprintf(stderr, "%s%d", a ? "," : "", fb.fg_nb[a]);
+            fprintf(stderr, "]");
             fprintf(stderr, "\n");
         }
         ProfEvents pe{};
@@ -726,7 +738,7 @@ int Round::launch(const FusedAux *aux)
             return rc;
         {
             HtScope ht_f(g_ht.fused);
-            HIPCHK(h, launch_fused((int)h->n, fb, h->d_win, h->d_tw0g, h->d_twag, h->knobs.fft3 ? h->d_tw3g : nullptr, h->stream, pe.a,
+            HIPCHK(h, launch_fused((int)h->n, fb, h->d_win, h->d_tw0g, h->d_twag, tw3g, h->stream, pe.a,
                                    pe.b, aux));
         }
         if ((rc = prof_end(pe, first, false)))
