@@ -40,7 +40,9 @@
 #include "waterfall.h"
 #include "waterfall_plan.h"
 #include "waterfall_read.h"
+#include "waterfall_robust.h"
 #include "host_runtime.h"
+#include "../../include/psdcascade_robust.h"
 
 #include <algorithm>
 #include <cmath>
@@ -62,6 +64,7 @@ hipError_t launch_iq_pair_mix_int(const SintPairMixJob &j, int kind, hipStream_t
 inline hipError_t launch_cvt_int(const SintCvtJob &, int, hipStream_t) { return hipErrorInvalidValue; }
 // (nor a waterfall read-out kernel: psdc_wf_image[_device] fail there with a device error)
 inline hipError_t launch_wf_image(const WfImageJob &, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_wf_robust(const WfRobustJob &, hipStream_t) { return hipErrorInvalidValue; } // (psdcx_*_robust[_device] too)
 } // namespace psdk
 #endif
 
@@ -3392,6 +3395,74 @@ int wf_image_impl(XObj *h, uint32_t channel, uint32_t stage, uint32_t max_rows, 
     return PSDC_OK;
 }
 
+// median / min / max / excised: [sides][n/2 + 1] f32 and kept: the same in u32, over the newest min(max_rows, complete blocks,
+// 4096) complete blocks through wf_robust_kernel (include/psdcascade_robust.h); device: the five are device memory, else host arrays
+// filled through a device buffer of the call's own
+int wf_robust_impl(XObj *h, uint32_t channel, uint32_t stage, uint32_t max_rows, double sk_lo, double sk_hi, float *median, float *mn,
+                   float *mx, float *excised, uint32_t *kept, bool device, psdcx_robust_info *info, const char *who)
+{
+    X_HANDLE(h, who);
+    if (!info)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null info (it is always written)");
+    if (!median && !mn && !mx && !excised && !kept)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": null output (give at least one of median, min, max, excised, kept)");
+    if ((excised || kept) && !(sk_lo <= sk_hi)) // (false for a NaN)
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": sk_lo = " + std::to_string(sk_lo) + ", sk_hi = " + std::to_string(sk_hi) +
+                                          ": excised and kept need limits sk_lo <= sk_hi that are not NaN");
+    X_ON_DEVICE(h);
+    WfStage w;
+    int rc = wf_stage(h, channel, stage, &w, who);
+    if (rc)
+        return rc;
+    uint64_t last = 0;
+    const uint32_t R = wf_robust_rows(w.started, w.newest, h->wf_block, h->wf_depth, max_rows, &last);
+    info->rows = R;
+    info->block = h->wf_block;
+    info->first_block = R ? last - (R - 1) : 0;
+    info->last_block = R ? last : 0;
+    if (!R)
+        return PSDC_OK;
+    const uint32_t sides = h->rows() / 2;
+    const size_t row = (size_t)sides * bins(h);
+    void *out[5] = {median, mn, mx, excised, kept}; // (f32 and u32: four bytes an element each)
+    float *tmp = nullptr;
+    if (!device)
+        XCHK(h, hipMalloc(&tmp, sizeof(float) * row * 5));
+    const float dec = (float)((uint64_t)1 << (3 * stage)); // (the stitch's `decimation` of this stage)
+    void *dev[5];
+    for (int i = 0; i < 5; ++i)
+        dev[i] = device ? out[i] : (out[i] ? tmp + (size_t)i * row : nullptr);
+    WfRobustJob j{};
+    j.ring = w.s->acc;
+    j.median = static_cast<float *>(dev[0]);
+    j.min = static_cast<float *>(dev[1]);
+    j.max = static_cast<float *>(dev[2]);
+    j.excised = static_cast<float *>(dev[3]);
+    j.kept = static_cast<unsigned *>(dev[4]);
+    j.started = w.started;
+    j.last = last;
+    j.depth = h->wf_depth;
+    j.rows = R;
+    j.nbins = (unsigned)bins(h);
+    j.sides = sides;
+    j.block = h->wf_block;
+    j.g = (double)(1.0f / (psdrt::stage_gain(h->n, h->wf_block, h->nenbw, h->power) * dec)); // wf_image_impl's gsc_block
+    j.sk_lo = sk_lo;
+    j.sk_hi = sk_hi;
+    hipError_t e = launch_wf_robust(j, h->stream);
+    if (e == hipSuccess) {
+        ++h->launches;
+        e = hipStreamSynchronize(h->stream);
+    }
+    for (int i = 0; i < 5 && !device; ++i)
+        if (e == hipSuccess && out[i])
+            e = hipMemcpy(out[i], dev[i], sizeof(float) * row, hipMemcpyDeviceToHost);
+    if (tmp)
+        (void)hipFree(tmp);
+    XCHK(h, e);
+    return PSDC_OK;
+}
+
 } // namespace
 
 struct psdc_wf : XObj {};
@@ -3529,5 +3600,33 @@ int psdc_zwf_stats_read(psdc_zwf *h, uint64_t *launches, uint64_t *samples_in, i
 }
 
 const char *psdc_zwf_last_error(const psdc_zwf *h) { return h ? h->err.c_str() : x_last_error.c_str(); }
+
+// ---- the robust read-outs of include/psdcascade_robust.h ----
+
+int psdcx_wf_robust(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, double sk_lo, double sk_hi, float *median, float *min,
+                    float *max, float *excised, uint32_t *kept, psdcx_robust_info *info)
+{
+    return wf_robust_impl(h, channel, stage, max_rows, sk_lo, sk_hi, median, min, max, excised, kept, false, info, "psdcx_wf_robust");
+}
+
+int psdcx_wf_robust_device(psdc_wf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, double sk_lo, double sk_hi, float *d_median,
+                           float *d_min, float *d_max, float *d_excised, uint32_t *d_kept, psdcx_robust_info *info)
+{
+    return wf_robust_impl(h, channel, stage, max_rows, sk_lo, sk_hi, d_median, d_min, d_max, d_excised, d_kept, true, info,
+                          "psdcx_wf_robust_device");
+}
+
+int psdcx_zwf_robust(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, double sk_lo, double sk_hi, float *median, float *min,
+                     float *max, float *excised, uint32_t *kept, psdcx_robust_info *info)
+{
+    return wf_robust_impl(h, channel, stage, max_rows, sk_lo, sk_hi, median, min, max, excised, kept, false, info, "psdcx_zwf_robust");
+}
+
+int psdcx_zwf_robust_device(psdc_zwf *h, uint32_t channel, uint32_t stage, uint32_t max_rows, double sk_lo, double sk_hi, float *d_median,
+                            float *d_min, float *d_max, float *d_excised, uint32_t *d_kept, psdcx_robust_info *info)
+{
+    return wf_robust_impl(h, channel, stage, max_rows, sk_lo, sk_hi, d_median, d_min, d_max, d_excised, d_kept, true, info,
+                          "psdcx_zwf_robust_device");
+}
 
 } // extern "C"

@@ -26,13 +26,15 @@ PSDK_WF_HD inline uint32_t wf_row_slot(uint64_t started, uint32_t K, uint32_t nr
 // count and decimation
 PSDK_WF_HD inline float wf_psd(double s1, float gsc) { return (float)(s1 * (double)gsc); }
 
-// the estimator of include/psdcascade.h ("spectral kurtosis cascade") in f64, rounded once: NaN below two segments and without power
-PSDK_WF_HD inline float wf_sk(uint32_t count, double s1, double s2)
+// the estimator of include/psdcascade.h ("spectral kurtosis cascade") in f64: NaN below two segments and without power
+PSDK_WF_HD inline double wf_sk_f64(uint32_t count, double s1, double s2)
 {
     if (count < 2 || s1 == 0.0)
-        return __builtin_nanf("");
+        return __builtin_nan("");
     const double m = (double)count;
-    return (float)((m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0));
+    return (m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0);
 }
+// ... rounded once (the image's element; the robust read-out of waterfall_robust.h compares the f64 value)
+PSDK_WF_HD inline float wf_sk(uint32_t count, double s1, double s2) { return (float)wf_sk_f64(count, s1, s2); }
 
 } // namespace psdk

@@ -88,6 +88,13 @@ ZoomSkCascadeBank(n, 1).  Leg B: WaterfallCascadeBank(n, 1) / ZoomWaterfallCasca
 4096.  A, B, A in turn --reps times; B / A of every turn, the largest |A' - A| / A, the launches a steady call of both, and the time
 of one image_device call of every stage are recorded as findings, none is a gate.  Each writes its entry ("real" / "zoom") of
 profiles/waterfall_probe.json unless --out names another file.
+--waterfall --robust [--zoom]: what the robust read-out costs beside the image.  One device-resident real f32 stream (carrier 0.2
+for --zoom) into a WaterfallCascadeBank(n, 1, block=64, depth=64) / ZoomWaterfallCascadeBank until the ring of stage 0 is full, at
+N = 512, 1024, 4096.  Leg A: one image_device call of stage 0 (both images, 64 rows).  Leg B: one robust.stage_robust_device call of
+stage 0 with all five outputs (64 rows).  Both return when their kernel has completed, so a leg is a window of >= --seconds of
+back-to-back calls on the host clock, and its figure the time a call.  A, B, A in turn --reps times; B / A of every turn and the
+largest |A' - A| / A are recorded as findings, none is a gate.  Each writes its entry ("real" / "zoom") of
+profiles/waterfall_robust_probe.json unless --out names another file.
 """
 import argparse
 import json
@@ -463,6 +470,69 @@ def waterfall_legs(pkg, torch, seconds, reps, call, zoom):
                          "b_launches_per_call": launches[1], "stages": wb.num_stages(0), "image_device": image_us})
             sa.close()
             wb.close()
+    return legs
+
+
+def per_call_us(step, seconds):
+    """microseconds a call of back-to-back step() calls that each return when their kernel has completed: a window of >= seconds"""
+    for _ in range(5):
+        step()
+    calls = 16
+    while True:
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            step()
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return dt / calls * 1e6
+        calls = int(calls * 1.2 * seconds / dt) + 1
+
+
+def waterfall_robust_legs(pkg, torch, seconds, reps, call, zoom):
+    """One device-resident real f32 stream (zoom: carrier 0.2) into a waterfall bank with block 64 and depth 64 until stage 0's ring
+    is full.  A: image_device of stage 0 (psd and sk, 64 rows); B: robust.stage_robust_device of stage 0 (all five outputs, 64
+    rows).  A / B / A in turn, the time a call."""
+    from stabilizer_stream_amd import robust
+    x = torch.randn(call, device="cuda")
+    torch.cuda.synchronize()
+    legs = []
+    r2 = lambda vs: [round(v, 2) for v in vs]  # noqa: E731
+    for n in (512, 1024, 4096):
+        wb = (pkg.ZoomWaterfallCascadeBank if zoom else pkg.WaterfallCascadeBank)(n, 1, block=64, depth=64)
+        if zoom:
+            wb.set_carrier(0, f0=0.2)
+        while not wb.num_stages(0) or wb.stage_blocks(0, 0)["started"] <= 64:
+            wb.process_device(0, x.data_ptr(), call)
+        sides = 2 if zoom else 1
+        img = torch.empty((64, sides, n // 2 + 1), device="cuda")
+        sk = torch.empty_like(img)
+        outs = {k: torch.empty((sides, n // 2 + 1), device="cuda", dtype=torch.int32 if k == "kept" else torch.float32)
+                for k in ("median", "min", "max", "excised", "kept")}
+        ptrs = {k: v.data_ptr() for k, v in outs.items()}
+        lim = robust.sk_limits(64)
+        torch.cuda.synchronize()
+        rows_a = int(wb.image_device(0, 0, img.data_ptr(), sk.data_ptr())[0].size)
+        info = robust.stage_robust_device(wb, 0, ptrs, sk_limits=lim)
+
+        def a_step():
+            wb.image_device(0, 0, img.data_ptr(), sk.data_ptr())
+
+        def b_step():
+            robust.stage_robust_device(wb, 0, ptrs, sk_limits=lim)
+
+        a1, b, a2 = [], [], []
+        for _ in range(reps):
+            a1.append(per_call_us(a_step, seconds))
+            b.append(per_call_us(b_step, seconds))
+            a2.append(per_call_us(a_step, seconds))
+        ratios = [y / u for u, y in zip(a1, b)]
+        spread = max(abs(y - u) / u for u, y in zip(a1, a2))
+        legs.append({"n": n, "block": 64, "depth": 64, "stage": 0, "image_rows": rows_a, "robust_rows": info["rows"],
+                     "a_image_device_us": r2(a1), "b_stage_robust_device_us": r2(b), "a_again_us": r2(a2),
+                     "ratio_b_over_a": [round(v, 3) for v in ratios], "ratio_min": round(min(ratios), 3),
+                     "ratio_max": round(max(ratios), 3), "aa_spread_max": round(spread, 4),
+                     "ring_bytes_a_pass": 64 * 2 * sides * (n // 2 + 1) * 8})
+        wb.close()
     return legs
 
 
@@ -1126,9 +1196,31 @@ def main():
                                                         "the eight-row object; writes profiles/zoom_ampm_cross_probe.json")
     ap.add_argument("--waterfall", action="store_true", help="WaterfallCascadeBank against SkCascadeBank (with --zoom: the zoom objects) "
                                                              "at block 64 and 4096, depth 64; writes profiles/waterfall_probe.json")
+    ap.add_argument("--robust", action="store_true", help="with --waterfall: one robust.stage_robust_device call against one image_device "
+                                                          "call on the same ring; writes profiles/waterfall_robust_probe.json")
     a = ap.parse_args()
     import torch
     pkg = entry.load_package()
+    if a.waterfall and a.robust:
+        fam = "zoom" if a.zoom else "real"
+        path = a.out or os.path.join(ROOT, "profiles", "waterfall_robust_probe.json")
+        record = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                record = json.loads(f.read() or "{}")
+        record.update({"metric": "waterfall_robust_call_us", "unit": "microseconds a call (host clock; the call returns when its kernel has completed)",
+                       "note": "findings, no gate: A is image_device of stage 0 (psd and sk images of 64 rows), B stage_robust_device of the "
+                               "same ring (median, min, max, excised, kept over 64 rows), both one launch and one stream synchronise a "
+                               "call; not measured here: kernel time alone, host outputs, other depths and blocks, banks"})
+        before = gpu_state()
+        legs = waterfall_robust_legs(pkg, torch, a.seconds, a.reps, 1 << a.call_log2, a.zoom)
+        record[fam] = {"object": "ZoomWaterfallCascadeBank" if a.zoom else "WaterfallCascadeBank", "gpu_before": before,
+                       "gpu_after": gpu_state(), "legs": legs}
+        line = json.dumps(record)
+        print(line)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.waterfall:
         fam = "zoom" if a.zoom else "real"
         path = a.out or os.path.join(ROOT, "profiles", "waterfall_probe.json")

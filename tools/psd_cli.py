@@ -37,6 +37,11 @@ of BLOCK segments, each with its own PSD and spectral kurtosis (every segment ha
 Each prints, or with --csv writes to DIR/waterfall_<trace>_stage<k>.csv / DIR/zoom_waterfall_<trace>_<F0>_stage<k>.csv, one file a
 stage: a header line with the block indices and counts, then one line a block, oldest first, with the PSD of every bin followed by
 the SK of every bin (the zoom option: upper then lower sideband of each).
+--robust KIND[:NSIGMA] (repeatable; KIND one of median, min, max, excised) adds to every --waterfall / --zoom-waterfall trace the
+robust read-out of every stage (robust.stage_robust: over the stage's complete blocks, made on the device): behind the lines above,
+or with --csv in DIR/<the stage's file name>_robust.csv, a header line with the rows and blocks considered, then one line a KIND
+with the value of every bin (the zoom option: upper then lower).  excised is the mean of the blocks whose spectral kurtosis lies
+within NSIGMA (default 3) sk_sigma(BLOCK) of 1, and is followed by a line with the number of blocks kept a bin.
 --zoom-ampm F0[:TRACE] (repeatable; as --zoom) feeds that trace to a ZoomAmPmCascade(512) around the carrier F0, and --iq-ampm
 I:Q[:F0] (repeatable; as --iq) the complex stream I + i Q to an IqAmPmCascade(512).  Both run without a detrend whatever --detrend
 says: the carrier's amplitude and phase are read from bin 0 (carrier()), which a detrend removes.  Each prints, or with --csv writes
@@ -104,6 +109,9 @@ def main(argv=None):
                          "BLOCK segments (repeatable)")
     ap.add_argument("--zoom-waterfall", action="append", default=[],
                     help="F0:BLOCK:DEPTH[:TRACE] -- the same, two-sided around the carrier F0 (repeatable)")
+    ap.add_argument("--robust", action="append", default=[],
+                    help="KIND[:NSIGMA] -- with --waterfall / --zoom-waterfall: per stage the median, min, max or SK-excised mean (within "
+                         "NSIGMA sk_sigma of 1, default 3) over its complete blocks (repeatable)")
     ap.add_argument("--zoom-ampm", action="append", default=[],
                     help="F0[:TRACE] -- amplitude and phase noise spectra of the carrier F0 of that trace (repeatable)")
     ap.add_argument("--iq-ampm", action="append", default=[],
@@ -378,6 +386,43 @@ def waterfall_report(pkg, g, label, stem, a):
         else:
             sys.stdout.write(head)
             sys.stdout.writelines(lines)
+        if a.robust:
+            robust_report(g, k, stem, a)
+
+
+def robust_spec(z):
+    """KIND[:NSIGMA] of --robust: (kind, nsigma)"""
+    kind, _, ns = z.partition(":")
+    try:
+        nsigma = float(ns) if ns else 3.0
+    except ValueError:
+        nsigma = -1.0
+    if kind not in ("median", "min", "max", "excised") or not nsigma > 0 or (ns and kind != "excised"):
+        raise SystemExit("--robust takes median, min, max or excised[:NSIGMA]")
+    return kind, nsigma
+
+
+def robust_report(g, k, stem, a):
+    """--robust: the robust rows of stage k of a waterfall object, one line a KIND (excised: a line of kept counts behind it)"""
+    from stabilizer_stream_amd import robust
+    lines, rows = [], None
+    for kind, nsigma in map(robust_spec, a.robust):
+        r = robust.stage_robust(g, k, sk_limits=robust.sk_limits(g.block, nsigma) if kind == "excised" else None)
+        rows = r
+        lines.append(",".join(f"{v:.9g}" for v in r[kind].ravel()) + "\n")
+        if kind == "excised":
+            lines.append(",".join(str(int(v)) for v in r["kept"].ravel()) + "\n")
+    blocks = f"blocks {rows['first_block']} ... {rows['last_block']}" if rows["rows"] else "no complete block"
+    head = (f"# stage {k} robust: {rows['rows']} rows, {blocks}; lines: " +
+            " ".join(z + (" kept" if z.startswith("excised") else "") for z in a.robust) + "\n")
+    if a.csv:
+        safe = "".join(ch if ch.isalnum() else "_" for ch in f"{stem}_stage{k}_robust")
+        with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
+            f.write(head)
+            f.writelines(lines)
+    else:
+        sys.stdout.write(head)
+        sys.stdout.writelines(lines)
 
 
 def waterfall_spec(z, opt, lead):
