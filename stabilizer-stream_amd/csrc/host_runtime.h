@@ -7,6 +7,7 @@
 //   frame_scan.h       which frames of a call are taken and what Loss becomes: run_start / scan_piece, the one header scanner of
 //                      every frames call (here and in cross_runtime.cpp); wire_format.h is the one table of the payload layouts
 //   readout.cpp        PsdStage accessors, PsdCascade::psd stitch, Break, packed read-out, Var / Trace::plot, the single-stage Psd<N>
+//   bank_readout.cpp   psdcr_*: every selected channel stitched on the device in one launch, frequencies, band power
 //
 // Mirrors PsdCascade<N> (src/psd.rs:399-544) for `n_channels` independent traces on one MI355X: per (channel, stage) the
 // stream position, the count and a device stream buffer.  There is no CPU compute path: every spectrum comes from the HIP kernels.
@@ -19,6 +20,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -245,6 +247,9 @@ struct psdc_handle {
     psdc_profile prof{};
     psdc_loss loss{};
     std::string err;
+    // the bank read-out's job-table slots and host-form buffers (bank_readout.cpp; include/psdcascade_readout.h), made by its first
+    // call.  Owned here so that they go with the handle: psdc_destroy's `delete h` runs the deleter, after the streams are idle
+    std::shared_ptr<void> bank_read;
 };
 
 namespace psdrt {

@@ -37,6 +37,9 @@ of BLOCK segments, each with its own PSD and spectral kurtosis (every segment ha
 Each prints, or with --csv writes to DIR/waterfall_<trace>_stage<k>.csv / DIR/zoom_waterfall_<trace>_<F0>_stage<k>.csv, one file a
 stage: a header line with the block indices and counts, then one line a block, oldest first, with the PSD of every bin followed by
 the SK of every bin (the zoom option: upper then lower sideband of each).
+--bank-readout reads the spectra and frequencies of all traces of the main bank with ONE call (bankread.bank_psd: every trace
+stitched on the device in one launch, one copy to the host) where the default asks psd() trace by trace; the lines and the files
+are the same, byte for byte.
 --robust KIND[:NSIGMA] (repeatable; KIND one of median, min, max, excised) adds to every --waterfall / --zoom-waterfall trace the
 robust read-out of every stage (robust.stage_robust: over the stage's complete blocks, made on the device): behind the lines above,
 or with --csv in DIR/<the stage's file name>_robust.csv, a header line with the rows and blocks considered, then one line a KIND
@@ -109,6 +112,8 @@ def main(argv=None):
                          "BLOCK segments (repeatable)")
     ap.add_argument("--zoom-waterfall", action="append", default=[],
                     help="F0:BLOCK:DEPTH[:TRACE] -- the same, two-sided around the carrier F0 (repeatable)")
+    ap.add_argument("--bank-readout", action="store_true",
+                    help="read every trace's spectrum and frequencies with ONE bankread.bank_psd call (the same output, byte for byte)")
     ap.add_argument("--robust", action="append", default=[],
                     help="KIND[:NSIGMA] -- with --waterfall / --zoom-waterfall: per stage the median, min, max or SK-excised mean (within "
                          "NSIGMA sk_sigma of 1, default 3) over its complete blocks (repeatable)")
@@ -176,12 +181,19 @@ def main(argv=None):
     src.close()
     if a.csv:
         os.makedirs(a.csv, exist_ok=True)
+    if a.bank_readout:  # every trace stitched on the device in one launch, one copy (include/psdcascade_readout.h)
+        from stabilizer_stream_amd import bankread
+        allrows = bankread.bank_psd(bank, None, merge, frequencies=True)
     for i, name in enumerate(names):
         if bank.num_stages(i) == 0:
             print(f"{name}: no samples")
             continue
-        psd, breaks = bank.psd(i, merge)
-        freqs = pkg.Break.frequencies(breaks)
+        if a.bank_readout:
+            ln, breaks = allrows["lens"][i], allrows["breaks"][i]
+            psd, freqs = allrows["psd"][i, :ln], allrows["frequencies"][i, :ln]
+        else:
+            psd, breaks = bank.psd(i, merge)
+            freqs = pkg.Break.frequencies(breaks)
         rms, xy = pkg.trace_plot(psd, freqs, fs=a.fs, integrate=a.integrate, integral_start=integral_start, integral_end=integral_end)
         top = bank.stage_info(i, 0)["count"]
         print(f"{name}: stages {bank.num_stages(i)} top-stage averages {top} bins {psd.size} breaks {len(breaks)} rms {rms:.9g}")
