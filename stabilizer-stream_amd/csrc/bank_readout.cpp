@@ -14,36 +14,7 @@ using namespace psdrt;
 
 namespace {
 
-// What the handle keeps for these calls (psdc_handle::bank_read): two job-table slots, each a pinned host table, its device image
-// and an event recorded behind the kernels that read it; the host form's device buffer and its pinned image.
-struct BankRead {
-    char *h_tab[2] = {nullptr, nullptr};
-    char *d_tab[2] = {nullptr, nullptr};
-    size_t tab_cap[2] = {0, 0};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool busy[2] = {false, false};
-    int cur = 0;
-    char *d_out = nullptr, *h_out = nullptr;
-    size_t out_cap = 0;
-    ~BankRead()
-    {
-        for (int s = 0; s < 2; ++s) {
-            if (busy[s])
-                (void)hipEventSynchronize(ev[s]);
-            if (ev[s])
-                (void)hipEventDestroy(ev[s]);
-            if (d_tab[s])
-                (void)hipFree(d_tab[s]);
-            if (h_tab[s])
-                (void)hipHostFree(h_tab[s]);
-        }
-        if (d_out)
-            (void)hipFree(d_out);
-        if (h_out)
-            (void)hipHostFree(h_out);
-    }
-};
-
+// what the handle keeps for these calls (psdc_handle::bank_read): psdrt::BankRead of host_runtime.h
 BankRead *state_of(psdc_handle *h)
 {
     if (!h->bank_read)
@@ -176,27 +147,9 @@ int enqueue(psdc_handle *h, const Args &a, const Plan &pl, float *d_psd, float *
         return PSDC_OK;
     }
     BankRead *st = state_of(h);
-    const int s = st->cur;
-    st->cur ^= 1;
-    if (st->busy[s]) { // the kernels that read this slot's last table: not before they have run may it be rewritten
-        HIPCHK(h, hipEventSynchronize(st->ev[s]));
-        st->busy[s] = false;
-    }
-    if (!st->ev[s])
-        HIPCHK(h, hipEventCreateWithFlags(&st->ev[s], hipEventDisableTiming));
     const size_t job_bytes = sizeof(psdk::BankJob) * pl.jobs.size(), bytes = job_bytes + sizeof(psdk::BankRow) * S;
-    if (st->tab_cap[s] < bytes) {
-        const size_t grown = std::max<size_t>(bytes + bytes / 2, 4096);
-        if (st->d_tab[s])
-            HIPCHK(h, hipFree(st->d_tab[s]));
-        if (st->h_tab[s])
-            HIPCHK(h, hipHostFree(st->h_tab[s]));
-        st->d_tab[s] = st->h_tab[s] = nullptr;
-        st->tab_cap[s] = 0;
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&st->d_tab[s]), grown));
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&st->h_tab[s]), grown, hipHostMallocDefault));
-        st->tab_cap[s] = grown;
-    }
+    int s = 0;
+    HIPCHK(h, st->take_slot(bytes, &s));
     memcpy(st->h_tab[s], pl.jobs.data(), job_bytes);
     memcpy(st->h_tab[s] + job_bytes, pl.rows.data(), bytes - job_bytes);
     HIPCHK(h, hipMemcpyAsync(st->d_tab[s], st->h_tab[s], bytes, hipMemcpyHostToDevice, h->stream));
@@ -211,8 +164,7 @@ int enqueue(psdc_handle *h, const Args &a, const Plan &pl, float *d_psd, float *
         HIPCHK(h, psdk::launch_bank_band(d_jobs, d_rows, S, bb, d_band, h->stream));
         ++launches;
     }
-    HIPCHK(h, hipEventRecord(st->ev[s], h->stream));
-    st->busy[s] = true;
+    HIPCHK(h, st->mark_slot(s, h->stream));
     if (a.info)
         a.info->launches = launches;
     return PSDC_OK;
@@ -292,18 +244,7 @@ int psdcr_bank_psd(psdc_handle *h, const uint32_t *channels, uint32_t n_sel, int
     const size_t o_freq = psd ? row_bytes : 0, o_band = (o_freq + (freq ? row_bytes : 0) + 7) & ~(size_t)7;
     const size_t bytes = o_band + sizeof(double) * S * n_bands;
     BankRead *st = state_of(h);
-    if (st->out_cap < bytes) { // (every earlier use has been waited for)
-        const size_t grown = std::max<size_t>(bytes + bytes / 2, (size_t)1 << 16);
-        if (st->d_out)
-            HIPCHK(h, hipFree(st->d_out));
-        if (st->h_out)
-            HIPCHK(h, hipHostFree(st->h_out));
-        st->d_out = st->h_out = nullptr;
-        st->out_cap = 0;
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&st->d_out), grown));
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&st->h_out), grown, hipHostMallocDefault));
-        st->out_cap = grown;
-    }
+    HIPCHK(h, st->room_out(bytes));
     if ((rc = enqueue(h, a, pl, psd ? reinterpret_cast<float *>(st->d_out) : nullptr, freq ? reinterpret_cast<float *>(st->d_out + o_freq) : nullptr,
                       pl.max_len, bb, band_power ? reinterpret_cast<double *>(st->d_out + o_band) : nullptr)))
         return rc;

@@ -80,62 +80,89 @@ inline BankRow bank_row_jobs(const B *breaks, size_t n_breaks, uint32_t row, Job
 
 // one f32 multiply an element each: the bytes of psdc_psd and psdc_frequencies
 PSDK_BR_HD inline float bank_psd(const BankJob &j, uint32_t k) { return j.src[k] * j.gsc; }
-PSDK_BR_HD inline float bank_freq(const BankJob &j, uint32_t k) { return (float)k * j.rbw; }
+template <class Job>
+PSDK_BR_HD inline float bank_freq(const Job &j, uint32_t k) { return (float)k * j.rbw; }
 
-// What thread t of T adds up for one row: the trapezoids t_e of the elements e = t, t + T, ... < L, each into the bands that hold
-// f[e].  p[e] and f[e] come from the jobs (the row itself is not read); p[-1] = f[-1] = 0.
-PSDK_BR_HD inline void bank_band_thread(const BankJob *jobs, uint32_t nj, uint32_t L, uint32_t t, uint32_t T, const BankBands &bands,
-                                        double acc[BANK_MAX_BANDS])
+// What thread t of T adds up for one unit of R stitched rows that share their jobs (a PSD row: R = 1; the four rows of a pair,
+// cross_readout.h): the trapezoids t_e of the elements e = t, t + T, ... < L of each row r, each into the bands that hold f[e].
+// p[e] = val(job, r, bin) and f[e] come from the jobs (the rows themselves are not read); p[-1] = f[-1] = 0.
+template <uint32_t R, class Job, class Val>
+PSDK_BR_HD inline void bank_band_walk(const Job *jobs, uint32_t nj, uint32_t L, uint32_t t, uint32_t T, const BankBands &bands, Val val,
+                                      double (*acc)[BANK_MAX_BANDS])
 {
     uint32_t ji = 0;
     for (uint32_t e = t; e < L; e += T) {
         while (ji + 1 < nj && e >= jobs[ji + 1].start)
             ++ji;
-        const BankJob &j = jobs[ji];
+        const Job &j = jobs[ji];
         const uint32_t k = j.bins_start + (e - j.start);
-        const float p = bank_psd(j, k), f = bank_freq(j, k);
-        float p1 = 0.0f, f1 = 0.0f;
+        const Job *q = nullptr; // the job and bin of element e - 1
+        uint32_t kq = 0;
         if (e > j.start) {
-            p1 = bank_psd(j, k - 1);
-            f1 = bank_freq(j, k - 1);
+            q = &j;
+            kq = k - 1;
         } else if (ji > 0) {
-            const BankJob &q = jobs[ji - 1];
-            p1 = bank_psd(q, q.bins_end - 1);
-            f1 = bank_freq(q, q.bins_end - 1);
+            q = &jobs[ji - 1];
+            kq = q->bins_end - 1;
         }
-        const double tk = (0.5 * ((double)p + (double)p1)) * ((double)f - (double)f1); // rounded on its own: see the top
+        const float f = bank_freq(j, k), f1 = q ? bank_freq(*q, kq) : 0.0f;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-        for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b)
-            if (b < bands.n && bands.lo[b] <= f && f <= bands.hi[b])
-                acc[b] += tk;
+        for (uint32_t r = 0; r < R; ++r) {
+            const float p = val(j, r, k), p1 = q ? val(*q, r, kq) : 0.0f;
+            const double tk = (0.5 * ((double)p + (double)p1)) * ((double)f - (double)f1); // rounded on its own: see the top
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b)
+                if (b < bands.n && bands.lo[b] <= f && f <= bands.hi[b])
+                    acc[r][b] += tk;
+        }
     }
 }
 
-// The band sums of one row as bank_band_kernel forms them, on the host: BANK_BAND_THREADS threads, then within each wavefront
-// the tree v[l] += v[l + off] for off = 32, 16 ... 1 (lane 0 holds the wavefront's sum), then the wavefronts in order.
+PSDK_BR_HD inline void bank_band_thread(const BankJob *jobs, uint32_t nj, uint32_t L, uint32_t t, uint32_t T, const BankBands &bands,
+                                        double acc[BANK_MAX_BANDS])
+{
+    bank_band_walk<1>(
+        jobs, nj, L, t, T, bands, [](const BankJob &j, uint32_t, uint32_t k) { return bank_psd(j, k); },
+        reinterpret_cast<double(*)[BANK_MAX_BANDS]>(acc));
+}
+
+// The band sums of one unit as bank_band_kernel / cross_band_kernel form them, on the host: BANK_BAND_THREADS threads, then within
+// each wavefront the tree v[l] += v[l + off] for off = 32, 16 ... 1 (lane 0 holds the wavefront's sum), then the wavefronts in order.
+template <uint32_t R, class Job, class Val>
+inline void bank_band_rows_host(const Job *jobs, uint32_t nj, uint32_t L, const BankBands &bands, Val val, double (*out)[BANK_MAX_BANDS])
+{
+    static double acc[BANK_BAND_THREADS][R][BANK_MAX_BANDS];
+    for (uint32_t t = 0; t < BANK_BAND_THREADS; ++t) {
+        for (uint32_t r = 0; r < R; ++r)
+            for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b)
+                acc[t][r][b] = 0.0;
+        bank_band_walk<R>(jobs, nj, L, t, BANK_BAND_THREADS, bands, val, acc[t]);
+    }
+    for (uint32_t r = 0; r < R; ++r)
+        for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b) {
+            double sum = 0.0;
+            for (uint32_t w = 0; w < BANK_BAND_THREADS / BANK_WAVE; ++w) {
+                double v[BANK_WAVE];
+                for (uint32_t l = 0; l < BANK_WAVE; ++l)
+                    v[l] = acc[w * BANK_WAVE + l][r][b];
+                for (uint32_t off = BANK_WAVE / 2; off; off >>= 1)
+                    for (uint32_t l = 0; l < off; ++l)
+                        v[l] += v[l + off];
+                sum = w ? sum + v[0] : v[0];
+            }
+            out[r][b] = sum;
+        }
+}
+
 inline void bank_band_row_host(const BankJob *jobs, uint32_t nj, uint32_t L, const BankBands &bands, double out[BANK_MAX_BANDS])
 {
-    static double acc[BANK_BAND_THREADS][BANK_MAX_BANDS];
-    for (uint32_t t = 0; t < BANK_BAND_THREADS; ++t) {
-        for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b)
-            acc[t][b] = 0.0;
-        bank_band_thread(jobs, nj, L, t, BANK_BAND_THREADS, bands, acc[t]);
-    }
-    for (uint32_t b = 0; b < BANK_MAX_BANDS; ++b) {
-        double sum = 0.0;
-        for (uint32_t w = 0; w < BANK_BAND_THREADS / BANK_WAVE; ++w) {
-            double v[BANK_WAVE];
-            for (uint32_t l = 0; l < BANK_WAVE; ++l)
-                v[l] = acc[w * BANK_WAVE + l][b];
-            for (uint32_t off = BANK_WAVE / 2; off; off >>= 1)
-                for (uint32_t l = 0; l < off; ++l)
-                    v[l] += v[l + off];
-            sum = w ? sum + v[0] : v[0];
-        }
-        out[b] = sum;
-    }
+    bank_band_rows_host<1>(
+        jobs, nj, L, bands, [](const BankJob &j, uint32_t, uint32_t k) { return bank_psd(j, k); },
+        reinterpret_cast<double(*)[BANK_MAX_BANDS]>(out));
 }
 
 #if defined(__HIPCC__)

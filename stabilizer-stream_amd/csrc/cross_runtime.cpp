@@ -41,8 +41,10 @@
 #include "waterfall_plan.h"
 #include "waterfall_read.h"
 #include "waterfall_robust.h"
+#include "cross_readout.h"
 #include "host_runtime.h"
 #include "../../include/psdcascade_robust.h"
+#include "../../include/psdcascade_crossread.h"
 
 #include <algorithm>
 #include <cmath>
@@ -65,6 +67,10 @@ inline hipError_t launch_cvt_int(const SintCvtJob &, int, hipStream_t) { return 
 // (nor a waterfall read-out kernel: psdc_wf_image[_device] fail there with a device error)
 inline hipError_t launch_wf_image(const WfImageJob &, hipStream_t) { return hipErrorInvalidValue; }
 inline hipError_t launch_wf_robust(const WfRobustJob &, hipStream_t) { return hipErrorInvalidValue; } // (psdcx_*_robust[_device] too)
+// (nor the bank read-out kernels of cross_readout.hip: the psdcxr_ read-outs fail there with a device error once a stage is included)
+inline hipError_t launch_cross_stitch_pair(const CrossReadJob *, uint32_t, uint32_t, const CrossPairOut &, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_cross_stitch_rows(const CrossReadJob *, uint32_t, uint32_t, float *, float *, size_t, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_cross_band(const CrossReadJob *, const BankRow *, uint32_t, const BankBands &, double *, hipStream_t) { return hipErrorInvalidValue; }
 } // namespace psdk
 #endif
 
@@ -171,6 +177,9 @@ struct XObj {
     std::vector<uint64_t> ftw, phase0;
     float *d_land = nullptr;
     int64_t resident = 1024; // cross_kernel workgroups a launch is dealt to (twice what the device holds at once)
+    // the bank read-outs' job-table slots and host-form buffers (psdcxr_*, include/psdcascade_crossread.h), made by their first call;
+    // destroy_impl frees them with the object
+    psdrt::BankRead *bank_read = nullptr;
     std::string err;
 };
 
@@ -1091,6 +1100,8 @@ void destroy_impl(XObj *h)
     psdrt::DevScope scope(h->device);
     if (h->stream && h->copy_stream)
         free_all(h);
+    delete h->bank_read;
+    h->bank_read = nullptr;
     for (int i = 0; i < 2; ++i) {
         if (h->h_stage[i])
             (void)hipHostFree(h->h_stage[i]);
@@ -3628,5 +3639,299 @@ int psdcx_zwf_robust_device(psdc_zwf *h, uint32_t channel, uint32_t stage, uint3
     return wf_robust_impl(h, channel, stage, max_rows, sk_lo, sk_hi, d_median, d_min, d_max, d_excised, d_kept, true, info,
                           "psdcx_zwf_robust_device");
 }
+
+} // extern "C"
+
+// ---- the bank read-outs of include/psdcascade_crossread.h (pair and matrix objects) ----
+// One drain, the stitch of every selected unit planned on the host from XStage's bookkeeping (stitch_impl without an output row
+// gives the Breaks, cross_readout.h turns them into jobs), one launch of cross_stitch_kernel and at most one of cross_band_kernel
+// (cross_readout.hip) behind the drain on the object's stream.
+
+namespace {
+
+struct XrArgs {
+    const char *who;
+    const uint32_t *sel;
+    uint32_t n_sel;
+    int keep_overlap;
+    uint32_t min_count;
+    int keep_transition_band;
+    size_t *lens, *n_breaks;
+    psdc_break *breaks;
+    size_t breaks_cap;
+    psdcxr_info *info;
+};
+
+// one output of a call: `rows` rows a unit of `elem` bytes a bin each; p is the caller's memory (NULL: not wanted)
+struct XrOut {
+    void *p;
+    size_t elem;
+    uint32_t rows;
+};
+
+struct XrPlan {
+    std::vector<CrossReadJob> jobs;
+    std::vector<BankRow> units;
+    size_t max_len = 0;
+    uint32_t max_bins = 0;
+};
+
+int xr_bad(XObj *h, const XrArgs &a, const char *what) { return xfail(h, PSDC_ERR_ARG, std::string(a.who) + ": " + what); }
+
+// the checks every call shares; *units = the number of selected units
+int xr_selection(XObj *h, const XrArgs &a, uint32_t *units)
+{
+    X_HANDLE(h, a.who);
+    if (const char *why = cross_read_layout_refusal(a.lens, a.n_breaks, a.breaks))
+        return xr_bad(h, a, why);
+    const uint32_t S = a.sel ? a.n_sel : h->n_pairs;
+    if (S > BANK_MAX_ROWS)
+        return xr_bad(h, a, "more than PSDCXR_MAX_ROWS units selected");
+    for (uint32_t i = 0; a.sel && i < S; ++i)
+        if (int rc = check_pair(h, a.sel[i], a.who))
+            return rc;
+    *units = S;
+    return PSDC_OK;
+}
+
+// Drain, then the layout of every selected unit and its jobs.  Fills lens, n_breaks, info->max_len and info->jobs always, the
+// Breaks where they fit; PSDC_ERR_CAPACITY when some unit's Breaks do not.
+int xr_plan(XObj *h, const XrArgs &a, uint32_t S, XrPlan *pl)
+{
+    int rc = drain(h);
+    if (rc)
+        return rc;
+    bool overflow = false;
+    pl->units.resize(S);
+    for (uint32_t i = 0; i < S; ++i) {
+        const std::vector<XStage> &st = h->pairs[a.sel ? a.sel[i] : i];
+        const size_t ns = st.size();
+        uint32_t counts[X_MAX_STAGES], avgs[X_MAX_STAGES];
+        uint64_t pend[X_MAX_STAGES], counts64[X_MAX_STAGES];
+        for (size_t k = 0; k < ns; ++k) {
+            counts64[k] = st[k].count64;
+            counts[k] = count_report(st[k].count64);
+            avgs[k] = cur_avg(h, k);
+            pend[k] = pending_for(h->geo, st[k].total);
+        }
+        psdc_break br[X_MAX_STAGES];
+        size_t len = 0, nb = 0;
+        rc = psdrt::stitch_impl(h->n, h->nenbw, h->power, h->geo.overlap, (uint32_t)ns, counts, avgs, pend, nullptr, a.keep_overlap,
+                                a.min_count, a.keep_transition_band, nullptr, 0, &len, br, X_MAX_STAGES, &nb, counts64);
+        if (rc)
+            return xfail(h, rc, std::string(a.who) + ": internal: a unit with more than 16 stages");
+        a.lens[i] = len;
+        if (a.n_breaks)
+            a.n_breaks[i] = nb;
+        if (a.breaks) {
+            if (nb <= a.breaks_cap)
+                memcpy(a.breaks + (size_t)i * a.breaks_cap, br, sizeof(psdc_break) * nb);
+            else
+                overflow = true;
+        }
+        pl->units[i] = cross_row_jobs(
+            br, nb, i, h->rows(), (uint32_t)bins(h), pl->jobs, [&](uint32_t stage) { return (const double *)st[stage].acc; },
+            [&](uint32_t stage) { return psdrt::stage_gain(h->n, counts64[stage], h->nenbw, h->power); });
+        if (pl->units[i].len != len)
+            return xfail(h, PSDC_ERR_ARG, std::string(a.who) + ": internal: the jobs do not cover the row");
+        pl->max_len = std::max(pl->max_len, len);
+    }
+    for (const CrossReadJob &j : pl->jobs)
+        pl->max_bins = std::max(pl->max_bins, j.bins_end - j.bins_start);
+    if (a.info) {
+        a.info->launches = 0;
+        a.info->jobs = (uint32_t)pl->jobs.size();
+        a.info->max_len = pl->max_len;
+    }
+    return overflow ? xfail(h, PSDC_ERR_CAPACITY, std::string(a.who) + ": breaks_cap is smaller than a unit's number of breaks") : PSDC_OK;
+}
+
+int xr_layout(XObj *h, const XrArgs &a)
+{
+    uint32_t S = 0;
+    int rc = xr_selection(h, a, &S);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    XrPlan pl;
+    return xr_plan(h, a, S, &pl);
+}
+
+// The kernels of one call into the device memory dev[]: the table through a free slot, the stitch, the bands, the slot's event.
+// pair: dev[] = sxx, syy, sxy, freq, coherence, transfer; else rows, freq.
+int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, bool pair, void *const *dev, size_t stride, const BankBands &bb, double *d_band)
+{
+    const uint32_t S = (uint32_t)pl.units.size();
+    if (pl.jobs.empty()) { // nothing included anywhere: no kernel; the band sums are 0.0
+        if (d_band && S)
+            XCHK(h, hipMemsetAsync(d_band, 0, sizeof(double) * S * bb.n * XREAD_PAIR_ROWS, h->stream));
+        return PSDC_OK;
+    }
+    if (!h->bank_read)
+        h->bank_read = new psdrt::BankRead;
+    psdrt::BankRead *st = h->bank_read;
+    const size_t job_bytes = sizeof(CrossReadJob) * pl.jobs.size(), bytes = job_bytes + sizeof(BankRow) * S;
+    int s = 0;
+    XCHK(h, st->take_slot(bytes, &s));
+    memcpy(st->h_tab[s], pl.jobs.data(), job_bytes);
+    memcpy(st->h_tab[s] + job_bytes, pl.units.data(), bytes - job_bytes);
+    XCHK(h, hipMemcpyAsync(st->d_tab[s], st->h_tab[s], bytes, hipMemcpyHostToDevice, h->stream));
+    const CrossReadJob *d_jobs = reinterpret_cast<const CrossReadJob *>(st->d_tab[s]);
+    const BankRow *d_units = reinterpret_cast<const BankRow *>(st->d_tab[s] + job_bytes);
+    const uint32_t n_jobs = (uint32_t)pl.jobs.size();
+    uint32_t launches = 0;
+    if (pair) {
+        const CrossPairOut o{(float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (double *)dev[4], (double *)dev[5], stride};
+        if (o.any()) {
+            XCHK(h, launch_cross_stitch_pair(d_jobs, n_jobs, pl.max_bins, o, h->stream));
+            ++launches;
+        }
+    } else if (dev[0] || dev[1]) {
+        XCHK(h, launch_cross_stitch_rows(d_jobs, n_jobs, pl.max_bins, (float *)dev[0], (float *)dev[1], stride, h->stream));
+        ++launches;
+    }
+    if (d_band) {
+        XCHK(h, launch_cross_band(d_jobs, d_units, S, bb, d_band, h->stream));
+        ++launches;
+    }
+    XCHK(h, st->mark_slot(s, h->stream));
+    if (a.info)
+        a.info->launches = launches;
+    return PSDC_OK;
+}
+
+// One read-out call of either object in either form.  device: outs[].p and band_out are device memory, else host memory filled
+// from the object's buffer through one copy.
+int xr_read(XObj *h, const XrArgs &a, bool pair, const XrOut *outs, size_t n_outs, size_t stride, const float *bands, uint32_t n_bands,
+            double *band_out, bool device, void *done_event)
+{
+    uint32_t S = 0;
+    int rc = xr_selection(h, a, &S);
+    if (rc)
+        return rc;
+    bool any = false;
+    for (size_t o = 0; o < n_outs; ++o)
+        any = any || outs[o].p;
+    BankBands bb{};
+    if (const char *why = cross_read_band_refusal(bands, n_bands, band_out, any, &bb))
+        return xr_bad(h, a, why);
+    X_ON_DEVICE(h);
+    XrPlan pl;
+    if ((rc = xr_plan(h, a, S, &pl)))
+        return rc;
+    if (any && stride < pl.max_len)
+        return xfail(h, PSDC_ERR_CAPACITY, std::string(a.who) + ": stride is smaller than the longest row");
+    void *dev[6] = {};
+    if (device) {
+        for (size_t o = 0; o < n_outs; ++o)
+            dev[o] = outs[o].p;
+        if ((rc = xr_enqueue(h, a, pl, pair, dev, stride, bb, band_out)))
+            return rc;
+        if (done_event)
+            XCHK(h, hipEventRecord(static_cast<hipEvent_t>(done_event), h->stream));
+        else
+            XCHK(h, hipStreamSynchronize(h->stream));
+        return PSDC_OK;
+    }
+    const size_t band_bytes = sizeof(double) * S * n_bands * XREAD_PAIR_ROWS;
+    if (pl.jobs.empty()) { // nothing included anywhere: no row gets a value, the band sums are 0.0
+        if (band_out)
+            memset(band_out, 0, band_bytes);
+        return PSDC_OK;
+    }
+    // the object's buffer: the wanted outputs one behind the other in rows of max_len bins, then the band sums
+    size_t off[6] = {}, bytes = 0;
+    for (size_t o = 0; o < n_outs; ++o) {
+        off[o] = bytes;
+        if (outs[o].p)
+            bytes += (outs[o].elem * outs[o].rows * S * pl.max_len + 15) & ~(size_t)15;
+    }
+    const size_t o_band = bytes;
+    bytes += band_bytes;
+    if (!h->bank_read)
+        h->bank_read = new psdrt::BankRead;
+    psdrt::BankRead *st = h->bank_read;
+    XCHK(h, st->room_out(bytes));
+    for (size_t o = 0; o < n_outs; ++o)
+        dev[o] = outs[o].p ? st->d_out + off[o] : nullptr;
+    if ((rc = xr_enqueue(h, a, pl, pair, dev, pl.max_len, bb, band_out ? reinterpret_cast<double *>(st->d_out + o_band) : nullptr)))
+        return rc;
+    XCHK(h, hipMemcpyAsync(st->h_out, st->d_out, bytes, hipMemcpyDeviceToHost, h->stream));
+    XCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t o = 0; o < n_outs; ++o)
+        for (size_t r = 0; outs[o].p && r < (size_t)S * outs[o].rows; ++r)
+            memcpy(static_cast<char *>(outs[o].p) + r * stride * outs[o].elem, st->h_out + off[o] + r * pl.max_len * outs[o].elem,
+                   outs[o].elem * pl.units[r / outs[o].rows].len);
+    if (band_out)
+        memcpy(band_out, st->h_out + o_band, band_bytes);
+    return PSDC_OK;
+}
+
+int xr_release(XObj *h, const char *who)
+{
+    X_HANDLE(h, who);
+    X_ON_DEVICE(h);
+    delete h->bank_read; // (waits for the slots still in flight)
+    h->bank_read = nullptr;
+    return PSDC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int psdcxr_cross_layout(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count,
+                        int keep_transition_band, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcxr_info *info)
+{
+    return xr_layout(h, {"psdcxr_cross_layout", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info});
+}
+
+int psdcxr_cross_csd_device(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count,
+                            int keep_transition_band, float *d_sxx, float *d_syy, float *d_sxy, float *d_freq, double *d_coherence,
+                            double *d_transfer, size_t stride, const float *bands, uint32_t n_bands, double *d_band_sums, void *done_event,
+                            size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcxr_info *info)
+{
+    const XrOut outs[6] = {{d_sxx, 4, 1}, {d_syy, 4, 1}, {d_sxy, 8, 1}, {d_freq, 4, 1}, {d_coherence, 8, 1}, {d_transfer, 16, 1}};
+    return xr_read(h, {"psdcxr_cross_csd_device", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
+                   true, outs, 6, stride, bands, n_bands, d_band_sums, true, done_event);
+}
+
+int psdcxr_cross_csd(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                     float *sxx, float *syy, float *sxy, float *freq, double *coherence, double *transfer, size_t stride, const float *bands,
+                     uint32_t n_bands, double *band_sums, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap,
+                     psdcxr_info *info)
+{
+    const XrOut outs[6] = {{sxx, 4, 1}, {syy, 4, 1}, {sxy, 8, 1}, {freq, 4, 1}, {coherence, 8, 1}, {transfer, 16, 1}};
+    return xr_read(h, {"psdcxr_cross_csd", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}, true,
+                   outs, 6, stride, bands, n_bands, band_sums, false, nullptr);
+}
+
+int psdcxr_cross_release(psdc_cross *h) { return xr_release(h, "psdcxr_cross_release"); }
+
+int psdcxr_csm_layout(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                      size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcxr_info *info)
+{
+    return xr_layout(h, {"psdcxr_csm_layout", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info});
+}
+
+int psdcxr_csm_rows_device(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, int keep_overlap, uint32_t min_count,
+                           int keep_transition_band, float *d_rows, float *d_freq, size_t stride, void *done_event, size_t *lens,
+                           size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcxr_info *info)
+{
+    const XrOut outs[2] = {{d_rows, 4, h ? h->rows() : 0}, {d_freq, 4, 1}};
+    return xr_read(h, {"psdcxr_csm_rows_device", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
+                   false, outs, 2, stride, nullptr, 0, nullptr, true, done_event);
+}
+
+int psdcxr_csm_rows(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                    float *rows, float *freq, size_t stride, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap,
+                    psdcxr_info *info)
+{
+    const XrOut outs[2] = {{rows, 4, h ? h->rows() : 0}, {freq, 4, 1}};
+    return xr_read(h, {"psdcxr_csm_rows", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}, false,
+                   outs, 2, stride, nullptr, 0, nullptr, false, nullptr);
+}
+
+int psdcxr_csm_release(psdc_csm *h) { return xr_release(h, "psdcxr_csm_release"); }
 
 } // extern "C"

@@ -292,6 +292,97 @@ struct DevScope {
     if (dev_scope_.err != hipSuccess)                                                            \
         return fail(h, PSDC_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(dev_scope_.err))
 
+// What an object keeps for its bank read-outs (psdcr_* of bank_readout.cpp: psdc_handle::bank_read; psdcxr_* of
+// cross_runtime.cpp: XObj::bank_read): two job-table slots, each a pinned host table, its device image and an event recorded
+// behind the kernels that read it; the host form's device buffer and its pinned image.  All of it grows to the largest call.
+struct BankRead {
+    char *h_tab[2] = {nullptr, nullptr};
+    char *d_tab[2] = {nullptr, nullptr};
+    size_t tab_cap[2] = {0, 0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    int cur = 0;
+    char *d_out = nullptr, *h_out = nullptr;
+    size_t out_cap = 0;
+    BankRead() = default;
+    BankRead(const BankRead &) = delete;
+    BankRead &operator=(const BankRead &) = delete;
+    ~BankRead()
+    {
+        for (int s = 0; s < 2; ++s) {
+            if (busy[s])
+                (void)hipEventSynchronize(ev[s]);
+            if (ev[s])
+                (void)hipEventDestroy(ev[s]);
+            if (d_tab[s])
+                (void)hipFree(d_tab[s]);
+            if (h_tab[s])
+                (void)hipHostFree(h_tab[s]);
+        }
+        if (d_out)
+            (void)hipFree(d_out);
+        if (h_out)
+            (void)hipHostFree(h_out);
+    }
+    // the next slot, with room for a table of `bytes`: not before the kernels that read its last table have run may it be rewritten
+    hipError_t take_slot(size_t bytes, int *slot)
+    {
+        const int s = cur;
+        cur ^= 1;
+        hipError_t e = hipSuccess;
+        if (busy[s]) {
+            if ((e = hipEventSynchronize(ev[s])) != hipSuccess)
+                return e;
+            busy[s] = false;
+        }
+        if (!ev[s] && (e = hipEventCreateWithFlags(&ev[s], hipEventDisableTiming)) != hipSuccess)
+            return e;
+        if (tab_cap[s] < bytes) {
+            const size_t grown = std::max<size_t>(bytes + bytes / 2, 4096);
+            if (d_tab[s] && (e = hipFree(d_tab[s])) != hipSuccess)
+                return e;
+            d_tab[s] = nullptr;
+            tab_cap[s] = 0;
+            if (h_tab[s] && (e = hipHostFree(h_tab[s])) != hipSuccess)
+                return e;
+            h_tab[s] = nullptr;
+            if ((e = hipMalloc(reinterpret_cast<void **>(&d_tab[s]), grown)) != hipSuccess ||
+                (e = hipHostMalloc(reinterpret_cast<void **>(&h_tab[s]), grown, hipHostMallocDefault)) != hipSuccess)
+                return e;
+            tab_cap[s] = grown;
+        }
+        *slot = s;
+        return hipSuccess;
+    }
+    // the slot's event behind the kernels that read its table
+    hipError_t mark_slot(int s, hipStream_t stream)
+    {
+        const hipError_t e = hipEventRecord(ev[s], stream);
+        busy[s] = e == hipSuccess;
+        return e;
+    }
+    // d_out and h_out with room for `bytes` (every earlier use of them has been waited for)
+    hipError_t room_out(size_t bytes)
+    {
+        if (out_cap >= bytes)
+            return hipSuccess;
+        const size_t grown = std::max<size_t>(bytes + bytes / 2, (size_t)1 << 16);
+        hipError_t e = hipSuccess;
+        if (d_out && (e = hipFree(d_out)) != hipSuccess)
+            return e;
+        d_out = nullptr;
+        out_cap = 0;
+        if (h_out && (e = hipHostFree(h_out)) != hipSuccess)
+            return e;
+        h_out = nullptr;
+        if ((e = hipMalloc(reinterpret_cast<void **>(&d_out), grown)) != hipSuccess ||
+            (e = hipHostMalloc(reinterpret_cast<void **>(&h_out), grown, hipHostMallocDefault)) != hipSuccess)
+            return e;
+        out_cap = grown;
+        return hipSuccess;
+    }
+};
+
 // ---- runtime.cpp ------------------------------------------------------------------------------------------------------------
 bool window_consts(uint32_t n, int kind, WindowConsts *w);
 void window_weights(uint32_t n, int kind, float *win);

@@ -39,7 +39,8 @@ stage: a header line with the block indices and counts, then one line a block, o
 the SK of every bin (the zoom option: upper then lower sideband of each).
 --bank-readout reads the spectra and frequencies of all traces of the main bank with ONE call (bankread.bank_psd: every trace
 stitched on the device in one launch, one copy to the host) where the default asks psd() trace by trace; the lines and the files
-are the same, byte for byte.
+are the same, byte for byte.  With --pair it also reads the rows and frequencies of all pairs with ONE call (crossread.bank_csd)
+where the default asks csd() pair by pair; coherence and H1 are formed from those rows as before, so the lines and files are the same.
 --robust KIND[:NSIGMA] (repeatable; KIND one of median, min, max, excised) adds to every --waterfall / --zoom-waterfall trace the
 robust read-out of every stage (robust.stage_robust: over the stage's complete blocks, made on the device): behind the lines above,
 or with --csv in DIR/<the stage's file name>_robust.csv, a header line with the rows and blocks considered, then one line a KIND
@@ -113,7 +114,8 @@ def main(argv=None):
     ap.add_argument("--zoom-waterfall", action="append", default=[],
                     help="F0:BLOCK:DEPTH[:TRACE] -- the same, two-sided around the carrier F0 (repeatable)")
     ap.add_argument("--bank-readout", action="store_true",
-                    help="read every trace's spectrum and frequencies with ONE bankread.bank_psd call (the same output, byte for byte)")
+                    help="read every trace's spectrum and frequencies with ONE bankread.bank_psd call, and every --pair's rows with ONE "
+                         "crossread.bank_csd call (the same output, byte for byte)")
     ap.add_argument("--robust", action="append", default=[],
                     help="KIND[:NSIGMA] -- with --waterfall / --zoom-waterfall: per stage the median, min, max or SK-excised mean (within "
                          "NSIGMA sk_sigma of 1, default 3) over its complete blocks (repeatable)")
@@ -259,13 +261,21 @@ def cross_pairs(pkg, source, a, merge):
             break
         total += got
     src.close()
+    if a.bank_readout:  # every pair stitched on the device in one launch, one copy (include/psdcascade_crossread.h)
+        from stabilizer_stream_amd import crossread
+        allrows = crossread.bank_csd(cross, None, merge, frequencies=True)
     for i, (x, y) in enumerate(pairs):
         label = f"{x}:{y}"
         if cross.num_stages(i) == 0:
             print(f"{label}: no samples")
             continue
-        sxx, syy, sxy, breaks = cross.csd(i, merge)
-        freqs = pkg.Break.frequencies(breaks) * a.fs
+        if a.bank_readout:
+            ln = allrows["lens"][i]
+            sxx, syy, sxy = (allrows[k][i, :ln] for k in ("sxx", "syy", "sxy"))
+            freqs = allrows["frequencies"][i, :ln] * a.fs
+        else:
+            sxx, syy, sxy, breaks = cross.csd(i, merge)
+            freqs = pkg.Break.frequencies(breaks) * a.fs
         coh = pkg.coherence(sxx, syy, sxy)
         h1 = pkg.transfer(sxx, sxy)
         print(f"{label}: bins {sxx.size} median coherence {np.nanmedian(coh):.6g}")

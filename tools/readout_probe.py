@@ -13,6 +13,16 @@ the host clock.  All three go through the Python binding, as their callers do.  
 the rate ratios B / A and C / A of every turn (A: the mean of the turn's first two A legs for B, of its last two for C), and the
 largest |A' - A| / A between two A legs of a turn.  B and C hand their Breaks back unbuilt (the Python objects are made when
 `breaks` is first indexed; psd() builds them in every call): `breaks_us` is what building them once costs.  Findings, no gate.
+
+    python tools/readout_probe.py --cross [--seconds 0.3] [--out profiles/cross_readout_probe.json]
+
+The same for a CsdCascadeBank of P = 64 and 4 pairs at N = 1024, six live stages, read-outs only:
+  A  a loop over the P pairs of csd(p) plus numpy coherence() and transfer(): per pair two stream synchronisations, one blocking
+     copy a stage, four host stitches;
+  B  crossread.bank_csd(coherence=True, transfer=True): one launch, one copy, one synchronisation, host arrays;
+  C  crossread.bank_csd_device with the same five outputs into torch tensors, the form that returns when the kernel has completed.
+Five turns of A / B / C / A.  Reported: the median microseconds a read-out of all pairs of each leg, the rate ratios against the
+turn's two A legs, the largest |A' - A| / A of a turn, and `breaks_us`.  Findings, no gate.
 Needs a GPU."""
 import argparse
 import json
@@ -80,16 +90,98 @@ def config(pkg, bankread, torch, n, channels, seconds, reps):
             "A_spread_max": max(t["A_spread"] for t in turns)}
 
 
+CROSS_TURNS = 5
+
+
+def cross_config(pkg, crossread, torch, n, pairs, seconds):
+    import statistics
+    bank = pkg.CsdCascadeBank(n, pairs)
+    x = torch.rand(CALL, device="cuda", dtype=torch.float32) - 0.5
+    y = 0.6 * x + 0.8 * (torch.rand(CALL, device="cuda", dtype=torch.float32) - 0.5)
+    torch.cuda.synchronize()
+    need = int(1.1 * n * 8 ** (STAGES - 1))
+    for _ in range((need + CALL - 1) // CALL):
+        for p in range(pairs):
+            bank.process_device(p, x.data_ptr(), y.data_ptr(), CALL)
+    bank.sync()
+    lay = crossread.layout(bank)
+    live = [sum(b.count > 0 for b in br) for br in lay["breaks"]]
+    assert min(live) >= STAGES, live
+    width = lay["max_len"]
+    f32 = {k: torch.empty((pairs, w * width), device="cuda", dtype=torch.float32) for k, w in (("sxx", 1), ("syy", 1), ("sxy", 2))}
+    f64 = {k: torch.empty((pairs, w * width), device="cuda", dtype=torch.float64) for k, w in (("coherence", 1), ("transfer", 2))}
+    ptrs = {k: t.data_ptr() for k, t in {**f32, **f64}.items()}
+    torch.cuda.synchronize()
+
+    def leg_a():
+        out = []
+        for p in range(pairs):
+            sxx, syy, sxy, br = bank.csd(p)
+            out.append((sxx, syy, sxy, br, pkg.coherence(sxx, syy, sxy), pkg.transfer(sxx, sxy)))
+        return out
+
+    legs = {"A": leg_a, "B": lambda: crossread.bank_csd(bank, coherence=True, transfer=True),
+            "C": lambda: crossread.bank_csd_device(bank, width, **ptrs)}
+    # the three give the same rows before anything is timed
+    a, b = legs["A"](), legs["B"]()
+    legs["C"]()
+    dev = {k: t.cpu().numpy() for k, t in {**f32, **f64}.items()}
+    for p in range(pairs):
+        ln = b["lens"][p]
+        assert a[p][0].tobytes() == b["sxx"][p, :ln].tobytes() == dev["sxx"][p, :ln].tobytes(), p
+        assert a[p][2].tobytes() == b["sxy"][p, :ln].tobytes() == dev["sxy"][p, :2 * ln].tobytes(), p
+        assert b["coherence"][p, :ln].tobytes() == dev["coherence"][p, :ln].tobytes(), p
+    turns = []
+    for _ in range(CROSS_TURNS):
+        t = [window(legs[k], seconds) for k in "ABCA"]
+        turns.append({"A_us": [t[0], t[3]], "B_us": t[1], "C_us": t[2], "B_over_A": 0.5 * (t[0] + t[3]) / t[1],
+                      "C_over_A": 0.5 * (t[0] + t[3]) / t[2], "A_spread": abs(t[3] - t[0]) / t[0]})
+    r = legs["B"]()
+    t0 = time.perf_counter()
+    list(r["breaks"])
+    breaks_us = 1e6 * (time.perf_counter() - t0)
+    bank.close()
+    med = statistics.median
+    return {"n": n, "pairs": pairs, "breaks_us": breaks_us, "live_stages": min(live), "row_len": width, "launches_B": b["launches"], "turns": turns,
+            "A_us": med(v for t in turns for v in t["A_us"]), "B_us": med(t["B_us"] for t in turns), "C_us": med(t["C_us"] for t in turns),
+            "B_over_A": med(t["B_over_A"] for t in turns), "C_over_A": med(t["C_over_A"] for t in turns),
+            "A_spread_max": max(t["A_spread"] for t in turns)}
+
+
+def cross_main(a, torch, pkg):
+    from stabilizer_stream_amd import crossread
+    rows = [cross_config(pkg, crossread, torch, 1024, p, a.seconds) for p in (64, 4)]
+    rec = {"metric": "cross_readout_us", "unit": "microseconds a read-out of all pairs, median of the turns (host clock, through the Python binding)",
+           "note": "findings, no gate: A = csd(p) + numpy coherence() and transfer() over the pairs, B = crossread.bank_csd(coherence, transfer), "
+                   "C = crossread.bank_csd_device with the same five outputs (synchronising form); read-outs only, six live stages, no feed in the "
+                   "window; five turns of A / B / C / A; ratios are rates (above 1: faster than A); B and C do not build the Python Break objects "
+                   "(breaks_us: building them once), A's csd() does",
+           "device": torch.cuda.get_device_name(0), "seconds": a.seconds, "turns": CROSS_TURNS, "configs": rows}
+    line = json.dumps(rec)
+    with open(a.out or os.path.join(ROOT, "profiles", "cross_readout_probe.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+    for r in rows:
+        print(f"N={r['n']:5d} P={r['pairs']:3d}  A {r['A_us']:9.1f} us  B {r['B_us']:8.1f} us  C {r['C_us']:8.1f} us  "
+              f"B/A {r['B_over_A']:.2f}  C/A {r['C_over_A']:.2f}  A/A spread <= {r['A_spread_max']:.3f}  breaks {r['breaks_us']:.0f} us", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--seconds", type=float, default=None, help="a leg's window (default 0.5, with --cross 0.3)")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bank_readout_probe.json"))
+    ap.add_argument("--cross", action="store_true", help="measure the pair object's read-outs (crossread) instead")
+    ap.add_argument("--out", default=None, help="default profiles/bank_readout_probe.json, with --cross profiles/cross_readout_probe.json")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("readout_probe: no GPU is visible (there is nothing to measure without one)")
     pkg = entry.load_package()
+    if a.seconds is None:
+        a.seconds = 0.3 if a.cross else 0.5
+    if a.cross:
+        return cross_main(a, torch, pkg)
+    a.out = a.out or os.path.join(ROOT, "profiles", "bank_readout_probe.json")
     from stabilizer_stream_amd import bankread
     rows = [config(pkg, bankread, torch, n, c, a.seconds, a.reps) for n in (512, 1024, 4096) for c in (4, 64)]
     rec = {"metric": "bank_readout_us", "unit": "microseconds a read-out of all channels (host clock, through the Python binding)",
