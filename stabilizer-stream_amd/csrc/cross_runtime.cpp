@@ -25,6 +25,12 @@
 // Stage k + 1 consumes what stage k produced in earlier rounds, so a round is three launches whatever the depth and the pair
 // count (more only when a round's job tables overflow a launch).  Read-outs drain: rounds until no stage has work.
 // There is no CPU compute path.
+//
+// The host read-outs of a unit share one path ("the host read-outs of a unit", below): a stage read-out looks its stage up in one
+// place (drained_stage) and copies its rows through one copier (stage_rows); a stitched read-out takes ONE snapshot of the drained
+// unit (UnitSnap: counts, averages, pendings and, one copy a stage, the f64 accumulators), stitches the f32 cast of its leading
+// rows and writes len, n_breaks and the Breaks in one place (unit_stitch); what a family computes in f64 from the bins that stitch
+// took (SK, the sidebands) is an expression on one walk over them (Stitched::each_bin).
 #include "csm.h"
 #include "zoom_cross.h"
 #include "iq.h"
@@ -50,13 +56,14 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace psdk;
 
 #if !defined(__HIPCC__)
-// A host build of this file (tests/host/cross_feed_check: the HIP runtime modelled on the CPU, no device code) sees none of the
+// A host build of this file (tests/host/cross_feed_check and cross_read_check: the HIP runtime modelled on the CPU, no device code) sees none of the
 // launchers of sample_int.h, which declares them for hipcc alone.  The integer mixers are the check program's models; there is
 // no converter, as in a host build of runtime.cpp: the integer feeds of the pair and matrix objects fail there with a device error.
 namespace psdk {
@@ -1540,6 +1547,28 @@ int num_stages_impl(XObj *h, uint32_t pair, const char *who)
     return (int)h->pairs[pair].size();
 }
 
+// ---- the host read-outs of a unit --------------------------------------------------------------------------------------------
+// Every one is built from the five pieces below.  A stage read-out is drained_stage and stage_rows: the stage's f64 accumulators,
+// row by row, to where the call wants them.  A stitched read-out is unit_stitch: it drains, waits and takes ONE snapshot of the unit
+// (UnitSnap: counts, averages, pendings and, with one copy a stage, the f64 accumulators), casts the leading rows to f32 and hands
+// them to the row stitch of PsdCascade::psd (stitch_rows_impl), which also writes the f32 outputs; the capacity checks, len,
+// n_breaks and the Breaks are written in one place.  What a family computes in f64 from the bins that stitch took (SK, the
+// sidebands) is an expression on Stitched::each_bin.  The bank read-outs (psdcxr_*) take the snapshot's bookkeeping alone.
+
+// a drained stage of a unit (the caller has checked the handle and the unit and is on the device)
+int drained_stage(XObj *h, uint32_t unit, uint32_t stage, const XStage **out, const char *who)
+{
+    int rc = drain(h);
+    if (rc)
+        return rc;
+    const auto &st = h->pairs[unit];
+    if (stage >= st.size())
+        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": stage " + std::to_string(stage) + " out of range (" +
+                                          std::to_string(st.size()) + " stages)");
+    *out = &st[stage];
+    return PSDC_OK;
+}
+
 // one stage's statistics and, with acc != NULL, its rows() x bins accumulators as they lie on the device
 int stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, std::vector<double> *acc, const char *who)
 {
@@ -1548,13 +1577,10 @@ int stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, st
     if (rc)
         return rc;
     X_ON_DEVICE(h);
-    if ((rc = drain(h)))
+    const XStage *sp = nullptr;
+    if ((rc = drained_stage(h, pair, stage, &sp, who)))
         return rc;
-    auto &st = h->pairs[pair];
-    if (stage >= st.size())
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": stage " + std::to_string(stage) + " out of range (" +
-                                          std::to_string(st.size()) + " stages)");
-    const XStage &s = st[stage];
+    const XStage &s = *sp;
     if (stat) {
         const uint32_t c = count_report(s.count64);
         stat->count = c;
@@ -1571,79 +1597,243 @@ int stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, st
     return PSDC_OK;
 }
 
-// what a stitch of one pair / group needs: counts, averages, pendings and the f32 rows of every stage (n_stages x rows() x bins)
-struct StitchIn {
-    std::vector<uint64_t> c64, pend;
-    std::vector<uint32_t> avgs;
-    std::vector<float> rows;
-    uint32_t ns = 0;
+// where a row of a read-out goes: element k to p[k * step]; p == NULL: the row is not wanted.  The re and im rows of a complex
+// output are the two halves of one interleaved array (re_of, im_of)
+template <class T>
+struct RowOut {
+    T *p = nullptr;
+    size_t step = 1;
+};
+template <class T>
+RowOut<T> re_of(T *z) { return {z, 2}; }
+template <class T>
+RowOut<T> im_of(T *z) { return {z ? z + 1 : nullptr, 2}; }
+template <class T>
+void put_row(const RowOut<T> &o, const T *src, size_t len)
+{
+    for (size_t k = 0; o.p && k < len; ++k)
+        o.p[k * o.step] = src[k];
+}
+constexpr uint32_t X_MAX_ROWS = 16; // rows a stage has at most: CSM_MAX_M^2 (the AM/PM cross kinds: ZXAMPM_ROWS = 12)
+static_assert(CSM_MAX_M * CSM_MAX_M <= X_MAX_ROWS && ZXAMPM_ROWS <= X_MAX_ROWS, "RowOut tables hold every row of a stage");
+// nrows rows one behind the other, `stride` elements apart (rows == NULL: none is wanted)
+template <class T>
+void block_rows(T *rows, uint32_t nrows, size_t stride, RowOut<T> *outs)
+{
+    for (uint32_t r = 0; r < nrows; ++r)
+        outs[r] = {rows ? rows + (size_t)r * stride : nullptr, 1};
+}
+
+// the rows of one stage, each to where outs[r] says (T: float, cast from the f64 accumulators, or double); beside its statistics
+template <class T>
+int stage_rows(XObj *h, uint32_t unit, uint32_t stage, psdc_stage_stat *stat, const RowOut<T> *outs, uint32_t nrows, const char *who)
+{
+    std::vector<double> acc;
+    const bool any = std::any_of(outs, outs + nrows, [](const RowOut<T> &o) { return o.p != nullptr; });
+    int rc = stage_impl(h, unit, stage, stat, any ? &acc : nullptr, who);
+    if (rc || acc.empty())
+        return rc;
+    const size_t b = bins(h);
+    for (uint32_t r = 0; r < nrows; ++r)
+        for (size_t k = 0; outs[r].p && k < b; ++k)
+            outs[r].p[k * outs[r].step] = (T)acc[r * b + k];
+    return PSDC_OK;
+}
+// ... with every row of the stage one behind the other in `rows`
+template <class T>
+int stage_block(XObj *h, uint32_t unit, uint32_t stage, psdc_stage_stat *stat, T *rows, const char *who)
+{
+    RowOut<T> outs[X_MAX_ROWS];
+    const uint32_t nrows = h ? h->rows() : 0;
+    block_rows(rows, nrows, h ? bins(h) : 0, outs);
+    return stage_rows(h, unit, stage, stat, outs, nrows, who);
+}
+
+// which stages and bins a stitch takes (PsdCascade::psd's arguments), and where a stitched read-out puts what every one has
+struct StitchSel {
+    int keep_overlap;
+    uint32_t min_count;
+    int keep_transition_band;
+};
+struct StitchOut {
+    size_t cap; // elements every output row has room for
+    size_t *len;
+    psdc_break *breaks;
+    size_t breaks_cap;
+    size_t *n_breaks;
 };
 
-int stitch_in(XObj *h, uint32_t pair, StitchIn *in)
+// A drained unit as a stitch sees it: of every stage the count, the average and the pending samples and, where they were asked
+// for, the f64 accumulators as they lie on the device (ns x rows() x bins)
+struct UnitSnap {
+    uint32_t ns = 0;
+    size_t bins = 0, stage_elems = 0; // (rows() x bins)
+    std::vector<uint64_t> c64, pend;
+    std::vector<uint32_t> avgs;
+    std::unique_ptr<double[]> acc; // (not a vector: every element is copied over, none needs a zero first)
+    const double *stage(size_t i) const { return acc.get() + i * stage_elems; }
+    // the first nlead rows of every stage in f32, as the row stitch takes them (ns x nlead x bins)
+    std::unique_ptr<float[]> lead(uint32_t nlead) const
+    {
+        std::unique_ptr<float[]> rows(new float[std::max<size_t>(1, (size_t)ns * nlead * bins)]);
+        for (uint32_t i = 0; i < ns; ++i)
+            for (size_t k = 0; k < nlead * bins; ++k)
+                rows[(size_t)i * nlead * bins + k] = (float)stage(i)[k];
+        return rows;
+    }
+};
+
+// the bookkeeping of a unit (the caller has drained; no device call)
+void unit_layout(const XObj *h, uint32_t unit, UnitSnap *in)
 {
-    int rc;
-    if ((rc = drain(h)) || (rc = sync_all(h)))
-        return rc;
-    const auto &st = h->pairs[pair];
+    const auto &st = h->pairs[unit];
     const uint32_t ns = (uint32_t)st.size();
-    const size_t e = h->rows() * bins(h);
     in->ns = ns;
+    in->bins = bins(h);
+    in->stage_elems = h->rows() * in->bins;
     in->c64.resize(std::max<uint32_t>(ns, 1));
     in->pend.resize(std::max<uint32_t>(ns, 1));
     in->avgs.resize(std::max<uint32_t>(ns, 1));
-    in->rows.resize(std::max<size_t>(1, (size_t)ns * e));
-    std::vector<double> acc(e);
     for (uint32_t i = 0; i < ns; ++i) {
         in->c64[i] = st[i].count64;
         in->pend[i] = pending_for(h->geo, st[i].total);
         in->avgs[i] = cur_avg(h, i);
-        XCHK(h, hipMemcpy(acc.data(), st[i].acc, sizeof(double) * e, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < e; ++k)
-            in->rows[(size_t)i * e + k] = (float)acc[k];
     }
+}
+
+// drain, wait, and the unit with its accumulators: one copy a stage
+int unit_snap(XObj *h, uint32_t unit, UnitSnap *in)
+{
+    int rc;
+    if ((rc = drain(h)) || (rc = sync_all(h)))
+        return rc;
+    unit_layout(h, unit, in);
+    in->acc.reset(new double[std::max<size_t>(1, in->ns * in->stage_elems)]);
+    for (uint32_t i = 0; i < in->ns; ++i)
+        XCHK(h, hipMemcpy(in->acc.get() + i * in->stage_elems, h->pairs[unit][i].acc, sizeof(double) * in->stage_elems, hipMemcpyDeviceToHost));
     return PSDC_OK;
 }
 
-// psdc_stitch_window on each of `nrows` rows of caller stages (n_stages x nrows x (n/2+1)); outs[r] NULL: that row is not
-// wanted (its length is still computed); Breaks from row 0
+// psdc_stitch_window on each of `nrows` rows of caller stages (n_stages x nrows x (n/2+1)) into outs[r] (a row that is not wanted
+// still has its length computed; a row with a step is stitched aside and spread out once every row has come); Breaks from row 0
 int stitch_rows_impl(const char *who, uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
-                     const uint32_t *avgs, const uint64_t *pendings, const float *rows, uint32_t nrows, int keep_overlap,
-                     uint32_t min_count, int keep_transition_band, float *const *outs, size_t cap, size_t *len, psdc_break *breaks,
-                     size_t breaks_cap, size_t *n_breaks)
+                     const uint32_t *avgs, const uint64_t *pendings, const float *rows, uint32_t nrows, const StitchSel &sel,
+                     const RowOut<float> *outs, const StitchOut &o)
 {
-    if (n < 2 || overlap >= n || n_stages > 20)
+    if (n < 2 || overlap >= n || n_stages > 20 || nrows > X_MAX_ROWS)
         return xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": bad arguments");
     if (n_stages && (!counts64 || !avgs || !pendings || !rows))
         return xfail(nullptr, PSDC_ERR_ARG, std::string(who) + ": null input");
     const size_t b = n / 2 + 1;
     std::vector<float> sp(std::max<size_t>(1, (size_t)n_stages * b));
+    float *dst[X_MAX_ROWS];
+    size_t aside = 0;
+    for (uint32_t r = 0; r < nrows; ++r)
+        aside += outs[r].p && outs[r].step != 1;
+    std::vector<float> tmp(std::max<size_t>(1, aside * o.cap));
+    for (uint32_t r = 0, t = 0; r < nrows; ++r)
+        dst[r] = !outs[r].p ? nullptr : outs[r].step == 1 ? outs[r].p : &tmp[t++ * o.cap];
     size_t plen = 0;
     bool any = false;
     for (uint32_t r = 0; r < nrows; ++r) {
         for (uint32_t i = 0; i < n_stages; ++i)
             memcpy(&sp[(size_t)i * b], rows + ((size_t)i * nrows + r) * b, sizeof(float) * b);
-        any = any || outs[r];
+        any = any || dst[r];
         size_t l = 0, nb = 0;
-        int rc = psdc_stitch_window(n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, sp.data(), keep_overlap,
-                                    min_count, keep_transition_band, outs[r], outs[r] ? cap : 0, &l, r == 0 ? breaks : nullptr,
-                                    r == 0 ? breaks_cap : 0, &nb);
+        int rc = psdc_stitch_window(n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, sp.data(), sel.keep_overlap,
+                                    sel.min_count, sel.keep_transition_band, dst[r], dst[r] ? o.cap : 0, &l, r == 0 ? o.breaks : nullptr,
+                                    r == 0 ? o.breaks_cap : 0, &nb);
         if (rc == PSDC_ERR_CAPACITY)
             return xfail(nullptr, rc, std::string(who) + ": output too small");
         if (rc)
             return xfail(nullptr, rc, std::string(who) + ": " + psdc_last_error(nullptr));
         if (r == 0) {
             plen = l;
-            if (n_breaks)
-                *n_breaks = nb;
-            if (breaks && nb > breaks_cap)
+            if (o.n_breaks)
+                *o.n_breaks = nb;
+            if (o.breaks && nb > o.breaks_cap)
                 return xfail(nullptr, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
         }
     }
-    if (any && plen > cap)
+    if (any && plen > o.cap)
         return xfail(nullptr, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
-    if (len)
-        *len = plen;
+    for (uint32_t r = 0; r < nrows; ++r)
+        if (dst[r] && dst[r] != outs[r].p)
+            put_row(outs[r], dst[r], plen);
+    if (o.len)
+        *o.len = plen;
     return PSDC_OK;
+}
+
+// what unit_stitch leaves for a caller that goes on: the unit, and the length and the Breaks of its stitch
+struct Stitched {
+    UnitSnap snap;
+    psdc_break br[X_MAX_STAGES];
+    size_t len = 0, nb = 0;
+    // f(stage, bin, out, Break) for every bin the stitch took: bin `bin` of stage `stage` is element `out` of an output row
+    template <class F>
+    void each_bin(F f) const
+    {
+        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
+            if (!br[i].include)
+                continue;
+            for (uint64_t k = br[i].bins_start; k < br[i].bins_end; ++k)
+                f(snap.ns - 1 - i, (size_t)k, (size_t)(br[i].start + (k - br[i].bins_start)), br[i]);
+        }
+    }
+};
+
+// Who keeps the Breaks while the rows are stitched.  The two answer a too small breaks_cap differently, and each family's answer
+// is kept as it was (tests/golden/cross_read_dump.bin holds both):
+//   CALLER  the families whose every row is an f32 output (pair, matrix, zoom, IQ and their cross forms) hand the caller's array to
+//           the stitch: it is filled up to breaks_cap, row 0 alone is written, len and n_breaks are not, and the text is
+//           "<stitch_who>: output too small";
+//   OWN     the families that go on in f64 (SK, zoom / IQ SK, AM/PM and AM/PM cross) stitch into Stitched::br: every row, len and
+//           n_breaks are written, no Break is, and the text is "<who>: breaks output too small".
+enum class BreaksOf { CALLER, OWN };
+
+// The stitched read-out of a unit: the checks of the handle, the unit and the device, the snapshot, the f32 stitch of the unit's
+// first nlead rows into outs, then the capacity checks, len, n_breaks and the Breaks.  more: the caller has further outputs of `cap`
+// elements to fill (from st).  stitch_who: the name the row stitch gives its errors.
+int unit_stitch(XObj *h, uint32_t unit, const StitchSel &sel, uint32_t nlead, const RowOut<float> *outs, bool more, const StitchOut &o,
+                BreaksOf breaks_of, const char *stitch_who, const char *who, Stitched *st)
+{
+    X_HANDLE(h, who);
+    int rc = check_pair(h, unit);
+    if (rc)
+        return rc;
+    X_ON_DEVICE(h);
+    if ((rc = unit_snap(h, unit, &st->snap)))
+        return rc;
+    const UnitSnap &in = st->snap;
+    const bool own = breaks_of == BreaksOf::OWN;
+    const StitchOut so = own ? StitchOut{o.cap, &st->len, st->br, X_MAX_STAGES, &st->nb} : StitchOut{o.cap, &st->len, o.breaks, o.breaks_cap, o.n_breaks};
+    rc = stitch_rows_impl(stitch_who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
+                          in.lead(nlead).get(), nlead, sel, outs, so);
+    if (rc)
+        return xfail(h, rc, x_last_error);
+    if (own && more && st->len > o.cap)
+        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
+    if (o.len)
+        *o.len = st->len;
+    if (!own)
+        return PSDC_OK;
+    if (o.n_breaks)
+        *o.n_breaks = st->nb;
+    if (o.breaks) {
+        if (st->nb > o.breaks_cap)
+            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
+        std::copy(st->br, st->br + st->nb, o.breaks);
+    }
+    return PSDC_OK;
+}
+
+// ... of a family whose every row is an f32 output: all nrows = rows() of them
+int unit_stitch_rows(XObj *h, uint32_t unit, const StitchSel &sel, const RowOut<float> *outs, uint32_t nrows, const StitchOut &o,
+                     const char *stitch_who, const char *who)
+{
+    Stitched st;
+    return unit_stitch(h, unit, sel, nrows, outs, false, o, BreaksOf::CALLER, stitch_who, who, &st);
 }
 
 int stats_impl(XObj *h, uint64_t *launches, uint64_t *in, int reset, const char *who)
@@ -1724,38 +1914,14 @@ int set_carrier_impl(XObj *h, uint32_t channel, uint64_t ftw, uint64_t phase0, c
 // the two rows of one stage / the stitched two rows of a channel (psdc_zoom, psdc_iq)
 int two_rows_stage_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, float *upper, float *lower, const char *who)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, channel, stage, stat, upper || lower ? &acc : nullptr, who);
-    if (rc || acc.empty())
-        return rc;
-    const size_t b = bins(h);
-    for (size_t k = 0; k < b; ++k) {
-        if (upper)
-            upper[k] = (float)acc[k];
-        if (lower)
-            lower[k] = (float)acc[b + k];
-    }
-    return PSDC_OK;
+    const RowOut<float> outs[2] = {{upper}, {lower}};
+    return stage_rows(h, channel, stage, stat, outs, 2, who);
 }
 
-int two_rows_psd_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
-                      float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+int two_rows_psd_impl(XObj *h, uint32_t channel, const StitchSel &sel, float *upper, float *lower, const StitchOut &o, const char *who)
 {
-    X_HANDLE(h, who);
-    int rc = check_pair(h, channel);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, channel, &in)))
-        return rc;
-    float *outs[2] = {upper, lower};
-    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                          in.rows.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap,
-                          n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    return PSDC_OK;
+    const RowOut<float> outs[2] = {{upper}, {lower}};
+    return unit_stitch_rows(h, channel, sel, outs, 2, o, who, who);
 }
 
 // the carrier of one side of a pair of a two-channels-a-unit object (psdc_zcsd, psdc_iqcsd)
@@ -1776,53 +1942,13 @@ int pair_carrier_impl(XObj *h, uint32_t pair, uint32_t side, uint64_t ftw, uint6
     return PSDC_OK;
 }
 
-// the eight rows of one stage / the stitched rows of a pair (psdc_zcsd, psdc_iqcsd)
-int eight_rows_stage_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows, const char *who)
+// the stitched rows of a pair (psdc_zcsd, psdc_iqcsd): the complex rows are stitched as their real and imaginary rows, as
+// psdc_cross_stitch does
+int eight_rows_csd_impl(XObj *h, uint32_t pair, const StitchSel &sel, float *saa_upper, float *saa_lower, float *sbb_upper, float *sbb_lower,
+                        float *sab_upper, float *sab_lower, const StitchOut &o, const char *who)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, who);
-    if (rc)
-        return rc;
-    for (size_t e = 0; e < acc.size(); ++e)
-        rows[e] = (float)acc[e];
-    return PSDC_OK;
-}
-
-int eight_rows_csd_impl(XObj *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
-                        float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap,
-                        size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
-{
-    X_HANDLE(h, who);
-    int rc = check_pair(h, pair);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, pair, &in)))
-        return rc;
-    // the complex rows are stitched as their real and imaginary rows and interleaved afterwards, as psdc_cross_stitch does
-    std::vector<float> tmp(4 * (cap ? cap : 1));
-    float *outs[8] = {saa_upper, saa_lower, sbb_upper, sbb_lower, sab_upper ? &tmp[0] : nullptr, sab_lower ? &tmp[cap] : nullptr,
-                      sab_upper ? &tmp[2 * cap] : nullptr, sab_lower ? &tmp[3 * cap] : nullptr};
-    size_t plen = 0;
-    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                          in.rows.data(), 8, keep_overlap, min_count, keep_transition_band, outs, cap, &plen, breaks, breaks_cap,
-                          n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    for (size_t k = 0; k < plen; ++k) {
-        if (sab_upper) {
-            sab_upper[2 * k] = tmp[k];
-            sab_upper[2 * k + 1] = tmp[2 * cap + k];
-        }
-        if (sab_lower) {
-            sab_lower[2 * k] = tmp[cap + k];
-            sab_lower[2 * k + 1] = tmp[3 * cap + k];
-        }
-    }
-    if (len)
-        *len = plen;
-    return PSDC_OK;
+    const RowOut<float> outs[8] = {{saa_upper}, {saa_lower}, {sbb_upper}, {sbb_lower}, re_of(sab_upper), re_of(sab_lower), im_of(sab_upper), im_of(sab_lower)};
+    return unit_stitch_rows(h, pair, sel, outs, 8, o, who, who);
 }
 
 int loss_impl(XObj *h, psdc_loss *out, int reset, const char *who)
@@ -1878,22 +2004,8 @@ int psdc_cross_num_stages(psdc_cross *h, uint32_t pair) { return num_stages_impl
 int psdc_cross_stage_spectra(psdc_cross *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *sxx, float *syy,
                              float *sxy)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, pair, stage, stat, sxx || syy || sxy ? &acc : nullptr, "psdc_cross_stage_spectra");
-    if (rc || acc.empty())
-        return rc;
-    const size_t b = bins(h);
-    for (size_t k = 0; k < b; ++k) {
-        if (sxx)
-            sxx[k] = (float)acc[k];
-        if (syy)
-            syy[k] = (float)acc[b + k];
-        if (sxy) {
-            sxy[2 * k] = (float)acc[2 * b + k];
-            sxy[2 * k + 1] = (float)acc[3 * b + k];
-        }
-    }
-    return PSDC_OK;
+    const RowOut<float> outs[4] = {{sxx}, {syy}, re_of(sxy), im_of(sxy)};
+    return stage_rows(h, pair, stage, stat, outs, 4, "psdc_cross_stage_spectra");
 }
 
 int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
@@ -1902,40 +2014,17 @@ int psdc_cross_stitch(uint32_t n, float power, float nenbw, size_t overlap, uint
                       psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
     // the four rows of every stage as four spectra slabs, each stitched exactly as PsdCascade::psd
-    std::vector<float> re(cap ? cap : 1), im(cap ? cap : 1);
-    float *outs[4] = {sxx, syy, sxy ? re.data() : nullptr, sxy ? im.data() : nullptr};
-    size_t plen = 0;
-    int rc = stitch_rows_impl("psdc_cross_stitch", n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, rows, 4, keep_overlap,
-                              min_count, keep_transition_band, outs, cap, &plen, breaks, breaks_cap, n_breaks);
-    if (rc)
-        return rc;
-    if (sxy)
-        for (size_t k = 0; k < plen; ++k) {
-            sxy[2 * k] = re[k];
-            sxy[2 * k + 1] = im[k];
-        }
-    if (len)
-        *len = plen;
-    return PSDC_OK;
+    const RowOut<float> outs[4] = {{sxx}, {syy}, re_of(sxy), im_of(sxy)};
+    return stitch_rows_impl("psdc_cross_stitch", n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, rows, 4,
+                            {keep_overlap, min_count, keep_transition_band}, outs, {cap, len, breaks, breaks_cap, n_breaks});
 }
 
 int psdc_cross_csd(psdc_cross *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *sxx,
                    float *syy, float *sxy, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    X_HANDLE(h, "psdc_cross_csd");
-    int rc = check_pair(h, pair);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, pair, &in)))
-        return rc;
-    rc = psdc_cross_stitch(h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                           in.rows.data(), keep_overlap, min_count, keep_transition_band, sxx, syy, sxy, cap, len, breaks,
-                           breaks_cap, n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    return PSDC_OK;
+    const RowOut<float> outs[4] = {{sxx}, {syy}, re_of(sxy), im_of(sxy)};
+    return unit_stitch_rows(h, pair, {keep_overlap, min_count, keep_transition_band}, outs, 4, {cap, len, breaks, breaks_cap, n_breaks},
+                            "psdc_cross_stitch", "psdc_cross_csd");
 }
 
 int psdc_cross_stats_read(psdc_cross *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -2008,13 +2097,7 @@ int psdc_csm_num_stages(psdc_csm *h, uint32_t group) { return num_stages_impl(h,
 
 int psdc_csm_stage_spectra(psdc_csm *h, uint32_t group, uint32_t stage, psdc_stage_stat *stat, float *rows)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, group, stage, stat, rows ? &acc : nullptr, "psdc_csm_stage_spectra");
-    if (rc)
-        return rc;
-    for (size_t e = 0; e < acc.size(); ++e)
-        rows[e] = (float)acc[e];
-    return PSDC_OK;
+    return stage_block(h, group, stage, stat, rows, "psdc_csm_stage_spectra");
 }
 
 int psdc_csm_stitch(uint32_t n, uint32_t m, float power, float nenbw, size_t overlap, uint32_t n_stages, const uint64_t *counts64,
@@ -2024,30 +2107,20 @@ int psdc_csm_stitch(uint32_t n, uint32_t m, float power, float nenbw, size_t ove
 {
     if (m < 2 || m > CSM_MAX_M)
         return xfail(nullptr, PSDC_ERR_ARG, "psdc_csm_stitch: m must be 2, 3 or 4");
-    float *outs[CSM_MAX_M * CSM_MAX_M];
-    for (uint32_t r = 0; r < m * m; ++r)
-        outs[r] = rows ? rows + (size_t)r * cap : nullptr;
+    RowOut<float> outs[X_MAX_ROWS];
+    block_rows(rows, m * m, cap, outs);
     return stitch_rows_impl("psdc_csm_stitch", n, power, nenbw, overlap, n_stages, counts64, avgs, pendings, rows_in, m * m,
-                            keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks);
+                            {keep_overlap, min_count, keep_transition_band}, outs, {cap, len, breaks, breaks_cap, n_breaks});
 }
 
 int psdc_csm_csd(psdc_csm *h, uint32_t group, int keep_overlap, uint32_t min_count, int keep_transition_band, float *rows,
                  size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    X_HANDLE(h, "psdc_csm_csd");
-    int rc = check_pair(h, group);
-    if (rc)
-        return rc;
-    X_ON_DEVICE(h);
-    StitchIn in;
-    if ((rc = stitch_in(h, group, &in)))
-        return rc;
-    rc = psdc_csm_stitch(h->n, h->m, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                         in.rows.data(), keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap,
-                         n_breaks);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    return PSDC_OK;
+    RowOut<float> outs[X_MAX_ROWS];
+    const uint32_t nrows = h ? h->rows() : 0;
+    block_rows(rows, nrows, cap, outs);
+    return unit_stitch_rows(h, group, {keep_overlap, min_count, keep_transition_band}, outs, nrows, {cap, len, breaks, breaks_cap, n_breaks},
+                            "psdc_csm_stitch", "psdc_csm_csd");
 }
 
 int psdc_csm_stats_read(psdc_csm *h, uint64_t *launches, uint64_t *sample_times_in, int reset)
@@ -2118,8 +2191,8 @@ int psdc_zoom_stage_spectra(psdc_zoom *h, uint32_t channel, uint32_t stage, psdc
 int psdc_zoom_psd(psdc_zoom *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
                   float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return two_rows_psd_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, cap, len, breaks, breaks_cap,
-                             n_breaks, "psdc_zoom_psd");
+    return two_rows_psd_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower,
+                             {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zoom_psd");
 }
 
 int psdc_zoom_stats_read(psdc_zoom *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -2198,8 +2271,8 @@ int psdc_iq_stage_spectra(psdc_iq *h, uint32_t channel, uint32_t stage, psdc_sta
 int psdc_iq_psd(psdc_iq *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
                 float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return two_rows_psd_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, cap, len, breaks, breaks_cap,
-                             n_breaks, "psdc_iq_psd");
+    return two_rows_psd_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower,
+                             {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iq_psd");
 }
 
 int psdc_iq_stats_read(psdc_iq *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -2253,15 +2326,16 @@ int psdc_zcsd_num_stages(psdc_zcsd *h, uint32_t pair) { return num_stages_impl(h
 
 int psdc_zcsd_stage_spectra(psdc_zcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows)
 {
-    return eight_rows_stage_impl(h, pair, stage, stat, rows, "psdc_zcsd_stage_spectra");
+    return stage_block(h, pair, stage, stat, rows, "psdc_zcsd_stage_spectra");
 }
 
 int psdc_zcsd_csd(psdc_zcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
                   float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap, size_t *len,
                   psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return eight_rows_csd_impl(h, pair, keep_overlap, min_count, keep_transition_band, saa_upper, saa_lower, sbb_upper, sbb_lower,
-                               sab_upper, sab_lower, cap, len, breaks, breaks_cap, n_breaks, "psdc_zcsd_csd");
+    return eight_rows_csd_impl(h, pair, {keep_overlap, min_count, keep_transition_band}, saa_upper, saa_lower, sbb_upper,
+                               sbb_lower, sab_upper, sab_lower,
+                               {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zcsd_csd");
 }
 
 int psdc_zcsd_stats_read(psdc_zcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -2361,15 +2435,16 @@ int psdc_iqcsd_num_stages(psdc_iqcsd *h, uint32_t pair) { return num_stages_impl
 
 int psdc_iqcsd_stage_spectra(psdc_iqcsd *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, float *rows)
 {
-    return eight_rows_stage_impl(h, pair, stage, stat, rows, "psdc_iqcsd_stage_spectra");
+    return stage_block(h, pair, stage, stat, rows, "psdc_iqcsd_stage_spectra");
 }
 
 int psdc_iqcsd_csd(psdc_iqcsd *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, float *saa_upper,
                    float *saa_lower, float *sbb_upper, float *sbb_lower, float *sab_upper, float *sab_lower, size_t cap, size_t *len,
                    psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return eight_rows_csd_impl(h, pair, keep_overlap, min_count, keep_transition_band, saa_upper, saa_lower, sbb_upper, sbb_lower,
-                               sab_upper, sab_lower, cap, len, breaks, breaks_cap, n_breaks, "psdc_iqcsd_csd");
+    return eight_rows_csd_impl(h, pair, {keep_overlap, min_count, keep_transition_band}, saa_upper, saa_lower, sbb_upper,
+                               sbb_lower, sab_upper, sab_lower,
+                               {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqcsd_csd");
 }
 
 int psdc_iqcsd_stats_read(psdc_iqcsd *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -2471,58 +2546,18 @@ double sk_estimate(uint32_t count, double s1, double s2)
 }
 
 // the stitch of row 0 (psd != NULL: written) and, with sk != NULL, the SK of every bin the stitch takes, selected by its Breaks
-int sk_readout_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *psd, double *sk,
-                    size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+int sk_readout_impl(XObj *h, uint32_t channel, const StitchSel &sel, float *psd, double *sk, const StitchOut &o, const char *who)
 {
-    X_HANDLE(h, who);
-    int rc = check_pair(h, channel);
-    if (rc)
+    const RowOut<float> outs[1] = {{psd}};
+    Stitched st;
+    int rc = unit_stitch(h, channel, sel, 1, outs, sk != nullptr, o, BreaksOf::OWN, who, who, &st);
+    if (rc || !sk)
         return rc;
-    X_ON_DEVICE(h);
-    if ((rc = drain(h)) || (rc = sync_all(h)))
-        return rc;
-    const auto &st = h->pairs[channel];
-    const uint32_t ns = (uint32_t)st.size();
     const size_t b = bins(h);
-    std::vector<uint64_t> c64(std::max<uint32_t>(ns, 1)), pend(std::max<uint32_t>(ns, 1));
-    std::vector<uint32_t> avgs(std::max<uint32_t>(ns, 1));
-    std::vector<double> acc((size_t)ns * SK_ROWS * b);
-    std::vector<float> row0(std::max<size_t>(1, (size_t)ns * b));
-    for (uint32_t i = 0; i < ns; ++i) {
-        c64[i] = st[i].count64;
-        pend[i] = pending_for(h->geo, st[i].total);
-        avgs[i] = cur_avg(h, i);
-        double *a = &acc[(size_t)i * SK_ROWS * b];
-        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * SK_ROWS * b, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < b; ++k)
-            row0[(size_t)i * b + k] = (float)a[k];
-    }
-    psdc_break own[X_MAX_STAGES];
-    size_t l = 0, nb = 0;
-    rc = psdc_stitch_window(h->n, h->power, h->nenbw, h->geo.overlap, ns, c64.data(), avgs.data(), pend.data(), row0.data(),
-                            keep_overlap, min_count, keep_transition_band, psd, psd ? cap : 0, &l, own, X_MAX_STAGES, &nb);
-    if (rc == PSDC_ERR_CAPACITY || ((psd || sk) && l > cap))
-        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
-    if (rc)
-        return xfail(h, rc, std::string(who) + ": " + psdc_last_error(nullptr));
-    if (len)
-        *len = l;
-    if (n_breaks)
-        *n_breaks = nb;
-    if (breaks) {
-        if (nb > breaks_cap)
-            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
-        std::copy(own, own + nb, breaks);
-    }
-    if (sk)
-        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
-            const psdc_break &br = own[i];
-            if (!br.include)
-                continue;
-            const double *a = &acc[(size_t)(ns - 1 - i) * SK_ROWS * b];
-            for (uint64_t k = br.bins_start; k < br.bins_end; ++k)
-                sk[br.start + (k - br.bins_start)] = sk_estimate(br.count, a[k], a[b + k]);
-        }
+    st.each_bin([&](size_t stage, size_t k, size_t out, const psdc_break &br) {
+        const double *a = st.snap.stage(stage);
+        sk[out] = sk_estimate(br.count, a[k], a[b + k]);
+    });
     return PSDC_OK;
 }
 
@@ -2565,30 +2600,22 @@ int psdc_sk_num_stages(psdc_sk *h, uint32_t channel) { return num_stages_impl(h,
 
 int psdc_sk_stage_moments(psdc_sk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1, double *s2)
 {
-    std::vector<double> acc;
-    int rc = stage_impl(h, channel, stage, stat, s1 || s2 ? &acc : nullptr, "psdc_sk_stage_moments");
-    if (rc || acc.empty())
-        return rc;
-    const size_t b = bins(h);
-    if (s1)
-        std::copy(acc.begin(), acc.begin() + b, s1);
-    if (s2)
-        std::copy(acc.begin() + b, acc.begin() + 2 * b, s2);
-    return PSDC_OK;
+    const RowOut<double> outs[SK_ROWS] = {{s1}, {s2}};
+    return stage_rows(h, channel, stage, stat, outs, SK_ROWS, "psdc_sk_stage_moments");
 }
 
 int psdc_sk_psd(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *psd, size_t cap,
                 size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return sk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, psd, nullptr, cap, len, breaks, breaks_cap,
-                           n_breaks, "psdc_sk_psd");
+    return sk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, psd, nullptr,
+                           {cap, len, breaks, breaks_cap, n_breaks}, "psdc_sk_psd");
 }
 
 int psdc_sk_sk(psdc_sk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk, size_t cap,
                size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return sk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, sk, cap, len, breaks, breaks_cap,
-                           n_breaks, "psdc_sk_sk");
+    return sk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, nullptr, sk,
+                           {cap, len, breaks, breaks_cap, n_breaks}, "psdc_sk_sk");
 }
 
 int psdc_sk_stats_read(psdc_sk *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -2604,108 +2631,33 @@ const char *psdc_sk_last_error(const psdc_sk *h) { return h ? h->err.c_str() : x
 
 namespace {
 
-// the f64 rows of every stage of a unit (ns x rows() x bins: ZSK_ROWS of them for the SK and AM/PM kinds, ZXAMPM_ROWS for the AM/PM
-// cross kinds) and what a stitch needs beside them; rows 0 and 1 in f32 as
-// two_rows_psd_impl hands a zoom object's to the stitch (ns x 2 x bins)
-struct ZskIn {
-    std::vector<uint64_t> c64, pend;
-    std::vector<uint32_t> avgs;
-    std::vector<double> acc;
-    std::vector<float> rows01;
-    uint32_t ns = 0;
-};
-
-int zsk_in(XObj *h, uint32_t channel, ZskIn *in)
-{
-    int rc;
-    if ((rc = drain(h)) || (rc = sync_all(h)))
-        return rc;
-    const auto &st = h->pairs[channel];
-    const uint32_t ns = (uint32_t)st.size();
-    const size_t b = bins(h), nr = h->rows();
-    in->ns = ns;
-    in->c64.resize(std::max<uint32_t>(ns, 1));
-    in->pend.resize(std::max<uint32_t>(ns, 1));
-    in->avgs.resize(std::max<uint32_t>(ns, 1));
-    in->acc.resize(std::max<size_t>(1, (size_t)ns * nr * b));
-    in->rows01.resize(std::max<size_t>(1, (size_t)ns * 2 * b));
-    for (uint32_t i = 0; i < ns; ++i) {
-        in->c64[i] = st[i].count64;
-        in->pend[i] = pending_for(h->geo, st[i].total);
-        in->avgs[i] = cur_avg(h, i);
-        double *a = &in->acc[(size_t)i * nr * b];
-        XCHK(h, hipMemcpy(a, st[i].acc, sizeof(double) * nr * b, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < 2 * b; ++k)
-            in->rows01[(size_t)i * 2 * b + k] = (float)a[k];
-    }
-    return PSDC_OK;
-}
-
 // the zoom read-out of rows 0 and 1 (sk_upper == sk_lower == NULL: upper / lower written where given), or the SK of every bin
 // that read-out takes, both sides, selected by its Breaks (upper == lower == NULL)
-int zsk_readout_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
-                     float *lower, double *sk_upper, double *sk_lower, size_t cap, size_t *len, psdc_break *breaks,
-                     size_t breaks_cap, size_t *n_breaks, const char *who)
+int zsk_readout_impl(XObj *h, uint32_t channel, const StitchSel &sel, float *upper, float *lower, double *sk_upper, double *sk_lower,
+                     const StitchOut &o, const char *who)
 {
-    X_HANDLE(h, who);
-    int rc = check_pair(h, channel);
-    if (rc)
+    const RowOut<float> outs[2] = {{upper}, {lower}};
+    Stitched st;
+    int rc = unit_stitch(h, channel, sel, 2, outs, sk_upper || sk_lower, o, BreaksOf::OWN, who, who, &st);
+    if (rc || !(sk_upper || sk_lower))
         return rc;
-    X_ON_DEVICE(h);
-    ZskIn in;
-    if ((rc = zsk_in(h, channel, &in)))
-        return rc;
-    float *outs[2] = {upper, lower};
-    psdc_break own[X_MAX_STAGES];
-    size_t l = 0, nb = 0;
-    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                          in.rows01.data(), 2, keep_overlap, min_count, keep_transition_band, outs, cap, &l, own, X_MAX_STAGES, &nb);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    if ((sk_upper || sk_lower) && l > cap)
-        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
-    if (len)
-        *len = l;
-    if (n_breaks)
-        *n_breaks = nb;
-    if (breaks) {
-        if (nb > breaks_cap)
-            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
-        std::copy(own, own + nb, breaks);
-    }
-    if (sk_upper || sk_lower) {
-        const size_t b = bins(h);
-        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
-            const psdc_break &br = own[i];
-            if (!br.include)
-                continue;
-            const double *a = &in.acc[(size_t)(in.ns - 1 - i) * ZSK_ROWS * b];
-            for (uint64_t k = br.bins_start; k < br.bins_end; ++k) {
-                const size_t o = br.start + (k - br.bins_start);
-                if (sk_upper)
-                    sk_upper[o] = sk_estimate(br.count, a[k], a[2 * b + k]);
-                if (sk_lower)
-                    sk_lower[o] = sk_estimate(br.count, a[b + k], a[3 * b + k]);
-            }
-        }
-    }
+    const size_t b = bins(h);
+    st.each_bin([&](size_t stage, size_t k, size_t out, const psdc_break &br) {
+        const double *a = st.snap.stage(stage);
+        if (sk_upper)
+            sk_upper[out] = sk_estimate(br.count, a[k], a[2 * b + k]);
+        if (sk_lower)
+            sk_lower[out] = sk_estimate(br.count, a[b + k], a[3 * b + k]);
+    });
     return PSDC_OK;
 }
 
-int zsk_stage_moments_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
-                           double *s2_upper, double *s2_lower, const char *who)
+// the four f64 rows of one stage (the moments of the SK kinds, the rows of the AM/PM kinds)
+int four_rows_stage_impl(XObj *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *r0, double *r1, double *r2, double *r3,
+                         const char *who)
 {
-    std::vector<double> acc;
-    double *outs[ZSK_ROWS] = {s1_upper, s1_lower, s2_upper, s2_lower};
-    const bool any = s1_upper || s1_lower || s2_upper || s2_lower;
-    int rc = stage_impl(h, channel, stage, stat, any ? &acc : nullptr, who);
-    if (rc || acc.empty())
-        return rc;
-    const size_t b = bins(h);
-    for (int r = 0; r < ZSK_ROWS; ++r)
-        if (outs[r])
-            std::copy(acc.begin() + r * b, acc.begin() + (r + 1) * b, outs[r]);
-    return PSDC_OK;
+    const RowOut<double> outs[ZSK_ROWS] = {{r0}, {r1}, {r2}, {r3}};
+    return stage_rows(h, channel, stage, stat, outs, ZSK_ROWS, who);
 }
 
 } // namespace
@@ -2752,21 +2704,21 @@ int psdc_zsk_num_stages(psdc_zsk *h, uint32_t channel) { return num_stages_impl(
 int psdc_zsk_stage_moments(psdc_zsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
                            double *s2_upper, double *s2_lower)
 {
-    return zsk_stage_moments_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_zsk_stage_moments");
+    return four_rows_stage_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_zsk_stage_moments");
 }
 
 int psdc_zsk_psd(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
                  float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
-                            breaks_cap, n_breaks, "psdc_zsk_psd");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, nullptr, nullptr,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zsk_psd");
 }
 
 int psdc_zsk_sk(psdc_zsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
                 double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, nullptr, sk_upper, sk_lower, cap, len,
-                            breaks, breaks_cap, n_breaks, "psdc_zsk_sk");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, nullptr, nullptr, sk_upper, sk_lower,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zsk_sk");
 }
 
 int psdc_zsk_stats_read(psdc_zsk *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -2824,21 +2776,21 @@ int psdc_iqsk_num_stages(psdc_iqsk *h, uint32_t channel) { return num_stages_imp
 int psdc_iqsk_stage_moments(psdc_iqsk *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *s1_upper, double *s1_lower,
                             double *s2_upper, double *s2_lower)
 {
-    return zsk_stage_moments_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_iqsk_stage_moments");
+    return four_rows_stage_impl(h, channel, stage, stat, s1_upper, s1_lower, s2_upper, s2_lower, "psdc_iqsk_stage_moments");
 }
 
 int psdc_iqsk_psd(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper,
                   float *lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
-                            breaks_cap, n_breaks, "psdc_iqsk_psd");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, nullptr, nullptr,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqsk_psd");
 }
 
 int psdc_iqsk_sk(psdc_iqsk *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *sk_upper,
                  double *sk_lower, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, nullptr, nullptr, sk_upper, sk_lower, cap, len,
-                            breaks, breaks_cap, n_breaks, "psdc_iqsk_sk");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, nullptr, nullptr, sk_upper, sk_lower,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqsk_sk");
 }
 
 int psdc_iqsk_stats_read(psdc_iqsk *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -2854,67 +2806,37 @@ const char *psdc_iqsk_last_error(const psdc_iqsk *h) { return h ? h->err.c_str()
 
 namespace {
 
-static_assert(ZAMPM_ROWS == ZSK_ROWS, "the AM/PM read-out takes its stages through zsk_in: four f64 rows a stage");
+static_assert(ZAMPM_ROWS == ZSK_ROWS, "the AM/PM stage read-out is four_rows_stage_impl: four f64 rows a stage");
 
 // the rows() rows of a unit stitched in f64 into outs[r] (NULL: that row is not wanted): the row stitch picks the stages and bins
 // from rows 0 and 1 (one set of Breaks, the zoom read-out's), and every selected bin of the f64 accumulators is scaled by the f32
 // factor that stitch applies to the stage
-int rows_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *const *outs,
-                        size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+int rows_sidebands_impl(XObj *h, uint32_t channel, const StitchSel &sel, double *const *outs, uint32_t nrows, const StitchOut &o, const char *who)
 {
-    X_HANDLE(h, who);
-    int rc = check_pair(h, channel);
-    if (rc)
+    const RowOut<float> none[2];
+    const bool any = std::any_of(outs, outs + nrows, [](double *p) { return p != nullptr; });
+    Stitched st;
+    int rc = unit_stitch(h, channel, sel, 2, none, any, o, BreaksOf::OWN, who, who, &st);
+    if (rc || !any)
         return rc;
-    X_ON_DEVICE(h);
-    ZskIn in;
-    if ((rc = zsk_in(h, channel, &in)))
-        return rc;
-    float *none[2] = {nullptr, nullptr};
-    const size_t nr = h->rows();
-    const bool any = std::any_of(outs, outs + nr, [](double *o) { return o != nullptr; });
-    psdc_break own[X_MAX_STAGES];
-    size_t l = 0, nb = 0;
-    rc = stitch_rows_impl(who, h->n, h->power, h->nenbw, h->geo.overlap, in.ns, in.c64.data(), in.avgs.data(), in.pend.data(),
-                          in.rows01.data(), 2, keep_overlap, min_count, keep_transition_band, none, 0, &l, own, X_MAX_STAGES, &nb);
-    if (rc)
-        return xfail(h, rc, x_last_error);
-    if (any && l > cap)
-        return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": output too small");
-    if (len)
-        *len = l;
-    if (n_breaks)
-        *n_breaks = nb;
-    if (breaks) {
-        if (nb > breaks_cap)
-            return xfail(h, PSDC_ERR_CAPACITY, std::string(who) + ": breaks output too small");
-        std::copy(own, own + nb, breaks);
-    }
-    if (any) {
-        const size_t b = bins(h);
-        for (size_t i = 0; i < nb; ++i) { // Break i is stage ns - 1 - i (lowest rate first)
-            const psdc_break &br = own[i];
-            if (!br.include)
-                continue;
-            const size_t si = in.ns - 1 - i;
-            const double *a = &in.acc[si * nr * b];
-            const double gsc = 1.0f / (psdrt::stage_gain(h->n, in.c64[si], h->nenbw, h->power) * (float)br.decimation);
-            for (size_t r = 0; r < nr; ++r)
-                if (outs[r])
-                    for (uint64_t k = br.bins_start; k < br.bins_end; ++k)
-                        outs[r][br.start + (k - br.bins_start)] = a[r * b + k] * gsc;
-        }
-    }
+    double gsc[X_MAX_STAGES] = {};
+    for (size_t i = 0; i < st.nb; ++i)
+        if (st.br[i].include)
+            gsc[st.snap.ns - 1 - i] = 1.0f / (psdrt::stage_gain(h->n, st.snap.c64[st.snap.ns - 1 - i], h->nenbw, h->power) * (float)st.br[i].decimation);
+    const size_t b = bins(h);
+    st.each_bin([&](size_t stage, size_t k, size_t out, const psdc_break &) {
+        for (uint32_t r = 0; r < nrows; ++r)
+            if (outs[r])
+                outs[r][out] = st.snap.stage(stage)[r * b + k] * gsc[stage];
+    });
     return PSDC_OK;
 }
 
-int ampm_sidebands_impl(XObj *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
-                        double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks,
-                        size_t breaks_cap, size_t *n_breaks, const char *who)
+int ampm_sidebands_impl(XObj *h, uint32_t channel, const StitchSel &sel, double *upper, double *lower, double *comp_re, double *comp_im,
+                        const StitchOut &o, const char *who)
 {
     double *outs[ZAMPM_ROWS] = {upper, lower, comp_re, comp_im};
-    return rows_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks,
-                               who);
+    return rows_sidebands_impl(h, channel, sel, outs, ZAMPM_ROWS, o, who);
 }
 
 } // namespace
@@ -2961,22 +2883,22 @@ int psdc_zampm_num_stages(psdc_zampm *h, uint32_t channel) { return num_stages_i
 int psdc_zampm_stage_rows(psdc_zampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower, double *comp_re,
                           double *comp_im)
 {
-    return zsk_stage_moments_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_zampm_stage_rows");
+    return four_rows_stage_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_zampm_stage_rows");
 }
 
 int psdc_zampm_psd(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper, float *lower,
                    size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
-                            breaks_cap, n_breaks, "psdc_zampm_psd");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, nullptr, nullptr,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zampm_psd");
 }
 
 int psdc_zampm_sidebands(psdc_zampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
                          double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
                          size_t *n_breaks)
 {
-    return ampm_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, comp_re, comp_im, cap, len,
-                               breaks, breaks_cap, n_breaks, "psdc_zampm_sidebands");
+    return ampm_sidebands_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, comp_re, comp_im,
+                               {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zampm_sidebands");
 }
 
 int psdc_zampm_stats_read(psdc_zampm *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -3034,22 +2956,22 @@ int psdc_iqampm_num_stages(psdc_iqampm *h, uint32_t channel) { return num_stages
 int psdc_iqampm_stage_rows(psdc_iqampm *h, uint32_t channel, uint32_t stage, psdc_stage_stat *stat, double *upper, double *lower, double *comp_re,
                            double *comp_im)
 {
-    return zsk_stage_moments_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_iqampm_stage_rows");
+    return four_rows_stage_impl(h, channel, stage, stat, upper, lower, comp_re, comp_im, "psdc_iqampm_stage_rows");
 }
 
 int psdc_iqampm_psd(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, float *upper, float *lower,
                     size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return zsk_readout_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, nullptr, nullptr, cap, len, breaks,
-                            breaks_cap, n_breaks, "psdc_iqampm_psd");
+    return zsk_readout_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, nullptr, nullptr,
+                            {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqampm_psd");
 }
 
 int psdc_iqampm_sidebands(psdc_iqampm *h, uint32_t channel, int keep_overlap, uint32_t min_count, int keep_transition_band, double *upper,
                           double *lower, double *comp_re, double *comp_im, size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap,
                           size_t *n_breaks)
 {
-    return ampm_sidebands_impl(h, channel, keep_overlap, min_count, keep_transition_band, upper, lower, comp_re, comp_im, cap, len,
-                               breaks, breaks_cap, n_breaks, "psdc_iqampm_sidebands");
+    return ampm_sidebands_impl(h, channel, {keep_overlap, min_count, keep_transition_band}, upper, lower, comp_re, comp_im,
+                               {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqampm_sidebands");
 }
 
 int psdc_iqampm_stats_read(psdc_iqampm *h, uint64_t *launches, uint64_t *samples_in, int reset)
@@ -3065,26 +2987,14 @@ const char *psdc_iqampm_last_error(const psdc_iqampm *h) { return h ? h->err.c_s
 
 namespace {
 
-// the twelve f64 rows of one stage as they lie on the device: rows[12][n/2 + 1]
-int xampm_stage_rows_impl(XObj *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows, const char *who)
-{
-    std::vector<double> acc;
-    int rc = stage_impl(h, pair, stage, stat, rows ? &acc : nullptr, who);
-    if (rc)
-        return rc;
-    std::copy(acc.begin(), acc.end(), rows);
-    return PSDC_OK;
-}
-
 // the twelve rows stitched in f64 into rows[12][cap] (rows_sidebands_impl: one set of Breaks, from rows 0 and 1 -- the zoom
 // read-out's of channel a)
-int xampm_sidebands_impl(XObj *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows, size_t cap,
-                         size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks, const char *who)
+int xampm_sidebands_impl(XObj *h, uint32_t pair, const StitchSel &sel, double *rows, const StitchOut &o, const char *who)
 {
     double *outs[ZXAMPM_ROWS];
     for (int r = 0; r < ZXAMPM_ROWS; ++r)
-        outs[r] = rows ? rows + (size_t)r * cap : nullptr;
-    return rows_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, outs, cap, len, breaks, breaks_cap, n_breaks, who);
+        outs[r] = rows ? rows + (size_t)r * o.cap : nullptr;
+    return rows_sidebands_impl(h, pair, sel, outs, ZXAMPM_ROWS, o, who);
 }
 
 } // namespace
@@ -3131,14 +3041,14 @@ int psdc_zxampm_num_stages(psdc_zxampm *h, uint32_t pair) { return num_stages_im
 
 int psdc_zxampm_stage_rows(psdc_zxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows)
 {
-    return xampm_stage_rows_impl(h, pair, stage, stat, rows, "psdc_zxampm_stage_rows");
+    return stage_block(h, pair, stage, stat, rows, "psdc_zxampm_stage_rows");
 }
 
 int psdc_zxampm_sidebands(psdc_zxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
                           size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return xampm_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap, n_breaks,
-                                "psdc_zxampm_sidebands");
+    return xampm_sidebands_impl(h, pair, {keep_overlap, min_count, keep_transition_band}, rows,
+                                {cap, len, breaks, breaks_cap, n_breaks}, "psdc_zxampm_sidebands");
 }
 
 int psdc_zxampm_stats_read(psdc_zxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -3201,14 +3111,14 @@ int psdc_iqxampm_num_stages(psdc_iqxampm *h, uint32_t pair) { return num_stages_
 
 int psdc_iqxampm_stage_rows(psdc_iqxampm *h, uint32_t pair, uint32_t stage, psdc_stage_stat *stat, double *rows)
 {
-    return xampm_stage_rows_impl(h, pair, stage, stat, rows, "psdc_iqxampm_stage_rows");
+    return stage_block(h, pair, stage, stat, rows, "psdc_iqxampm_stage_rows");
 }
 
 int psdc_iqxampm_sidebands(psdc_iqxampm *h, uint32_t pair, int keep_overlap, uint32_t min_count, int keep_transition_band, double *rows,
                            size_t cap, size_t *len, psdc_break *breaks, size_t breaks_cap, size_t *n_breaks)
 {
-    return xampm_sidebands_impl(h, pair, keep_overlap, min_count, keep_transition_band, rows, cap, len, breaks, breaks_cap, n_breaks,
-                                "psdc_iqxampm_sidebands");
+    return xampm_sidebands_impl(h, pair, {keep_overlap, min_count, keep_transition_band}, rows,
+                                {cap, len, breaks, breaks_cap, n_breaks}, "psdc_iqxampm_sidebands");
 }
 
 int psdc_iqxampm_stats_read(psdc_iqxampm *h, uint64_t *launches, uint64_t *pairs_in, int reset)
@@ -3274,16 +3184,11 @@ int wf_stage(XObj *h, uint32_t channel, uint32_t stage, WfStage *out, const char
     int rc = check_pair(h, channel);
     if (rc)
         return rc;
-    if ((rc = drain(h)))
+    if ((rc = drained_stage(h, channel, stage, &out->s, who)))
         return rc;
-    const auto &st = h->pairs[channel];
-    if (stage >= st.size())
-        return xfail(h, PSDC_ERR_ARG, std::string(who) + ": stage " + std::to_string(stage) + " out of range (" +
-                                          std::to_string(st.size()) + " stages)");
-    out->s = &st[stage];
-    out->started = wf_blocks_started(st[stage].segs, h->wf_block);
+    out->started = wf_blocks_started(out->s->segs, h->wf_block);
     out->valid = wf_valid_rows(out->started, h->wf_depth);
-    out->newest = wf_newest_count(st[stage].segs, h->wf_block);
+    out->newest = wf_newest_count(out->s->segs, h->wf_block);
     return PSDC_OK;
 }
 
@@ -3705,19 +3610,15 @@ int xr_plan(XObj *h, const XrArgs &a, uint32_t S, XrPlan *pl)
     pl->units.resize(S);
     for (uint32_t i = 0; i < S; ++i) {
         const std::vector<XStage> &st = h->pairs[a.sel ? a.sel[i] : i];
-        const size_t ns = st.size();
-        uint32_t counts[X_MAX_STAGES], avgs[X_MAX_STAGES];
-        uint64_t pend[X_MAX_STAGES], counts64[X_MAX_STAGES];
-        for (size_t k = 0; k < ns; ++k) {
-            counts64[k] = st[k].count64;
-            counts[k] = count_report(st[k].count64);
-            avgs[k] = cur_avg(h, k);
-            pend[k] = pending_for(h->geo, st[k].total);
-        }
+        UnitSnap in; // (the bookkeeping alone: the kernels read the accumulators where they lie)
+        unit_layout(h, a.sel ? a.sel[i] : i, &in);
+        uint32_t counts[X_MAX_STAGES];
+        for (uint32_t k = 0; k < in.ns; ++k)
+            counts[k] = count_report(in.c64[k]);
         psdc_break br[X_MAX_STAGES];
         size_t len = 0, nb = 0;
-        rc = psdrt::stitch_impl(h->n, h->nenbw, h->power, h->geo.overlap, (uint32_t)ns, counts, avgs, pend, nullptr, a.keep_overlap,
-                                a.min_count, a.keep_transition_band, nullptr, 0, &len, br, X_MAX_STAGES, &nb, counts64);
+        rc = psdrt::stitch_impl(h->n, h->nenbw, h->power, h->geo.overlap, in.ns, counts, in.avgs.data(), in.pend.data(), nullptr, a.keep_overlap,
+                                a.min_count, a.keep_transition_band, nullptr, 0, &len, br, X_MAX_STAGES, &nb, in.c64.data());
         if (rc)
             return xfail(h, rc, std::string(a.who) + ": internal: a unit with more than 16 stages");
         a.lens[i] = len;
@@ -3731,7 +3632,7 @@ int xr_plan(XObj *h, const XrArgs &a, uint32_t S, XrPlan *pl)
         }
         pl->units[i] = cross_row_jobs(
             br, nb, i, h->rows(), (uint32_t)bins(h), pl->jobs, [&](uint32_t stage) { return (const double *)st[stage].acc; },
-            [&](uint32_t stage) { return psdrt::stage_gain(h->n, counts64[stage], h->nenbw, h->power); });
+            [&](uint32_t stage) { return psdrt::stage_gain(h->n, in.c64[stage], h->nenbw, h->power); });
         if (pl->units[i].len != len)
             return xfail(h, PSDC_ERR_ARG, std::string(a.who) + ": internal: the jobs do not cover the row");
         pl->max_len = std::max(pl->max_len, len);
