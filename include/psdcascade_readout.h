@@ -76,8 +76,8 @@
  * a band with NaN or lo > hi; NULL lens; breaks without n_breaks; all of psd, freq and the band output NULL in the two read-out
  * calls.
  *
- * Out of scope: the cross-runtime objects (psdc_cross_* ... the waterfalls: f64 accumulators behind other handle types), Var and
- * Trace::plot's decibel conversion. */
+ * Out of scope: the cross-runtime objects (psdc_cross_* ... the waterfalls: f64 accumulators behind other handle types) and
+ * Trace::plot's decibel conversion.  Var (the Allan-type variance curves of the same selection) is psdcascade_var.h's. */
 #ifndef PSDCASCADE_READOUT_H
 #define PSDCASCADE_READOUT_H
 

@@ -4,43 +4,22 @@
 // stream.  The device form writes caller memory and may return before the kernels have run; the host form runs the same kernels
 // into the handle's buffer and copies it out once.
 #include "../../include/psdcascade_readout.h"
-#include "bank_readout.h"
-#include "host_runtime.h"
+#include "bank_plan.h"
 
 #include <cmath>
 #include <cstring>
 
 using namespace psdrt;
 
-namespace {
+namespace psdrt {
+namespace bankread { // shared with bank_var.cpp through bank_plan.h
 
-// what the handle keeps for these calls (psdc_handle::bank_read): psdrt::BankRead of host_runtime.h
 BankRead *state_of(psdc_handle *h)
 {
     if (!h->bank_read)
         h->bank_read = std::shared_ptr<void>(new BankRead, [](void *p) { delete static_cast<BankRead *>(p); });
     return static_cast<BankRead *>(h->bank_read.get());
 }
-
-struct Plan {
-    std::vector<psdk::BankJob> jobs;
-    std::vector<psdk::BankRow> rows;
-    size_t max_len = 0;
-    uint32_t max_bins = 0;
-};
-
-struct Args {
-    const char *who;
-    const uint32_t *channels;
-    uint32_t n_sel;
-    int keep_overlap;
-    uint32_t min_count;
-    int keep_transition_band;
-    size_t *lens, *n_breaks;
-    psdc_break *breaks;
-    size_t breaks_cap;
-    psdcr_info *info;
-};
 
 int bad(psdc_handle *h, const Args &a, const char *what) { return fail(h, PSDC_ERR_ARG, std::string(a.who) + ": " + what); }
 
@@ -114,6 +93,13 @@ int plan_rows(psdc_handle *h, const Args &a, uint32_t S, Plan *pl)
     }
     return overflow ? fail(h, PSDC_ERR_CAPACITY, std::string(a.who) + ": breaks_cap is smaller than a row's number of breaks") : PSDC_OK;
 }
+
+} // namespace bankread
+} // namespace psdrt
+
+using namespace psdrt::bankread;
+
+namespace {
 
 int check_outputs(psdc_handle *h, const Args &a, const void *psd, const void *freq, const float *bands, uint32_t n_bands, const void *band_out,
                   psdk::BankBands *bb)

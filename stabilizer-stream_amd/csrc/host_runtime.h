@@ -8,6 +8,7 @@
 //                      every frames call (here and in cross_runtime.cpp); wire_format.h is the one table of the payload layouts
 //   readout.cpp        PsdStage accessors, PsdCascade::psd stitch, Break, packed read-out, Var / Trace::plot, the single-stage Psd<N>
 //   bank_readout.cpp   psdcr_*: every selected channel stitched on the device in one launch, frequencies, band power
+//   bank_var.cpp       psdcv_*: the Allan-type variance curves of the same selection from the accumulators (bank_plan.h is shared)
 //
 // Mirrors PsdCascade<N> (src/psd.rs:399-544) for `n_channels` independent traces on one MI355X: per (channel, stage) the
 // stream position, the count and a device stream buffer.  There is no CPU compute path: every spectrum comes from the HIP kernels.

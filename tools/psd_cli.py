@@ -41,6 +41,11 @@ the SK of every bin (the zoom option: upper then lower sideband of each).
 stitched on the device in one launch, one copy to the host) where the default asks psd() trace by trace; the lines and the files
 are the same, byte for byte.  With --pair it also reads the rows and frequencies of all pairs with ONE call (crossread.bank_csd)
 where the default asks csd() pair by pair; coherence and H1 are formed from those rows as before, so the lines and files are the same.
+--var KIND[:PER_DECADE] (repeatable, at most 4; KIND one of avar, mvar, fvar; needs --bank-readout) prints behind the traces the
+Allan, modified Allan or main-lobe deviation curve of every trace of the main bank, all from ONE call (bankvar.bank_var: one launch
+reads the accumulators, no spectrum is copied): a header line a trace and kind, then one line `tau,deviation` a tau, with --csv in
+DIR/<trace>_<kind>.csv.  The spectra are taken as phase PSDs; taus run from one sample to the period of the lowest bin that counts, with
+PER_DECADE points a decade (default 10, the largest given; at most 4096 taus), printed in seconds (tau / fs) with fs sqrt(var).
 --robust KIND[:NSIGMA] (repeatable; KIND one of median, min, max, excised) adds to every --waterfall / --zoom-waterfall trace the
 robust read-out of every stage (robust.stage_robust: over the stage's complete blocks, made on the device): behind the lines above,
 or with --csv in DIR/<the stage's file name>_robust.csv, a header line with the rows and blocks considered, then one line a KIND
@@ -74,6 +79,43 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def var_curves(pkg, a, bank, merge, names):
+    """--var: the deviation curves of every trace of the main bank from one bankvar.bank_var call"""
+    from stabilizer_stream_amd import bankread, bankvar
+    kinds, per_decade = [], 0
+    for spec in a.var:
+        kind, _, n = spec.partition(":")
+        if kind not in ("avar", "mvar", "fvar") or (n and not n.isdigit()) or (n and int(n) < 1):
+            raise SystemExit(f"--var {spec}: KIND[:PER_DECADE] with KIND one of avar, mvar, fvar")
+        kinds.append(kind)
+        per_decade = max(per_decade, int(n) if n else 0)
+    if len(kinds) > bankvar.MAX_VARS:
+        raise SystemExit(f"--var: at most {bankvar.MAX_VARS} curves a call")
+    vs = [getattr(bankvar.Var, k)() for k in kinds]
+    lay = bankread.layout(bank, None, merge)
+    lowest = [pkg.Break.frequencies(br)[vs[0].dc_cut] for ln, br in zip(lay["lens"], lay["breaks"]) if ln > vs[0].dc_cut]
+    if not lowest:
+        print("var: no samples")
+        return
+    decades = max(0.0, float(np.log10(1.0 / min(lowest))))
+    count = min(bankvar.MAX_TAUS, int(decades * (per_decade or 10)) + 1)
+    taus = np.logspace(0.0, decades, count).astype(np.float32)
+    r = bankvar.bank_var(bank, taus, vs, None, merge)  # float64 [traces][kinds][taus]
+    for i, name in enumerate(names):
+        if r["lens"][i] == 0:
+            continue
+        for k, kind in enumerate(kinds):
+            dev = a.fs * np.sqrt(r["var"][i, k])
+            print(f"{name}: {kind} taus {count} bins {r['lens'][i]}")
+            lines = [f"{t / a.fs:.9g},{d:.9g}\n" for t, d in zip(taus, dev)]
+            if a.csv:
+                safe = "".join(ch if ch.isalnum() else "_" for ch in name)
+                with open(os.path.join(a.csv, f"{safe}_{kind}.csv"), "w") as f:
+                    f.writelines(lines)
+            else:
+                sys.stdout.writelines(lines)
 
 
 def main(argv=None):
@@ -116,6 +158,9 @@ def main(argv=None):
     ap.add_argument("--bank-readout", action="store_true",
                     help="read every trace's spectrum and frequencies with ONE bankread.bank_psd call, and every --pair's rows with ONE "
                          "crossread.bank_csd call (the same output, byte for byte)")
+    ap.add_argument("--var", action="append", default=[],
+                    help="KIND[:PER_DECADE] -- with --bank-readout: the avar, mvar or fvar deviation curve of every trace from one "
+                         "bankvar.bank_var call (repeatable, at most 4)")
     ap.add_argument("--robust", action="append", default=[],
                     help="KIND[:NSIGMA] -- with --waterfall / --zoom-waterfall: per stage the median, min, max or SK-excised mean (within "
                          "NSIGMA sk_sigma of 1, default 3) over its complete blocks (repeatable)")
@@ -141,6 +186,8 @@ def main(argv=None):
         raise SystemExit("--scale needs --sample-format s16 or s8")
     if a.pair and a.raw:
         raise SystemExit("--pair needs --file")
+    if a.var and not a.bank_readout:
+        raise SystemExit("--var needs --bank-readout")
     import __graft_entry__ as entry
     pkg = entry.load_package()
     from stabilizer_stream_amd import source
@@ -203,6 +250,8 @@ def main(argv=None):
             safe = "".join(ch if ch.isalnum() else "_" for ch in name)
             with open(os.path.join(a.csv, safe + ".csv"), "w") as f:
                 f.writelines(f"{x:.9g},{y:.9g}\n" for x, y in xy)
+    if a.var:
+        var_curves(pkg, a, bank, merge, names)
     if a.pair:
         cross_pairs(pkg, source, a, merge)
     if a.zoom:

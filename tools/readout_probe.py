@@ -23,6 +23,20 @@ The same for a CsdCascadeBank of P = 64 and 4 pairs at N = 1024, six live stages
   C  crossread.bank_csd_device with the same five outputs into torch tensors, the form that returns when the kernel has completed.
 Five turns of A / B / C / A.  Reported: the median microseconds a read-out of all pairs of each leg, the rate ratios against the
 turn's two A legs, the largest |A' - A| / A of a turn, and `breaks_us`.  Findings, no gate.
+
+    python tools/readout_probe.py --var [--seconds 0.3] [--out profiles/bank_var_probe.json]
+
+The Var read-out (bankvar) of a PsdCascadeBank of C = 64 and 4 channels at N = 1024, six live stages, read-outs only, for T = 64 and
+1024 taus (log-spaced from 1 to 10^6 samples) and for AVAR alone and AVAR + MVAR + FVAR:
+  A  bankread.bank_psd(frequencies=True) plus the Python loop of var_eval over rows x descriptors x taus: the sequential f32 fold on
+     the host, the only way there was;
+  B  bankvar.bank_var: one launch, one copy of the curves, host arrays;
+  C  bankvar.bank_var_device into a torch tensor, the form that returns when the kernel has completed.
+A does f32 work and B / C do f64 work (one f64 sine a term where A takes one sinf): the comparison is of unequal arithmetic.  Five
+turns of A / B / C / A; a leg is a window of at least --seconds, and at least one call (an A leg of the largest condition is one
+call of several seconds).  Reported: the median microseconds a read-out of all channels of each leg, the rate ratios against the
+turn's two A legs, the largest |A' - A| / A of a turn, and the largest |B - A| over the curves, relative to each curve's largest value (the f32 fold against f64).
+Findings, no gate.
 Needs a GPU."""
 import argparse
 import json
@@ -148,6 +162,92 @@ def cross_config(pkg, crossread, torch, n, pairs, seconds):
             "A_spread_max": max(t["A_spread"] for t in turns)}
 
 
+def window_warm(fn, seconds):
+    """microseconds a call of fn over a window of at least `seconds` and at least one call; fn has been called before"""
+    calls, t0 = 0, time.perf_counter()
+    while True:
+        fn()
+        calls += 1
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return 1e6 * dt / calls
+
+
+def var_bank(pkg, bankread, torch, n, channels):
+    bank = pkg.PsdCascadeBank(n, channels)
+    x = torch.rand(CALL, device="cuda", dtype=torch.float32) - 0.5
+    torch.cuda.synchronize()
+    need = int(1.1 * n * 8 ** (STAGES - 1))
+    for _ in range((need + CALL - 1) // CALL):
+        for c in range(channels):
+            bank.process_device(c, x.data_ptr(), CALL)
+    bank.sync()
+    live = [sum(b.count > 0 for b in br) for br in bankread.layout(bank)["breaks"]]
+    assert min(live) >= STAGES, live
+    return bank, min(live)
+
+
+def var_config(pkg, bankread, bankvar, torch, np, bank, live, n_taus, vs, seconds):
+    import statistics
+    channels = bank.n_channels
+    taus = np.logspace(0, 6, n_taus).astype(np.float32)
+    out = torch.empty((channels, len(vs), n_taus), device="cuda", dtype=torch.float64)
+    torch.cuda.synchronize()
+
+    def leg_a():
+        r = bankread.bank_psd(bank, frequencies=True)
+        curves = np.empty((channels, len(vs), n_taus))
+        for c in range(channels):
+            ln = r["lens"][c]
+            p, f = r["psd"][c, :ln], r["frequencies"][c, :ln]
+            for k, v in enumerate(vs):
+                for j, tau in enumerate(taus):
+                    curves[c, k, j] = pkg.var_eval(p, f, float(tau), v.x_exp, v.sinx_exp, v.clip, v.dc_cut)
+        return curves
+
+    legs = {"A": leg_a, "B": lambda: bankvar.bank_var(bank, taus, vs), "C": lambda: bankvar.bank_var_device(bank, out.data_ptr(), taus, vs)}
+    a, b = legs["A"](), legs["B"]()
+    legs["C"]()
+    assert out.cpu().numpy().tobytes() == b["var"].tobytes()
+    gap = float(np.max(np.abs(b["var"] - a) / np.maximum(np.max(np.abs(b["var"]), axis=-1, keepdims=True), 1e-300)))  # of a curve's largest value
+    turns = []
+    for _ in range(CROSS_TURNS):
+        t = [window_warm(legs[k], seconds) for k in "ABCA"]
+        turns.append({"A_us": [t[0], t[3]], "B_us": t[1], "C_us": t[2], "B_over_A": 0.5 * (t[0] + t[3]) / t[1],
+                      "C_over_A": 0.5 * (t[0] + t[3]) / t[2], "A_spread": abs(t[3] - t[0]) / t[0]})
+    med = statistics.median
+    return {"n": bank.n, "channels": channels, "taus": n_taus, "vars": len(vs), "live_stages": live, "row_len": max(b["lens"]), "launches_B": b["launches"],
+            "f32_fold_against_f64_max_rel": gap, "turns": turns,
+            "A_us": med(v for t in turns for v in t["A_us"]), "B_us": med(t["B_us"] for t in turns), "C_us": med(t["C_us"] for t in turns),
+            "B_over_A": med(t["B_over_A"] for t in turns), "C_over_A": med(t["C_over_A"] for t in turns),
+            "A_spread_max": max(t["A_spread"] for t in turns)}
+
+
+def var_main(a, torch, pkg):
+    import numpy as np
+    from stabilizer_stream_amd import bankread, bankvar
+    rows = []
+    for channels in (64, 4):
+        bank, live = var_bank(pkg, bankread, torch, 1024, channels)
+        for n_taus in (64, 1024):
+            for vs in ([bankvar.Var.avar()], [bankvar.Var.avar(), bankvar.Var.mvar(), bankvar.Var.fvar()]):
+                rows.append(var_config(pkg, bankread, bankvar, torch, np, bank, live, n_taus, vs, a.seconds))
+                r = rows[-1]
+                print(f"N={r['n']:5d} C={r['channels']:3d} T={r['taus']:5d} V={r['vars']}  A {r['A_us']:11.1f} us  B {r['B_us']:9.1f} us  C {r['C_us']:9.1f} us  "
+                      f"B/A {r['B_over_A']:.1f}  C/A {r['C_over_A']:.1f}  A/A spread <= {r['A_spread_max']:.3f}", file=sys.stderr, flush=True)
+        bank.close()
+    rec = {"metric": "bank_var_us", "unit": "microseconds a read-out of all channels, median of the turns (host clock, through the Python binding)",
+           "note": "findings, no gate: A = bankread.bank_psd(frequencies) + the Python loop of var_eval over rows x descriptors x taus (the sequential "
+                   "f32 fold on the host), B = bankvar.bank_var, C = bankvar.bank_var_device (synchronising form); A does f32 work and B / C do f64 "
+                   "work: unequal arithmetic; read-outs only, six live stages, no feed in the window; taus log-spaced from 1 to 1e6 samples; "
+                   "vars = 1: AVAR, 3: AVAR + MVAR + FVAR; five turns of A / B / C / A; ratios are rates (above 1: faster than A)",
+           "device": torch.cuda.get_device_name(0), "seconds": a.seconds, "turns": CROSS_TURNS, "configs": rows}
+    line = json.dumps(rec)
+    with open(a.out or os.path.join(ROOT, "profiles", "bank_var_probe.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def cross_main(a, torch, pkg):
     from stabilizer_stream_amd import crossread
     rows = [cross_config(pkg, crossread, torch, 1024, p, a.seconds) for p in (64, 4)]
@@ -168,17 +268,21 @@ def cross_main(a, torch, pkg):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=None, help="a leg's window (default 0.5, with --cross 0.3)")
+    ap.add_argument("--seconds", type=float, default=None, help="a leg's window (default 0.5, with --cross and --var 0.3)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--cross", action="store_true", help="measure the pair object's read-outs (crossread) instead")
-    ap.add_argument("--out", default=None, help="default profiles/bank_readout_probe.json, with --cross profiles/cross_readout_probe.json")
+    ap.add_argument("--var", action="store_true", help="measure the Var read-out (bankvar) against the host loop of var_eval instead")
+    ap.add_argument("--out", default=None, help="default profiles/bank_readout_probe.json, with --cross profiles/cross_readout_probe.json, "
+                                                "with --var profiles/bank_var_probe.json")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("readout_probe: no GPU is visible (there is nothing to measure without one)")
     pkg = entry.load_package()
     if a.seconds is None:
-        a.seconds = 0.3 if a.cross else 0.5
+        a.seconds = 0.3 if a.cross or a.var else 0.5
+    if a.var:
+        return var_main(a, torch, pkg)
     if a.cross:
         return cross_main(a, torch, pkg)
     a.out = a.out or os.path.join(ROOT, "profiles", "bank_readout_probe.json")
