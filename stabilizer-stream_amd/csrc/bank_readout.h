@@ -110,8 +110,9 @@ PSDK_BR_HD inline void bank_band_walk(const Job *jobs, uint32_t nj, uint32_t L, 
 #pragma unroll
 #endif
         for (uint32_t r = 0; r < R; ++r) {
-            const float p = val(j, r, k), p1 = q ? val(*q, r, kq) : 0.0f;
-            const double tk = (0.5 * ((double)p + (double)p1)) * ((double)f - (double)f1); // rounded on its own: see the top
+            // (val yields the stitched f32 value, or an f64 that was never cast to f32: carrier_readout.h; float to double is exact)
+            const double p = val(j, r, k), p1 = q ? (double)val(*q, r, kq) : 0.0;
+            const double tk = (0.5 * (p + p1)) * ((double)f - (double)f1); // rounded on its own: see the top
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif

@@ -33,7 +33,16 @@ struct CrossPairOut {
     bool any() const { return sxx || syy || sxy || freq || coherence || transfer; }
 };
 
-// The jobs of one unit from its Breaks, as bank_row_jobs makes them (Break i belongs to stage n_breaks - 1 - i).
+// what a job type derived from CrossReadJob takes from its Break beyond the fields below (carrier_readout.h: the count); nothing here.
+// (cross_row_jobs calls this unqualified on a dependent type: an overload for a derived job, declared later beside that type in
+// namespace psdk, is found by argument-dependent lookup at instantiation)
+template <class B>
+inline void cross_job_break(CrossReadJob &, const B &)
+{
+}
+
+// The jobs of one unit from its Breaks, as bank_row_jobs makes them (Break i belongs to stage n_breaks - 1 - i).  Jobs: a vector
+// of CrossReadJob or of a type derived from it.
 template <class B, class Jobs, class Src, class Gain>
 inline BankRow cross_row_jobs(const B *breaks, size_t n_breaks, uint32_t row, uint32_t rows, uint32_t bins, Jobs &jobs, Src src_of, Gain gain_of)
 {
@@ -43,7 +52,8 @@ inline BankRow cross_row_jobs(const B *breaks, size_t n_breaks, uint32_t row, ui
         if (!b.include || b.bins_end <= b.bins_start)
             continue;
         const uint32_t stage = (uint32_t)(n_breaks - 1 - i);
-        CrossReadJob j;
+        typename Jobs::value_type j;
+        cross_job_break(j, b);
         j.src = src_of(stage);
         j.row = row;
         j.start = (uint32_t)b.start;

@@ -48,9 +48,11 @@
 #include "waterfall_read.h"
 #include "waterfall_robust.h"
 #include "cross_readout.h"
+#include "carrier_readout.h"
 #include "host_runtime.h"
 #include "../../include/psdcascade_robust.h"
 #include "../../include/psdcascade_crossread.h"
+#include "../../include/psdcascade_carrierread.h"
 
 #include <algorithm>
 #include <cmath>
@@ -78,6 +80,9 @@ inline hipError_t launch_wf_robust(const WfRobustJob &, hipStream_t) { return hi
 inline hipError_t launch_cross_stitch_pair(const CrossReadJob *, uint32_t, uint32_t, const CrossPairOut &, hipStream_t) { return hipErrorInvalidValue; }
 inline hipError_t launch_cross_stitch_rows(const CrossReadJob *, uint32_t, uint32_t, float *, float *, size_t, hipStream_t) { return hipErrorInvalidValue; }
 inline hipError_t launch_cross_band(const CrossReadJob *, const BankRow *, uint32_t, const BankBands &, double *, hipStream_t) { return hipErrorInvalidValue; }
+// (nor those of carrier_readout.hip: the psdczr_ read-outs fail there in the same way)
+inline hipError_t launch_carrier_stitch(int, const CarrierReadJob *, uint32_t, uint32_t, const CarrierOut &, const CarrierUnit *, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_carrier_band(uint32_t, const CarrierReadJob *, const BankRow *, const CarrierUnit *, uint32_t, const BankBands &, double *, hipStream_t) { return hipErrorInvalidValue; }
 } // namespace psdk
 #endif
 
@@ -2536,14 +2541,7 @@ int psdc_sint_csm_process_device(psdc_csm *h, uint32_t group, const void *const 
 
 namespace {
 
-// SK of one bin from its moments (include/psdcascade.h, "spectral kurtosis cascade"): NaN below two averages and without power
-double sk_estimate(uint32_t count, double s1, double s2)
-{
-    if (count < 2 || s1 == 0.0)
-        return std::numeric_limits<double>::quiet_NaN();
-    const double m = (double)count;
-    return (m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0);
-}
+// (SK of one bin from its moments: sk_estimate of carrier_readout.h, the text the device read-out runs too)
 
 // the stitch of row 0 (psd != NULL: written) and, with sk != NULL, the SK of every bin the stitch takes, selected by its Breaks
 int sk_readout_impl(XObj *h, uint32_t channel, const StitchSel &sel, float *psd, double *sk, const StitchOut &o, const char *who)
@@ -3574,9 +3572,23 @@ struct XrOut {
     uint32_t rows;
 };
 
+// which kernels a call runs: the pair and matrix forms of cross_readout.hip (psdcxr_*), or a mode of carrier_readout.hip (psdczr_*)
+enum class XrMode { PAIR, ROWS, SIDES, SK, AMPM };
+bool xr_carrier_mode(XrMode m) { return m == XrMode::SIDES || m == XrMode::SK || m == XrMode::AMPM; }
+// rows of a band sum (0: the mode has no bands)
+uint32_t xr_band_rows(XrMode m) { return m == XrMode::PAIR || m == XrMode::AMPM ? XREAD_PAIR_ROWS : m == XrMode::SIDES ? CREAD_SIDE_ROWS : 0; }
+
+// what an AM/PM call adds: the given amplitudes [S][2] on the host (NULL: from bin 0 of stage 0) and the carrier records [S][4]
+// (NULL: not wanted; device or host memory as the call's other outputs)
+struct XrCarrier {
+    const double *carriers;
+    double *out;
+};
+
 struct XrPlan {
-    std::vector<CrossReadJob> jobs;
+    std::vector<CarrierReadJob> jobs; // (the pair and matrix forms send the CrossReadJob of each)
     std::vector<BankRow> units;
+    std::vector<CarrierUnit> cunits; // AM/PM alone
     size_t max_len = 0;
     uint32_t max_bins = 0;
 };
@@ -3659,43 +3671,81 @@ int xr_layout(XObj *h, const XrArgs &a)
 }
 
 // The kernels of one call into the device memory dev[]: the table through a free slot, the stitch, the bands, the slot's event.
-// pair: dev[] = sxx, syy, sxy, freq, coherence, transfer; else rows, freq.
-int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, bool pair, void *const *dev, size_t stride, const BankBands &bb, double *d_band)
+// PAIR: dev[] = sxx, syy, sxy, freq, coherence, transfer; ROWS: rows, freq; SIDES: upper, lower, freq; SK: those and sk_upper,
+// sk_lower; AM/PM: those three and s_am, s_pm, s_ampm, with the carrier records to d_carrier.
+int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, XrMode mode, void *const *dev, size_t stride, const BankBands &bb, double *d_band,
+               double *d_carrier)
 {
     const uint32_t S = (uint32_t)pl.units.size();
-    if (pl.jobs.empty()) { // nothing included anywhere: no kernel; the band sums are 0.0
-        if (d_band && S)
-            XCHK(h, hipMemsetAsync(d_band, 0, sizeof(double) * S * bb.n * XREAD_PAIR_ROWS, h->stream));
+    const bool records = d_carrier && S; // (a channel without an included stage still gets its record)
+    if (pl.jobs.empty() && d_band && S) // nothing included anywhere: no band kernel; the band sums are 0.0
+        XCHK(h, hipMemsetAsync(d_band, 0, sizeof(double) * S * bb.n * xr_band_rows(mode), h->stream));
+    if (pl.jobs.empty() && !records)
         return PSDC_OK;
-    }
     if (!h->bank_read)
         h->bank_read = new psdrt::BankRead;
     psdrt::BankRead *st = h->bank_read;
-    const size_t job_bytes = sizeof(CrossReadJob) * pl.jobs.size(), bytes = job_bytes + sizeof(BankRow) * S;
+    const bool carrier = xr_carrier_mode(mode);
+    const size_t job_size = carrier ? sizeof(CarrierReadJob) : sizeof(CrossReadJob);
+    const size_t job_bytes = job_size * pl.jobs.size(), unit_bytes = sizeof(BankRow) * S, cunit_bytes = sizeof(CarrierUnit) * pl.cunits.size();
+    const size_t bytes = job_bytes + unit_bytes + cunit_bytes;
     int s = 0;
     XCHK(h, st->take_slot(bytes, &s));
-    memcpy(st->h_tab[s], pl.jobs.data(), job_bytes);
-    memcpy(st->h_tab[s] + job_bytes, pl.units.data(), bytes - job_bytes);
+    // The plan keeps one job type for every mode, the 48-byte CarrierReadJob.  The carrier kernels take the vector as it lies; the
+    // pair and matrix kernels take CrossReadJob, so their table is packed here from the 40-byte base of each job: the bytes the
+    // device saw before, for a copy of 40 bytes a job (a few dozen jobs a call) into pinned memory instead of one memcpy.
+    if (carrier)
+        memcpy(st->h_tab[s], pl.jobs.data(), job_bytes);
+    else
+        for (size_t i = 0; i < pl.jobs.size(); ++i)
+            memcpy(st->h_tab[s] + i * job_size, &static_cast<const CrossReadJob &>(pl.jobs[i]), job_size);
+    memcpy(st->h_tab[s] + job_bytes, pl.units.data(), unit_bytes);
+    if (cunit_bytes)
+        memcpy(st->h_tab[s] + job_bytes + unit_bytes, pl.cunits.data(), cunit_bytes);
     XCHK(h, hipMemcpyAsync(st->d_tab[s], st->h_tab[s], bytes, hipMemcpyHostToDevice, h->stream));
     const CrossReadJob *d_jobs = reinterpret_cast<const CrossReadJob *>(st->d_tab[s]);
+    const CarrierReadJob *d_cjobs = reinterpret_cast<const CarrierReadJob *>(st->d_tab[s]);
     const BankRow *d_units = reinterpret_cast<const BankRow *>(st->d_tab[s] + job_bytes);
+    const CarrierUnit *d_cunits = cunit_bytes ? reinterpret_cast<const CarrierUnit *>(st->d_tab[s] + job_bytes + unit_bytes) : nullptr;
     const uint32_t n_jobs = (uint32_t)pl.jobs.size();
     uint32_t launches = 0;
-    if (pair) {
+    if (mode == XrMode::PAIR) {
         const CrossPairOut o{(float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (double *)dev[4], (double *)dev[5], stride};
         if (o.any()) {
             XCHK(h, launch_cross_stitch_pair(d_jobs, n_jobs, pl.max_bins, o, h->stream));
             ++launches;
         }
-    } else if (dev[0] || dev[1]) {
-        XCHK(h, launch_cross_stitch_rows(d_jobs, n_jobs, pl.max_bins, (float *)dev[0], (float *)dev[1], stride, h->stream));
-        ++launches;
+    } else if (mode == XrMode::ROWS) {
+        if (dev[0] || dev[1]) {
+            XCHK(h, launch_cross_stitch_rows(d_jobs, n_jobs, pl.max_bins, (float *)dev[0], (float *)dev[1], stride, h->stream));
+            ++launches;
+        }
+    } else {
+        CarrierOut o{(float *)dev[0], (float *)dev[1], (float *)dev[2], nullptr, nullptr, nullptr, nullptr, nullptr, d_carrier, stride};
+        if (mode == XrMode::SK) {
+            o.sk_upper = (double *)dev[3];
+            o.sk_lower = (double *)dev[4];
+        } else if (mode == XrMode::AMPM) {
+            o.s_am = (double *)dev[3];
+            o.s_pm = (double *)dev[4];
+            o.s_ampm = (double *)dev[5];
+        }
+        if ((o.any_row() && n_jobs) || records) {
+            const int km = mode == XrMode::SK ? CREAD_SK : mode == XrMode::AMPM ? CREAD_AMPM : CREAD_SIDES;
+            XCHK(h, launch_carrier_stitch(km, d_cjobs, n_jobs, pl.max_bins, o, d_cunits, S, h->stream));
+            ++launches;
+        }
     }
-    if (d_band) {
-        XCHK(h, launch_cross_band(d_jobs, d_units, S, bb, d_band, h->stream));
+    if (d_band && n_jobs) {
+        if (carrier)
+            XCHK(h, launch_carrier_band(xr_band_rows(mode), d_cjobs, d_units, d_cunits, S, bb, d_band, h->stream));
+        else
+            XCHK(h, launch_cross_band(d_jobs, d_units, S, bb, d_band, h->stream));
         ++launches;
     }
     XCHK(h, st->mark_slot(s, h->stream));
+    if (carrier)
+        h->launches += launches;
     if (a.info)
         a.info->launches = launches;
     return PSDC_OK;
@@ -3703,8 +3753,8 @@ int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, bool pair, void *cons
 
 // One read-out call of either object in either form.  device: outs[].p and band_out are device memory, else host memory filled
 // from the object's buffer through one copy.
-int xr_read(XObj *h, const XrArgs &a, bool pair, const XrOut *outs, size_t n_outs, size_t stride, const float *bands, uint32_t n_bands,
-            double *band_out, bool device, void *done_event)
+int xr_read(XObj *h, const XrArgs &a, XrMode mode, const XrOut *outs, size_t n_outs, size_t stride, const float *bands, uint32_t n_bands,
+            double *band_out, bool device, void *done_event, const XrCarrier *car = nullptr)
 {
     uint32_t S = 0;
     int rc = xr_selection(h, a, &S);
@@ -3713,20 +3763,38 @@ int xr_read(XObj *h, const XrArgs &a, bool pair, const XrOut *outs, size_t n_out
     bool any = false;
     for (size_t o = 0; o < n_outs; ++o)
         any = any || outs[o].p;
+    double *carrier_out = car ? car->out : nullptr;
     BankBands bb{};
-    if (const char *why = cross_read_band_refusal(bands, n_bands, band_out, any, &bb))
+    if (const char *why = cross_read_band_refusal(bands, n_bands, band_out, any || carrier_out, &bb))
         return xr_bad(h, a, why);
-    X_ON_DEVICE(h);
     XrPlan pl;
+    if (mode == XrMode::AMPM) { // the refusals of the carrier that the host knows: nothing is drained, nothing launched
+        const bool split = outs[3].p || outs[4].p || outs[5].p || carrier_out || band_out;
+        if (!car->carriers && split && h->detrend != PSDC_DETREND_NONE)
+            return xr_bad(h, a, "bin 0 holds the carrier under PSDC_DETREND_NONE only: pass the carriers");
+        CarrierUnit u{};
+        u.n2p = (double)h->n * (double)h->n * (double)h->power;
+        u.bins = (uint32_t)bins(h);
+        pl.cunits.assign(S, u);
+        for (uint32_t i = 0; car->carriers && i < S; ++i)
+            if (const char *why = carrier_given(car->carriers[2 * i], car->carriers[2 * i + 1], &pl.cunits[i]))
+                return xr_bad(h, a, why);
+    }
+    X_ON_DEVICE(h);
     if ((rc = xr_plan(h, a, S, &pl)))
         return rc;
     if (any && stride < pl.max_len)
         return xfail(h, PSDC_ERR_CAPACITY, std::string(a.who) + ": stride is smaller than the longest row");
+    for (uint32_t i = 0; i < (uint32_t)pl.cunits.size(); ++i) { // (drained: stage 0 of each selected channel as it lies)
+        const std::vector<XStage> &st = h->pairs[a.sel ? a.sel[i] : i];
+        pl.cunits[i].src0 = st.empty() ? nullptr : st[0].acc;
+        pl.cunits[i].count0 = st.empty() ? 0 : count_report(st[0].count64);
+    }
     void *dev[6] = {};
     if (device) {
         for (size_t o = 0; o < n_outs; ++o)
             dev[o] = outs[o].p;
-        if ((rc = xr_enqueue(h, a, pl, pair, dev, stride, bb, band_out)))
+        if ((rc = xr_enqueue(h, a, pl, mode, dev, stride, bb, band_out, carrier_out)))
             return rc;
         if (done_event)
             XCHK(h, hipEventRecord(static_cast<hipEvent_t>(done_event), h->stream));
@@ -3734,28 +3802,30 @@ int xr_read(XObj *h, const XrArgs &a, bool pair, const XrOut *outs, size_t n_out
             XCHK(h, hipStreamSynchronize(h->stream));
         return PSDC_OK;
     }
-    const size_t band_bytes = sizeof(double) * S * n_bands * XREAD_PAIR_ROWS;
-    if (pl.jobs.empty()) { // nothing included anywhere: no row gets a value, the band sums are 0.0
+    const size_t band_bytes = sizeof(double) * S * n_bands * xr_band_rows(mode);
+    const size_t carrier_bytes = carrier_out ? sizeof(double) * 4 * S : 0;
+    if (pl.jobs.empty() && !carrier_bytes) { // nothing included anywhere: no row gets a value, the band sums are 0.0
         if (band_out)
             memset(band_out, 0, band_bytes);
         return PSDC_OK;
     }
-    // the object's buffer: the wanted outputs one behind the other in rows of max_len bins, then the band sums
+    // the object's buffer: the wanted outputs one behind the other in rows of max_len bins, then the band sums and the carrier records
     size_t off[6] = {}, bytes = 0;
     for (size_t o = 0; o < n_outs; ++o) {
         off[o] = bytes;
         if (outs[o].p)
             bytes += (outs[o].elem * outs[o].rows * S * pl.max_len + 15) & ~(size_t)15;
     }
-    const size_t o_band = bytes;
-    bytes += band_bytes;
+    const size_t o_band = bytes, o_carrier = bytes + band_bytes;
+    bytes += band_bytes + carrier_bytes;
     if (!h->bank_read)
         h->bank_read = new psdrt::BankRead;
     psdrt::BankRead *st = h->bank_read;
     XCHK(h, st->room_out(bytes));
     for (size_t o = 0; o < n_outs; ++o)
         dev[o] = outs[o].p ? st->d_out + off[o] : nullptr;
-    if ((rc = xr_enqueue(h, a, pl, pair, dev, pl.max_len, bb, band_out ? reinterpret_cast<double *>(st->d_out + o_band) : nullptr)))
+    if ((rc = xr_enqueue(h, a, pl, mode, dev, pl.max_len, bb, band_out ? reinterpret_cast<double *>(st->d_out + o_band) : nullptr,
+                         carrier_out ? reinterpret_cast<double *>(st->d_out + o_carrier) : nullptr)))
         return rc;
     XCHK(h, hipMemcpyAsync(st->h_out, st->d_out, bytes, hipMemcpyDeviceToHost, h->stream));
     XCHK(h, hipStreamSynchronize(h->stream));
@@ -3765,7 +3835,22 @@ int xr_read(XObj *h, const XrArgs &a, bool pair, const XrOut *outs, size_t n_out
                    outs[o].elem * pl.units[r / outs[o].rows].len);
     if (band_out)
         memcpy(band_out, st->h_out + o_band, band_bytes);
+    if (carrier_out)
+        memcpy(carrier_out, st->h_out + o_carrier, carrier_bytes);
     return PSDC_OK;
+}
+
+// the handle of a psdczr_ call: one of the six single-channel carrier kinds (need: 0 any of them, 1 an SK kind, 2 an AM/PM kind)
+int zr_handle(XObj *h, const char *who, int need)
+{
+    X_HANDLE(h, who);
+    const size_t k = (size_t)(h->kind - KINDS);
+    const bool sides = k == K_ZOOM || k == K_IQ, sk = k == K_ZSK || k == K_IQSK, ampm = k == K_ZAMPM || k == K_IQAMPM;
+    if (need == 1 ? sk : need == 2 ? ampm : sides || sk || ampm)
+        return PSDC_OK;
+    return xfail(h, PSDC_ERR_ARG, std::string(who) + (need == 1   ? ": takes a zoom SK or IQ SK object"
+                                                     : need == 2 ? ": takes a zoom AM/PM or IQ AM/PM object"
+                                                                 : ": takes a zoom, IQ, zoom / IQ SK or zoom / IQ AM/PM object"));
 }
 
 int xr_release(XObj *h, const char *who)
@@ -3794,7 +3879,7 @@ int psdcxr_cross_csd_device(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel
 {
     const XrOut outs[6] = {{d_sxx, 4, 1}, {d_syy, 4, 1}, {d_sxy, 8, 1}, {d_freq, 4, 1}, {d_coherence, 8, 1}, {d_transfer, 16, 1}};
     return xr_read(h, {"psdcxr_cross_csd_device", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
-                   true, outs, 6, stride, bands, n_bands, d_band_sums, true, done_event);
+                   XrMode::PAIR, outs, 6, stride, bands, n_bands, d_band_sums, true, done_event);
 }
 
 int psdcxr_cross_csd(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
@@ -3803,8 +3888,8 @@ int psdcxr_cross_csd(psdc_cross *h, const uint32_t *pairs, uint32_t n_sel, int k
                      psdcxr_info *info)
 {
     const XrOut outs[6] = {{sxx, 4, 1}, {syy, 4, 1}, {sxy, 8, 1}, {freq, 4, 1}, {coherence, 8, 1}, {transfer, 16, 1}};
-    return xr_read(h, {"psdcxr_cross_csd", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}, true,
-                   outs, 6, stride, bands, n_bands, band_sums, false, nullptr);
+    return xr_read(h, {"psdcxr_cross_csd", pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
+                   XrMode::PAIR, outs, 6, stride, bands, n_bands, band_sums, false, nullptr);
 }
 
 int psdcxr_cross_release(psdc_cross *h) { return xr_release(h, "psdcxr_cross_release"); }
@@ -3821,7 +3906,7 @@ int psdcxr_csm_rows_device(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, 
 {
     const XrOut outs[2] = {{d_rows, 4, h ? h->rows() : 0}, {d_freq, 4, 1}};
     return xr_read(h, {"psdcxr_csm_rows_device", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
-                   false, outs, 2, stride, nullptr, 0, nullptr, true, done_event);
+                   XrMode::ROWS, outs, 2, stride, nullptr, 0, nullptr, true, done_event);
 }
 
 int psdcxr_csm_rows(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
@@ -3829,10 +3914,105 @@ int psdcxr_csm_rows(psdc_csm *h, const uint32_t *groups, uint32_t n_sel, int kee
                     psdcxr_info *info)
 {
     const XrOut outs[2] = {{rows, 4, h ? h->rows() : 0}, {freq, 4, 1}};
-    return xr_read(h, {"psdcxr_csm_rows", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}, false,
-                   outs, 2, stride, nullptr, 0, nullptr, false, nullptr);
+    return xr_read(h, {"psdcxr_csm_rows", groups, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info},
+                   XrMode::ROWS, outs, 2, stride, nullptr, 0, nullptr, false, nullptr);
 }
 
 int psdcxr_csm_release(psdc_csm *h) { return xr_release(h, "psdcxr_csm_release"); }
+
+// ---- the bank read-outs of include/psdcascade_carrierread.h (zoom, IQ, zoom / IQ SK and zoom / IQ AM/PM objects) ----
+// The same plan and the same two table slots; the jobs carry their Break's count, an AM/PM call adds one unit record a channel
+// (carrier_readout.h), the kernels are those of carrier_readout.hip.
+
+#define ZR_ARGS(name) {name, channels, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}
+
+int psdczr_layout(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                  size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_layout", 0))
+        return rc;
+    return xr_layout(x, ZR_ARGS("psdczr_layout"));
+}
+
+int psdczr_sides_device(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                        float *d_upper, float *d_lower, float *d_freq, size_t stride, const float *bands, uint32_t n_bands,
+                        double *d_band_sums, void *done_event, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap,
+                        psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_sides_device", 0))
+        return rc;
+    const XrOut outs[3] = {{d_upper, 4, 1}, {d_lower, 4, 1}, {d_freq, 4, 1}};
+    return xr_read(x, ZR_ARGS("psdczr_sides_device"), XrMode::SIDES, outs, 3, stride, bands, n_bands, d_band_sums, true, done_event);
+}
+
+int psdczr_sides(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                 float *upper, float *lower, float *freq, size_t stride, const float *bands, uint32_t n_bands, double *band_sums,
+                 size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_sides", 0))
+        return rc;
+    const XrOut outs[3] = {{upper, 4, 1}, {lower, 4, 1}, {freq, 4, 1}};
+    return xr_read(x, ZR_ARGS("psdczr_sides"), XrMode::SIDES, outs, 3, stride, bands, n_bands, band_sums, false, nullptr);
+}
+
+int psdczr_sk_device(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                     float *d_upper, float *d_lower, float *d_freq, double *d_sk_upper, double *d_sk_lower, size_t stride,
+                     void *done_event, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_sk_device", 1))
+        return rc;
+    const XrOut outs[5] = {{d_upper, 4, 1}, {d_lower, 4, 1}, {d_freq, 4, 1}, {d_sk_upper, 8, 1}, {d_sk_lower, 8, 1}};
+    return xr_read(x, ZR_ARGS("psdczr_sk_device"), XrMode::SK, outs, 5, stride, nullptr, 0, nullptr, true, done_event);
+}
+
+int psdczr_sk(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+              float *upper, float *lower, float *freq, double *sk_upper, double *sk_lower, size_t stride, size_t *lens, size_t *n_breaks,
+              psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_sk", 1))
+        return rc;
+    const XrOut outs[5] = {{upper, 4, 1}, {lower, 4, 1}, {freq, 4, 1}, {sk_upper, 8, 1}, {sk_lower, 8, 1}};
+    return xr_read(x, ZR_ARGS("psdczr_sk"), XrMode::SK, outs, 5, stride, nullptr, 0, nullptr, false, nullptr);
+}
+
+int psdczr_ampm_device(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                       const double *carriers, float *d_upper, float *d_lower, float *d_freq, double *d_s_am, double *d_s_pm,
+                       double *d_s_ampm, double *d_carrier, size_t stride, const float *bands, uint32_t n_bands, double *d_band_sums,
+                       void *done_event, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_ampm_device", 2))
+        return rc;
+    const XrOut outs[6] = {{d_upper, 4, 1}, {d_lower, 4, 1}, {d_freq, 4, 1}, {d_s_am, 8, 1}, {d_s_pm, 8, 1}, {d_s_ampm, 16, 1}};
+    const XrCarrier car{carriers, d_carrier};
+    return xr_read(x, ZR_ARGS("psdczr_ampm_device"), XrMode::AMPM, outs, 6, stride, bands, n_bands, d_band_sums, true, done_event, &car);
+}
+
+int psdczr_ampm(void *h, const uint32_t *channels, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                const double *carriers, float *upper, float *lower, float *freq, double *s_am, double *s_pm, double *s_ampm,
+                double *carrier, size_t stride, const float *bands, uint32_t n_bands, double *band_sums, size_t *lens, size_t *n_breaks,
+                psdc_break *breaks, size_t breaks_cap, psdczr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_ampm", 2))
+        return rc;
+    const XrOut outs[6] = {{upper, 4, 1}, {lower, 4, 1}, {freq, 4, 1}, {s_am, 8, 1}, {s_pm, 8, 1}, {s_ampm, 16, 1}};
+    const XrCarrier car{carriers, carrier};
+    return xr_read(x, ZR_ARGS("psdczr_ampm"), XrMode::AMPM, outs, 6, stride, bands, n_bands, band_sums, false, nullptr, &car);
+}
+
+int psdczr_release(void *h)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = zr_handle(x, "psdczr_release", 0))
+        return rc;
+    return xr_release(x, "psdczr_release");
+}
+#undef ZR_ARGS
 
 } // extern "C"

@@ -37,6 +37,22 @@ turns of A / B / C / A; a leg is a window of at least --seconds, and at least on
 call of several seconds).  Reported: the median microseconds a read-out of all channels of each leg, the rate ratios against the
 turn's two A legs, the largest |A' - A| / A of a turn, and the largest |B - A| over the curves, relative to each curve's largest value (the f32 fold against f64).
 Findings, no gate.
+
+    python tools/readout_probe.py --carrier [--sk|--ampm] [--seconds 0.3] [--out profiles/carrier_readout_probe.json]
+
+The carrier banks' read-outs (carrierread) of a zoom bank of C = 64 and 4 channels at N = 1024 with a carrier at the tuning word,
+six live stages, read-outs only; the mode picks the bank: ZoomCascadeBank, with --sk ZoomSkCascadeBank, with --ampm
+ZoomAmPmCascadeBank:
+  A  the per-channel route over the C channels, unchanged in this build: psd(c); with --sk psd(c) and sk(c); with --ampm am_pm(c),
+     which reads carrier() with a snapshot of stage 0 and then sidebands() with another.  Per call a drain, both streams
+     synchronised, one blocking copy a stage, a host stitch;
+  B  carrierread.bank_sides / bank_sk / bank_am_pm: one launch, one copy, one synchronisation, host arrays;
+  C  the device form into torch tensors, the form that returns when the kernel has completed: upper and lower; with --sk also
+     sk_upper and sk_lower; with --ampm s_am, s_pm, s_ampm and the carrier records.
+Five turns of A / B / C / A.  Reported: the median microseconds a read-out of all channels of each leg, the rate ratios against the
+turn's two A legs, the largest |A' - A| / A of a turn, and `breaks_us`: B and C hand their Breaks back unbuilt (the Python objects
+are made when `breaks` is first indexed), A's calls build them every time.  The file keeps the three modes side by side; a run
+replaces the rows of its own mode.  Findings, no gate.
 Needs a GPU."""
 import argparse
 import json
@@ -223,6 +239,104 @@ def var_config(pkg, bankread, bankvar, torch, np, bank, live, n_taus, vs, second
             "A_spread_max": max(t["A_spread"] for t in turns)}
 
 
+CARRIER_F0 = 0.25
+CARRIER_CLASSES = {"sides": "ZoomCascadeBank", "sk": "ZoomSkCascadeBank", "ampm": "ZoomAmPmCascadeBank"}
+
+
+def carrier_config(pkg, carrierread, torch, np, mode, n, channels, seconds):
+    import statistics
+    bank = getattr(pkg, CARRIER_CLASSES[mode])(n, channels)
+    for c in range(channels):
+        bank.set_carrier(c, f0=CARRIER_F0)
+    j = np.arange(CALL, dtype=np.float64)  # (CALL * CARRIER_F0 is whole: every call continues the carrier's phase)
+    x = torch.from_numpy((np.cos(2 * np.pi * CARRIER_F0 * j + 0.3)).astype(np.float32)).cuda()
+    x += 0.01 * (torch.rand(CALL, device="cuda", dtype=torch.float32) - 0.5)
+    torch.cuda.synchronize()
+    need = int(1.1 * n * 8 ** (STAGES - 1))
+    for _ in range((need + CALL - 1) // CALL):
+        for c in range(channels):
+            bank.process_device(c, x.data_ptr(), CALL)
+    bank.sync()
+    lay = carrierread.layout(bank)
+    live = [sum(b.count > 0 for b in br) for br in lay["breaks"]]
+    assert min(live) >= STAGES, live
+    width = lay["max_len"]
+    f32 = {k: torch.empty((channels, width), device="cuda", dtype=torch.float32) for k in ("upper", "lower")}
+    f64 = {k: torch.empty((channels, w * width), device="cuda", dtype=torch.float64)
+           for k, w in {"sides": (), "sk": (("sk_upper", 1), ("sk_lower", 1)), "ampm": (("s_am", 1), ("s_pm", 1), ("s_ampm", 2))}[mode]}
+    if mode == "ampm":
+        f64["carrier"] = torch.empty((channels, 4), device="cuda", dtype=torch.float64)
+    tensors = {**f64} if mode == "ampm" else {**f32, **f64}  # (am_pm(c) returns no upper / lower: C writes none)
+    ptrs = {k: t.data_ptr() for k, t in tensors.items()}
+    torch.cuda.synchronize()
+    # A: the parent's route for every channel, unchanged in this build
+    leg_a = {"sides": lambda: [bank.psd(c) for c in range(channels)],
+             "sk": lambda: [(bank.psd(c), bank.sk(c)) for c in range(channels)],
+             "ampm": lambda: [bank.am_pm(c) for c in range(channels)]}[mode]
+    host = {"sides": carrierread.bank_sides, "sk": carrierread.bank_sk, "ampm": carrierread.bank_am_pm}[mode]
+    dev = {"sides": carrierread.bank_sides_device, "sk": carrierread.bank_sk_device, "ampm": carrierread.bank_am_pm_device}[mode]
+    legs = {"A": leg_a, "B": lambda: host(bank), "C": lambda: dev(bank, width, **ptrs)}
+    # the three agree before anything is timed: bytes for the f32 rows and SK, am_pm(c) to 1e-12 of a row's largest value
+    a, b = legs["A"](), legs["B"]()
+    legs["C"]()
+    got = {k: t.cpu().numpy() for k, t in tensors.items()}
+    for c in range(channels):
+        ln = b["lens"][c]
+        if mode == "sides":
+            assert a[c][0].tobytes() == b["upper"][c, :ln].tobytes() == got["upper"][c, :ln].tobytes(), c
+        elif mode == "sk":
+            assert a[c][0][1].tobytes() == b["lower"][c, :ln].tobytes() == got["lower"][c, :ln].tobytes(), c
+            assert a[c][1][0].tobytes() == b["sk_upper"][c, :ln].tobytes() == got["sk_upper"][c, :ln].tobytes(), c
+        else:
+            assert b["s_pm"][c, :ln].tobytes() == got["s_pm"][c, :ln].tobytes() and b["carrier"][c].tobytes() == got["carrier"][c].tobytes(), c
+            # (at the carrier's own bins s_pm is the small difference of two large terms: the scale is s_am's there)
+            assert np.max(np.abs(a[c][1] - b["s_pm"][c, :ln])) <= 1e-12 * max(np.max(np.abs(a[c][0])), np.max(np.abs(a[c][1]))), c
+    turns = []
+    for _ in range(CROSS_TURNS):
+        t = [window(legs[k], seconds) for k in "ABCA"]
+        turns.append({"A_us": [t[0], t[3]], "B_us": t[1], "C_us": t[2], "B_over_A": 0.5 * (t[0] + t[3]) / t[1],
+                      "C_over_A": 0.5 * (t[0] + t[3]) / t[2], "A_spread": abs(t[3] - t[0]) / t[0]})
+    r = legs["B"]()
+    t0 = time.perf_counter()
+    list(r["breaks"])
+    breaks_us = 1e6 * (time.perf_counter() - t0)
+    bank.close()
+    med = statistics.median
+    return {"mode": mode, "n": n, "channels": channels, "breaks_us": breaks_us, "live_stages": min(live), "row_len": width, "launches_B": b["launches"],
+            "outputs_C": sorted(ptrs), "turns": turns,
+            "A_us": med(v for t in turns for v in t["A_us"]), "B_us": med(t["B_us"] for t in turns), "C_us": med(t["C_us"] for t in turns),
+            "B_over_A": med(t["B_over_A"] for t in turns), "C_over_A": med(t["C_over_A"] for t in turns),
+            "A_spread_max": max(t["A_spread"] for t in turns)}
+
+
+def carrier_main(a, torch, pkg):
+    import numpy as np
+    from stabilizer_stream_amd import carrierread
+    mode = "sk" if a.sk else "ampm" if a.ampm else "sides"
+    rows = [carrier_config(pkg, carrierread, torch, np, mode, 1024, c, a.seconds) for c in (64, 4)]
+    path = a.out or os.path.join(ROOT, "profiles", "carrier_readout_probe.json")
+    rec = {}
+    if os.path.exists(path):  # (one file for the three modes: a run replaces its own mode's rows)
+        with open(path) as f:
+            rec = json.loads(f.read())
+    rec.update({"metric": "carrier_readout_us",
+                "unit": "microseconds a read-out of all channels, median of the turns (host clock, through the Python binding)",
+                "note": "findings, no gate: A = the per-channel route over the channels (sides: psd(c); sk: psd(c) + sk(c); ampm: am_pm(c), which "
+                        "reads carrier() and sidebands()), B = carrierread.bank_sides / bank_sk / bank_am_pm (host arrays), C = the device form "
+                        "with the outputs named in outputs_C (synchronising form); a zoom bank with a carrier at the tuning word, read-outs "
+                        "only, six live stages, no feed in the window; five turns of A / B / C / A; ratios are rates (above 1: faster than A); "
+                        "B and C do not build the Python Break objects (breaks_us: building them once), A's calls do",
+                "device": torch.cuda.get_device_name(0), "turns": CROSS_TURNS})
+    rec.setdefault("modes", {})[mode] = {"seconds": a.seconds, "configs": rows}
+    line = json.dumps(rec)
+    with open(path, "w") as f:
+        f.write(line + "\n")
+    print(line)
+    for r in rows:
+        print(f"{mode:5s} N={r['n']:5d} C={r['channels']:3d}  A {r['A_us']:9.1f} us  B {r['B_us']:8.1f} us  C {r['C_us']:8.1f} us  "
+              f"B/A {r['B_over_A']:.2f}  C/A {r['C_over_A']:.2f}  A/A spread <= {r['A_spread_max']:.3f}  breaks {r['breaks_us']:.0f} us", file=sys.stderr)
+
+
 def var_main(a, torch, pkg):
     import numpy as np
     from stabilizer_stream_amd import bankread, bankvar
@@ -272,15 +386,23 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--cross", action="store_true", help="measure the pair object's read-outs (crossread) instead")
     ap.add_argument("--var", action="store_true", help="measure the Var read-out (bankvar) against the host loop of var_eval instead")
+    ap.add_argument("--carrier", action="store_true", help="measure the carrier banks' read-outs (carrierread) instead: the zoom bank's "
+                                                           "sidebands, with --sk the zoom SK bank's SK, with --ampm the zoom AM/PM bank's split")
+    ap.add_argument("--sk", action="store_true")
+    ap.add_argument("--ampm", action="store_true")
     ap.add_argument("--out", default=None, help="default profiles/bank_readout_probe.json, with --cross profiles/cross_readout_probe.json, "
-                                                "with --var profiles/bank_var_probe.json")
+                                                "with --var profiles/bank_var_probe.json, with --carrier profiles/carrier_readout_probe.json")
     a = ap.parse_args()
+    if (a.sk or a.ampm) and not a.carrier or (a.sk and a.ampm):
+        ap.error("--sk and --ampm select the mode of --carrier, one at a time")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("readout_probe: no GPU is visible (there is nothing to measure without one)")
     pkg = entry.load_package()
     if a.seconds is None:
-        a.seconds = 0.3 if a.cross or a.var else 0.5
+        a.seconds = 0.3 if a.cross or a.var or a.carrier else 0.5
+    if a.carrier:
+        return carrier_main(a, torch, pkg)
     if a.var:
         return var_main(a, torch, pkg)
     if a.cross:
