@@ -73,8 +73,8 @@
  *                        AM/PM kinds: the three outputs above, s_am, s_pm, s_ampm, carrier and band_sums [S][n_bands][4].
  *   psdczr_release       frees the object's read-out buffers (they are made again by the next call).
  *
- * Out of scope: the real spectral kurtosis object (psdc_sk) and the pair kinds (psdc_zcsd, psdc_iqcsd, psdc_zxampm,
- * psdc_iqxampm); the waterfall rings; two-sided reordering and dB / dBc outputs; the command line tool; feeding
+ * Out of scope: the real spectral kurtosis object (psdc_sk); the pair kinds (psdc_zcsd, psdc_iqcsd, psdc_zxampm, psdc_iqxampm),
+ * which ext/psdcascade_pairread.h reads; the waterfall rings; two-sided reordering and dB / dBc outputs; the command line tool; feeding
  * psdcv_rows_var_device (psdcascade_var.h), which takes a psdc_handle. */
 #ifndef PSDCASCADE_CARRIERREAD_H
 #define PSDCASCADE_CARRIERREAD_H

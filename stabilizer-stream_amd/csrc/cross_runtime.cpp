@@ -49,10 +49,12 @@
 #include "waterfall_robust.h"
 #include "cross_readout.h"
 #include "carrier_readout.h"
+#include "pair_readout.h"
 #include "host_runtime.h"
 #include "../../include/psdcascade_robust.h"
 #include "../../include/psdcascade_crossread.h"
 #include "../../include/psdcascade_carrierread.h"
+#include "../../include/ext/psdcascade_pairread.h"
 
 #include <algorithm>
 #include <cmath>
@@ -83,6 +85,10 @@ inline hipError_t launch_cross_band(const CrossReadJob *, const BankRow *, uint3
 // (nor those of carrier_readout.hip: the psdczr_ read-outs fail there in the same way)
 inline hipError_t launch_carrier_stitch(int, const CarrierReadJob *, uint32_t, uint32_t, const CarrierOut &, const CarrierUnit *, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
 inline hipError_t launch_carrier_band(uint32_t, const CarrierReadJob *, const BankRow *, const CarrierUnit *, uint32_t, const BankBands &, double *, hipStream_t) { return hipErrorInvalidValue; }
+// (nor those of pair_readout.hip: the psdcpr_ read-outs fail there in the same way)
+inline hipError_t launch_pair_stitch_csd(const CarrierReadJob *, uint32_t, uint32_t, const PairCsdOut &, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_pair_stitch_ampm(const CarrierReadJob *, uint32_t, uint32_t, const PairAmPmOut &, const PairUnit *, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
+inline hipError_t launch_pair_band(int, const CarrierReadJob *, const BankRow *, const PairUnit *, uint32_t, const BankBands &, double *, hipStream_t) { return hipErrorInvalidValue; }
 } // namespace psdk
 #endif
 
@@ -3572,14 +3578,25 @@ struct XrOut {
     uint32_t rows;
 };
 
-// which kernels a call runs: the pair and matrix forms of cross_readout.hip (psdcxr_*), or a mode of carrier_readout.hip (psdczr_*)
-enum class XrMode { PAIR, ROWS, SIDES, SK, AMPM };
-bool xr_carrier_mode(XrMode m) { return m == XrMode::SIDES || m == XrMode::SK || m == XrMode::AMPM; }
+// which kernels a call runs: the pair and matrix forms of cross_readout.hip (psdcxr_*), a mode of carrier_readout.hip (psdczr_*),
+// or a mode of pair_readout.hip (psdcpr_*)
+enum class XrMode { PAIR, ROWS, SIDES, SK, AMPM, PCSD, PAMPM };
+bool xr_pair_carrier_mode(XrMode m) { return m == XrMode::PCSD || m == XrMode::PAMPM; }
+// the modes whose kernels take CarrierReadJob and whose launches count in the object's stats_read
+bool xr_carrier_mode(XrMode m) { return m == XrMode::SIDES || m == XrMode::SK || m == XrMode::AMPM || xr_pair_carrier_mode(m); }
 // rows of a band sum (0: the mode has no bands)
-uint32_t xr_band_rows(XrMode m) { return m == XrMode::PAIR || m == XrMode::AMPM ? XREAD_PAIR_ROWS : m == XrMode::SIDES ? CREAD_SIDE_ROWS : 0; }
+uint32_t xr_band_rows(XrMode m)
+{
+    if (xr_pair_carrier_mode(m))
+        return PREAD_BAND_ROWS;
+    return m == XrMode::PAIR || m == XrMode::AMPM ? XREAD_PAIR_ROWS : m == XrMode::SIDES ? CREAD_SIDE_ROWS : 0;
+}
+// f64 values of a carrier record
+uint32_t xr_record(XrMode m) { return m == XrMode::PAMPM ? PREAD_RECORD : 4; }
+constexpr size_t XR_MAX_OUTS = 11; // the outputs of psdcpr_csd
 
-// what an AM/PM call adds: the given amplitudes [S][2] on the host (NULL: from bin 0 of stage 0) and the carrier records [S][4]
-// (NULL: not wanted; device or host memory as the call's other outputs)
+// what an AM/PM call adds: the given carriers on the host (AMPM: the amplitudes [S][2]; PAMPM: [S][5] = p_ab, w, q; NULL: from bin 0
+// of stage 0) and the carrier records [S][4] or [S][7] (NULL: not wanted; device or host memory as the call's other outputs)
 struct XrCarrier {
     const double *carriers;
     double *out;
@@ -3589,6 +3606,7 @@ struct XrPlan {
     std::vector<CarrierReadJob> jobs; // (the pair and matrix forms send the CrossReadJob of each)
     std::vector<BankRow> units;
     std::vector<CarrierUnit> cunits; // AM/PM alone
+    std::vector<PairUnit> punits;    // pair AM/PM alone
     size_t max_len = 0;
     uint32_t max_bins = 0;
 };
@@ -3672,7 +3690,8 @@ int xr_layout(XObj *h, const XrArgs &a)
 
 // The kernels of one call into the device memory dev[]: the table through a free slot, the stitch, the bands, the slot's event.
 // PAIR: dev[] = sxx, syy, sxy, freq, coherence, transfer; ROWS: rows, freq; SIDES: upper, lower, freq; SK: those and sk_upper,
-// sk_lower; AM/PM: those three and s_am, s_pm, s_ampm, with the carrier records to d_carrier.
+// sk_lower; AM/PM: those three and s_am, s_pm, s_ampm, with the carrier records to d_carrier; PCSD: PairCsdOut's eleven in order;
+// PAMPM: PairAmPmOut's seven in order, with the carrier records to d_carrier.
 int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, XrMode mode, void *const *dev, size_t stride, const BankBands &bb, double *d_band,
                double *d_carrier)
 {
@@ -3688,7 +3707,8 @@ int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, XrMode mode, void *co
     const bool carrier = xr_carrier_mode(mode);
     const size_t job_size = carrier ? sizeof(CarrierReadJob) : sizeof(CrossReadJob);
     const size_t job_bytes = job_size * pl.jobs.size(), unit_bytes = sizeof(BankRow) * S, cunit_bytes = sizeof(CarrierUnit) * pl.cunits.size();
-    const size_t bytes = job_bytes + unit_bytes + cunit_bytes;
+    const size_t punit_bytes = sizeof(PairUnit) * pl.punits.size(); // (a call has units of one kind at most)
+    const size_t bytes = job_bytes + unit_bytes + cunit_bytes + punit_bytes;
     int s = 0;
     XCHK(h, st->take_slot(bytes, &s));
     // The plan keeps one job type for every mode, the 48-byte CarrierReadJob.  The carrier kernels take the vector as it lies; the
@@ -3702,14 +3722,31 @@ int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, XrMode mode, void *co
     memcpy(st->h_tab[s] + job_bytes, pl.units.data(), unit_bytes);
     if (cunit_bytes)
         memcpy(st->h_tab[s] + job_bytes + unit_bytes, pl.cunits.data(), cunit_bytes);
+    if (punit_bytes)
+        memcpy(st->h_tab[s] + job_bytes + unit_bytes + cunit_bytes, pl.punits.data(), punit_bytes);
     XCHK(h, hipMemcpyAsync(st->d_tab[s], st->h_tab[s], bytes, hipMemcpyHostToDevice, h->stream));
     const CrossReadJob *d_jobs = reinterpret_cast<const CrossReadJob *>(st->d_tab[s]);
     const CarrierReadJob *d_cjobs = reinterpret_cast<const CarrierReadJob *>(st->d_tab[s]);
     const BankRow *d_units = reinterpret_cast<const BankRow *>(st->d_tab[s] + job_bytes);
     const CarrierUnit *d_cunits = cunit_bytes ? reinterpret_cast<const CarrierUnit *>(st->d_tab[s] + job_bytes + unit_bytes) : nullptr;
+    const PairUnit *d_punits = punit_bytes ? reinterpret_cast<const PairUnit *>(st->d_tab[s] + job_bytes + unit_bytes + cunit_bytes) : nullptr;
     const uint32_t n_jobs = (uint32_t)pl.jobs.size();
     uint32_t launches = 0;
-    if (mode == XrMode::PAIR) {
+    if (mode == XrMode::PCSD) {
+        const PairCsdOut o{(float *)dev[0], (float *)dev[1], (float *)dev[2],  (float *)dev[3],  (float *)dev[4],  (float *)dev[5],
+                           (float *)dev[6], (double *)dev[7], (double *)dev[8], (double *)dev[9], (double *)dev[10], stride};
+        if (o.any_row() && n_jobs) {
+            XCHK(h, launch_pair_stitch_csd(d_cjobs, n_jobs, pl.max_bins, o, h->stream));
+            ++launches;
+        }
+    } else if (mode == XrMode::PAMPM) {
+        const PairAmPmOut o{(float *)dev[0], (double *)dev[1], (double *)dev[2], (double *)dev[3], (double *)dev[4],
+                            (double *)dev[5], (double *)dev[6], d_carrier,        stride};
+        if ((o.any_row() && n_jobs) || records) {
+            XCHK(h, launch_pair_stitch_ampm(d_cjobs, n_jobs, pl.max_bins, o, d_punits, S, h->stream));
+            ++launches;
+        }
+    } else if (mode == XrMode::PAIR) {
         const CrossPairOut o{(float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (double *)dev[4], (double *)dev[5], stride};
         if (o.any()) {
             XCHK(h, launch_cross_stitch_pair(d_jobs, n_jobs, pl.max_bins, o, h->stream));
@@ -3737,7 +3774,9 @@ int xr_enqueue(XObj *h, const XrArgs &a, const XrPlan &pl, XrMode mode, void *co
         }
     }
     if (d_band && n_jobs) {
-        if (carrier)
+        if (xr_pair_carrier_mode(mode))
+            XCHK(h, launch_pair_band(mode == XrMode::PAMPM ? PREAD_AMPM : PREAD_CSD, d_cjobs, d_units, d_punits, S, bb, d_band, h->stream));
+        else if (carrier)
             XCHK(h, launch_carrier_band(xr_band_rows(mode), d_cjobs, d_units, d_cunits, S, bb, d_band, h->stream));
         else
             XCHK(h, launch_cross_band(d_jobs, d_units, S, bb, d_band, h->stream));
@@ -3780,6 +3819,18 @@ int xr_read(XObj *h, const XrArgs &a, XrMode mode, const XrOut *outs, size_t n_o
             if (const char *why = carrier_given(car->carriers[2 * i], car->carriers[2 * i + 1], &pl.cunits[i]))
                 return xr_bad(h, a, why);
     }
+    if (mode == XrMode::PAMPM) { // the same for the carriers of a pair
+        const bool split = outs[3].p || outs[4].p || outs[5].p || outs[6].p || carrier_out || band_out;
+        if (!car->carriers && split && h->detrend != PSDC_DETREND_NONE)
+            return xr_bad(h, a, "bin 0 holds the carrier under PSDC_DETREND_NONE only: pass the carriers");
+        PairUnit u{};
+        u.n2p = (double)h->n * (double)h->n * (double)h->power;
+        u.bins = (uint32_t)bins(h);
+        pl.punits.assign(S, u);
+        for (uint32_t i = 0; car->carriers && i < S; ++i)
+            if (const char *why = pair_given(car->carriers + 5 * (size_t)i, &pl.punits[i]))
+                return xr_bad(h, a, why);
+    }
     X_ON_DEVICE(h);
     if ((rc = xr_plan(h, a, S, &pl)))
         return rc;
@@ -3790,7 +3841,12 @@ int xr_read(XObj *h, const XrArgs &a, XrMode mode, const XrOut *outs, size_t n_o
         pl.cunits[i].src0 = st.empty() ? nullptr : st[0].acc;
         pl.cunits[i].count0 = st.empty() ? 0 : count_report(st[0].count64);
     }
-    void *dev[6] = {};
+    for (uint32_t i = 0; i < (uint32_t)pl.punits.size(); ++i) {
+        const std::vector<XStage> &st = h->pairs[a.sel ? a.sel[i] : i];
+        pl.punits[i].src0 = st.empty() ? nullptr : st[0].acc;
+        pl.punits[i].count0 = st.empty() ? 0 : count_report(st[0].count64);
+    }
+    void *dev[XR_MAX_OUTS] = {};
     if (device) {
         for (size_t o = 0; o < n_outs; ++o)
             dev[o] = outs[o].p;
@@ -3803,14 +3859,14 @@ int xr_read(XObj *h, const XrArgs &a, XrMode mode, const XrOut *outs, size_t n_o
         return PSDC_OK;
     }
     const size_t band_bytes = sizeof(double) * S * n_bands * xr_band_rows(mode);
-    const size_t carrier_bytes = carrier_out ? sizeof(double) * 4 * S : 0;
+    const size_t carrier_bytes = carrier_out ? sizeof(double) * xr_record(mode) * S : 0;
     if (pl.jobs.empty() && !carrier_bytes) { // nothing included anywhere: no row gets a value, the band sums are 0.0
         if (band_out)
             memset(band_out, 0, band_bytes);
         return PSDC_OK;
     }
     // the object's buffer: the wanted outputs one behind the other in rows of max_len bins, then the band sums and the carrier records
-    size_t off[6] = {}, bytes = 0;
+    size_t off[XR_MAX_OUTS] = {}, bytes = 0;
     for (size_t o = 0; o < n_outs; ++o) {
         off[o] = bytes;
         if (outs[o].p)
@@ -3851,6 +3907,18 @@ int zr_handle(XObj *h, const char *who, int need)
     return xfail(h, PSDC_ERR_ARG, std::string(who) + (need == 1   ? ": takes a zoom SK or IQ SK object"
                                                      : need == 2 ? ": takes a zoom AM/PM or IQ AM/PM object"
                                                                  : ": takes a zoom, IQ, zoom / IQ SK or zoom / IQ AM/PM object"));
+}
+
+// the handle of a psdcpr_ call: one of the four pair carrier kinds (ampm: a 12-row kind)
+int pr_handle(XObj *h, const char *who, bool ampm)
+{
+    X_HANDLE(h, who);
+    const size_t k = (size_t)(h->kind - KINDS);
+    const bool csd = k == K_ZCSD || k == K_IQCSD, xampm = k == K_ZXAMPM || k == K_IQXAMPM;
+    if (ampm ? xampm : csd || xampm)
+        return PSDC_OK;
+    return xfail(h, PSDC_ERR_ARG, std::string(who) + (ampm ? ": takes a zoom AM/PM cross or IQ AM/PM cross object"
+                                                           : ": takes a zoom cross, IQ cross or zoom / IQ AM/PM cross object"));
 }
 
 int xr_release(XObj *h, const char *who)
@@ -4014,5 +4082,88 @@ int psdczr_release(void *h)
     return xr_release(x, "psdczr_release");
 }
 #undef ZR_ARGS
+
+// ---- the bank read-outs of include/ext/psdcascade_pairread.h (zoom cross, IQ cross and zoom / IQ AM/PM cross objects) ----
+// The same plan, jobs and table slots; an AM/PM call adds one unit record a pair (pair_readout.h), the kernels are those of
+// pair_readout.hip.
+
+#define PR_ARGS(name) {name, pairs, n_sel, keep_overlap, min_count, keep_transition_band, lens, n_breaks, breaks, breaks_cap, info}
+#define PR_CSD_OUTS(p) \
+    {{p##saa_up, 4, 1}, {p##saa_lo, 4, 1}, {p##sbb_up, 4, 1}, {p##sbb_lo, 4, 1}, {p##sab_up, 8, 1}, {p##sab_lo, 8, 1}, \
+     {p##freq, 4, 1},   {p##coh_up, 8, 1}, {p##coh_lo, 8, 1}, {p##h1_up, 16, 1}, {p##h1_lo, 16, 1}}
+#define PR_AMPM_OUTS(p) \
+    {{p##freq, 4, 1}, {p##cab, 16, 1}, {p##cba, 16, 1}, {p##s_am, 16, 1}, {p##s_pm, 16, 1}, {p##s_am_pm, 16, 1}, {p##s_pm_am, 16, 1}}
+
+int psdcpr_layout(void *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                  size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcpr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_layout", false))
+        return rc;
+    return xr_layout(x, PR_ARGS("psdcpr_layout"));
+}
+
+int psdcpr_csd_device(void *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                      float *d_saa_up, float *d_saa_lo, float *d_sbb_up, float *d_sbb_lo, float *d_sab_up, float *d_sab_lo, float *d_freq,
+                      double *d_coh_up, double *d_coh_lo, double *d_h1_up, double *d_h1_lo, size_t stride, const float *bands,
+                      uint32_t n_bands, double *d_band_sums, void *done_event, size_t *lens, size_t *n_breaks, psdc_break *breaks,
+                      size_t breaks_cap, psdcpr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_csd_device", false))
+        return rc;
+    const XrOut outs[11] = PR_CSD_OUTS(d_);
+    return xr_read(x, PR_ARGS("psdcpr_csd_device"), XrMode::PCSD, outs, 11, stride, bands, n_bands, d_band_sums, true, done_event);
+}
+
+int psdcpr_csd(void *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+               float *saa_up, float *saa_lo, float *sbb_up, float *sbb_lo, float *sab_up, float *sab_lo, float *freq, double *coh_up,
+               double *coh_lo, double *h1_up, double *h1_lo, size_t stride, const float *bands, uint32_t n_bands, double *band_sums,
+               size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcpr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_csd", false))
+        return rc;
+    const XrOut outs[11] = PR_CSD_OUTS();
+    return xr_read(x, PR_ARGS("psdcpr_csd"), XrMode::PCSD, outs, 11, stride, bands, n_bands, band_sums, false, nullptr);
+}
+
+int psdcpr_ampm_device(void *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                       const double *carriers, float *d_freq, double *d_cab, double *d_cba, double *d_s_am, double *d_s_pm,
+                       double *d_s_am_pm, double *d_s_pm_am, double *d_carrier, size_t stride, const float *bands, uint32_t n_bands,
+                       double *d_band_sums, void *done_event, size_t *lens, size_t *n_breaks, psdc_break *breaks, size_t breaks_cap,
+                       psdcpr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_ampm_device", true))
+        return rc;
+    const XrOut outs[7] = PR_AMPM_OUTS(d_);
+    const XrCarrier car{carriers, d_carrier};
+    return xr_read(x, PR_ARGS("psdcpr_ampm_device"), XrMode::PAMPM, outs, 7, stride, bands, n_bands, d_band_sums, true, done_event, &car);
+}
+
+int psdcpr_ampm(void *h, const uint32_t *pairs, uint32_t n_sel, int keep_overlap, uint32_t min_count, int keep_transition_band,
+                const double *carriers, float *freq, double *cab, double *cba, double *s_am, double *s_pm, double *s_am_pm,
+                double *s_pm_am, double *carrier, size_t stride, const float *bands, uint32_t n_bands, double *band_sums, size_t *lens,
+                size_t *n_breaks, psdc_break *breaks, size_t breaks_cap, psdcpr_info *info)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_ampm", true))
+        return rc;
+    const XrOut outs[7] = PR_AMPM_OUTS();
+    const XrCarrier car{carriers, carrier};
+    return xr_read(x, PR_ARGS("psdcpr_ampm"), XrMode::PAMPM, outs, 7, stride, bands, n_bands, band_sums, false, nullptr, &car);
+}
+
+int psdcpr_release(void *h)
+{
+    XObj *x = static_cast<XObj *>(h);
+    if (int rc = pr_handle(x, "psdcpr_release", false))
+        return rc;
+    return xr_release(x, "psdcpr_release");
+}
+#undef PR_ARGS
+#undef PR_CSD_OUTS
+#undef PR_AMPM_OUTS
 
 } // extern "C"
